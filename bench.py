@@ -6,13 +6,20 @@ per-shard verdict bitmaps. N = 1 runs configs[1] of BASELINE.js
 N > 1 runs configs[4] (64M requests split into N contiguous 64-aligned shards, i.e. 8M per GPU at
 N = 8: fixed total work). About 0.1 % of the records are tampered so the verdict check compares
 bitmaps, not "all ones". Inputs are uploaded to HBM before the timed region; host serialization and
-PCIe are reported separately, never as `value`. Beside the headline at N = 1: configs[2] (2 %
-adversarial, verdicts compared with libsodium's), configs[3] (3 signatures per request), the
-forced Straus path, host-buffer latency and the CPU baselines. The multi-GPU harness uses no
+PCIe are reported separately, never as `value`. A plain run does only what the headline needs:
+generate and upload the batch, W warm-up steps, K timed steps, the verdict check, the result line.
+With --full, beside the headline: the stage breakdown and roofline of a second timed run, the
+sustained-load figure, and at N = 1 configs[2] (2 % adversarial, verdicts compared with
+libsodium's), configs[3] (3 signatures per request), the forced Straus path, host-buffer latency,
+the ingress legs and the CPU baselines (at N > 1 the host-path, single-process and CPU-baseline
+legs). --dump-outputs DIR writes the verdicts of the last timed step as DIR/verdicts.npy (float32,
+one 0/1 value per request; at N > 1 every shard's gathered verdicts, shard-major), a fixed seeded
+sample of them beside its positions (verdicts_index.npy) when they would exceed 64 MB. The workload is
+seeded, so the same arguments give the same inputs in every run. The multi-GPU harness uses no
 framework: rank 0's RCCL id travels through a file, barriers and the max over ranks are RCCL
 all-gathers (class Comm).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--per-gpu REQUESTS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--per-gpu REQUESTS] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -64,6 +71,10 @@ class DeviceBatch:
         arr = np.ascontiguousarray(arr)
         _native.check(_native.lib().pv_memcpy_h2d(p, arr.ctypes.data, arr.nbytes), "pv_memcpy_h2d")
         return p
+
+    def _clear(self, p, nbytes):
+        z = np.zeros(nbytes, np.uint8)
+        _native.check(_native.lib().pv_memcpy_h2d(p, z.ctypes.data, nbytes), "pv_memcpy_h2d")
 
     def verify(self):
         _native.check(self.L.pv_verify_batch_device(self.d_blob, self.d_off, self.n, self.d_pk, self.d_verdict, None),
@@ -657,6 +668,22 @@ def bits(words, n):
     return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, verdicts):
+    """--dump-outputs: the verdict bits a caller of the timed path receives, as DIR/verdicts.npy (float32,
+    1.0 = accepted). Above 64 MB a fixed sample instead: 4M positions (the limit / 16) drawn with seed 0,
+    ascending, written beside the values as verdicts_index.npy (float64), 48 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    out = verdicts.astype(np.float32)
+    if out.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(len(out), size=DUMP_MAX_BYTES // 16, replace=False))
+        np.save(os.path.join(path, "verdicts_index.npy"), idx.astype(np.float64))
+        out = out[idx]
+    np.save(os.path.join(path, "verdicts.npy"), out)
+
+
 def config3_leg(db_like, blob0, off, pks, steps, warmup, timed_fn):
     """configs[2]: the headline's 1M requests with 2 % adversarial records (tools/adversarial_batch.py,
     every SURVEY §8c(iv) class, mixed-order keys forged with libsodium), verified in the default AUTO
@@ -700,10 +727,28 @@ def assemble_result(world, n, steps, warmup, elapsed, stage_ms, chunks, comb, nk
     added by the caller): value = requests of all ranks / the max-over-ranks time of `steps` steps,
     the roofline of the dominant kernel from its HIP-event launch time (stage "msm" / chunks), the
     whole-pipeline figures from the stage times. fused: the comb path's MSM stage is pv_comb_ab_kernel
-    ([S]B and [k](-A) in one kernel), else pv_comb_a_kernel ([k](-A) only)."""
+    ([S]B and [k](-A) in one kernel), else pv_comb_a_kernel ([k](-A) only). stage_ms = None (a run
+    without the second, stage-timed pass): the line without `roofline`, `pipeline` and the chunk count."""
     total = n * world * steps
     value = total / elapsed
     ms_per_step = 1e3 * elapsed / steps
+    result = {
+        "metric": METRIC, "value": round(value, 1), "unit": "verifies/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak" if world == 1 or per_gpu_fixed else "strong",
+        "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": workload_name(n, world) + ", %d of them tampered (must-reject), device-resident" % (
+                       tamper_count(n) * world),
+                   "requests_per_gpu": n, "global_batch": n * world, "parallelism": "dp%d" % world,
+                   "record_bytes_avg": round(record_bytes_avg, 1),
+                   "path": "keyed comb (%d distinct keys per chunk, tables built inside every step)" % nkeys if comb
+                   else "per-request Straus"},
+        "verdicts_ok": bool(ok_local and (ok_all is None or ok_all)),
+        "verdicts_check": "bitmap == known bits (valid except %d tampered records per GPU)%s" % (
+            tamper_count(n), ", all %d shards' gathered bitmaps checked on every rank" % world if world > 1 else ""),
+    }
+    if stage_ms is None:
+        return result
     mac_kernel = ((BC.MAC_COMB_AB_KERNEL if fused else BC.MAC_COMB_MSM_KERNEL) if comb
                   else BC.MAC_MSM_HALF_KERNEL)
     launch_ms = stage_ms["msm"] / chunks  # the roofline kernel's average launch (one per chunk)
@@ -713,36 +758,23 @@ def assemble_result(world, n, steps, warmup, elapsed, stage_ms, chunks, comb, nk
     mac_executed = (BC.MAC_COMB_MSM + BC.MAC_ENCODE / 4 + BC.MAC_COMB_PER_KEY * nkeys / (n / chunks)) if comb \
         else (BC.MAC_PER_VERIFY - BC.MAC_ENCODE * 3 / 4)
     kernel = ("pv_comb_ab_kernel" if fused else "pv_comb_a_kernel") if comb else "pv_msm_kernel"
-    return {
-        "metric": METRIC, "value": round(value, 1), "unit": "verifies/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-        "scaling": "weak" if world == 1 or per_gpu_fixed else "strong",
-        "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": workload_name(n, world) + ", %d of them tampered (must-reject), device-resident" % (
-                       tamper_count(n) * world),
-                   "requests_per_gpu": n, "global_batch": n * world, "parallelism": "dp%d" % world,
-                   "chunks_per_gpu_step": chunks, "record_bytes_avg": round(record_bytes_avg, 1),
-                   "path": "keyed comb (%d distinct keys per chunk, tables built inside every step)" % nkeys if comb
-                   else "per-request Straus"},
-        "roofline": {"bound": "valu", "kernel": kernel,
-                     "achieved": round(achieved / 1e12, 3), "peak": round(BC.PEAK_MAC_PER_S / 1e12, 3),
-                     "unit": "TMAC/s (v_mad_u64_u32 int32 MACs)", "frac": round(achieved / BC.PEAK_MAC_PER_S, 4),
-                     "traffic": pmc_traffic(kernel),
-                     "algorithmic_mac_per_verify": round(mac_kernel), "launch_ms": round(launch_ms, 4),
-                     "frac_of_measured_mad_stream": round(achieved / BC.MEASURED_MAD_STREAM_MAC_PER_S, 4),
-                     "valu_issue_per_cu_cycle_pmc": pmc_valu_issue(kernel)},
-        "pipeline": {**{s + "_ms": round(v, 4) for s, v in stage_ms.items()},
-                     "kernel_verifies_per_s_per_gpu": round(per_gpu_rate, 1),
-                     "whole_pipeline_valu_frac": round(mac_executed * per_gpu_rate / BC.PEAK_MAC_PER_S, 4),
-                     "libsodium_equivalent_mac_rate_over_peak": round(
-                         BC.MAC_PER_VERIFY * per_gpu_rate / BC.PEAK_MAC_PER_S, 4),
-                     "hbm_staging_GBps": round(BC.ALGO_BYTES_PER_VERIFY * per_gpu_rate / 1e9, 2),
-                     "note": "stage times (and the roofline kernel's launch time) from a second timed run with "
-                             "stage-boundary events on the stream; value / ms_per_step from the run without them"},
-        "verdicts_ok": bool(ok_local and (ok_all is None or ok_all)),
-        "verdicts_check": "bitmap == known bits (valid except %d tampered records per GPU)%s" % (
-            tamper_count(n), ", all %d shards' gathered bitmaps checked on every rank" % world if world > 1 else ""),
-    }
+    result["config"]["chunks_per_gpu_step"] = chunks
+    result["roofline"] = {"bound": "valu", "kernel": kernel,
+                          "achieved": round(achieved / 1e12, 3), "peak": round(BC.PEAK_MAC_PER_S / 1e12, 3),
+                          "unit": "TMAC/s (v_mad_u64_u32 int32 MACs)", "frac": round(achieved / BC.PEAK_MAC_PER_S, 4),
+                          "traffic": pmc_traffic(kernel),
+                          "algorithmic_mac_per_verify": round(mac_kernel), "launch_ms": round(launch_ms, 4),
+                          "frac_of_measured_mad_stream": round(achieved / BC.MEASURED_MAD_STREAM_MAC_PER_S, 4),
+                          "valu_issue_per_cu_cycle_pmc": pmc_valu_issue(kernel)}
+    result["pipeline"] = {**{s + "_ms": round(v, 4) for s, v in stage_ms.items()},
+                          "kernel_verifies_per_s_per_gpu": round(per_gpu_rate, 1),
+                          "whole_pipeline_valu_frac": round(mac_executed * per_gpu_rate / BC.PEAK_MAC_PER_S, 4),
+                          "libsodium_equivalent_mac_rate_over_peak": round(
+                              BC.MAC_PER_VERIFY * per_gpu_rate / BC.PEAK_MAC_PER_S, 4),
+                          "hbm_staging_GBps": round(BC.ALGO_BYTES_PER_VERIFY * per_gpu_rate / 1e9, 2),
+                          "note": "stage times (and the roofline kernel's launch time) from a second timed run with "
+                                  "stage-boundary events on the stream; value / ms_per_step from the run without them"}
+    return result
 
 
 def add_cpu_baseline(result, cb, c1=None):
@@ -934,8 +966,15 @@ def main():
     ap.add_argument("--no-multisig", action="store_true", help="skip the configs[3] multi-signature measurement")
     ap.add_argument("--no-single-process", action="store_true",
                     help="N > 1: skip rank 0's pv_verify_batch_multi_gpu leg over every GPU of the node")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the stage-timed second run (roofline, pipeline), sustained load, "
+                         "configs[2] / configs[3], the Straus path, the host-path, latency, ingress and "
+                         "single-process legs and the CPU baselines (each with its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step to DIR/verdicts.npy (float32 0/1 per request)")
     ap.add_argument("--rank-stub", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    full = args.full
 
     # one process per GPU: under a launcher (torch.distributed.run) WORLD_SIZE must equal --gpus;
     # without one, --gpus N > 1 starts the N ranks itself (fresh processes, before anything here
@@ -972,8 +1011,8 @@ def main():
     if args.dataset and os.path.exists(args.dataset):
         blob0, off, pks, lo = nym_workload.load(args.dataset)
         assert lo == rank * n and len(off) - 1 == n, "dataset does not match this rank's shard"
-    elif world == 1 and not args.no_ingress:
-        blob0, off, pks, *wire = nym_workload.generate_wire(rank * n, n)
+    elif full and world == 1 and not args.no_ingress:
+        blob0, off, pks, *wire = nym_workload.generate_wire(rank * n, n)  # the same records, plus their wire form
     else:
         # configs[4] shards are 8-32M requests per rank: more signing workers per rank where the node
         # has the cores (16 is the per-GPU CPU share of a 1-GPU box; never above 64)
@@ -987,12 +1026,12 @@ def main():
     import adversarial_batch
     blob, tampered = adversarial_batch.tamper(blob0, off, tamper_count(n), seed=1000 + rank)
     c1 = None
-    if world == 1 and wire and not args.no_cpu_baseline:
+    if full and world == 1 and wire and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         c1 = config1_legs(wire)  # CPU leg, forked workers: before the device comes up
         phases["config1_cpu_leg"] = time.perf_counter() - t0
     multi = None
-    if world == 1 and not args.no_multisig and not args.dataset:
+    if full and world == 1 and not args.no_multisig and not args.dataset:
         t0 = time.perf_counter()
         # before the device comes up (forked); ~1 % corrupted signatures among the 3 per request
         multi = nym_workload.generate_multisig(0, min(n, 1 << 20), 3, bad_frac=0.01, seed=4)
@@ -1004,7 +1043,7 @@ def main():
     _native.ensure_device(local_rank)
     L = _native.lib()
     phases["pv_init"] = time.perf_counter() - t0
-    hbm_ctx = hbm_in_use()  # the engine context: fixed-base comb, workspace, staging
+    hbm_ctx = hbm_in_use() if full else None  # the engine context: fixed-base comb, workspace, staging
     log("rank %d: device %d up (pv_init) in %.1f s" % (rank, local_rank, phases["pv_init"]))
     t0 = time.perf_counter()
     db = DeviceBatch(blob, off, pks)
@@ -1053,12 +1092,24 @@ def main():
     _native.check(L.pv_sync(), "pv_sync")
     phases["warmup"] = time.perf_counter() - t0
     log("rank %d: %d warm-up steps in %.1f s" % (rank, args.warmup, phases["warmup"]))
+    # the verdict buffers are cleared after the warm-up, so what is read back after the timed steps
+    # (checked below, written by --dump-outputs) was computed by them
+    db._clear(db.d_verdict, db.words * 8)
+    if world > 1:
+        db._clear(d_all, db.words * 8 * world)
     t0 = time.perf_counter()
     elapsed, _ = timed(args.steps, stages=False)  # the headline: no stage events in the measured loop
-    _, stage_ms = timed(args.steps)                # stage breakdown and the roofline kernel's launch time
+    got_local = bits(db.verdict_words(), n)       # the last timed step's verdicts
+    got_all = None
+    if world > 1:
+        allw = db.verdict_words(d_all, db.words * world).reshape(world, db.words)
+        got_all = [bits(allw[r], n) for r in range(world)]
+    stage_ms = chunks = None
+    if full:
+        _, stage_ms = timed(args.steps)            # stage breakdown and the roofline kernel's launch time
+        chunks = timed.chunks
     phases["timed"] = time.perf_counter() - t0
     log("rank %d: timed runs in %.1f s (headline %.3f s for %d steps)" % (rank, phases["timed"], elapsed, args.steps))
-    chunks = timed.chunks
     path, nkeys = _native.last_path()
     comb = path == _native.PV_PATH_COMB
 
@@ -1066,16 +1117,17 @@ def main():
     # construction except the tampered records), on this rank and, gathered, on every rank
     want_local = np.ones(n, bool)
     want_local[tampered] = False
-    ok_local = bool(np.array_equal(bits(db.verdict_words(), n), want_local))
+    ok_local = bool(np.array_equal(got_local, want_local))
     ok_all = None
     if world > 1:
-        allw = db.verdict_words(d_all, db.words * world).reshape(world, db.words)
-        ok_all = all(np.array_equal(bits(allw[r], n), expected_bits(n, r)) for r in range(world))
+        ok_all = all(np.array_equal(got_all[r], expected_bits(n, r)) for r in range(world))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, got_local if world == 1 else np.concatenate(got_all))
 
     result = assemble_result(world, n, args.steps, args.warmup, elapsed, stage_ms, chunks, comb, nkeys,
                              float(blob.nbytes) / n, ok_local, ok_all, per_gpu_fixed=bool(args.per_gpu),
-                             fused=_native.comb_fused() and n / chunks > FUSED_MIN_REQ)
-    if world == 1 and args.sustain_s > 0:
+                             fused=bool(full and _native.comb_fused() and n / chunks > FUSED_MIN_REQ))
+    if full and world == 1 and args.sustain_s > 0:
         # the same step under sustained load: the MI355X raises its clock over ~2 s of back-to-back
         # launches (1.74-1.80 GHz in the first step after idle, ~2.0 after 10 steps, ~2.2 after 2.5 s:
         # in-kernel s_memtime / s_memrealtime stamps, profiles/r06/clock/), so the headline's 5 warm-up +
@@ -1103,7 +1155,7 @@ def main():
                                  "(hipMemGetInfo, device-wide)"}
     if world > 1:
         result["rccl"] = rccl_summary(world, *comm.rccl_ranks())
-    if world > 1 and not args.no_host_path:
+    if full and world > 1 and not args.no_host_path:
         # SURVEY.md §8e host traffic: each rank's shard from host buffers (pv_verify_batch: pinned
         # staging pipelined with the H2D DMA, kernels, verdicts back), on up to configs[4]'s 8M-request
         # shard; max over ranks. Reported beside the device-resident headline, never as `value`.
@@ -1130,7 +1182,7 @@ def main():
                                    "seconds": round(hel, 4), "ok": bool(np.array_equal(hv, want_local[:hs])),
                                    "note": "pv_verify_batch from host buffers on every rank at once, PCIe "
                                            "included, max over ranks"}
-    if comb and not args.no_straus and world == 1:
+    if full and comb and not args.no_straus and world == 1:
         # the same batch forced through the per-request Straus path (what a batch of all-distinct
         # keys gets): reported beside the headline, never as `value`
         _native.set_path(_native.PV_PATH_STRAUS)
@@ -1152,10 +1204,10 @@ def main():
                          "valu_issue_per_cu_cycle_pmc": pmc_valu_issue("pv_msm_kernel")},
             "verdicts_ok": ok2}
     c3 = None
-    if rank == 0 and world == 1 and not args.no_config3:
+    if full and rank == 0 and world == 1 and not args.no_config3:
         c3, c3_got, c3_batch = config3_leg(db, blob0, off, pks, max(3, args.steps), args.warmup, timed)
         result["config3"] = c3
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if full and rank == 0 and world == 1 and not args.no_host_path:
         # PCIe-inclusive host-buffer path (pv_verify_batch) on the headline batch itself
         t0 = time.perf_counter()
         result["host_path"] = host_path_leg(blob, off, pks, want_local)
@@ -1251,7 +1303,7 @@ def main():
         result["host_path"]["batch_latency"] = lat
         result["host_prep"] = {"workload_generation_s": round(gen_s, 2), "note": "serialize + sign, %d workers" % min(
             16, os.cpu_count() or 1)}
-    if rank == 0 and world == 1 and wire and not args.no_host_path:
+    if full and rank == 0 and world == 1 and wire and not args.no_host_path:
         # configs[0] through the unmodified per-call drop-in with the HIP engine (one launch per
         # signature), beside the libsodium leg of the same loop (cpu_baseline.config1_python_authenticate)
         t0 = time.perf_counter()
@@ -1277,20 +1329,20 @@ def main():
         phases["drop_in_per_call"] = time.perf_counter() - t0
     if multi is not None:
         result["multisig"] = multisig_leg(multi, min(n, 1 << 20), 3, max(3, args.steps // 4))
-    if rank == 0 and world == 1 and wire:
+    if full and rank == 0 and world == 1 and wire:
         result["ingress"] = ingress_leg(n, blob0, off, wire, max(3, args.steps // 4), 1)
     # rank 0's own legs at N > 1 (the other ranks wait on a file, idle): the single-process multi-GPU
     # entry over every GPU of the node, then the CPU baseline on the node's host cores -- each in a
     # try/except so that a failure records an error and never costs the headline line
     fb = FileBarrier(world, rank) if world > 1 else None
-    if rank == 0 and world > 1 and not args.no_single_process:
+    if full and rank == 0 and world > 1 and not args.no_single_process:
         t0 = time.perf_counter()
         try:
             result["single_process"] = single_process_leg(blob, off, pks, want_local, world)
         except Exception as ex:
             result["single_process"] = {"error": repr(ex)[:300]}
         phases["single_process_leg"] = time.perf_counter() - t0
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         try:
             cb, c3_want = cpu_baseline(blob0, off, pks, min(args.cpu_sample, n), args.cpu_seconds,

@@ -69,6 +69,38 @@ def test_assemble_result_single_gpu_straus():
     assert r["roofline"]["kernel"] == "pv_msm_kernel" and r["scaling"] == "weak"
 
 
+def test_assemble_result_plain_run():
+    """A run without --full has no stage-timed pass: the same headline fields, no roofline / pipeline."""
+    n = 1 << 20
+    full = bench.assemble_result(1, n, 20, 5, 20 * 2.7e-3, _stub_stages(2.7), 1, True, 1024, 299.0, True, None)
+    plain = bench.assemble_result(1, n, 20, 5, 20 * 2.7e-3, None, None, True, 1024, 299.0, True, None)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus",
+              "verdicts_ok", "verdicts_check"):
+        assert plain[k] == full[k]
+    assert plain["ms_per_step"] == 2.7 and plain["value"] == round(n / 2.7e-3, 1)
+    assert "roofline" not in plain and "pipeline" not in plain and "chunks_per_gpu_step" not in plain["config"]
+    assert {k: v for k, v in full["config"].items() if k != "chunks_per_gpu_step"} == plain["config"]
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    v = np.random.default_rng(1).random(1000) < 0.9
+    bench.dump_outputs(str(tmp_path / "a"), v)
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    assert os.listdir(tmp_path / "a") == ["verdicts.npy"]
+    # above the size limit: the same seeded sample every time, positions beside the values
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), v)
+    idx = np.load(tmp_path / "b" / "verdicts_index.npy")
+    got = np.load(tmp_path / "b" / "verdicts.npy")
+    assert idx.dtype == np.float64 and len(idx) == 64 and np.all(np.diff(idx) > 0)
+    assert got.dtype == np.float32 and np.array_equal(got, v[idx.astype(int)].astype(np.float32))
+    assert got.nbytes + idx.nbytes <= 1024
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "verdicts_index.npy"))
+
+
 def test_file_barrier_releases_waiting_rank(tmp_path, monkeypatch):
     monkeypatch.setenv("PV_BENCH_JOB", "test_%d" % os.getpid())
     r0, r1 = bench.FileBarrier(2, 0), bench.FileBarrier(2, 1)

@@ -10,7 +10,7 @@ timeout -k 10 300 python3 tools/nym_workload.py --out $DS > /dev/null || exit $?
 for round in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then unset PLENUM_AMD_LIB; else export PLENUM_AMD_LIB=variants/$v/libplenum_verify.so; fi
-    timeout -k 10 300 python3 bench.py --dataset $DS --no-cpu-baseline --no-host-path \
+    timeout -k 10 300 python3 bench.py --full --dataset $DS --no-cpu-baseline --no-host-path \
       --no-ingress --no-multisig --no-straus --steps 20 --warmup 5 > $OUT/$v.$round.json 2> $OUT/$v.$round.log || exit $?
     python3 - "$v" "$OUT/$v.$round.json" <<'PY'
 import json, sys

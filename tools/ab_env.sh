@@ -11,7 +11,7 @@ DS=/tmp/nym_ab.npz
 for round in $(seq 1 $ROUNDS); do
   for spec in "$@"; do
     name="${spec%%:*}"; envs="${spec#*:}"
-    env $envs timeout -k 10 300 python3 bench.py --dataset $DS --no-cpu-baseline --no-host-path \
+    env $envs timeout -k 10 300 python3 bench.py --full --dataset $DS --no-cpu-baseline --no-host-path \
       --no-ingress --no-multisig --no-straus ${AB_EXTRA:-} --steps 20 --warmup 5 > $OUT/$name.$round.json 2> $OUT/$name.$round.log || exit $?
     python3 - "$name" "$OUT/$name.$round.json" <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ DS=/tmp/nym_ab.npz
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     if [ "$v" = base ]; then lib=""; else lib="PLENUM_AMD_LIB=variants/$v/libplenum_verify.so"; fi
-    out=$(env $lib timeout -k 10 200 python3 bench.py --dataset $DS --no-cpu-baseline --no-config3 --sustain-s 0 \
+    out=$(env $lib timeout -k 10 200 python3 bench.py --full --dataset $DS --no-cpu-baseline --no-config3 --sustain-s 0 \
           --no-host-path --no-ingress --no-multisig --steps 12 --warmup 2 2>/dev/null | tail -1) || exit $?
     echo "$out" | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['straus_path']; print('$v', d['ms_per_step'], d['stages_ms'], d['verdicts_ok'])"
   done

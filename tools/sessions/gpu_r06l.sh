@@ -7,4 +7,4 @@ export TMPDIR=/tmp
 O=gpurun_out/r06l
 mkdir -p $O
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || exit $?
-timeout -k 10 900 python3 bench.py > $O/bench.json 2> $O/bench.log || exit $?
+timeout -k 10 900 python3 bench.py --full > $O/bench.json 2> $O/bench.log || exit $?

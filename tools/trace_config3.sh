@@ -9,7 +9,7 @@ OUT=gpurun_out/c3trace${1:+_$1}
 mkdir -p $OUT
 DS=/tmp/nym_c3.npz
 timeout -k 10 300 python3 tools/nym_workload.py --out $DS > /dev/null || exit $?
-timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/trace -o run -- python3 bench.py --dataset $DS --no-cpu-baseline \
+timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/trace -o run -- python3 bench.py --full --dataset $DS --no-cpu-baseline \
   --no-host-path --no-ingress --no-multisig --no-straus --steps 4 --warmup 1 > $OUT/bench.json 2> $OUT/trace.log || exit $?
 DB=$(ls $OUT/trace/*/run_results.db $OUT/trace/*.db $OUT/trace/*/*.db 2>/dev/null | head -1)
 echo "db: $DB"
