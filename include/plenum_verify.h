@@ -342,6 +342,33 @@ int pv_ingress_verify(const char* sig_chars, const uint64_t* sig_off, const uint
                       uint8_t* verdict_bits);
 int pv_ingress_front_ms(double* ms);
 
+/* Batch Ed25519 signing, byte-identical to libsodium 1.0.18. Replaces the reference's per-call chain
+ * stp_core/crypto/nacl_wrappers.py:141 SigningKey.__init__ -> libnacl.crypto_sign_seed_keypair and
+ * :170 SigningKey.sign -> libnacl.crypto_sign -> libsodium, for a whole batch in one call. A 64-byte
+ * secret key is libsodium's: seed || public key, and the public-key half is hashed AS GIVEN.
+ * NOT hardened against timing or memory-access side channels (table lookups are indexed by secret
+ * digits): for load generation, fixtures and test wallets, not for custody of production keys. The
+ * library overwrites its own copies of seeds and derived secrets before a host-entry call returns.
+ * Batches are signed in chunks of 262,144 messages inside the library.
+ *   pv_sign_seed_keypairs  crypto_sign_seed_keypair for n seeds (n x 32): pk_out n x 32, sk_out n x 64
+ *                          (seed || pk); either may be NULL. Synchronous, host buffers.
+ *   pv_sign_batch          crypto_sign_detached: message i = msg[msg_off[i] : msg_off[i+1]] signed with
+ *                          sk[64 * signer_idx[i]]; signer_idx NULL means signer i (then n_signers == n).
+ *                          sig_out n x 64. Synchronous, host buffers. Validates its arguments
+ *                          (non-decreasing offsets, indices < n_signers, n_signers > 0 when n > 0) and
+ *                          returns PV_ERR_ARG instead of launching on bad input.
+ *   pv_sign_batch_device   the same on device buffers, enqueued on `stream` (NULL = the library stream),
+ *                          no synchronise. d_msg readable to msg_off[n] + PV_BLOB_SLACK, d_sk and
+ *                          d_sig_out 16-byte aligned. An out-of-range signer index gives an all-zero
+ *                          signature, never a fault (the convention of ingress status 3). The workspace
+ *                          is handed over between streams as for pv_verify_batch_device.
+ * n = 0 returns PV_OK and launches nothing; without pv_init every entry returns PV_ERR_NOT_INIT. */
+int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uint8_t* sk_out);
+int pv_sign_batch(const uint8_t* msg, const uint64_t* msg_off, uint64_t n, const uint8_t* sk,
+                  uint64_t n_signers, const uint32_t* signer_idx, uint8_t* sig_out);
+int pv_sign_batch_device(const uint8_t* d_msg, const uint64_t* d_msg_off, uint64_t n, const uint8_t* d_sk,
+                         uint64_t n_signers, const uint32_t* d_signer_idx, uint8_t* d_sig_out, void* stream);
+
 /* Signing serialization of received JSON requests on the host, many threads:
  * request i is the JSON text json[off[i] : off[i+1]] that ZStack.deserializeMsg decodes
  * (stp_zmq/zstack.py:881-885); the output is the signing-serialized message

@@ -18,6 +18,7 @@ PV_OK = 0
 PV_ERR_ARG = -4
 PV_BLOB_SLACK = 256
 PV_ABI_VERSION = 1
+PV_SIGN_CHUNK = 262144  # messages per launch inside pv_sign_batch (csrc/pv_engine.hip PV_SIGN_CHUNK)
 PV_BUILD_COMB_FUSED = 1  # pv_build_flags(): [S]B and [k](-A) of the comb path in one kernel
 
 PV_STAGES = ("keys", "prep", "table", "msm", "encode")  # PV_STAGE_* order
@@ -98,6 +99,11 @@ SIGNATURES = {
     "pv_stream_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)]),
     "pv_stream_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "pv_stream_sync": (ctypes.c_int, [ctypes.c_void_p]),
+    "pv_sign_seed_keypairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_sign_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_sign_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -231,6 +237,54 @@ def verify_one(pk, sm):
     off = np.array([0, len(sm)], dtype=np.uint64)
     return bool(verify_sm_batch(np.frombuffer(bytes(sm) or b"\0", dtype=np.uint8), off,
                                 np.frombuffer(bytes(pk), dtype=np.uint8))[0])
+
+
+def seed_keypairs(seeds):
+    """crypto_sign_seed_keypair for a batch: seeds uint8 (n, 32) (or n x 32 bytes) -> (pks (n, 32),
+    sks (n, 64) = seed || pk), byte-identical to libsodium. One GPU call (pv_sign_seed_keypairs)."""
+    if _device is None:
+        ensure_device()
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1)
+    if seeds.size % 32:
+        raise ValueError("seeds must be 32 bytes each")
+    n = seeds.size // 32
+    pks, sks = np.zeros((n, 32), np.uint8), np.zeros((n, 64), np.uint8)
+    if n:
+        check(lib().pv_sign_seed_keypairs(_ptr(seeds), n, _ptr(pks), _ptr(sks)), "pv_sign_seed_keypairs")
+    return pks, sks
+
+
+def sign_batch(blob, off, sks, signer_idx=None):
+    """crypto_sign_detached for a batch: message i = blob[off[i]:off[i+1]] signed with the 64-byte secret
+    key sks[signer_idx[i]] (signer_idx None: sks[i]). Returns the signatures, uint8 (n, 64),
+    byte-identical to libsodium. One GPU call (pv_sign_batch)."""
+    if _device is None:
+        ensure_device()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = off.shape[0] - 1
+    if n <= 0:
+        return np.zeros((0, 64), np.uint8)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    if int(off[n]) > blob.size or int(off[0]) > int(off[n]):
+        raise ValueError("sign: offsets reach past the message blob")
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    sks = np.ascontiguousarray(sks, dtype=np.uint8).reshape(-1)
+    if sks.size % 64 or sks.size == 0:
+        raise ValueError("secret keys must be 64 bytes each (seed || public key)")
+    n_signers = sks.size // 64
+    if signer_idx is None:
+        if n_signers != n:
+            raise ValueError("without signer_idx there must be one secret key per message")
+        idx = None
+    else:
+        idx = np.ascontiguousarray(signer_idx, dtype=np.uint32)
+        if idx.shape != (n,):
+            raise ValueError("signer_idx must hold one index per message")
+    sigs = np.zeros((n, 64), np.uint8)
+    check(lib().pv_sign_batch(_ptr(blob), _ptr(off), n, _ptr(sks), n_signers, _ptr(idx) if idx is not None else None,
+                              _ptr(sigs)), "pv_sign_batch")
+    return sigs
 
 
 PV_INJECT_STAGE = 1  # pv_test_inject: fail the next host-buffer stagings of a device

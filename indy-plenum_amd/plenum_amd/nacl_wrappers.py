@@ -1,4 +1,4 @@
-"""Drop-in for the verification half of ``stp_core/crypto/nacl_wrappers.py``.
+"""Drop-in for ``stp_core/crypto/nacl_wrappers.py``: the verification half and the signing half.
 
   VerifyKey (nacl_wrappers.py:62-108)   32-byte Ed25519 public key; ``verify(smessage, signature=None)``
                                         returns the message or raises ValueError, like libnacl.
@@ -8,6 +8,17 @@
                                         (ValueError('Invalid public key') / ('Failed to validate
                                         message')), computed by the HIP engine.
 
+  SigningKey (nacl_wrappers.py:111-178) 32-byte seed; ``verify_key``, ``generate()``, ``sign(message,
+                                        encoder) -> SignedMessage``; ``bytes(key)`` is the seed.
+  Signer    (nacl_wrappers.py:181-209)  ``keyhex`` / ``keyraw`` (the seed), ``verhex`` / ``verraw``,
+                                        ``sign(msg)``, ``signature(msg)``.
+  crypto_sign_seed_keypair, crypto_sign libnacl semantics, computed by the HIP engine, byte-identical to
+                                        libsodium. One call is one small launch (slower than libsodium's
+                                        20-40 us on a CPU): batches go through
+                                        ``plenum_amd.signing.sign_requests``. The signer is not hardened
+                                        against side channels (csrc/sign_core.h): load generation,
+                                        fixtures and test wallets, not custody of production keys.
+
 Every verification goes to the GPU engine. Inside an ``authenticate_batch`` call the verdicts were
 already computed in one batched launch and are looked up (plenum_amd.batch); outside one, a
 single-request launch is made. There is no CPU fallback: without the library/GPU this raises
@@ -15,10 +26,20 @@ single-request launch is made. There is no CPU fallback: without the library/GPU
 """
 import binascii
 
-from . import batch
+import os
+
+import numpy as np
+
+from . import _native, batch
 
 crypto_sign_PUBLICKEYBYTES = 32
 crypto_sign_BYTES = 64
+crypto_sign_SEEDBYTES = 32
+crypto_sign_SECRETKEYBYTES = 64
+
+
+def randombytes(size):
+    return os.urandom(size)
 
 
 class RawEncoder:
@@ -56,6 +77,43 @@ def crypto_sign_open(sm, vk):
     return sm[crypto_sign_BYTES:]
 
 
+def crypto_sign_seed_keypair(seed):
+    """libnacl.crypto_sign_seed_keypair: (public key, 64-byte secret key = seed || public key)."""
+    if len(seed) != crypto_sign_SEEDBYTES:
+        raise ValueError('Invalid Seed')
+    pks, sks = _native.seed_keypairs(np.frombuffer(bytes(seed), np.uint8))
+    return pks.tobytes(), sks.tobytes()
+
+
+def crypto_sign(msg, sk):
+    """libnacl.crypto_sign: the 64-byte signature followed by the message."""
+    if len(sk) != crypto_sign_SECRETKEYBYTES:
+        raise ValueError('Invalid secret key')
+    msg = bytes(msg)
+    sig = _native.sign_batch(np.frombuffer(msg or b"\0", np.uint8), np.array([0, len(msg)], np.uint64),
+                             np.frombuffer(bytes(sk), np.uint8))
+    return sig.tobytes() + msg
+
+
+class SignedMessage(bytes):
+    """The signed message (signature + message) with its two parts."""
+
+    @classmethod
+    def _from_parts(cls, signature, message, combined):
+        obj = cls(combined)
+        obj._signature = signature
+        obj._message = message
+        return obj
+
+    @property
+    def signature(self):
+        return self._signature
+
+    @property
+    def message(self):
+        return self._message
+
+
 class VerifyKey(Encodable):
     def __init__(self, key, encoder=RawEncoder):
         key = encoder.decode(key)
@@ -71,6 +129,54 @@ class VerifyKey(Encodable):
             smessage = signature + smessage
         smessage = encoder.decode(smessage)
         return crypto_sign_open(smessage, self._key)
+
+
+class SigningKey(Encodable):
+    def __init__(self, seed, encoder=RawEncoder):
+        seed = encoder.decode(seed)
+        if len(seed) != crypto_sign_SEEDBYTES:
+            raise ValueError("The seed must be exactly %d bytes long" % crypto_sign_SEEDBYTES)
+        public_key, secret_key = crypto_sign_seed_keypair(seed)
+        self._seed = seed
+        self._signing_key = secret_key
+        self.verify_key = VerifyKey(public_key)
+
+    def __bytes__(self):
+        return self._seed
+
+    @classmethod
+    def generate(cls):
+        return cls(randombytes(crypto_sign_SEEDBYTES), encoder=RawEncoder)
+
+    def sign(self, message, encoder=RawEncoder):
+        raw_signed = crypto_sign(message, self._signing_key)
+        signature = encoder.encode(raw_signed[:crypto_sign_BYTES])
+        message = encoder.encode(raw_signed[crypto_sign_BYTES:])
+        signed = encoder.encode(raw_signed)
+        return SignedMessage._from_parts(signature, message, signed)
+
+
+class Signer:
+    def __init__(self, key=None):
+        if key:
+            if not isinstance(key, SigningKey):  # a seed, raw or hex
+                if len(key) == 32:
+                    key = SigningKey(seed=key, encoder=RawEncoder)
+                else:
+                    key = SigningKey(seed=key, encoder=HexEncoder)
+        else:
+            key = SigningKey.generate()
+        self.key = key
+        self.keyhex = self.key.encode(HexEncoder)  # the seed
+        self.keyraw = self.key.encode(RawEncoder)
+        self.verhex = self.key.verify_key.encode(HexEncoder)
+        self.verraw = self.key.verify_key.encode(RawEncoder)
+
+    def sign(self, msg):
+        return self.key.sign(msg)
+
+    def signature(self, msg):
+        return self.key.sign(msg).signature
 
 
 class Verifier:
