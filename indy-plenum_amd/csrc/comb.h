@@ -191,52 +191,18 @@ PV_HD void pv_sel_pm(fe& ypx, fe& ymx, const uint32_t w[20], bool neg) {
     }
 }
 
-// acc + sign(e) T[|e|] for a cached-form table entry (pv_add_a's arithmetic, entry via `load`).
-template <class Entry>
-PV_HD void pv_comb_add_cached(ge_p1p1& r, const ge_p3& p, const Entry& ent, int e) {
-    const int j = e < 0 ? -e : e;
-    const bool neg = e < 0;
-    fe ypx, ymx, t, a, b, c, d;
-    uint32_t w[20];
-    ent.load_half(j, 0, w);
-    pv_sel_pm(ypx, ymx, w, neg);
-    fe_sub(t, p.Y, p.X);
-    fe_mul(a, t, ymx);
-    fe_add(t, p.Y, p.X);
-    fe_mul(b, t, ypx);
-    fe z2, t2d;
-    ent.load_half(j, 1, w);
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-        z2.v[i] = w[i];
-        t2d.v[i] = w[10 + i];
-    }
-    fe_cneg(t2d, t2d, neg);
-    fe_mul(c, p.T, t2d);
-    fe_mul(d, p.Z, z2);
-    fe_sub(r.X, b, a);
-    fe_add(r.Y, b, a);
-    fe_add(r.Z, d, c);
-    fe_sub(r.T, d, c);
-}
-
 // The two halves of a comb verification, split so that [S]B (which needs only the fixed-base table)
 // can run while the per-key tables are still being built:
-//   pv_comb_b_acc:  acc = [S]B = sum_j T_B[j][f_j]          16 niels additions, extended result
-//   pv_comb_a_xyz:  Q = acc + sum_i T_A[i][e_i]              32 cached additions, projective result
-// arows.row(i) / brows.row(j) give the A row of radix-256 position i and the B row of radix-65536
-// position j (objects with load_half / load_part); dig holds the packed digits (ek: 4 signed bytes
-// of k per word, fs: 2 signed halfwords of S per word).
-
-// Software-pipelined variant (PV_COMB_PIPELINE): a table entry is a dependent load (digit ->
-// address) from L2 / Infinity Cache / HBM, so each addition starts the fetch of the NEXT addition's
+//   pv_comb_b_acc_staged:  acc = [S]B = sum_j T_B[j][f_j]      16 niels additions, extended result
+//   pv_comb_a_xyz_staged:  Q = acc + sum_i T_A[i][e_i]          32 cached additions, projective result
+// dig holds the packed digits (ek: 4 signed bytes of k per word, fs: 2 signed halfwords of S per word).
+//
+// Both are software-pipelined: a table entry is a dependent load (digit -> address) from L2 /
+// Infinity Cache / HBM, so each addition starts the fetch of the NEXT addition's
 // entry as soon as it has read its own: `st.stage(row, d)` starts fetching entry d of a row into the
 // lane's staging buffer (on the device: LDS-DMA, no VGPRs held while in flight), `st.staged(part, w)`
 // reads part of the staged entry back (A: halves of 20 words; B: 20 words, then 10). The fetch of
 // entry i - 1 is in flight during the last two multiplications of addition i and its p1p1 -> p3.
-#ifndef PV_COMB_PIPELINE
-#define PV_COMB_PIPELINE 1
-#endif
 template <class BStage, class Dig>
 PV_HD void pv_comb_b_acc_staged(ge_p3& acc, const BStage& st, const Dig& dig) {
     ge_p3_identity(acc);
@@ -404,45 +370,12 @@ struct PvRowsStageB {
     PV_HD void staged(int part, uint32_t w[20]) const { rows.row(row_i).load_part(ent, part, w); }
 };
 
-template <class BRows, class Dig>
-PV_HD void pv_comb_b_acc(ge_p3& acc, const BRows& brows, const Dig& dig) {
-    ge_p3_identity(acc);
-    ge_p1p1 t;
-    uint32_t fw = 0;
-    for (int j = PV_BCOMB_POS - 1; j >= 0; j--) {
-        if ((j & 1) == 1) fw = dig.fs(j >> 1);
-        pv_add_b(t, acc, brows.row(j), pv_half(fw, j));
-        ge_niels_p1p1_to_p3(acc, t);
-    }
-}
-
-template <class ARows, class Dig>
-PV_HD void pv_comb_a_xyz(fe& X, fe& Y, fe& Z, const ge_p3& accB, const ARows& arows, const Dig& dig) {
-    ge_p3 acc = accB;
-    ge_p1p1 t;
-    uint32_t ew = 0;
-    for (int i = PV_COMB_POS - 1; i >= 0; i--) {
-        if ((i & 3) == 3) ew = dig.ek(i >> 2);
-        pv_comb_add_cached(t, acc, arows.row(i), pv_byte(ew, i));
-        if (i > 0) {
-            ge_p1p1_to_p3(acc, t);
-        } else {
-            ge_p1p1_to_p2(X, Y, Z, t);
-        }
-    }
-}
-
 // Q = [S]B + [k](-A) from the comb tables (both halves in one call: host tests).
 template <class ARows, class BRows, class Dig>
 PV_HD void pv_comb_xyz(fe& X, fe& Y, fe& Z, const ARows& arows, const BRows& brows, const Dig& dig) {
     ge_p3 acc;
-#if PV_COMB_PIPELINE
     pv_comb_b_acc_staged(acc, PvRowsStageB<BRows>{brows, 0, 0}, dig);
     pv_comb_a_xyz_staged(X, Y, Z, acc, PvRowsStageA<ARows>{arows, 0, 0}, dig);
-#else
-    pv_comb_b_acc(acc, brows, dig);
-    pv_comb_a_xyz(X, Y, Z, acc, arows, dig);
-#endif
 }
 
 // ---------------------------------------------------------------- wide fixed-base comb

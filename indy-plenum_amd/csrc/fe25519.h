@@ -10,7 +10,7 @@
 // v_mad_u64_u32 chain whose accumulator starts at the carry out of column k-1, so carrying costs
 // one v_lshrrev_b64 + one v_and_b32 per limb and no separate 64-bit adds. The wrapped products
 // use 19*g (computed once per operand by the caller when it is shared, fe_mul_pre) and odd x odd
-// products use 2*f. Each column stays a single v_mad_u64_u32 chain on the device (PV_MAD_CHAIN
+// products use 2*f. Each column stays a single v_mad_u64_u32 chain on the device (pv_madcol
 // below).
 //
 // Bound discipline (asserted by the PV_BOUNDS_CHECK host build, tests/test_native_host.py):
@@ -64,24 +64,13 @@ PV_HD void fe_check_reduced(const fe& f) {
 
 // ------------------------------------------------------------------ VALU primitives
 // acc + a*b (64-bit) and a*b: one v_mad_u64_u32 each on the device.
-// PV_MAD_CHAIN: each product-scanning column stays ONE chain of v_mad_u64_u32 (the accumulator of
-// every mad is the previous mad's result). Left alone, the compiler re-associates a column into two
-// chains joined by a v_lshl_add_u64 (one extra 4-cycle VOP3 per column, ~80 per point addition); an
-// empty non-volatile asm on each partial sum hides the algebra from it without emitting anything or
-// constraining the schedule beyond the data dependence. (PV_MAD_ASM: the mad itself as inline asm,
-// kept for comparison: hipcc then pads the opaque instructions with hazard s_nops.)
-#ifndef PV_MAD_CHAIN
-#define PV_MAD_CHAIN 1
-#endif
-#ifndef PV_MAD_ASM
-#define PV_MAD_ASM 0
-#endif
+// A chain of mad64 stays ONE chain of v_mad_u64_u32 (the accumulator of every mad is the previous
+// mad's result). Left alone, the compiler re-associates a column into two chains joined by a
+// v_lshl_add_u64 (one extra 4-cycle VOP3 per column, ~80 per point addition); an empty non-volatile
+// asm on each partial sum hides the algebra from it without emitting anything or constraining the
+// schedule beyond the data dependence.
 PV_HD uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
-#if defined(__HIP_DEVICE_COMPILE__) && PV_MAD_ASM
-    uint64_t r, cc;
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(r), "=s"(cc) : "v"(a), "v"(b), "v"(c));
-    return r;
-#elif defined(__HIP_DEVICE_COMPILE__) && PV_MAD_CHAIN
+#if defined(__HIP_DEVICE_COMPILE__)
     uint64_t r = (uint64_t)a * b + c;
     asm("" : "+v"(r));
     return r;
@@ -90,14 +79,11 @@ PV_HD uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
 #endif
 }
 PV_HD uint64_t mul64(uint32_t a, uint32_t b) { return (uint64_t)a * b; }
-// PV_MAD_COLASM: each product-scanning column is ONE inline-asm block of N dependent
-// v_mad_u64_u32 (accumulator in place). The per-mad empty asm of PV_MAD_CHAIN keeps the chain but
+// On the device each product-scanning column of fe_mul / fe_sq is ONE inline-asm block of N dependent
+// v_mad_u64_u32 (accumulator in place). The per-mad empty asm of mad64 keeps the chain but
 // the hazard recognizer cannot see through inline asm and pads EVERY mad that follows one with an
 // `s_nop 0` (it assumes the asm may have been a transcendental op writing the VGPR: ~100 s_nop per
 // field multiplication). A whole column per block leaves at most one pad per column. Device only.
-#ifndef PV_MAD_COLASM
-#define PV_MAD_COLASM 1
-#endif
 #define PV_MA(a, b) "v_mad_u64_u32 %0, %1, %" #a ", %" #b ", %0\n\t"
 #define PV_M0(a, b) "v_mad_u64_u32 %0, %1, %" #a ", %" #b ", 0\n\t"
 // acc (+)= sum_i a[i] * b[i], N terms; FIRST: acc starts at 0 (the first mad adds the constant 0)
@@ -140,15 +126,6 @@ __device__ __forceinline__ void pv_madcol(uint64_t& acc, const uint32_t* a, cons
 #undef PV_MA
 #undef PV_M0
 
-// Opaque copy: stops the compiler from re-associating a column sum so that the carry from the
-// previous column is added by a separate v_lshl_add_u64 instead of entering the first
-// v_mad_u64_u32 of the column as its accumulator (no instruction is emitted).
-PV_HD uint64_t pv_opaque64(uint64_t x) {
-#if defined(__HIP_DEVICE_COMPILE__) && !PV_MAD_ASM && !PV_MAD_CHAIN
-    asm volatile("" : "+v"(x));
-#endif
-    return x;
-}
 // 2x as a VOP2 add (2 cycles per wave64 instruction) rather than the VOP3-rate shift the compiler
 // picks for x << 1.
 PV_HD uint32_t dbl32(uint32_t x) {
@@ -283,15 +260,12 @@ PV_HD void fe_mul_pre(fe& hout, const fe& f, const fe& g, const uint32_t g19[10]
             ca[i] = a;
             cb[i] = b;
         }
-#if defined(__HIP_DEVICE_COMPILE__) && PV_MAD_COLASM
+#if defined(__HIP_DEVICE_COMPILE__)
         if (k == 0) pv_madcol<10, true>(acc, ca, cb);
         else pv_madcol<10, false>(acc, ca, cb);
 #else
 #pragma unroll
-        for (int i = 0; i < 10; i++) {
-            acc = (k == 0 && i == 0) ? mul64(ca[i], cb[i]) : mad64(ca[i], cb[i], acc);
-            if (i == 0 && k > 0) acc = pv_opaque64(acc);
-        }
+        for (int i = 0; i < 10; i++) acc = (k == 0 && i == 0) ? mul64(ca[i], cb[i]) : mad64(ca[i], cb[i], acc);
 #endif
 #ifdef PV_BOUNDS_CHECK
         if (k > 0) col128[k] += col128[k - 1] >> ((k & 1) ? 26 : 25);
@@ -349,16 +323,13 @@ PV_HD void fe_sq(fe& hout, const fe& f) {
             }
         }
         // even columns have 6 terms, odd columns 5
-#if defined(__HIP_DEVICE_COMPILE__) && PV_MAD_COLASM
+#if defined(__HIP_DEVICE_COMPILE__)
         if (k == 0) pv_madcol<6, true>(acc, ca, cb);
         else if (k & 1) pv_madcol<5, false>(acc, ca, cb);
         else pv_madcol<6, false>(acc, ca, cb);
 #else
 #pragma unroll
-        for (int t = 0; t < 6 - (k & 1); t++) {
-            acc = (k == 0 && t == 0) ? mul64(ca[t], cb[t]) : mad64(ca[t], cb[t], acc);
-            if (t == 0 && k > 0) acc = pv_opaque64(acc);
-        }
+        for (int t = 0; t < 6 - (k & 1); t++) acc = (k == 0 && t == 0) ? mul64(ca[t], cb[t]) : mad64(ca[t], cb[t], acc);
 #endif
 #ifdef PV_BOUNDS_CHECK
         if (k > 0) col128[k] += col128[k - 1] >> ((k & 1) ? 26 : 25);

@@ -906,13 +906,9 @@ LP_FN bool lp_t_small(const LpLane& c, const lu& st) {
     return lp_ballot(bad) == 0;
 }
 
-// PV_LP_SPLIT_53 = 1: a Lehmer block reads 53 leading bits (exact doubles), takes one division per
-// quotient and accepts it under Jebelean's conditions (~25 bits per block: ~5 blocks); 0: sc_halfsize's
-// 31-bit blocks with Knuth's two-division test (~9 blocks). Both settle only true quotients, so both
-// give sc_halfsize's split.
-#ifndef PV_LP_SPLIT_53
-#define PV_LP_SPLIT_53 1
-#endif
+// A Lehmer block reads 53 leading bits (exact doubles), takes one division per quotient and accepts it
+// under Jebelean's conditions (~25 bits per block: ~5 blocks). Only true quotients are settled, so the
+// result is sc_halfsize's split.
 // 1 / x to 1 ulp (v_rcp_f32 on the device)
 LP_FN float lp_rcpf(float x) {
 #if LP_DEVICE
@@ -942,7 +938,6 @@ LP_FN void lp_halfsize(const LpLane& c, pv_halfk& h, const uint32_t k[8], uint32
         if (stats) stats[0]++;
         LP_SPLIT_MARK(0);
         const int w = 31 - __builtin_clz((uint32_t)nz & 0x1FFu);  // >= 4 (r0 > r1 >= 2^131)
-#if PV_LP_SPLIT_53
         // 53 leading bits of r0 (2^52 <= xh < 2^53) and r1 at the same shift e, exact in doubles
         const uint32_t a1 = lp_readlane(st, w), a0 = lp_readlane(st, w - 1), a2 = lp_readlane(st, w - 2);
         const uint32_t b1 = lp_readlane(st, 16 + w), b0 = lp_readlane(st, 15 + w), b2 = lp_readlane(st, 14 + w);
@@ -994,34 +989,6 @@ LP_FN void lp_halfsize(const LpLane& c, pv_halfk& h, const uint32_t k[8], uint32
         // even row (P, -N), odd row (-N, P); n even: (A, B) even, (C, D) odd; n odd: the reverse
         const double A = (n & 1) ? -No : Pe, B = (n & 1) ? Po : -Ne;
         const double C = (n & 1) ? Pe : -No, D = (n & 1) ? -Ne : Po;
-#else
-        const uint32_t a1 = lp_readlane(st, w), a0 = lp_readlane(st, w - 1);
-        const uint32_t b1 = lp_readlane(st, 16 + w), b0 = lp_readlane(st, 15 + w);
-        const int sh = 33 - (int)__builtin_clz(a1);
-        const int s = sh > 0 ? sh : 0;
-        int32_t xh = (int32_t)((((uint64_t)a1 << 32) | a0) >> s);
-        int32_t yh = (int32_t)((((uint64_t)b1 << 32) | b0) >> s);
-        const int e = 32 * (w - 1) + s;
-        const int32_t ythr = e >= 130 ? 1 : (int32_t)(1u << (130 - e));
-        int32_t A = 1, B = 0, C = 0, D = 1;
-        for (int it = 0; it < 24; it++) {
-            const int32_t n1 = xh + A, d1 = yh + C, n2 = xh + B, d2 = yh + D;
-            bool ok1, ok2;
-            const uint32_t q = pv_qdiv31(n1, d1, ok1);
-            const uint32_t q2 = pv_qdiv31(n2, d2, ok2);
-            if (!ok1 || !ok2 || q != q2) break;
-            const int64_t ny = (int64_t)xh - (int64_t)q * yh;
-            const int64_t nC = (int64_t)A - (int64_t)q * C, nD = (int64_t)B - (int64_t)q * D;
-            if (ny < ythr || nC >= 32768 || nC <= -32768 || nD >= 32768 || nD <= -32768) break;
-            A = C;
-            C = (int32_t)nC;
-            B = D;
-            D = (int32_t)nD;
-            xh = yh;
-            yh = (int32_t)ny;
-            if (stats) stats[1]++;
-        }
-#endif
         LP_SPLIT_MARK(1);
         if (B == 0) {
             // one exact step: q from the top three words, then fixed by whole additions of r0

@@ -7,6 +7,10 @@
 //
 // Replaces (per request) stp_core/crypto/nacl_wrappers.py:108 libnacl.crypto_sign_open(sm, pk);
 // see include/plenum_verify.h for the ABI contract and verify_core.h for the arithmetic.
+//
+// The #ifndef switches in this file are numeric tuning constants (microbench/build_variants.sh varies
+// them) and diagnostic builds. The kernel forms, priorities and stream layouts that lost their A/B are
+// not in the source any more: DESIGN.md, "Variants tried and retired", has each one's result.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <stdint.h>
@@ -39,11 +43,6 @@
 #include "../../include/plenum_verify_test.h"
 
 static constexpr int PV_BLOCK = 256;
-#ifndef PV_CHAIN_MODE
-// per-key chain kernel: 2 = limb-parallel, one wave per key (pv_key_chain_lp_kernel); 1 = four lanes
-// per key (pv_key_chain_quad_kernel, round 1); 0 = one lane per key (pv_key_chain_kernel)
-#define PV_CHAIN_MODE 2
-#endif
 // an integer from the environment (A/B knobs read once at first use), or dflt
 static int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
@@ -56,33 +55,14 @@ static int env_int(const char* name, int dflt) {
 #ifndef PV_FILL_MINBLOCKS
 #define PV_FILL_MINBLOCKS 2
 #endif
-// [S]B of a keyed chunk per request from the chunk's start, beside the dedup (A/B knob, off): the
-// dedup's atomics slow 2-4x under it and the headline gains nothing measurable; config 3 loses
-// 0.1 ms (profiles/r03/half/ab_comb_b_early)
-#ifndef PV_ZERO_COPY  // small latency-path host-buffer calls read the pinned staging buffer in place
-#define PV_ZERO_COPY 1
-#endif
-#ifndef PV_ZC_SPIN  // ... and the host spins on their verdict bytes instead of a stream sync
-#define PV_ZC_SPIN 1
-#endif
-#ifndef PV_COMB_B_EARLY
-#define PV_COMB_B_EARLY 0
-#endif
-#ifndef PV_ATAB_NT  // per-request Straus tables read with the streaming (evict-first) cache policy
-#define PV_ATAB_NT 0
-#endif
-#ifndef PV_SIDE_PRIO
-#define PV_SIDE_PRIO 0
-#endif
 #ifndef PV_MSM_MINBLOCKS
-// workgroups per CU the msm kernel's register budget is sized for (3: <= 168 VGPRs, 3 waves/SIMD; the
-// full-length loop fits that at 2 as well)
+// workgroups per CU the msm kernel's register budget is sized for (3: <= 168 VGPRs, 3 waves/SIMD)
 #define PV_MSM_MINBLOCKS 3
 #endif
 #ifndef PV_PREP_MINBLOCKS
 #define PV_PREP_MINBLOCKS 2  // Straus prep (decompression + SHA-512 + recoding)
 #endif
-// Dynamic LDS requested by every pv_comb_prep_kernel workgroup, unused: it caps the kernel's residency
+// Dynamic LDS requested by every pv_comb_prep_req_kernel workgroup, unused: it caps the kernel's residency
 // so that the key chain, launched beside it on the key stream, finds a wave slot on every SIMD at
 // once instead of waiting for prep workgroups to retire (env PV_PREP_LDS_PAD overrides at pv_init).
 // 41,984 B: 3 workgroups per CU (126 KB of the 160 KB), 3 prep waves per SIMD leave the chain's wave a
@@ -106,7 +86,7 @@ static constexpr uint32_t PV_XT_KEYS = 2048;      // tables shared by a pipeline
 static constexpr uint32_t PV_XT_HASH = 4096;      // their hash table (>= 2 x keys)
 // An all-comb chunk of at most PV_SPARSE_CHUNK requests and at most PV_SPARSE_PER_KEY requests per key
 // on average builds only the table entries its digits use (comb.h pv_comb_fill_sparse; the need
-// masks are set by pv_comb_prep_kernel). A/B on MI355X (1,024 signers, device time,
+// masks are set by pv_comb_prep_req_kernel). A/B on MI355X (1,024 signers, device time,
 // profiles/r02/ab_sparse_fill.txt): 6k requests 0.71 -> 0.54 ms, 10k 0.70 -> 0.56; at 32 requests
 // per key the per-position thread's serial additions outlast the parallel full fill (32k 0.69 ->
 // 0.72, 64k 0.74 -> 0.89), hence the per-key bound.
@@ -116,17 +96,6 @@ static constexpr uint32_t PV_XT_HASH = 4096;      // their hash table (>= 2 x ke
 #ifndef PV_SPARSE_PER_KEY
 #define PV_SPARSE_PER_KEY 16
 #endif
-// Key chain launches per keyed chunk (the table fill of part p overlaps the chain of part p + 1).
-// A/B on MI355X (profiles/r02/ab_chain_parts.txt, interleaved): 1 part is best -- 10k requests
-// 0.70 ms device vs 0.74 (4 parts) / 0.92 (8), 1M 3.02 ms/step vs 3.04-3.11 / 3.15: the fill of a
-// part competes with the next chain part for the SIMDs and each part is a launch of its own.
-#ifndef PV_CHAIN_PARTS
-#define PV_CHAIN_PARTS 1
-#endif
-#ifndef PV_DIRECT_FILL  // large chunks: fill on the key stream right behind the chain (no fstream hop)
-#define PV_DIRECT_FILL 1
-#endif
-static_assert(32 % PV_CHAIN_PARTS == 0, "PV_CHAIN_PARTS must divide the 32 comb positions");
 #ifndef PV_LP_CHAIN_BLOCKS
 #define PV_LP_CHAIN_BLOCKS 2048  // waves of the limb-parallel key chain (one key each at a time)
 #endif
@@ -136,9 +105,6 @@ static_assert(32 % PV_CHAIN_PARTS == 0, "PV_CHAIN_PARTS must divide the 32 comb 
 // (+ 8 us seed) with the counters split 8 ways (16: 86, 32: 87 -- the assign kernel's sums grow).
 #ifndef PV_KEY_SEED
 #define PV_KEY_SEED 4096  // requests of a keyed chunk whose keys are inserted first (pv_key_seed_kernel)
-#endif
-#ifndef PV_INSERT_PLAIN_LOAD
-#define PV_INSERT_PLAIN_LOAD 1  // the insert's first slot read is a plain load (0: an atomic load)
 #endif
 // Per-key request counters of the dedup are split PV_RANK_SUB ways (sub-table = the request's
 // workgroup index mod PV_RANK_SUB), so the ~1,000 requests of a hot key queue on PV_RANK_SUB
@@ -157,13 +123,6 @@ static_assert((PV_RANK_SUB & (PV_RANK_SUB - 1)) == 0, "PV_RANK_SUB must be a pow
 #endif
 
 // ---------------------------------------------------------------------------------------- device
-
-// Row r of a [rows][S] structure-of-arrays buffer: a wave-uniform pointer (SGPRs), so each access
-// is one global_load/store with a 32-bit per-lane offset instead of a live 64-bit address per row.
-template <class T>
-__device__ __forceinline__ T* pv_row(T* base, uint32_t r, uint32_t S) {
-    return base + (size_t)r * S;
-}
 
 // [rows][S] u32 structure-of-arrays buffer through a buffer resource: every access is one
 // buffer_load/store_dword with the lane's 32-bit byte offset in a VGPR and the row offset in an
@@ -186,37 +145,21 @@ struct Soa {
 
 // Per-lane cached table of [j](-A) in HBM. Indices are 32-bit (chunk <= 2^20 slots, 90 quads per
 // slot < 2^32) so each access is a uniform 64-bit base plus one per-lane 32-bit offset instead of ten
-// live 64-bit addresses. Layout PV_ATAB_AOS = 1: [slot][entry][quad] uint4 -- the lanes of a wave pick
-// different entries (their own digits), so each lane reads its own contiguous 160 B entry (two
-// 128 B lines) instead of a 16 B piece of a line shared with lanes that want other entries
-// ([entry][quad][slot], PV_ATAB_AOS = 0: coalesced only when every lane has the same digit).
-#ifndef PV_ATAB_AOS
-#define PV_ATAB_AOS 1
-#endif
-// Half-size Straus path (sc25519.h sc_halfsize, verify_core.h pv_straus_ar_xyz): k = k1 / k2 (mod 8L)
-// with |k1|, k2 ~ 2^128, so the per-request loop runs ~33 windows of both scalars against two tables
-// ([j](+-A) and [j](-R')) instead of 64 windows of k against one. 0: the full-length loop over k.
-#ifndef PV_STRAUS_HALF
-#define PV_STRAUS_HALF 1
-#endif
-static constexpr uint32_t PV_ATAB_ENT = PV_STRAUS_HALF ? 18u : 9u;  // table entries per slot
-// half-size msm: table entries fetched one addition ahead into LDS (pv_straus_ar_xyz_staged)
-#ifndef PV_MSM_STAGED
-#define PV_MSM_STAGED 0
-#endif
+// live 64-bit addresses. Layout [slot][entry][quad] uint4 -- the lanes of a wave pick different entries
+// (their own digits), so each lane reads its own contiguous 160 B entry (two 128 B lines) instead of a
+// 16 B piece of a line shared with lanes that want other entries.
+// The Straus path is half-size (sc25519.h sc_halfsize, verify_core.h pv_straus_ar_xyz): k = k1 / k2
+// (mod 8L) with |k1|, k2 ~ 2^128, so the per-request loop runs ~33 windows of both scalars against two
+// tables ([j](+-A) and [j](-R')) instead of 64 windows of k against one.
+static constexpr uint32_t PV_ATAB_ENT = 18u;  // table entries per slot (9 of each table)
 struct DevATab {
     uint4* base;
-    uint32_t nslots;
     uint32_t slot;
     uint32_t t0 = 0;  // first entry of this table in the slot (the R table starts at 9)
     __device__ __forceinline__ uint4& at(int j, int q) const {
-#if PV_ATAB_AOS
         // [slot / 64][entry][slot % 64][quad]: a lane's entry is 160 contiguous bytes, and one wave's
         // ten stores of an entry cover 10 KB contiguously (full lines reach HBM)
         return base[(((slot >> 6) * PV_ATAB_ENT + t0 + (uint32_t)j) * 64u + (slot & 63u)) * 10u + (uint32_t)q];
-#else
-        return base[(uint32_t)((t0 + j) * 10 + q) * nslots + slot];
-#endif
     }
     __device__ __forceinline__ void store(int j, const uint32_t w[40]) const {
 #pragma unroll
@@ -247,13 +190,7 @@ struct DevATab {
     __device__ __forceinline__ void load_half(int j, int h, uint32_t w[20]) const {
 #pragma unroll
         for (int q = 0; q < 5; q++) {
-#if PV_ATAB_NT
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(&at(j, 5 * h + q)));
-            const uint4 v = make_uint4(t.x, t.y, t.z, t.w);
-#else
             const uint4 v = at(j, 5 * h + q);
-#endif
             w[4 * q] = v.x;
             w[4 * q + 1] = v.y;
             w[4 * q + 2] = v.z;
@@ -266,43 +203,9 @@ struct DevATab {
     }
 };
 
-struct LdsBTab {
-    const uint32_t* base;  // LDS
-    __device__ __forceinline__ void load_part(int j, int part, uint32_t w[20]) const {
-        const uint4* e = reinterpret_cast<const uint4*>(base + j * PV_BTAB_STRIDE + 20 * part);
-#pragma unroll
-        for (int i = 0; i < (part ? 3 : 5); i++) {
-            const uint4 v = e[i];
-            if (4 * i < (part ? 10 : 20)) w[4 * i] = v.x;
-            if (4 * i + 1 < (part ? 10 : 20)) w[4 * i + 1] = v.y;
-            if (4 * i + 2 < (part ? 10 : 20)) w[4 * i + 2] = v.z;
-            if (4 * i + 3 < (part ? 10 : 20)) w[4 * i + 3] = v.w;
-        }
-    }
-    __device__ __forceinline__ void load(int j, ge_niels& q) const {
-        const uint4* e = reinterpret_cast<const uint4*>(base + j * PV_BTAB_STRIDE);
-        uint32_t w[32];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const uint4 v = e[i];
-            w[4 * i] = v.x;
-            w[4 * i + 1] = v.y;
-            w[4 * i + 2] = v.z;
-            w[4 * i + 3] = v.w;
-        }
-#pragma unroll
-        for (int i = 0; i < 10; i++) {
-            q.yplusx.v[i] = w[i];
-            q.yminusx.v[i] = w[10 + i];
-            q.xy2d.v[i] = w[20 + i];
-        }
-    }
-};
-
-// Digit words of k (radix 16, rows 0..7) and S (radix 256, rows 8..15), one coalesced load each time
-// the Straus loop enters a new group of 8 windows.
-// digits rows: 0..7 k (both paths), 8.. S: 8 packed words (Straus, radix 256) or PV_BC2_POS signed
-// radix-2^W digits (comb path, wide fixed-base comb)
+// Digit rows, one coalesced load each time a loop enters a new group of windows. Rows 0..7: |k1|
+// (Straus path, radix 16) or k (comb path, radix 256); rows 8..: the signed radix-2^W digits of k2 S
+// (Straus) or S (comb) for the wide fixed-base comb.
 // Radix of the wide fixed-base comb chosen at pv_init: PV_BC2_W (24: 10.7 GB of HBM) or, when that
 // allocation fails (or PV_FORCE_BCOMB16 is set), W = 16 over the radix-65536 comb T_B the latency
 // path already holds (the same layout and digits: comb.h). Kernels that recode or read S's digits
@@ -313,10 +216,10 @@ struct Bc2 {
     static constexpr uint32_t ENT = (1u << (W - 1)) + 1u;
 };
 static_assert(Bc2<16>::ENT == PV_BCOMB_ENT && Bc2<16>::POS == PV_BCOMB_POS, "W = 16 is the radix-65536 comb");
-// half-size Straus path: rows PV_K2_ROW.. hold k2's radix-16 digits, row PV_NW_ROW the lane's window count
+// Straus path: rows PV_K2_ROW.. hold k2's radix-16 digits, row PV_NW_ROW the lane's window count
 static constexpr int PV_K2_ROW = 8 + (Bc2<16>::POS > PV_BC2_POS ? Bc2<16>::POS : PV_BC2_POS);
 static constexpr int PV_NW_ROW = PV_K2_ROW + 8;
-static constexpr int PV_DIGIT_ROWS = PV_STRAUS_HALF ? PV_NW_ROW + 1 : PV_K2_ROW;
+static constexpr int PV_DIGIT_ROWS = PV_NW_ROW + 1;
 struct DevDigits {
     Soa d;
     uint32_t slot;
@@ -325,7 +228,6 @@ struct DevDigits {
     __device__ __forceinline__ uint32_t ek(int q) const { return d.ld(q, slot); }
     __device__ __forceinline__ uint32_t ek2(int q) const { return d.ld(PV_K2_ROW + q, slot); }
     __device__ __forceinline__ uint32_t nw() const { return d.ld(PV_NW_ROW, slot); }
-    __device__ __forceinline__ uint32_t fs(int q) const { return d.ld(8 + q, slot); }
     __device__ __forceinline__ int fb(int j) const { return (int)d.ld(8 + j, slot); }
 };
 
@@ -342,10 +244,9 @@ struct DevMsg {
     }
 };
 
-// Per-request intermediate state between the two kernels (SoA, coalesced per wave):
-//   atab  [9 entries][10 quads][n] uint4   cached [j](-A), j = 0..8
-//   digits[PV_DIGIT_ROWS][n] uint32          radix-16 digits of k (8 words), radix-256 of S (8 words);
-//                                           comb path: radix-256 k, radix-2^W S (PV_BC2_POS words)
+// Per-request intermediate state between the kernels (SoA, coalesced per wave):
+//   atab  [n / 64][18][64][10] uint4        Straus path: cached [j](+-A) and [j](-R'), j = 0..8 (DevATab)
+//   digits[PV_DIGIT_ROWS][n] uint32          see DevDigits
 //   flags [n] uint32                        1 = every libsodium pre-check passed
 //   q     [40][n] uint32                    projective Q = (X, Y, Z) from the msm kernel (rows 0..29);
 //                                           the comb path's [S]B half parks an extended point here
@@ -354,7 +255,7 @@ struct Work {
     uint32_t* digits;
     uint32_t* flags;
     uint32_t* q;
-    uint4* qb;        // [S]B per REQUEST of a keyed chunk, 160 B each (pv_comb_b_req_kernel)
+    uint4* qb;        // not read by any kernel (kept: dropping it moves the kernel-argument layout)
     uint64_t stride;  // chunk capacity (requests)
     uint4* aos;       // per REQUEST comb-prep results, PrepAos<W>::Q uint4 each (pv_comb_prep_req_kernel)
 };
@@ -468,14 +369,10 @@ static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call'
 #define PV_COMB_MIN_REQ 48
 #endif
 
-// LDS-DMA staging of one table entry per lane (comb.h, PV_COMB_PIPELINE). An entry of Q uint4 is
+// LDS-DMA staging of one table entry per lane (comb.h, the staged comb loops). An entry of Q uint4 is
 // fetched by Q global_load_lds_dwordx4, each writing 1 KiB = 16 B x 64 lanes of the wave's staging
 // area, laid out [q][lane] so that reading it back is one conflict-free ds_read_b128 per q.
-__device__ __forceinline__ void pv_glds16(const uint4* g, uint4* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-// Q pieces of 16 B from g[0..Q) to l[q * 64 + lane] (a wave's [q][lane] staging area). The
+// pv_glds16_row: Q pieces of 16 B from g[0..Q) to l[q * 64 + lane] (a wave's [q][lane] staging area). The
 // instruction's immediate offset (16 q) applies to BOTH the global and the LDS address, so the LDS
 // base of piece q is moved back by the same 16 q bytes (M0 is set per instruction anyway): all Q
 // loads then share ONE 64-bit global address instead of Q 64-bit adds per staged entry.
@@ -503,7 +400,7 @@ __device__ __forceinline__ void pv_glds16_row10_skip56(const uint4* g, uint4* l,
 __device__ __forceinline__ void pv_lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Wide fixed-base comb rows (comb.h PV_BC2_*): row j = entries 0..PV_BC2_ENT-1 of [d 2^(W j)] B,
-// 8 uint4 each, LDS-staged like DevBStage; 64-bit entry index (the table is ~10.7 GB at W = 24).
+// 8 uint4 each, LDS-staged like DevCombStage; 64-bit entry index (the table is ~10.7 GB at W = 24).
 template <uint32_t ENT>
 struct DevB2Stage {
     const uint4* base;
@@ -527,38 +424,6 @@ struct DevB2Stage {
     }
 };
 
-#if PV_STRAUS_HALF
-// The half-size msm's per-lane tables (DevATab layout, tile-major): entry j of table t of slot i staged
-// into the wave's [10][64] area (pv_straus_ar_xyz_staged)
-struct DevATabStage {
-    uint4* base;
-    uint32_t slot;
-    uint4* lds;
-    uint32_t lane;
-    __device__ __forceinline__ void stage(int t, int j) const {
-        const uint4* e = &DevATab{base, 0u, slot, t ? 9u : 0u}.at(j, 0);
-        pv_lds_reads_done();
-        pv_glds16_row<10>(e, lds);
-    }
-    __device__ __forceinline__ void staged(int h, uint32_t w[20]) const {
-#pragma unroll
-        for (int q = 0; q < 5; q++) {
-            const uint4 v = lds[(5 * h + q) * 64 + lane];
-            w[4 * q] = v.x;
-            w[4 * q + 1] = v.y;
-            w[4 * q + 2] = v.z;
-            w[4 * q + 3] = v.w;
-        }
-    }
-};
-#endif
-// Straus path: [S]B from the wide fixed-base comb (pv_straus_b_kernel) and a Straus loop over k only
-// (pv_straus_a_xyz), instead of 32 B additions interleaved in the loop (LDS table of [j]B).
-#ifndef PV_STRAUS_WIDE_B
-#define PV_STRAUS_WIDE_B 1
-#endif
-static_assert(!PV_STRAUS_HALF || PV_STRAUS_WIDE_B, "the half-size path takes [k2 S]B from pv_straus_b_kernel");
-
 __device__ __forceinline__ void pv_load_pk(uint32_t A[8], const uint8_t* pk, uint32_t i) {
     const uint4* p4 = reinterpret_cast<const uint4*>(pk + 32 * (uint64_t)i);
     const uint4 a0 = p4[0], a1 = p4[1];
@@ -566,9 +431,8 @@ __device__ __forceinline__ void pv_load_pk(uint32_t A[8], const uint8_t* pk, uin
     A[4] = a1.x; A[5] = a1.y; A[6] = a1.z; A[7] = a1.w;
 }
 
-// Straus path, per slot i (request r): checks, decompression of A, k = SHA-512(R||A||M) mod L,
-// recoding; -A for the table kernel.
-template <int W>
+// Straus path, per slot i (request r): the signature checks, k = SHA-512(R||A||M) mod L, A's checks
+// and decompression; -A for the table kernel.
 __device__ __forceinline__ void pv_prep_slot(const uint8_t* __restrict__ sm, const uint64_t* __restrict__ off,
                                              const uint8_t* __restrict__ pk, const Work& wk, uint32_t i, uint32_t r) {
     const uint64_t o0 = off[r], o1 = off[r + 1];
@@ -585,93 +449,42 @@ __device__ __forceinline__ void pv_prep_slot(const uint8_t* __restrict__ sm, con
     const uint4 a0 = pk4[0], a1 = pk4[1];
     in.A[0] = a0.x; in.A[1] = a0.y; in.A[2] = a0.z; in.A[3] = a0.w;
     in.A[4] = a1.x; in.A[5] = a1.y; in.A[6] = a1.z; in.A[7] = a1.w;
-#if PV_STRAUS_HALF
-    {
-        // pv_prepare_half over three kernels: here the signature checks, k (to rows 0..7 for
-        // pv_split_kernel), A's checks and -A (table entry 1); the split of k and the digits in
-        // pv_split_kernel; the sign of k1 on -A, R's checks, -R' and both tables in pv_table_kernel
-        bool ok = pv_sig_ok(in, smlen);
-        const Soa ds(wk.digits, PV_DIGIT_ROWS, wk.stride);
-        {
-            uint32_t k[8];
-            pv_hash_k(k, in, smlen, mw);
-#pragma unroll
-            for (int q = 0; q < 8; q++) ds.st(q, (uint32_t)i, k[q]);
-        }
-        {
-            ge_p3 negA;
-            ok &= pv_key_ok_negate(negA, in.A);
-            const DevATab at{wk.atab, (uint32_t)wk.stride, (uint32_t)i};
-            at.store_p3(1, negA);
-        }
-        wk.flags[i] = ok ? 1u : 0u;
-        return;
-    }
-#endif
-
-    ge_p3 negA;
-    uint32_t k[8];
-    const bool ok = pv_prepare(negA, k, in, smlen, mw);
-    // -A goes to table slot 1 as an extended point; pv_table_kernel expands it to [j](-A)
-    uint32_t w[40];
-#pragma unroll
-    for (int q = 0; q < 10; q++) {
-        w[q] = negA.X.v[q];
-        w[10 + q] = negA.Y.v[q];
-        w[20 + q] = negA.Z.v[q];
-        w[30 + q] = negA.T.v[q];
-    }
-    const DevATab at{wk.atab, (uint32_t)wk.stride, (uint32_t)i};
-    at.store(1, w);
-    uint32_t ek[8];
-    sc_recode16(ek, k);
+    // pv_prepare_half over three kernels: here the signature checks, k (to rows 0..7 for
+    // pv_split_kernel), A's checks and -A (table entry 1); the split of k and the digits in
+    // pv_split_kernel; the sign of k1 on -A, R's checks, -R' and both tables in pv_table_kernel
+    bool ok = pv_sig_ok(in, smlen);
     const Soa ds(wk.digits, PV_DIGIT_ROWS, wk.stride);
+    {
+        uint32_t k[8];
+        pv_hash_k(k, in, smlen, mw);
 #pragma unroll
-    for (int q = 0; q < 8; q++) ds.st(q, (uint32_t)i, ek[q]);
-#if PV_STRAUS_WIDE_B
-    int32_t fb[Bc2<W>::POS];  // [S]B from the wide fixed-base comb (pv_straus_b_kernel)
-    sc_recode_w<W, Bc2<W>::POS>(fb, in.S);
-#pragma unroll
-    for (int j = 0; j < Bc2<W>::POS; j++) ds.st(8 + j, (uint32_t)i, (uint32_t)fb[j]);
-#else
-    uint32_t fs[8];
-    sc_recode256(fs, in.S);
-#pragma unroll
-    for (int q = 0; q < 8; q++) ds.st(8 + q, (uint32_t)i, fs[q]);
-#endif
+        for (int q = 0; q < 8; q++) ds.st(q, (uint32_t)i, k[q]);
+    }
+    {
+        ge_p3 negA;
+        ok &= pv_key_ok_negate(negA, in.A);
+        const DevATab at{wk.atab, (uint32_t)i};
+        at.store_p3(1, negA);
+    }
     wk.flags[i] = ok ? 1u : 0u;
 }
 
-// Optional wave priority (s_setprio) for the Straus-path kernels, which in a split chunk run on
-// their own stream beside the comb kernels. A/B on config 3 (tools/ab_config3.sh,
-// profiles/r02/ab_straus_prio.txt): priority 3 shortens the wait for the Straus side (msm stage
-// 1.55 -> 1.45 ms) but slows the key stream's table fill more (0.92 -> 1.07 ms): off by default.
-#ifndef PV_STRAUS_PRIO
-#define PV_STRAUS_PRIO 0
-#endif
-__device__ __forceinline__ void pv_straus_prio() {
-#if PV_STRAUS_PRIO > 0
-    __builtin_amdgcn_s_setprio(PV_STRAUS_PRIO);
-#endif
-}
-
-// Kernel 1 (Straus path): pv_prep_slot over the Straus slots.
+// Kernel 1 (Straus path): pv_prep_slot over the Straus slots. Its two instantiations are the same code
+// (the wide comb's digits are written by pv_split_kernel); both names are launched.
 template <int W>
 __global__ __launch_bounds__(PV_BLOCK, PV_PREP_MINBLOCKS) void pv_prep_kernel(const uint8_t* __restrict__ sm,
                                                                const uint64_t* __restrict__ off, uint64_t n,
                                                                const uint8_t* __restrict__ pk, Work wk, Gate gate) {
     if (gate.off()) return;
-    pv_straus_prio();
     const uint32_t nc = gate.ncomb(), ntiles = (uint32_t)((n + PV_BLOCK - 1) / PV_BLOCK);
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const uint32_t sb = gate.stile(t, ntiles);
         if ((sb + 1) * PV_BLOCK <= nc) break;  // this and every later tile: comb-path slots
         const uint32_t i = sb * PV_BLOCK + threadIdx.x;  // slot
-        if (i < n && i >= nc) pv_prep_slot<W>(sm, off, pk, wk, i, gate.req(i));
+        if (i < n && i >= nc) pv_prep_slot(sm, off, pk, wk, i, gate.req(i));
     }
 }
 
-#if PV_STRAUS_HALF
 // Kernel 1a (half-size path): the split k = k1 / k2 (mod 8L) of each Straus slot's k (rows 0..7, from
 // pv_prep_kernel), s2 = k2 S mod L; writes the digits of |k1| (rows 0..7), k2 (PV_K2_ROW..), the window
 // count and k1's sign (row PV_NW_ROW: nw | neg << 8) and the wide-comb digits of s2 (rows 8..). Its own
@@ -681,7 +494,6 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_split_kernel(const uint8_t* __res
                                                             const uint64_t* __restrict__ off, uint64_t n, Work wk,
                                                             Gate gate) {
     if (gate.off()) return;
-    pv_straus_prio();
     const uint32_t nc = gate.ncomb(), ntiles = (uint32_t)((n + PV_BLOCK - 1) / PV_BLOCK);
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const uint32_t sb = gate.stile(t, ntiles);
@@ -718,10 +530,9 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_split_kernel(const uint8_t* __res
         ds.st(PV_NW_ROW, i, (uint32_t)(nw1 > nw2 ? nw1 : nw2) | (hk.neg ? 0x100u : 0u));
     }
 }
-#endif
 
-// Kernel 1b: the cached table [j](-A), j = 0..8 (full-length path: -A from entry 1); half-size path:
-// decompression and checks of A and R, tables [j](+-A) (entries 0..8) and [j](-R') (entries 9..17).
+// Kernel 1b: decompression and checks of R, the cached tables [j](+-A) (entries 0..8, from -A in
+// entry 1) and [j](-R') (entries 9..17).
 #ifndef PV_TABLE_MINBLOCKS
 #define PV_TABLE_MINBLOCKS 2  // waves per SIMD (256 VGPRs; 3 spills 264 B)
 #endif
@@ -729,21 +540,19 @@ __global__ __launch_bounds__(PV_BLOCK, PV_TABLE_MINBLOCKS) void pv_table_kernel(
                                                                 const uint64_t* __restrict__ off, uint64_t n,
                                                                 const uint8_t* __restrict__ pk, Work wk, Gate gate) {
     if (gate.off()) return;
-    pv_straus_prio();
     const uint32_t nc = gate.ncomb(), ntiles = (uint32_t)((n + PV_BLOCK - 1) / PV_BLOCK);
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const uint32_t sb = gate.stile(t, ntiles);
         if ((sb + 1) * PV_BLOCK <= nc) break;
         const uint32_t i = sb * PV_BLOCK + threadIdx.x;  // slot
         if (i >= n || i < nc) continue;
-#if PV_STRAUS_HALF
         // [j](+-A) from -A (entry 1, pv_prep_kernel) and k1's sign (pv_split_kernel), then R's
         // canonical-decoding rule and [j](-R')
         const uint32_t r = gate.req(i);
         const uint64_t raddr = reinterpret_cast<uint64_t>(sm + off[r]);
         const DevMsg mw{reinterpret_cast<const uint32_t*>(raddr & ~3ull), (uint32_t)(raddr & 3)};
         {
-            DevATab at{wk.atab, (uint32_t)wk.stride, i};
+            DevATab at{wk.atab, i};
             ge_p3 PA;
             at.load_p3(1, PA);
             ge_p3_cneg(PA, (Soa(wk.digits, PV_DIGIT_ROWS, wk.stride).ld(PV_NW_ROW, i) & 0x100u) != 0);  // +-A
@@ -756,38 +565,17 @@ __global__ __launch_bounds__(PV_BLOCK, PV_TABLE_MINBLOCKS) void pv_table_kernel(
             for (int q = 0; q < 8; q++) R[q] = mw.dw(q);
             ge_p3 negR;
             ok = pv_r_decode_negate(negR, R);
-            DevATab rt{wk.atab, (uint32_t)wk.stride, i, 9u};
+            DevATab rt{wk.atab, i, 9u};
             pv_build_a_table(rt, negR);
         }
         if (!ok) wk.flags[i] = 0u;
-#else
-        const DevATab at{wk.atab, (uint32_t)wk.stride, i};
-        uint32_t w[40];
-        at.load(1, w);
-        ge_p3 negA;
-#pragma unroll
-        for (int q = 0; q < 10; q++) {
-            negA.X.v[q] = w[q];
-            negA.Y.v[q] = w[10 + q];
-            negA.Z.v[q] = w[20 + q];
-            negA.T.v[q] = w[30 + q];
-        }
-        pv_build_a_table(at, negA);
-#endif
     }
 }
 
-// Kernel 2: Q = [S]B + [k](-A) by the regular-window Straus loop, encode, compare with R, ballot.
-// PV_MSM_FUSED_B: [k2 S]B is added inside the loop's epilogue (the wide comb's niels additions straight
-// into the loop's point, entries LDS-staged one addition ahead) instead of pv_straus_b_kernel writing it
-// to q for the epilogue to read
-#ifndef PV_MSM_FUSED_B
-#define PV_MSM_FUSED_B 1
-#endif
-// PV_MSM_SORT: the msm kernel regroups each 256-slot tile's lanes by window count (below)
-#ifndef PV_MSM_SORT
-#define PV_MSM_SORT 1
-#endif
+// Kernel 2: Q = [k2 S]B + [k1](+-A) + [k2](-R') by the regular-window Straus loop over both half-size
+// scalars. [k2 S]B is added inside the loop's epilogue (the wide comb's niels additions straight into
+// the loop's point, entries LDS-staged one addition ahead), and each 256-slot tile's lanes are
+// regrouped by window count first (below). btab_g is not read.
 static constexpr int PV_MSM_SORT_CLS = 8;
 template <int W>
 __global__ __launch_bounds__(PV_BLOCK, PV_MSM_MINBLOCKS) void pv_msm_kernel(const uint8_t* __restrict__ sm,
@@ -798,33 +586,14 @@ __global__ __launch_bounds__(PV_BLOCK, PV_MSM_MINBLOCKS) void pv_msm_kernel(cons
     const uint32_t nc = gate.ncomb(), ntiles = (uint32_t)((n + PV_BLOCK - 1) / PV_BLOCK);
     // nothing for this block (or no Straus slot at all): leave before the LDS fill
     if (blockIdx.x >= ntiles || nc >= n || (gate.stile(blockIdx.x, ntiles) + 1) * PV_BLOCK <= nc) return;
-    pv_straus_prio();
-#if PV_STRAUS_HALF && PV_MSM_STAGED
-    __shared__ uint4 stg[PV_BLOCK / 64][10][64];
-    uint4* stg_wave = &stg[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)][0][0];
-#endif
-#if PV_STRAUS_HALF && PV_MSM_SORT
     __shared__ uint32_t s_wcnt[PV_BLOCK / 64][PV_MSM_SORT_CLS];
     __shared__ uint16_t s_perm[PV_BLOCK];
-#endif
-#if PV_STRAUS_HALF && PV_MSM_FUSED_B && !PV_MSM_STAGED
     __shared__ uint4 stgb[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
     uint4* stgb_wave = &stgb[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)][0][0];
-#else
-    (void)bcomb;
-#endif
-#if !PV_STRAUS_WIDE_B
-    __shared__ __attribute__((aligned(16))) uint32_t sbt[PV_BTAB_ENTRIES * PV_BTAB_STRIDE];
-    for (int t = threadIdx.x; t < PV_BTAB_ENTRIES * PV_BTAB_STRIDE / 4; t += PV_BLOCK)
-        reinterpret_cast<uint4*>(sbt)[t] = reinterpret_cast<const uint4*>(btab_g)[t];
-    __syncthreads();
-    const LdsBTab bt{sbt};
-#endif
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const uint32_t sb = gate.stile(t, ntiles);
         if ((sb + 1) * PV_BLOCK <= nc) break;
         const uint32_t i0 = sb * PV_BLOCK + threadIdx.x;  // slot
-#if PV_STRAUS_HALF && PV_MSM_SORT
         // the tile's lanes regrouped by their window count (a stable counting sort: lanes with no Straus
         // slot first, then counts <= 30, 31, ..., >= 36), so a wave runs the largest count of lanes that
         // need about as many: 33.1 windows per wave on average at random scalars instead of 33.9
@@ -855,66 +624,22 @@ __global__ __launch_bounds__(PV_BLOCK, PV_MSM_MINBLOCKS) void pv_msm_kernel(cons
             __syncthreads();  // the next tile rewrites s_wcnt and s_perm
         }
         const uint32_t is = sb * PV_BLOCK + src;
-#else
-        const uint32_t is = i0;
-#endif
         const bool active = is < n && is >= nc;
         const uint32_t i = active ? is : (uint32_t)n - 1;  // n - 1 >= nc here: a Straus slot
-#if !(PV_STRAUS_HALF && PV_MSM_STAGED)
-        const DevATab at{wk.atab, (uint32_t)wk.stride, i};
-#endif
+        const DevATab at{wk.atab, i};
         const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
         const Soa qs(wk.q, 40, wk.stride);
         fe X, Y, Z;
-#if PV_STRAUS_HALF
         // the wave's window count: its lanes' maximum (a lane's digits above its own count are 0)
         int nw = (int)(dig.nw() & 0xFFu);
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) nw = max(nw, __shfl_xor(nw, m));
         nw = __builtin_amdgcn_readfirstlane(nw);
-#if PV_MSM_STAGED
-        pv_straus_ar_xyz_staged(X, Y, Z, DevATabStage{wk.atab, i, stg_wave, threadIdx.x & 63u}, dig, nw,
-                                [&](ge_p3& accB) {  // [k2 S]B (pv_straus_b_kernel)
-#pragma unroll
-                                    for (int q = 0; q < 10; q++) {
-                                        accB.X.v[q] = qs.ld(q, i);
-                                        accB.Y.v[q] = qs.ld(10 + q, i);
-                                        accB.Z.v[q] = qs.ld(20 + q, i);
-                                        accB.T.v[q] = qs.ld(30 + q, i);
-                                    }
-                                });
-#else
-        const DevATab rt{wk.atab, (uint32_t)wk.stride, i, 9u};
-#if PV_MSM_FUSED_B
+        const DevATab rt{wk.atab, i, 9u};
         pv_straus_ar_xyz_addb(X, Y, Z, at, rt, dig, nw, [&](ge_p3& acc) {  // + [k2 S]B from the wide comb
             pv_comb_b_add_w<Bc2<W>::POS>(acc, DevB2Stage<Bc2<W>::ENT>{bcomb, stgb_wave, threadIdx.x & 63u},
                                          [&](int j) { return dig.fb(j); });
         });
-#else
-        pv_straus_ar_xyz(X, Y, Z, at, rt, dig, nw, [&](ge_p3& accB) {  // [k2 S]B (pv_straus_b_kernel)
-#pragma unroll
-            for (int q = 0; q < 10; q++) {
-                accB.X.v[q] = qs.ld(q, i);
-                accB.Y.v[q] = qs.ld(10 + q, i);
-                accB.Z.v[q] = qs.ld(20 + q, i);
-                accB.T.v[q] = qs.ld(30 + q, i);
-            }
-        });
-#endif
-#endif
-#elif PV_STRAUS_WIDE_B
-        pv_straus_a_xyz(X, Y, Z, at, dig, [&](ge_p3& accB) {  // [S]B, written by pv_straus_b_kernel
-#pragma unroll
-            for (int q = 0; q < 10; q++) {
-                accB.X.v[q] = qs.ld(q, i);
-                accB.Y.v[q] = qs.ld(10 + q, i);
-                accB.Z.v[q] = qs.ld(20 + q, i);
-                accB.T.v[q] = qs.ld(30 + q, i);
-            }
-        });
-#else
-        pv_straus_xyz(X, Y, Z, at, bt, dig);
-#endif
         if (active) {
 #pragma unroll
             for (int q = 0; q < 10; q++) {
@@ -928,7 +653,6 @@ __global__ __launch_bounds__(PV_BLOCK, PV_MSM_MINBLOCKS) void pv_msm_kernel(cons
 
 // ------------------------------------------------------------------ keyed comb path (comb.h)
 
-
 __device__ __forceinline__ uint32_t pv_key_hash(const uint32_t A[8], uint32_t seed) {
     uint32_t h = seed;
 #pragma unroll
@@ -939,77 +663,28 @@ __device__ __forceinline__ uint32_t pv_key_hash(const uint32_t A[8], uint32_t se
     return h;
 }
 
-// Sub-table of request i's per-key counter: its workgroup of the insert / scatter / unpermute grids
-// (all PV_BLOCK requests per workgroup, request i in workgroup i / PV_BLOCK).
-// PV_INSERT_LDS: the insert kernel's workgroup takes PV_INS_REQS consecutive requests, counts their
-// keys in an LDS table and makes ONE device atomic per (key, workgroup) for the whole group's ranks
-// (the per-request atomics on the keys' counters were ~56 of the kernel's ~74 us at 1M requests);
-// the sub-table is then the request's insert-workgroup index mod PV_RANK_SUB.
-#ifndef PV_INSERT_LDS
-#define PV_INSERT_LDS 1
-#endif
+// The insert kernel's workgroup takes PV_INS_REQS consecutive requests, counts their keys in an LDS
+// table and makes ONE device atomic per (key, workgroup) for the whole group's ranks (per-request
+// atomics on the keys' counters were ~56 of the kernel's ~74 us at 1M requests). The sub-table of
+// request i's per-key counter is its insert-workgroup index mod PV_RANK_SUB.
 static constexpr uint32_t PV_INS_THREADS = 1024, PV_INS_PER_THREAD = 4;
 static constexpr uint32_t PV_INS_REQS = PV_INS_THREADS * PV_INS_PER_THREAD;
 static constexpr uint32_t PV_INS_LT = 4096;  // LDS table entries (more distinct keys: direct atomics)
 __device__ __forceinline__ uint32_t pv_rank_sub(uint32_t i) {
-#if PV_INSERT_LDS
     return (i / PV_INS_REQS) & (PV_RANK_SUB - 1u);
-#else
-    return (i / PV_BLOCK) & (PV_RANK_SUB - 1u);
-#endif
 }
 
-// Dedup 1/2: open-addressing insert of every request's key; req_key[i] = the key's slot.
-__global__ __launch_bounds__(PV_BLOCK) void pv_key_insert_kernel(const uint8_t* __restrict__ pk, uint64_t n,
-                                                                  KeyWork kw) {
-    const uint32_t i = blockIdx.x * PV_BLOCK + threadIdx.x;
-    // the chunk's split counters start at 0 (the assign kernel, next on the stream, counts keys into
-    // them); done here instead of a separate hipMemsetAsync (~11 us of dispatch + gap per chunk)
-    if (i < PV_SPLIT_WORDS) kw.nkeys[i] = 0u;
-    if (i < PV_NSEG) kw.nkeys[PV_SEG_BASE + i * PV_SEG_STRIDE] = 0u;
-    if (i >= n) return;
-    uint32_t A[8];
-    pv_load_pk(A, pk, i);
-    uint32_t h = pv_key_hash(A, kw.seed) & kw.hmask;
-    for (uint32_t probe = 0; probe <= kw.hmask; probe++) {  // the table is >= 2x the chunk: never full
-        // a plain read first: once a key is in, its other requests find it without an atomic (the
-        // atomics of one key's requests all queue on one slot)
-#if PV_INSERT_PLAIN_LOAD
-        // a plain (L2-cached) read: a stale PV_EMPTY only sends the request to the CAS, which returns
-        // the slot's current value; a slot never changes once set within the kernel
-        uint32_t cur = kw.slot[h];
-#else
-        uint32_t cur = __hip_atomic_load(&kw.slot[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-        if (cur == PV_EMPTY) cur = atomicCAS(&kw.slot[h], PV_EMPTY, i);
-        if (cur == PV_EMPTY) break;
-        uint32_t B[8];
-        pv_load_pk(B, pk, cur);
-        if (pv_words_equal(A, B)) break;
-        h = (h + 1) & kw.hmask;
-    }
-    kw.req_key[i] = h;
-    // the request's rank among its key's requests, and (final after this kernel) the key's count;
-    // the 1,024-odd counters of a batch sit on distinct hash slots, i.e. mostly distinct L2 lines
-#ifdef PV_AB_NO_RANK_ATOMIC  // measurement-only: wrong slot order
-    kw.req_rank[i] = 0u;
-    kw.slot_cnt[pv_rank_sub(i) * (kw.hmask + 1ull) + h] = 1u;
-#else
-    kw.req_rank[i] = atomicAdd(&kw.slot_cnt[pv_rank_sub(i) * (kw.hmask + 1ull) + h], 1u);
-#endif
-}
-
-// The key's slot of request i (open addressing; the key is inserted if new), as pv_key_insert_kernel.
+// The key's slot of request i (open addressing; the key is inserted if new).
 __device__ __forceinline__ uint32_t pv_key_slot(const uint8_t* __restrict__ pk, const KeyWork& kw, uint32_t i) {
     uint32_t A[8];
     pv_load_pk(A, pk, i);
     uint32_t h = pv_key_hash(A, kw.seed) & kw.hmask;
     for (uint32_t probe = 0; probe <= kw.hmask; probe++) {  // the table is >= 2x the chunk: never full
-#if PV_INSERT_PLAIN_LOAD
+        // a plain (L2-cached) read first: once a key is in, its other requests find it without an
+        // atomic (the atomics of one key's requests all queue on one slot). A stale PV_EMPTY only sends
+        // the request to the CAS, which returns the slot's current value; a slot never changes once
+        // set within the kernel
         uint32_t cur = kw.slot[h];
-#else
-        uint32_t cur = __hip_atomic_load(&kw.slot[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
         if (cur == PV_EMPTY) cur = atomicCAS(&kw.slot[h], PV_EMPTY, i);
         if (cur == PV_EMPTY) break;
         uint32_t B[8];
@@ -1020,15 +695,17 @@ __device__ __forceinline__ uint32_t pv_key_slot(const uint8_t* __restrict__ pk, 
     return h;
 }
 
-// Dedup 1/2, LDS-aggregated form (PV_INSERT_LDS): every request's key slot as above, then its rank
-// among the key's requests = the workgroup's base for the key (one device atomic per distinct key of
-// the workgroup) + its rank inside the workgroup (an LDS atomic).
+// Dedup 1/2: every request's key slot as above (req_key[i]), then its rank among the key's requests
+// = the workgroup's base for the key (one device atomic per distinct key of the workgroup) + its rank
+// inside the workgroup (an LDS atomic).
 __global__ __launch_bounds__(PV_INS_THREADS) void pv_key_insert_lds_kernel(const uint8_t* __restrict__ pk, uint64_t n,
                                                                           KeyWork kw) {
     __shared__ uint32_t lkey[PV_INS_LT], lcnt[PV_INS_LT];
     const uint32_t t = threadIdx.x;
     const uint32_t g = blockIdx.x * PV_INS_THREADS + t;
-    if (g < PV_SPLIT_WORDS) kw.nkeys[g] = 0u;  // the chunk's split counters (see pv_key_insert_kernel)
+    // the chunk's split counters start at 0 (the assign kernel, next on the stream, counts keys into
+    // them); done here instead of a separate hipMemsetAsync (~11 us of dispatch + gap per chunk)
+    if (g < PV_SPLIT_WORDS) kw.nkeys[g] = 0u;
     if (g < PV_NSEG) kw.nkeys[PV_SEG_BASE + g * PV_SEG_STRIDE] = 0u;
     for (uint32_t e = t; e < PV_INS_LT; e += PV_INS_THREADS) {
         lkey[e] = PV_EMPTY;
@@ -1172,11 +849,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_xtab_publish_kernel(const uint8_t
 }
 
 // Exclusive prefix sum of one value per thread over a 1024-thread workgroup; *total = the sum.
-#ifndef PV_SCAN_WAVE
-#define PV_SCAN_WAVE 1
-#endif
 static constexpr uint32_t PV_SCAN_THREADS = 1024;  // pv_key_scan_kernel's block
-#if PV_SCAN_WAVE
 // Wave scans by shuffles, then the 16 wave totals (two barriers instead of Hillis-Steele's twenty).
 // Written for 64-lane waves and exactly 16 of them (the 1,024-thread pv_key_scan_kernel).
 #if defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
@@ -1204,22 +877,6 @@ __device__ uint32_t pv_block_scan(uint32_t v, uint32_t* part, uint32_t* total) {
     *total = all;
     return before + x - v;
 }
-#else
-__device__ uint32_t pv_block_scan(uint32_t v, uint32_t* part, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    __syncthreads();  // every thread is done with the previous scan's results
-    part[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {  // Hillis-Steele
-        const uint32_t x = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    *total = part[1023];
-    return t ? part[t - 1] : 0u;
-}
-#endif
 
 // Sort 2/3 (one workgroup): split the keys between the paths and give each key its slot range.
 // Comb keys (>= min_req requests, the first kcap of them in id order) take slots [0, CS) in id
@@ -1421,33 +1078,6 @@ struct DevCombRow {
         }
     }
 };
-struct DevCombRows {
-    uint4* base;  // key's table [32][129][10]
-    __device__ __forceinline__ DevCombRow row(int i) const { return DevCombRow{base + (uint32_t)i * PV_COMB_ENT * 10}; }
-};
-
-// One position's row of the fixed-base comb: entries d = 0..32768, PV_BCOMB_STRIDE words each.
-struct DevBRow {
-    const uint4* r;
-    __device__ __forceinline__ void load_part(int d, int part, uint32_t w[20]) const {
-        const uint4* e = r + d * (PV_BCOMB_STRIDE / 4) + 5 * part;
-#pragma unroll
-        for (int q = 0; q < (part ? 3 : 5); q++) {
-            const uint4 v = e[q];
-            const int lim = part ? 10 : 20;
-            if (4 * q < lim) w[4 * q] = v.x;
-            if (4 * q + 1 < lim) w[4 * q + 1] = v.y;
-            if (4 * q + 2 < lim) w[4 * q + 2] = v.z;
-            if (4 * q + 3 < lim) w[4 * q + 3] = v.w;
-        }
-    }
-};
-struct DevBRows {
-    const uint4* base;
-    __device__ __forceinline__ DevBRow row(int i) const {
-        return DevBRow{base + (uint32_t)i * PV_BCOMB_ENT * (PV_BCOMB_STRIDE / 4)};
-    }
-};
 
 struct DevCombStage {  // per-key comb table rows, entries of 10 uint4
     const uint4* key;  // the key's table [32][129][10]
@@ -1471,156 +1101,6 @@ struct DevCombStage {  // per-key comb table rows, entries of 10 uint4
         }
     }
 };
-struct DevBStage {  // fixed-base comb rows, entries of PV_BCOMB_STRIDE words (8 uint4, 30 words used)
-    const uint4* base;  // T_B [16][32769][8]
-    uint4* lds;         // this wave's [8][64] staging area
-    uint32_t lane;
-    __device__ __forceinline__ void stage(int j, int d) const {
-        const uint4* e = base + ((uint32_t)j * PV_BCOMB_ENT + (uint32_t)d) * (PV_BCOMB_STRIDE / 4);
-        pv_lds_reads_done();
-        pv_glds16_row<PV_BCOMB_STRIDE / 4>(e, lds);
-    }
-    __device__ __forceinline__ void staged(int part, uint32_t w[20]) const {
-#pragma unroll
-        for (int q = 0; q < (part ? 3 : 5); q++) {
-            const uint4 v = lds[(5 * part + q) * 64 + lane];
-            const int lim = part ? 10 : 20;
-            if (4 * q < lim) w[4 * q] = v.x;
-            if (4 * q + 1 < lim) w[4 * q + 1] = v.y;
-            if (4 * q + 2 < lim) w[4 * q + 2] = v.z;
-            if (4 * q + 3 < lim) w[4 * q + 3] = v.w;
-        }
-    }
-};
-
-// The key chain is the keyed path's long serial dependency and shares SIMDs with the per-request
-// prep kernel: its waves take issue priority (PV_CHAIN_PRIO, s_setprio).
-#ifndef PV_CHAIN_PRIO
-#define PV_CHAIN_PRIO 3
-#endif
-__device__ __forceinline__ void pv_chain_prio() {
-#if PV_CHAIN_PRIO > 0
-    __builtin_amdgcn_s_setprio(PV_CHAIN_PRIO);
-#endif
-}
-
-// Per distinct key: libsodium's key checks, -A, and the chain of bases [256^i](-A).
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_key_chain_kernel(const uint8_t* __restrict__ pk, KeyWork kw,
-                                                                    Gate gate) {
-    if (!gate.keyed() || gate.off()) return;
-    pv_chain_prio();
-    const uint32_t id = blockIdx.x * PV_BLOCK + threadIdx.x;  // comb index
-    if (id >= kw.nkeys[PV_SPLIT_COMB_KEYS] || kw.comb_cslot[id] != PV_EMPTY) return;
-    uint32_t A[8];
-    pv_load_pk(A, pk, kw.key_owner[kw.comb_key[id]]);
-    ge_p3 negA;
-    const bool ok = pv_key_ok_negate(negA, A);
-    kw.key_flag[id] = ok ? 1u : 0u;
-    pv_comb_chain(DevBases{kw.bases + (uint64_t)id * PV_COMB_POS * PV_COMB_PTS * 10}, negA);
-}
-
-// ---- quad-cooperative key chain: four lanes per key shorten the per-key critical path ~2x.
-// The chain of 248 doublings is the only long dependency of the comb path and it runs on very few
-// lanes (one per distinct key), so its LATENCY, not its work, is what the batch waits for. Each
-// doubling's four squarings (X^2, Y^2, Z^2, (X+Y)^2) run on the four lanes of a quad at once and
-// so do its three (or four) products; quad_perm DPP broadcasts exchange the results.
-__device__ __forceinline__ uint32_t pv_quad_bcast(uint32_t v, int r) {
-    switch (r) {
-        case 0: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x00, 0xF, 0xF, false);
-        case 1: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x55, 0xF, 0xF, false);
-        case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xAA, 0xF, 0xF, false);
-        default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xFF, 0xF, 0xF, false);
-    }
-}
-__device__ __forceinline__ void pv_fe_bcast(fe& h, const fe& f, int r) {
-#pragma unroll
-    for (int i = 0; i < 10; i++) h.v[i] = pv_quad_bcast(f.v[i], r);
-}
-// h = (role == 0) ? a : (role == 1) ? b : (role == 2) ? c : d, branch-free: the role masks are
-// opaque to the compiler (see pv_key_chain_quad_kernel), so it selects per lane with v_cndmask
-// instead of specialising the field arithmetic per role into divergent copies.
-struct QuadRole {
-    uint32_t m0, m1, m2;  // all-ones iff role == 0 / 1 / 2
-};
-__device__ __forceinline__ void pv_fe_sel4(fe& h, const fe& a, const fe& b, const fe& c, const fe& d,
-                                           const QuadRole& q) {
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-        const uint32_t cd = q.m2 ? c.v[i] : d.v[i];
-        const uint32_t bcd = q.m1 ? b.v[i] : cd;
-        h.v[i] = q.m0 ? a.v[i] : bcd;
-    }
-}
-
-// One doubling of (X : Y : Z) (ge_p2_dbl + ge_p1p1_to_p2/p3), quad-parallel; T is produced when
-// want_t (it is the fourth lane's product).
-__device__ __forceinline__ void pv_quad_dbl(fe& X, fe& Y, fe& Z, fe& T, const QuadRole& role, bool want_t) {
-    fe in, s, XX, YY, ZZ, S, t;
-    fe_add(t, X, Y);
-    pv_fe_sel4(in, X, Y, Z, t, role);
-    fe_sq(s, in);
-    pv_fe_bcast(XX, s, 0);
-    pv_fe_bcast(YY, s, 1);
-    pv_fe_bcast(ZZ, s, 2);
-    pv_fe_bcast(S, s, 3);
-    ge_p1p1 r;
-    fe_add(r.Y, YY, XX);
-    fe_sub(r.Z, YY, XX);
-    fe_sub4p(r.X, S, r.Y);
-    fe_add(t, ZZ, ZZ);
-    fe_sub4p(t, t, r.Z);
-    fe_carry(r.T, t);
-    // lane 0: X = rX rT, 1: Y = rY rZ, 2: Z = rZ rT, 3: T = rX rY (f side may be uncarried rX)
-    fe f, g, o;
-    pv_fe_sel4(f, r.X, r.Y, r.Z, r.X, role);
-    pv_fe_sel4(g, r.T, r.Z, r.T, r.Y, role);
-    fe_mul(o, f, g);
-    pv_fe_bcast(X, o, 0);
-    pv_fe_bcast(Y, o, 1);
-    pv_fe_bcast(Z, o, 2);
-    if (want_t) pv_fe_bcast(T, o, 3);
-}
-
-// Per distinct key, four lanes: libsodium's key checks, -A, and the bases [256^i](-A), i = 0..31.
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_key_chain_quad_kernel(const uint8_t* __restrict__ pk, KeyWork kw,
-                                                                         Gate gate) {
-    if (!gate.keyed() || gate.off()) return;
-    // the chain is the batch's critical path and shares SIMDs with the per-request prep kernel:
-    // take issue priority over it
-    pv_chain_prio();
-    const uint32_t g = blockIdx.x * PV_BLOCK + threadIdx.x;
-    const uint32_t nk = kw.nkeys[PV_SPLIT_COMB_KEYS];
-    const uint32_t id = g >> 2;  // comb index
-    uint32_t rl = g & 3;
-    asm volatile("" : "+v"(rl));  // opaque: keep the per-role selects branch-free
-    const QuadRole role{rl == 0 ? ~0u : 0u, rl == 1 ? ~0u : 0u, rl == 2 ? ~0u : 0u};
-    // whole quads exit together (nk is uniform), so the DPP partners of a live lane are live
-    if (id >= nk || kw.comb_cslot[id] != PV_EMPTY) return;  // uniform per quad
-    uint32_t A[8];
-    pv_load_pk(A, pk, kw.key_owner[kw.comb_key[id]]);
-    ge_p3 cur;
-    const bool ok = pv_key_ok_negate(cur, A);
-    if (rl == 0) kw.key_flag[id] = ok ? 1u : 0u;
-    uint32_t* b = reinterpret_cast<uint32_t*>(kw.bases + (uint64_t)id * PV_COMB_POS * PV_COMB_PTS * 10);
-    fe X = cur.X, Y = cur.Y, Z = cur.Z, T = cur.T;
-    // lane r stores component r (X, Y, Z, T) of a point: words 10 r .. 10 r + 9 of its 40
-    auto store = [&](int i, int m) {
-        fe mine;
-        pv_fe_sel4(mine, X, Y, Z, T, role);
-#pragma unroll
-        for (int q = 0; q < 10; q++) b[(i * PV_COMB_PTS + m) * 40 + 10 * rl + q] = mine.v[q];
-    };
-    for (int i = 0; i < PV_COMB_POS; i++) {
-        store(i, 0);
-        // [2] .. [256] P_i; [16], [32], [64] P_i are kept for the table fill (pv_comb_chain)
-        const int nd = i + 1 < PV_COMB_POS ? 8 : 6;
-        for (int j = 0; j < nd; j++) {
-            pv_quad_dbl(X, Y, Z, T, role, (j >= 3 && j <= 5) || j == 7);
-            if (j >= 3 && j <= 5) store(i, j - 2);
-        }
-    }
-}
-
 #if LP_DEVICE
 // Positions [lo, hi) of one key's chain. Part 0 decompresses -A and writes the key flag; a later part
 // resumes from P_lo, which the previous part stored as slot 0 of position lo.
@@ -1653,19 +1133,23 @@ __device__ __forceinline__ void pv_key_chain_lp(const uint8_t* __restrict__ pk, 
 #endif
 
 // Limb-parallel key chain (lp25519.h): ONE wave per key, every field element over a 16-lane row and
-// the four squarings / products of a doubling in the four rows at once, so the 254 dependent
-// doublings take ~4x less time than on a quad of lanes. Blocks stride over the keys (a batch with
+// the four squarings / products of a doubling in the four rows at once: the chain of 254 dependent
+// doublings is the only long dependency of the comb path and runs on very few keys, so its LATENCY,
+// not its work, is what the batch waits for. Blocks stride over the keys (a batch with
 // more keys than blocks runs them in turn), so the launch needs no host-side key count and no gated
 // companion kernel: a gated launch is not free on a saturated chip, its blocks wait ~0.2 ms for
-// dispatch slots (rocprofv3, profiles/r02/prof_a). Same outputs as pv_key_chain_quad_kernel: key_flag
-// and the bases [256^i](-A) with their [16], [32], [64] multiples, carried to reduced limbs.
+// dispatch slots (rocprofv3, profiles/r02/prof_a). Outputs: key_flag and the bases [256^i](-A) with
+// their [16], [32], [64] multiples, carried to reduced limbs. The launcher runs all 32 positions in one
+// launch (lo = 0, hi = 32).
 __global__ __launch_bounds__(64) void pv_key_chain_lp_kernel(const uint8_t* __restrict__ pk, KeyWork kw, Gate gate,
                                                               int lo, int hi) {
 #if LP_DEVICE
     if (!gate.keyed() || gate.off()) return;
     const uint32_t nk = kw.nkeys[PV_SPLIT_COMB_KEYS];
     if (blockIdx.x >= nk) return;
-    pv_chain_prio();
+    // the chain is the keyed path's long serial dependency and shares SIMDs with the per-request prep
+    // kernel: its waves take issue priority
+    __builtin_amdgcn_s_setprio(3);
     const LpLane c = LpLane::make();
     const LpConsts K = LpConsts::make(c);
     for (uint32_t id = blockIdx.x; id < nk; id += gridDim.x)
@@ -1675,17 +1159,9 @@ __global__ __launch_bounds__(64) void pv_key_chain_lp_kernel(const uint8_t* __re
 
 // Per (key, position in [lo, hi), block of 16 entries): the comb table rows. Grid-stride over
 // nkeys * (hi - lo) * 8 items.
-// Optional wave priority for the fill (A/B knob): it runs beside the request-order prep and is the
-// later of the two inputs of the comb kernel.
-#ifndef PV_FILL_PRIO
-#define PV_FILL_PRIO 0
-#endif
 __global__ __launch_bounds__(PV_BLOCK, PV_FILL_MINBLOCKS) void pv_key_fill_kernel(KeyWork kw, Gate gate, int lo,
                                                                                   int hi) {
     if (!gate.keyed() || gate.off() || kw.nkeys[PV_SPLIT_SPARSE]) return;
-#if PV_FILL_PRIO > 0
-    __builtin_amdgcn_s_setprio(PV_FILL_PRIO);
-#endif
     const uint32_t np = (uint32_t)(hi - lo);
     const uint32_t items = kw.nkeys[PV_SPLIT_COMB_KEYS] * np * PV_COMB_BLOCKS;
     for (uint32_t it = blockIdx.x * PV_BLOCK + threadIdx.x; it < items; it += gridDim.x * PV_BLOCK) {
@@ -1700,7 +1176,7 @@ __global__ __launch_bounds__(PV_BLOCK, PV_FILL_MINBLOCKS) void pv_key_fill_kerne
 
 // Sparse variant for small chunks (PV_SPLIT_SPARSE): one thread per (comb key, position), only the
 // entries the chunk's digits use (pv_comb_fill_sparse). Runs on the main stream after
-// pv_comb_prep_kernel (need masks) and the key chain (bases). Sparse chunks have <= PV_ALLCOMB_KEYS
+// pv_comb_prep_req_kernel (need masks) and the key chain (bases). Sparse chunks have <= PV_ALLCOMB_KEYS
 // comb keys: the grid covers that many.
 struct DevNeed {
     const uint32_t* p;  // the position's 5 mask words (registers of the caller)
@@ -1788,64 +1264,14 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_put_prep_kernel(KeyWork kw, ui
     }
 }
 
-// Per request on the comb path: signature checks, k, key id and validity, radix-256 digits of k, S.
-template <int W>
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_prep_kernel(const uint8_t* __restrict__ sm,
-                                                                    const uint64_t* __restrict__ off, uint64_t n,
-                                                                    const uint8_t* __restrict__ pk, Work wk,
-                                                                    KeyWork kw, Gate gate) {
-    if (!gate.keyed() || gate.off()) return;
-    const uint32_t i = blockIdx.x * PV_BLOCK + threadIdx.x;  // slot
-    if (i >= gate.ncomb()) return;
-    const uint32_t r = kw.slot_req[i];                         // request
-    const uint64_t o0 = off[r], o1 = off[r + 1];
-    const uint64_t smlen = o1 - o0;
-    const uint64_t raddr = reinterpret_cast<uint64_t>(sm + o0);
-    const DevMsg mw{reinterpret_cast<const uint32_t*>(raddr & ~3ull), (uint32_t)(raddr & 3)};
-    pv_sig_words in;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        in.R[q] = mw.dw(q);
-        in.S[q] = mw.dw(8 + q);
-    }
-    pv_load_pk(in.A, pk, r);
-    bool ok = pv_sig_ok(in, smlen);
-    uint32_t k[8];
-    pv_hash_k(k, in, smlen, mw);
-    // the key's own checks (key_flag) are written by the chain kernel on the key stream, which
-    // runs concurrently with this kernel: pv_comb_a_kernel folds them into flags[slot]
-    uint32_t ek[8];
-    int32_t fb[Bc2<W>::POS];
-    sc_recode256(ek, k);
-    sc_recode_w<W, Bc2<W>::POS>(fb, in.S);
-    const Soa ds(wk.digits, PV_DIGIT_ROWS, wk.stride);
-#pragma unroll
-    for (int q = 0; q < 8; q++) ds.st(q, i, ek[q]);
-#pragma unroll
-    for (int j = 0; j < Bc2<W>::POS; j++) ds.st(8 + j, i, (uint32_t)fb[j]);
-    wk.flags[i] = ok ? 1u : 0u;
-    if (kw.nkeys[PV_SPLIT_SPARSE]) {  // small chunk: record which entries of each row this request uses
-        uint32_t* nd = kw.need + (uint64_t)kw.skey[i] * PV_COMB_POS * 5;
-#pragma unroll
-        for (int pos = 0; pos < PV_COMB_POS; pos++) {
-            const int e = pv_byte(ek[pos >> 2], pos);
-            const uint32_t d = (uint32_t)(e < 0 ? -e : e);
-            atomicOr(nd + pos * 5 + (d >> 5), 1u << (d & 31));
-        }
-    }
-}
-
-// Request-order form of the comb prep (PV_PREP_REQ_ORDER). Slot order gives every lane a record at a
-// random place in the blob, and a record's 128-byte SHA-512 blocks straddle cache lines that the next
-// block re-reads long after they left L2 (round 3 PMC: 1.06 GB fetched per 1M launch for ~0.42 GB of
-// records and keys). In request order the 64 lanes of a wave read 64 CONSECUTIVE records, ~23 KB of
-// contiguous blob, so the lines that straddle two lanes' records or two blocks of one record are
-// reused within the wave's own burst. The per-request results (radix-256 digits of k, radix-2^W digits
-// of S, the signature-check flag) go to a per-request AoS record, written coalesced;
-// pv_comb_digits_kernel then gathers them into the slot-ordered rows the comb kernel reads.
-#ifndef PV_PREP_REQ_ORDER
-#define PV_PREP_REQ_ORDER 1
-#endif
+// Per request on the comb path: signature checks, k, radix-256 digits of k, radix-2^W digits of S. It
+// runs in REQUEST order: the 64 lanes of a wave read 64 CONSECUTIVE records, ~23 KB of contiguous blob,
+// so the lines that straddle two lanes' records or two SHA-512 blocks of one record are reused within
+// the wave's own burst (slot order gave every lane a record at a random place in the blob). The
+// per-request results (digits, the signature-check flag) go to a per-request AoS record, written
+// coalesced; pv_comb_digits_kernel then gathers them into the slot-ordered rows the comb kernel reads.
+// The key's own checks (key_flag) are written by the chain kernel on the key stream, which runs
+// concurrently with this kernel: the comb kernels fold them into flags[slot].
 template <int W>
 struct PrepAos {  // uint4 per request: ek[8], fb[POS], flag, padding
     static constexpr int WORDS = 8 + Bc2<W>::POS + 1;
@@ -1984,7 +1410,6 @@ __device__ __forceinline__ void pv_comb_store_q(const Work& wk, const KeyWork& k
     }
 }
 
-
 // Per request on the comb path, first half: acc = [S]B from the wide fixed-base comb (PV_BC2_POS
 // positions: one entry conversion + PV_BC2_POS - 1 additions). Needs no per-key data, so it runs on
 // the main stream while the key stream builds the tables. acc (extended, 40 words) goes to q rows
@@ -2009,84 +1434,6 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_b_kernel(uint64_t n, Work
         qs.st(10 + q, i, acc.Y.v[q]);
         qs.st(20 + q, i, acc.Z.v[q]);
         qs.st(30 + q, i, acc.T.v[q]);
-    }
-}
-
-// Keyed chunk, [S]B per REQUEST (not slot): needs only S, so it starts with the chunk on its own
-// stream and runs beside the dedup kernels (atomics and scattered stores that leave the ALUs idle for
-// ~0.14 ms) instead of after the key sort. acc (extended, 40 words) to qb[r], 160 contiguous bytes,
-// which pv_comb_a_kernel gathers by slot_req. Requests of Straus keys get a value nobody reads.
-template <int W>
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_b_req_kernel(const uint8_t* __restrict__ sm,
-                                                                     const uint64_t* __restrict__ off, uint64_t n,
-                                                                     Work wk, const uint4* __restrict__ bcomb) {
-    const uint32_t r0 = blockIdx.x * PV_BLOCK + threadIdx.x;  // request
-    if (blockIdx.x * PV_BLOCK >= n) return;
-    const uint32_t r = r0 < n ? r0 : (uint32_t)n - 1;  // whole waves stay in step for the staging
-    uint32_t S[8];
-    {
-        const uint64_t raddr = reinterpret_cast<uint64_t>(sm + off[r]);
-        const DevMsg mw{reinterpret_cast<const uint32_t*>(raddr & ~3ull), (uint32_t)(raddr & 3)};
-#pragma unroll
-        for (int q = 0; q < 8; q++) S[q] = mw.dw(8 + q);
-    }
-    constexpr int P = Bc2<W>::POS;
-    int32_t fb[P];
-    sc_recode_w<W, P>(fb, S);  // any S (an S >= L is rejected by the prep's check)
-    __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    ge_p3 acc;
-    pv_comb_b_acc_w<P>(acc, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u}, [&](int j) {
-        int32_t d = 0;
-#pragma unroll
-        for (int u = 0; u < P; u++) d = j == u ? fb[u] : d;
-        return (int)d;
-    });
-    if (r0 >= n) return;
-    uint4* o = wk.qb + (uint64_t)r * 10u;
-    uint32_t w[40];
-#pragma unroll
-    for (int q = 0; q < 10; q++) {
-        w[q] = acc.X.v[q];
-        w[10 + q] = acc.Y.v[q];
-        w[20 + q] = acc.Z.v[q];
-        w[30 + q] = acc.T.v[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 10; q++) o[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
-
-// Straus path, [S]B of every Straus slot from the wide fixed-base comb (tiles from the end of the
-// slot range, like the other Straus kernels), extended, to q rows 0..39 for pv_msm_kernel.
-template <int W>
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_straus_b_kernel(uint64_t n, Work wk, const uint4* __restrict__ bcomb,
-                                                                   Gate gate) {
-    if (gate.off()) return;
-    const uint32_t nc = gate.ncomb(), ntiles = (uint32_t)((n + PV_BLOCK - 1) / PV_BLOCK);
-    if (blockIdx.x >= ntiles || nc >= n || (gate.stile(blockIdx.x, ntiles) + 1) * PV_BLOCK <= nc) return;
-    pv_straus_prio();
-    __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const Soa qs(wk.q, 40, wk.stride);
-    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint32_t sb = gate.stile(t, ntiles);
-        if ((sb + 1) * PV_BLOCK <= nc) break;
-        const uint32_t i0 = sb * PV_BLOCK + threadIdx.x;  // slot
-        const bool active = i0 < n && i0 >= nc;
-        const uint32_t i = active ? i0 : (uint32_t)n - 1;  // whole waves stay in step for the staging
-        const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
-        ge_p3 acc;
-        pv_comb_b_acc_w<Bc2<W>::POS>(acc, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u},
-                                     [&](int j) { return dig.fb(j); });
-        if (active) {
-#pragma unroll
-            for (int q = 0; q < 10; q++) {
-                qs.st(q, i, acc.X.v[q]);
-                qs.st(10 + q, i, acc.Y.v[q]);
-                qs.st(20 + q, i, acc.Z.v[q]);
-                qs.st(30 + q, i, acc.T.v[q]);
-            }
-        }
     }
 }
 
@@ -2159,17 +1506,10 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_wide_kernel(KeyWork kw, const 
 // of b % 8; MI355X_MICROARCH.md, workgroup dispatch), each XCD with its own 4 MB L2. Slot order is
 // key-sorted, so mapping the blocks of XCD x to ONE contiguous range of slots keeps a key's table
 // rows in one L2 instead of fetching them into all eight. A bijection on [0, gridDim.x).
-#ifndef PV_XCD_REMAP
-#define PV_XCD_REMAP 1
-#endif
 __device__ __forceinline__ uint32_t pv_xcd_block() {
-#if PV_XCD_REMAP
     const uint32_t nb = gridDim.x, b = blockIdx.x;
     const uint32_t q = nb >> 3, r = nb & 7, x = b & 7, k = b >> 3;
     return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
-#else
-    return blockIdx.x;
-#endif
 }
 
 // Second half: Q = acc + [k](-A) from the key's comb table (32 additions, no doublings), projective
@@ -2185,15 +1525,10 @@ __device__ __forceinline__ void pv_comb_a_from(const Work& wk, const KeyWork& kw
     const Soa qs(wk.q, 40, wk.stride);
     const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
     fe X, Y, Z;
-#if PV_COMB_PIPELINE
     // a cached key with affine rows: additions without the Z1 Z2 product (comb.h pv_comb_row_to_affine)
     const bool aff = cslot != PV_EMPTY && !xt && kw.kc_ntab;
     if (aff) ktab = kw.kc_ntab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
     pv_comb_a_xyz_staged(X, Y, Z, acc, DevCombStage{ktab, stg_wave, threadIdx.x & 63u, aff}, dig);
-#else
-    const DevCombRows arows{const_cast<uint4*>(ktab)};
-    pv_comb_a_xyz(X, Y, Z, acc, arows, dig);
-#endif
     if (kw.key_flag[id] == 0) wk.flags[i] = 0;
 #pragma unroll
     for (int q = 0; q < 10; q++) {
@@ -2203,32 +1538,10 @@ __device__ __forceinline__ void pv_comb_a_from(const Work& wk, const KeyWork& kw
     }
 }
 
-// comb_a after a separate pv_comb_b_kernel: acc = [S]B from q rows 0..39 (or qb, PV_COMB_B_EARLY).
+// comb_a after a separate pv_comb_b_kernel: acc = [S]B from q rows 0..39.
 __device__ __forceinline__ void pv_comb_a_slot(const Work& wk, const KeyWork& kw, uint32_t i, uint4* stg_wave) {
-    const uint32_t S = (uint32_t)wk.stride;
     const Soa qs(wk.q, 40, wk.stride);
     ge_p3 acc;
-#if PV_COMB_B_EARLY
-    {
-        const uint4* a = wk.qb + (uint64_t)kw.slot_req[i] * 10u;  // [S]B of the slot's request
-        uint32_t w[40];
-#pragma unroll
-        for (int q = 0; q < 10; q++) {
-            const uint4 v = a[q];
-            w[4 * q] = v.x;
-            w[4 * q + 1] = v.y;
-            w[4 * q + 2] = v.z;
-            w[4 * q + 3] = v.w;
-        }
-#pragma unroll
-        for (int q = 0; q < 10; q++) {
-            acc.X.v[q] = w[q];
-            acc.Y.v[q] = w[10 + q];
-            acc.Z.v[q] = w[20 + q];
-            acc.T.v[q] = w[30 + q];
-        }
-    }
-#else
 #pragma unroll
     for (int q = 0; q < 10; q++) {
         acc.X.v[q] = qs.ld(q, i);
@@ -2236,8 +1549,6 @@ __device__ __forceinline__ void pv_comb_a_slot(const Work& wk, const KeyWork& kw
         acc.Z.v[q] = qs.ld(20 + q, i);
         acc.T.v[q] = qs.ld(30 + q, i);
     }
-#endif
-    (void)S;
     pv_comb_a_from(wk, kw, i, acc, stg_wave);
 }
 
@@ -2255,19 +1566,15 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_a_kerne
     pv_comb_a_slot(wk, kw, i, &stg[wv][0][0]);
 }
 
-// [S]B and [k](-A) of a comb slot in ONE kernel (PV_COMB_FUSED): the 10 niels additions from the wide
+// [S]B and [k](-A) of a comb slot in ONE kernel: the 10 niels additions from the wide
 // fixed-base comb (random 128 B entries in HBM, LDS-staged one addition ahead in the first 8 rows of
 // the wave's staging area) run inside the issue-bound comb kernel, where the other waves of the SIMD
 // cover their fetch latency, instead of as a latency-bound kernel of their own between comb_prep and
 // the per-key tables; and acc never round-trips through q. The kernel then starts as soon as the
-// per-key tables are built.
-#ifndef PV_COMB_FUSED
-#define PV_COMB_FUSED 1
-#endif
-// ... for chunks above this many requests. Below it the two-kernel form stays: a small chunk's [S]B
-// kernel is a latency-bound chain of 10 dependent HBM lookups that the split form hides beside the
-// table fill, while the fused kernel would add it after the fill (4,096-32,768-request calls were
-// 0.08-0.12 ms slower fused).
+// per-key tables are built. The launcher takes it for chunks above PV_FUSED_MIN_REQ requests. Below
+// that the two-kernel form stays: a small chunk's [S]B kernel is a latency-bound chain of 10 dependent
+// HBM lookups that the split form hides beside the table fill, while the fused kernel would add it
+// after the fill (4,096-32,768-request calls were 0.08-0.12 ms slower fused).
 #ifndef PV_FUSED_MIN_REQ
 #define PV_FUSED_MIN_REQ 262144
 #endif
@@ -2291,47 +1598,23 @@ __device__ __forceinline__ void pv_clock_stamp(uint64_t& t, uint64_t& r) {
 }
 #endif
 
-#ifndef PV_COMB_AB_PRIO
-#define PV_COMB_AB_PRIO 0
-#endif
-// 0: off; k: the last 1/k of the grid at priority 1. Measured slower (base 393.5-400.9 M/s, last 1/4
-// 391.4-394.6, last 1/8 385.9-397.6: profiles/r06/ab/ab_comb_ab_tail_prio.txt): off
-#ifndef PV_COMB_AB_TAIL_PRIO
-#define PV_COMB_AB_TAIL_PRIO 0
-#endif
-// Workgroup size of the fused comb kernel (A/B knob): its waves share nothing (each stages its own
-// rows in its own 10 KB of LDS), so one-wave workgroups release a slot per wave instead of per four.
-// Measured: 64 within noise of 256, 128 3 % slower (profiles/r06/ab/ab_comb_ab_block.txt); 256 kept.
-#ifndef PV_COMB_AB_BLOCK
-#define PV_COMB_AB_BLOCK PV_BLOCK
-#endif
 template <int W>
-__global__ __launch_bounds__(PV_COMB_AB_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_ab_kernel(uint64_t n, Work wk,
-                                                                                        KeyWork kw,
-                                                                                        const uint4* __restrict__ bcomb,
-                                                                                        Gate gate) {
+__global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_ab_kernel(uint64_t n, Work wk, KeyWork kw,
+                                                                                const uint4* __restrict__ bcomb,
+                                                                                Gate gate) {
     if (!gate.keyed() || gate.off()) return;
-    const uint32_t i = pv_xcd_block() * PV_COMB_AB_BLOCK + threadIdx.x;  // slot
+    const uint32_t i = pv_xcd_block() * PV_BLOCK + threadIdx.x;  // slot
     if (i >= gate.ncomb()) return;
 #if PV_CLOCK_PROBE
     uint64_t t0 = 0, r0 = 0;
     pv_clock_stamp(t0, r0);
 #endif
-    __shared__ uint4 stg[PV_COMB_AB_BLOCK / 64][10][64];
+    __shared__ uint4 stg[PV_BLOCK / 64][10][64];
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
     ge_p3 acc;
     const uint4* wkey = pv_kw_rows(kw, i);
-#if PV_COMB_AB_PRIO  // A/B knob: the [S]B phase at a higher issue priority than the [k](-A) phase
-    __builtin_amdgcn_s_setprio(PV_COMB_AB_PRIO);
-#endif
-#if PV_COMB_AB_TAIL_PRIO  // A/B knob: the workgroups dispatched last (the final round) at a higher priority
-    if (blockIdx.x >= gridDim.x - gridDim.x / PV_COMB_AB_TAIL_PRIO) __builtin_amdgcn_s_setprio(1);
-#endif
     pv_comb_bw_acc<W>(acc, bcomb, wkey, dig, &stg[wv][0][0]);
-#if PV_COMB_AB_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     if (wkey)  // [k](-A) came from the key's wide rows in the same loop
         pv_comb_store_q(wk, kw, i, acc);
     else
@@ -2409,25 +1692,13 @@ struct DevEncSink {
         if (l == 0 && r0 < n) verdict[r0 >> 6] = bits;
     }
 };
-// The encode's one inversion per lane done by the whole wave (PV_ENC_WAVE_INV): the 64 lanes' products
-// are multiplied pairwise across lanes (xor partners 32, 16, 8, 4, and 2 with PV_ENC_INV_DUAL) down to
-// four products, one per lane residue mod 4 (two, mod 2), which are inverted at once in limb-parallel form
-// (lp_invert: row r = the product of the lanes = r mod 4; DUAL: rows 0, 1 the two products, repeated in
-// rows 2, 3, and five column terms per lane, a shorter dependent chain per product), and the inverses
+// The encode's one inversion per lane done by the whole wave: the 64 lanes' products are multiplied
+// pairwise across lanes (xor partners 32, 16, 8, 4, 2) down to two products, one per lane residue mod 2,
+// which are inverted at once in limb-parallel form (lp_invert<true>: rows 0, 1 the two products, repeated
+// in rows 2, 3, and five column terms per lane, a shorter dependent chain per product), and the inverses
 // walked back down the same tree (one product per level). Where every lane ran its own ~27k-instruction
 // exponentiation chain (the chain's latency was most of the kernel's time), the wave now runs ~265
 // limb-parallel products. Every lane of the wave must be active (pv_encode_kernel: all lanes run the batch).
-#ifndef PV_ENC_WAVE_INV
-#define PV_ENC_WAVE_INV 1
-#endif
-#ifndef PV_ENC_INV_DUAL
-#define PV_ENC_INV_DUAL 1
-#endif
-// A/B knob: one chain per workgroup (its 4 waves' products shared through LDS). Parity-green; encode stage
-// 0.139-0.141 vs 0.143-0.145 ms, step within noise (profiles/r06/ab/ab_encode_wg_inv.txt): off, no barrier
-#ifndef PV_ENC_WG_INV
-#define PV_ENC_WG_INV 0
-#endif
 __device__ __forceinline__ void pv_shfl_xor_fe(fe& o, const fe& a, int m) {
 #pragma unroll
     for (int k = 0; k < 10; k++) o.v[k] = __shfl_xor(a.v[k], m);
@@ -2435,8 +1706,8 @@ __device__ __forceinline__ void pv_shfl_xor_fe(fe& o, const fe& a, int m) {
 struct PvWaveInvert {
     __device__ void operator()(fe& x) const {
 #if LP_DEVICE
-        constexpr int LV = PV_ENC_INV_DUAL ? 5 : 4;  // tree levels
-        constexpr uint32_t RES = PV_ENC_INV_DUAL ? 1u : 3u;  // lane residue a row's product covers
+        constexpr int LV = 5;         // tree levels
+        constexpr uint32_t RES = 1u;  // lane residue a row's product covers
         const uint32_t lane = threadIdx.x & 63u;
         constexpr int M[5] = {32, 16, 8, 4, 2};
         fe p[LV + 1], q;
@@ -2449,48 +1720,6 @@ struct PvWaveInvert {
         const LpLane c = LpLane::make();
         const int src = (int)((lane >> 4) & RES);
         fe inv;
-#if PV_ENC_WG_INV
-        // the workgroup's waves share ONE chain: their (two) products meet in LDS, wave 0 inverts the
-        // workgroup's products, and each wave takes its own inverse as that times the other waves' products
-        static_assert(PV_ENC_INV_DUAL, "PV_ENC_WG_INV: the dual-row form (two products per wave)");
-        constexpr int NW = PV_BLOCK / 64;
-        __shared__ uint32_t wg_p[NW][2][10];
-        __shared__ uint32_t wg_inv[2][10];
-        const uint32_t wv = threadIdx.x >> 6, r = lane & 1u;
-        if (lane < 2) {
-#pragma unroll
-            for (int k = 0; k < 10; k++) wg_p[wv][lane][k] = p[LV].v[k];
-        }
-        __syncthreads();
-        fe others;  // the product of the other waves' products of residue r
-        bool have = false;
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            if ((uint32_t)w == wv) continue;
-            fe o;
-#pragma unroll
-            for (int k = 0; k < 10; k++) o.v[k] = wg_p[w][r][k];
-            if (have) fe_mul(others, others, o);
-            else others = o;
-            have = true;
-        }
-        if (wv == 0) {  // wave-uniform
-            fe tot;
-            fe_mul(tot, others, p[LV]);
-            uint32_t z = 0;
-#pragma unroll
-            for (int k = 0; k < 10; k++) {
-                const uint32_t t = __shfl(tot.v[k], src);
-                z = (lane & 15u) == (uint32_t)k ? t : z;
-            }
-            const lu zi = lp_invert<true>(c, lu(z));
-            if ((lane >> 4) < 2u && (lane & 15u) < 10u) wg_inv[lane >> 4][lane & 15u] = static_cast<uint32_t>(zi);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 10; k++) inv.v[k] = wg_inv[r][k];
-        fe_mul(inv, inv, others);
-#else
         // row r (lanes 16 r + k) gets limb k of lane (r & RES)'s product
         uint32_t z = 0;
 #pragma unroll
@@ -2498,10 +1727,9 @@ struct PvWaveInvert {
             const uint32_t t = __shfl(p[LV].v[k], src);
             z = (lane & 15u) == (uint32_t)k ? t : z;
         }
-        const lu zi = lp_invert<PV_ENC_INV_DUAL != 0>(c, lu(z));
+        const lu zi = lp_invert<true>(c, lu(z));
 #pragma unroll
         for (int k = 0; k < 10; k++) inv.v[k] = __shfl(static_cast<uint32_t>(zi), (int)(16u * (lane & RES)) + k);
-#endif
 #pragma unroll
         for (int i = LV - 1; i >= 0; i--) {
             pv_shfl_xor_fe(q, p[i], M[i]);
@@ -2530,13 +1758,8 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_encode_kernel(const uint8_t* _
         const uint32_t r = w * (64u * B) + l + 64 * t;
         use[t] = r < n && wk.flags[r < n ? r : 0] != 0;
     }
-#if PV_ENC_WAVE_INV
     pv_encode_batch_stream_b<B>(src, use, DevEncSink<B>{sm, off, comb ? kw.sverdict : verdict,
                                                         comb ? kw.slot_req : nullptr, w, l, n}, PvWaveInvert{});
-#else
-    pv_encode_batch_stream_b<B>(src, use, DevEncSink<B>{sm, off, comb ? kw.sverdict : verdict,
-                                                        comb ? kw.slot_req : nullptr, w, l, n});
-#endif
 }
 
 // ---------------------------------------------------------------------------------------- signing
@@ -2640,11 +1863,9 @@ struct Ctx {
     hipEvent_t ev_keys_ready = nullptr;      // dedup done (main -> Straus side stream)
     hipEvent_t ev_scan_done = nullptr;       // comb keys chosen (main -> kstream, before the scatter)
     hipEvent_t ev_tables_ready = nullptr;    // comb tables done (fstream -> main)
-    hipStream_t fstream = nullptr;           // table fill, one launch per chain part
-    hipEvent_t ev_chain[PV_CHAIN_PARTS] = {};  // chain part done (kstream -> fstream)
+    hipStream_t fstream = nullptr;           // table fill of a chunk that may fill sparsely
+    hipEvent_t ev_chain = nullptr;           // chain done (kstream -> fstream)
     hipEvent_t ev_prep_done = nullptr;        // comb_prep done: need masks ready (main -> fstream)
-    hipStream_t bstream = nullptr;           // [S]B per request of a keyed chunk (PV_COMB_B_EARLY)
-    hipEvent_t ev_b_start = nullptr, ev_b_done = nullptr;
     hipStream_t sstream = nullptr;           // Straus-path slots of a split chunk, overlapped
     hipEvent_t ev_straus_done = nullptr;     // their q / flags written (sstream -> main)
     // Workspace hand-over between callers' streams: every launch ends by recording ev_launch_done
@@ -2948,12 +2169,6 @@ int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const 
     return rc;
 }
 
-// kstream (key chain + fill) forks from the main stream right after the scan kernel instead of after
-// the scatter (A/B switch; the chain is on the step's critical path, profiles/r06/).
-#ifndef PV_FORK_AFTER_SCAN
-#define PV_FORK_AFTER_SCAN 1
-#endif
-
 // Chunk c of the batch on `stream` (the workspace is the context's; key / fill / side streams join it).
 int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, const uint8_t* d_pk,
                  uint64_t* d_verdict, hipStream_t stream, bool latency, bool dev_choice, int evb) {
@@ -3034,7 +2249,8 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             kw.dense_only = 1;
         }
         const uint32_t limit = kw.kcap;  // comb keys a chunk can hold (launch grids of the key stream)
-        const bool direct_fill = PV_CHAIN_MODE == 2 && PV_CHAIN_PARTS == 1 && PV_DIRECT_FILL && m > PV_SPARSE_CHUNK;
+        // a chunk above PV_SPARSE_CHUNK never fills sparsely: its fill follows the chain on kstream
+        const bool direct_fill = m > PV_SPARSE_CHUNK;
         if (keyed) {
             // the hash table and need masks are left empty by the previous keyed chunk (unpermute and
             // sparse fill kernels); after an enqueue failure they may not be, and are cleared here
@@ -3046,40 +2262,16 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                        PV_ERR_LAUNCH);
             }
             g_ctx.slots_dirty = true;  // until this chunk's unpermute kernel is enqueued
-#if PV_COMB_B_EARLY
-            // [S]B per request on bstream from the chunk's start (after everything already on the
-            // main stream, e.g. the previous chunk's comb_a reading qb); joined before comb_a
-            auto launch_b_early = [&]() -> int {
-                PV_HIP(hipEventRecord(g_ctx.ev_b_start, stream), PV_ERR_LAUNCH);
-                PV_HIP(hipStreamWaitEvent(g_ctx.bstream, g_ctx.ev_b_start, 0), PV_ERR_LAUNCH);
-                PV_LAUNCH_BC2(pv_comb_b_req_kernel, dim3(grid), dim3(PV_BLOCK), 0, g_ctx.bstream, d_sm, d_off + c0, m,
-                              g_ctx.work, g_ctx.d_bc2);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-                PV_HIP(hipEventRecord(g_ctx.ev_b_done, g_ctx.bstream), PV_ERR_LAUNCH);
-                return PV_OK;
-            };
-#ifndef PV_COMB_B_AFTER
-#define PV_COMB_B_AFTER 0  // 0: at the chunk's start, 1: after the insert kernel
-#endif
-            if (PV_COMB_B_AFTER == 0 && (rc = launch_b_early())) return rc;
-#endif
-            // kw.nkeys is cleared by pv_key_insert_kernel (m >= 1 here: the grid has a thread 0)
+            // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
             if (PV_KEY_SEED > 0 && m > 16ull * PV_KEY_SEED) {  // small chunks: no contention worth a launch
                 const uint64_t ms = std::min<uint64_t>(m, PV_KEY_SEED);
                 hipLaunchKernelGGL(pv_key_seed_kernel, dim3((unsigned)((ms + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0,
                                    stream, d_pk + 32 * c0, ms, kw);
                 PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             }
-#if PV_INSERT_LDS
             hipLaunchKernelGGL(pv_key_insert_lds_kernel, dim3((unsigned)((m + PV_INS_REQS - 1) / PV_INS_REQS)),
                                dim3(PV_INS_THREADS), 0, stream, d_pk + 32 * c0, m, kw);
-#else
-            hipLaunchKernelGGL(pv_key_insert_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_pk + 32 * c0, m, kw);
-#endif
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#if PV_COMB_B_EARLY
-            if (PV_COMB_B_AFTER == 1 && (rc = launch_b_early())) return rc;
-#endif
             hipLaunchKernelGGL(pv_key_assign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             if (kc_active) {
@@ -3095,55 +2287,28 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             // the per-key chain (few, long-latency lanes) and the table fill run on kstream, overlapped
             // with the scatter and the per-request prep on the main stream: the chain needs only the
             // scan's comb-key list (comb_key, comb_cslot), so kstream forks before the scatter
-#if PV_FORK_AFTER_SCAN
             PV_HIP(hipEventRecord(g_ctx.ev_scan_done, stream), PV_ERR_LAUNCH);
             PV_HIP(hipStreamWaitEvent(g_ctx.kstream, g_ctx.ev_scan_done, 0), PV_ERR_LAUNCH);
-#endif
             hipLaunchKernelGGL(pv_key_scatter_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             PV_HIP(hipEventRecord(g_ctx.ev_keys_ready, stream), PV_ERR_LAUNCH);
-#if !PV_FORK_AFTER_SCAN
-            PV_HIP(hipStreamWaitEvent(g_ctx.kstream, g_ctx.ev_keys_ready, 0), PV_ERR_LAUNCH);
-#endif
-            // a chunk above PV_SPARSE_CHUNK never fills sparsely: chain and fill back to back on kstream
+            // one chain launch over all positions, then the fill. direct_fill: back to back on kstream
             // and the tables-ready event right after the fill (no event hop to fstream, no gated
-            // sparse-fill launch in the dependency chain of the comb kernel)
-            // the chain runs in PV_CHAIN_PARTS launches of consecutive positions; the fill of a part
-            // runs on fstream as soon as its chain part is done, beside the chain of the next part
-#if PV_CHAIN_MODE == 2
-            constexpr int parts = PV_CHAIN_PARTS;
-#else
-            constexpr int parts = 1;
-#endif
-            const uint64_t items = (uint64_t)limit * (PV_COMB_POS / parts) * PV_COMB_BLOCKS;
+            // sparse-fill launch in the dependency chain of the comb kernel). Otherwise the fill runs on
+            // fstream, where the sparse fill follows it (below).
+            const uint64_t items = (uint64_t)limit * PV_COMB_POS * PV_COMB_BLOCKS;
             const unsigned fgrid = (unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096);
-            if (direct_fill) {  // one part, no sparse fill possible: the fill follows the chain on kstream
-                hipLaunchKernelGGL(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64),
-                                   0, g_ctx.kstream, d_pk + 32 * c0, kw, gate, 0, PV_COMB_POS);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-                hipLaunchKernelGGL(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, g_ctx.kstream, kw, gate, 0,
-                                   PV_COMB_POS);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-                PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.kstream), PV_ERR_LAUNCH);
+            hipStream_t fs = direct_fill ? g_ctx.kstream : g_ctx.fstream;
+            hipLaunchKernelGGL(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64), 0,
+                               g_ctx.kstream, d_pk + 32 * c0, kw, gate, 0, PV_COMB_POS);
+            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            if (!direct_fill) {
+                PV_HIP(hipEventRecord(g_ctx.ev_chain, g_ctx.kstream), PV_ERR_LAUNCH);
+                PV_HIP(hipStreamWaitEvent(fs, g_ctx.ev_chain, 0), PV_ERR_LAUNCH);
             }
-            for (int part = 0; part < parts && !direct_fill; part++) {
-                const int lo = part * PV_COMB_POS / parts, hi = (part + 1) * PV_COMB_POS / parts;
-#if PV_CHAIN_MODE == 2
-                hipLaunchKernelGGL(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64),
-                                   0, g_ctx.kstream, d_pk + 32 * c0, kw, gate, lo, hi);
-#elif PV_CHAIN_MODE == 1
-                hipLaunchKernelGGL(pv_key_chain_quad_kernel, dim3((4 * limit + PV_BLOCK - 1) / PV_BLOCK),
-                                   dim3(PV_BLOCK), 0, g_ctx.kstream, d_pk + 32 * c0, kw, gate);
-#else
-                hipLaunchKernelGGL(pv_key_chain_kernel, dim3((limit + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0,
-                                   g_ctx.kstream, d_pk + 32 * c0, kw, gate);
-#endif
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-                PV_HIP(hipEventRecord(g_ctx.ev_chain[part], g_ctx.kstream), PV_ERR_LAUNCH);
-                PV_HIP(hipStreamWaitEvent(g_ctx.fstream, g_ctx.ev_chain[part], 0), PV_ERR_LAUNCH);
-                hipLaunchKernelGGL(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, g_ctx.fstream, kw, gate, lo, hi);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-            }
+            hipLaunchKernelGGL(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, fs, kw, gate, 0, PV_COMB_POS);
+            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            if (direct_fill) PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.kstream), PV_ERR_LAUNCH);
         }
         if ((rc = mark(PV_STAGE_PREP))) return rc;
         if (keyed) {
@@ -3159,35 +2324,20 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             const unsigned sgrid = std::min<unsigned>(
                 grid, std::max(1u, (unsigned)(PV_SIDE_GRID_PER_CU * std::max(1, g_ctx.cus))));
             PV_HIP(hipStreamWaitEvent(ss, g_ctx.ev_keys_ready, 0), PV_ERR_LAUNCH);
-#ifndef PV_AB_NO_SIDE  // measurement-only switch: drops the Straus side (wrong verdicts if it has work)
             PV_LAUNCH_BC2(pv_prep_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m,
                                d_pk + 32 * c0, g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#if PV_STRAUS_HALF
             PV_LAUNCH_BC2(pv_split_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
             hipLaunchKernelGGL(pv_table_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, d_pk + 32 * c0,
                                g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#if PV_STRAUS_WIDE_B
-#if !PV_MSM_FUSED_B
-            PV_LAUNCH_BC2(pv_straus_b_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, m, g_ctx.work, g_ctx.d_bc2, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
-#endif
             PV_LAUNCH_BC2(pv_msm_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.d_btab,
                           g_ctx.work, g_ctx.d_bc2, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
             PV_HIP(hipEventRecord(g_ctx.ev_straus_done, ss), PV_ERR_LAUNCH);
-#if PV_PREP_REQ_ORDER
             PV_LAUNCH_BC2(pv_comb_prep_req_kernel, dim3(grid), dim3(PV_BLOCK), g_ctx.prep_lds_pad, stream, d_sm,
                           d_off + c0, m, d_pk + 32 * c0, g_ctx.work, kw, gate);
-#else
-            PV_LAUNCH_BC2(pv_comb_prep_kernel, dim3(grid), dim3(PV_BLOCK), g_ctx.prep_lds_pad, stream, d_sm,
-                          d_off + c0, m, d_pk + 32 * c0, g_ctx.work, kw, gate);
-#endif
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             if (!direct_fill) {
                 // a small chunk's sparse table fill (needs the chain's bases and the need masks comb_prep
@@ -3199,27 +2349,21 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                 PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
                 PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.fstream), PV_ERR_LAUNCH);
             }
-#if PV_PREP_REQ_ORDER
             // the per-request results to slot-ordered rows, while the key stream finishes the tables
             PV_LAUNCH_BC2(pv_comb_digits_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, g_ctx.work, kw, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
             if ((rc = mark(PV_STAGE_TABLE))) return rc;
-            const bool fused = PV_COMB_FUSED && !PV_COMB_B_EARLY && m > PV_FUSED_MIN_REQ;
-#if PV_COMB_B_EARLY
-            PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_b_done, 0), PV_ERR_LAUNCH);
-#else
+            const bool fused = m > PV_FUSED_MIN_REQ;
             if (!fused) {  // [S]B while the key stream finishes the tables, then join
                 PV_LAUNCH_BC2(pv_comb_b_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
                               gate);
                 PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             }
-#endif
             PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_tables_ready, 0), PV_ERR_LAUNCH);
             if ((rc = mark(PV_STAGE_MSM))) return rc;
             if (fused)  // [S]B + [k](-A) in one kernel as soon as the tables are built
-                PV_LAUNCH_BC2(pv_comb_ab_kernel, dim3((unsigned)((m + PV_COMB_AB_BLOCK - 1) / PV_COMB_AB_BLOCK)),
-                              dim3(PV_COMB_AB_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2, gate);
+                PV_LAUNCH_BC2(pv_comb_ab_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
+                              gate);
             else
                 hipLaunchKernelGGL(pv_comb_a_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
@@ -3228,21 +2372,12 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             PV_LAUNCH_BC2(pv_prep_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
                                d_pk + 32 * c0, g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#if PV_STRAUS_HALF
             PV_LAUNCH_BC2(pv_split_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
             if ((rc = mark(PV_STAGE_TABLE))) return rc;
             hipLaunchKernelGGL(pv_table_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, d_pk + 32 * c0,
                                g_ctx.work, gate);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#if PV_STRAUS_WIDE_B && !PV_MSM_FUSED_B
-            // (run beside the table kernel on the side stream it gains nothing: the table kernel's blocks hold
-            // every slot, profiles/r05/ab_straus_fork_b.txt)
-            PV_LAUNCH_BC2(pv_straus_b_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, g_ctx.d_bc2,
-                               gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-#endif
             if ((rc = mark(PV_STAGE_MSM))) return rc;
             PV_LAUNCH_BC2(pv_msm_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.d_btab,
                           g_ctx.work, g_ctx.d_bc2, gate);
@@ -3289,7 +2424,7 @@ int pv_fail(int code, const std::string& msg) { return fail(code, msg); }
 extern "C" {
 
 int pv_abi_version(void) { return PV_ABI_VERSION; }
-uint32_t pv_build_flags(void) { return (PV_COMB_FUSED && !PV_COMB_B_EARLY) ? PV_BUILD_COMB_FUSED : 0u; }
+uint32_t pv_build_flags(void) { return PV_BUILD_COMB_FUSED; }
 
 int pv_device_count(void) {
     int n = 0;
@@ -3320,9 +2455,6 @@ int lane_alloc_buffers(Work& w, KeyWork& kw) {
     PV_HIP(hipMalloc((void**)&w.flags, S * 4), PV_ERR_ALLOC);
     PV_HIP(hipMalloc((void**)&w.q, S * 40 * 4), PV_ERR_ALLOC);
     PV_HIP(hipMalloc((void**)&w.aos, S * PV_PREP_AOS_QMAX * 16), PV_ERR_ALLOC);
-#if PV_COMB_B_EARLY
-    PV_HIP(hipMalloc((void**)&w.qb, S * 160), PV_ERR_ALLOC);
-#endif
     const uint64_t H = 2 * S;
     kw.hmask = (uint32_t)(H - 1);
     kw.kcap = PV_KEY_CAP;
@@ -3380,15 +2512,7 @@ int ctx_init_parts(int device) {
         return fail(PV_ERR_NO_DEVICE, std::string("pv_init: built for gfx950, device is ") + prop.gcnArchName);
     g_ctx.cus = prop.multiProcessorCount;
     PV_HIP(hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-#if PV_SIDE_PRIO >= 2
-    {
-        int least = 0, greatest = 0;
-        PV_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest), PV_ERR_NO_DEVICE);
-        PV_HIP(hipStreamCreateWithPriority(&g_ctx.kstream, hipStreamNonBlocking, greatest), PV_ERR_NO_DEVICE);
-    }
-#else
     PV_HIP(hipStreamCreateWithFlags(&g_ctx.kstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-#endif
     // stream-to-stream hand-overs inside the engine (one device, never read by the host) are recorded with
     // a device-scope release instead of the default system-scope fence: headline step 2.612-2.618 against
     // 2.620-2.624 ms interleaved (profiles/r05/ab_event_devscope.txt); PV_EVENT_DEVSCOPE=0 restores it
@@ -3397,26 +2521,10 @@ int ctx_init_parts(int device) {
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_scan_done, evf), PV_ERR_NO_DEVICE);
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_tables_ready, evf), PV_ERR_NO_DEVICE);
     PV_HIP(hipStreamCreateWithFlags(&g_ctx.fstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-    for (auto& e : g_ctx.ev_chain) PV_HIP(hipEventCreateWithFlags(&e, evf), PV_ERR_NO_DEVICE);
+    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_chain, evf), PV_ERR_NO_DEVICE);
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_prep_done, evf), PV_ERR_NO_DEVICE);
-#if PV_SIDE_PRIO
-    {
-        // Straus-side requests (one-off keys) are a short dependent chain of small grids; a
-        // high-priority queue lets their workgroups dispatch ahead of the comb grids so the
-        // chain ends before comb_a instead of overlapping it.
-        int least = 0, greatest = 0;
-        PV_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest), PV_ERR_NO_DEVICE);
-        PV_HIP(hipStreamCreateWithPriority(&g_ctx.sstream, hipStreamNonBlocking, greatest), PV_ERR_NO_DEVICE);
-    }
-#else
     PV_HIP(hipStreamCreateWithFlags(&g_ctx.sstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-#endif
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_straus_done, evf), PV_ERR_NO_DEVICE);
-#if PV_COMB_B_EARLY
-    PV_HIP(hipStreamCreateWithFlags(&g_ctx.bstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-#endif
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_b_start, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_b_done, evf), PV_ERR_NO_DEVICE);
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_launch_done, evf), PV_ERR_NO_DEVICE);
     {
         // the host path's copy stream at the greatest priority: the runtime keeps such streams on hardware
@@ -3543,13 +2651,9 @@ void ctx_free() {
     if (g_ctx.ev_scan_done) (void)hipEventDestroy(g_ctx.ev_scan_done);
     if (g_ctx.ev_tables_ready) (void)hipEventDestroy(g_ctx.ev_tables_ready);
     if (g_ctx.fstream) (void)hipStreamDestroy(g_ctx.fstream);
-    for (hipEvent_t e : g_ctx.ev_chain)
-        if (e) (void)hipEventDestroy(e);
+    if (g_ctx.ev_chain) (void)hipEventDestroy(g_ctx.ev_chain);
     if (g_ctx.ev_prep_done) (void)hipEventDestroy(g_ctx.ev_prep_done);
     if (g_ctx.sstream) (void)hipStreamDestroy(g_ctx.sstream);
-    if (g_ctx.bstream) (void)hipStreamDestroy(g_ctx.bstream);
-    if (g_ctx.ev_b_start) (void)hipEventDestroy(g_ctx.ev_b_start);
-    if (g_ctx.ev_b_done) (void)hipEventDestroy(g_ctx.ev_b_done);
     if (g_ctx.ev_straus_done) (void)hipEventDestroy(g_ctx.ev_straus_done);
     if (g_ctx.ev_launch_done) (void)hipEventDestroy(g_ctx.ev_launch_done);
     if (g_ctx.cstream) (void)hipStreamDestroy(g_ctx.cstream);
@@ -3844,7 +2948,6 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
     if (!sm || !sm_off || !pk || !verdict_bits) return fail(PV_ERR_ARG, "null pointer");
     if (!offsets_nondecreasing(sm_off, n)) return fail(PV_ERR_ARG, "sm_off must be non-decreasing");
     std::lock_guard<std::mutex> lk(g_mu);
-#if PV_ZERO_COPY
     {
         // a small call that takes the latency path (the same choice launch_chunks makes for a host-buffer
         // call) and whose records fit a 2 KB slot: the kernel reads the pinned staging slots over PCIe
@@ -3859,7 +2962,7 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
             if (rc) return rc;
             uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
             uint8_t* slots = g_ctx.h_stage;
-            memset(vb, 0xFF, n);  // pending (PV_ZC_SPIN)
+            memset(vb, 0xFF, n);  // pending: the host spins on these bytes instead of a stream sync
             auto fill_at = [&](uint8_t* base, uint64_t a, uint64_t b) {
                 for (uint64_t i = a; i < b; i++) {
                     uint8_t* sl = base + i * stride;
@@ -3903,7 +3006,6 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
             return PV_OK;
         }
     }
-#endif
     uint64_t *dver = nullptr, *hver = nullptr;
     int rc = stage_and_launch(sm, sm_off, n, pk, nullptr, &dver, &hver);
     if (rc) return rc;
@@ -4183,7 +3285,6 @@ namespace {
 // on them instead of the runtime's completion wait (a kernel fault surfaces at the next call's
 // synchronisation); bounded at 50 ms, then false and the caller waits on the stream.
 bool pv_spin_verdict_bytes(const uint8_t* vb, uint64_t n) {
-#if PV_ZC_SPIN
     const auto t0 = std::chrono::steady_clock::now();
     volatile const uint8_t* vv = vb;
     uint64_t i = 0;
@@ -4196,11 +3297,6 @@ bool pv_spin_verdict_bytes(const uint8_t* vb, uint64_t n) {
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     return true;
-#else
-    (void)vb;
-    (void)n;
-    return false;
-#endif
 }
 
 // Automatic key-cache admission after a host-buffer batch whose verdicts are the last thing enqueued on

@@ -35,11 +35,6 @@
 #include "pv_internal.h"
 #include "../../include/plenum_verify.h"
 
-// PV_LAT_HALF = 0: the single-chain form for A/B (wave 0 runs [k](-A) as 63 x 4 doublings + 64
-// additions, wave 1 [S]B); 1: the half-size split over both waves (above).
-#ifndef PV_LAT_HALF
-#define PV_LAT_HALF 1
-#endif
 // PV_LAT_TRACE (measurement builds only): block 0 stamps s_memrealtime (100 MHz) at its phase
 // boundaries into pv_lat_trace, read back by pv_debug_lat_trace.
 #ifdef PV_LAT_TRACE
@@ -65,14 +60,11 @@ struct LatMsg {
 
 [[maybe_unused]] constexpr uint32_t PV_ZC_MSG_WORDS = PV_ZC_MAX_STRIDE / 4;
 
-// PV_LAT_SHA_CALL = 1: the four-wave form's SHA-512 (wave 1) is a real call with its own register
-// allocation, so its speed does not move with the code around it (inlined, one request's hash took
-// 24.0-26.4 us depending on the rest of the kernel); 0: inlined. The two-wave form keeps it inlined
+// The four-wave form's SHA-512 (wave 1) is a real call with its own register allocation, so its speed
+// does not move with the code around it (inlined, one request's hash took 24.0-26.4 us depending on
+// the rest of the kernel). The two-wave form keeps it inlined
 // (a call raises every caller's VGPR count to the callee's, and that form runs several workgroups
 // per CU).
-#ifndef PV_LAT_SHA_CALL
-#define PV_LAT_SHA_CALL 1
-#endif
 struct LatK {
     uint32_t k[8];
 };
@@ -82,13 +74,9 @@ __device__ __noinline__ LatK lat_hash_k_call(pv_sig_words in, uint64_t smlen, co
     return o;
 }
 [[maybe_unused]] __device__ __forceinline__ void lat_hash_k(uint32_t k[8], const pv_sig_words& in, uint64_t smlen, const LatMsg& mw) {
-#if PV_LAT_SHA_CALL
     const LatK o = lat_hash_k_call(in, smlen, mw.ap, mw.sh);
 #pragma unroll
     for (int q = 0; q < 8; q++) k[q] = o.k[q];
-#else
-    pv_hash_k(k, in, smlen, mw);
-#endif
 }
 
 // ZC: zero-copy host-buffer call (pv_latency_launch_zc; slot layout and verdict bytes as in
@@ -154,7 +142,7 @@ __global__ __launch_bounds__(LAT_THREADS) void pv_lat_kernel(const uint8_t* __re
     if (wave == 1) {
         LAT_STAMP(8);
         const bool sig_ok = pv_sig_ok(in, smlen);
-        if (cached || !PV_LAT_HALF) {
+        if (cached) {
             // [S]B: the 16 fixed-base entries are fetched first, then k, then the additions
             uint32_t fs[8];
             sc_recode65536(fs, in.S);
@@ -254,10 +242,8 @@ __global__ __launch_bounds__(LAT_THREADS) void pv_lat_kernel(const uint8_t* __re
         key_ok = pv_ge_is_canonical(in.A) && !pv_has_small_order(in.A) && dec.ok_a;
         const lu negA = lp_ext_from_xy(c, K, dec.X, dec.Y, 0);
         lp_build_a_table(c, K, negA, [&](int j, const lu& q) { s_tab[j + 8][lane] = q; });
-        if (PV_LAT_HALF) {
-            const lu Rp = lp_ext_from_xy(c, K, dec.X, dec.Y, 1);
-            lp_build_a_table(c, K, Rp, [&](int j, const lu& q) { s_rtab[j + 8][lane] = q; });
-        }
+        const lu Rp = lp_ext_from_xy(c, K, dec.X, dec.Y, 1);
+        lp_build_a_table(c, K, Rp, [&](int j, const lu& q) { s_rtab[j + 8][lane] = q; });
         LAT_STAMP(2);
         __syncthreads();  // 1
         LAT_STAMP(3);
@@ -266,7 +252,7 @@ __global__ __launch_bounds__(LAT_THREADS) void pv_lat_kernel(const uint8_t* __re
         auto digit = [&](int i) { return sgn * pv_nibble(s_k16[i >> 3], i); };
         auto load = [&](int e) -> lu { return s_tab[e + 8][lane]; };
         QA = lp_straus_nw(c, nw, digit, load);
-        if (PV_LAT_HALF) QA = lp_add_cached(c, QA, s_rtab[9][lane]);  // + R'
+        QA = lp_add_cached(c, QA, s_rtab[9][lane]);  // + R'
     }
     LAT_STAMP(4);
     __syncthreads();  // 2
@@ -303,11 +289,7 @@ __global__ __launch_bounds__(LAT_THREADS) void pv_lat_kernel(const uint8_t* __re
 #ifndef PV_LAT4_SPLIT
 #define PV_LAT4_SPLIT 17
 #endif
-// PV_LAT4_RTAB_SPLIT = 1: R''s table is built by waves 0 (entries 0..4), 2 (5, 6) and 3 (7, 8); 0: all
-// by wave 0
-#ifndef PV_LAT4_RTAB_SPLIT
-#define PV_LAT4_RTAB_SPLIT 1
-#endif
+// R''s table is built by waves 0 (entries 0..4), 2 (5, 6) and 3 (7, 8).
 constexpr int LAT4_THREADS = 256;
 // ZC (zero-copy host-buffer calls, pv_latency_launch_zc): the requests sit in pinned host memory in
 // fixed-stride slots (pv_internal.h: smlen, the key, the record, slack for the hash's read-ahead); the
@@ -433,8 +415,7 @@ __device__ __forceinline__ void lat4_body(const uint32_t* __restrict__ zsrc, con
             lp_build_a_table(c, K, P, [&](int j, const lu& q) { s_tab[wave][j + 8][lane] = q; });
             // waves 2 and 3 also build the upper entries of R''s table (wave 0 the lower ones): wave
             // 0's decompression + tables were the longest chain before barrier 1
-            if (PV_LAT4_RTAB_SPLIT)
-                lp_build_a_table_part(c, K, lu(s_pr[lane]), wave - 1, [&](int j, const lu& q) { s_tab[1][j + 8][lane] = q; });
+            lp_build_a_table_part(c, K, lu(s_pr[lane]), wave - 1, [&](int j, const lu& q) { s_tab[1][j + 8][lane] = q; });
         }
         __syncthreads();  // 1: split, tables ready
         if (!cached) {
@@ -548,10 +529,7 @@ __device__ __forceinline__ void lat4_body(const uint32_t* __restrict__ zsrc, con
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) s_pts_ready = 1u;
         lp_build_a_table(c, K, negA, [&](int j, const lu& q) { s_tab[0][j + 8][lane] = q; });
-        if (PV_LAT4_RTAB_SPLIT)
-            lp_build_a_table_part(c, K, Rp, 0, [&](int j, const lu& q) { s_tab[1][j + 8][lane] = q; });  // waves 2, 3: 5..8
-        else
-            lp_build_a_table(c, K, Rp, [&](int j, const lu& q) { s_tab[1][j + 8][lane] = q; });
+        lp_build_a_table_part(c, K, Rp, 0, [&](int j, const lu& q) { s_tab[1][j + 8][lane] = q; });  // waves 2, 3: 5..8
         LAT_STAMP(2);
         __syncthreads();  // 1
         LAT_STAMP(3);

@@ -168,14 +168,10 @@ static constexpr uint32_t SC_8L[8] = {0xe7ae9f68u, 0xc09318d2u, 0x17bce6b2u, 0xa
 #define PV_HALF_MAXIT 64  // exact single steps (after the Lehmer blocks: ~3-12)
 #endif
 #ifndef PV_HALF_BLOCKS
-#define PV_HALF_BLOCKS 24  // Lehmer blocks (~9 of 31 bits / ~6 of 53 bits from 2^255 to 2^131)
+#define PV_HALF_BLOCKS 24  // Lehmer blocks (~6 of 53 bits from 2^255 to 2^131)
 #endif
-// PV_SC_SPLIT_53 = 1: Lehmer blocks on 53 leading bits with one division per quotient and
-// Jebelean's conditions (~6 blocks); 0: 31-bit blocks with Knuth's two-division test (~10 blocks).
-// Both settle only true quotients, so both give the same split.
-#ifndef PV_SC_SPLIT_53
-#define PV_SC_SPLIT_53 1
-#endif
+// The Lehmer blocks read 53 leading bits (exact doubles), take one division per quotient and accept it
+// under Jebelean's conditions (~6 blocks).
 struct pv_halfk {
     uint32_t k1[8];  // |k1|
     uint32_t k2[8];  // k2: odd, > 0, < 2^160 (words 5..7 zero: sc_mul<5>)
@@ -265,31 +261,6 @@ PV_HD float pv_rcpf(float x) {
 #endif
 }
 
-// floor(n / d) for 0 <= n < 2^31, 0 < d < 2^31 from a single-precision reciprocal estimate, fixed by
-// one exact step each way; ok = false (the caller ends its Lehmer block) for n < 0, d <= 0, a
-// quotient >= 2^20 or an estimate one step could not fix
-PV_HD uint32_t pv_qdiv31(int32_t n, int32_t d, bool& ok) {
-    ok = n >= 0 && d > 0;
-    const uint32_t un = ok ? (uint32_t)n : 0u, ud = ok ? (uint32_t)d : 1u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const float qf = (float)un * __builtin_amdgcn_rcpf((float)ud);
-#else
-    const float qf = (float)un / (float)ud;
-#endif
-    uint32_t q = qf < 1048576.0f ? (uint32_t)qf : 1048576u;
-    uint64_t p = (uint64_t)q * ud;
-    if (p > un) {
-        q--;
-        p -= ud;
-    }
-    if (p + ud <= un) {
-        q++;
-        p += ud;
-    }
-    ok = ok && q < 1048576u && p <= un && p + ud > un;
-    return q;
-}
-
 // stats (measurement only, nullptr otherwise): [0] Lehmer blocks, [1] quotients settled inside them,
 // [2] exact single steps
 PV_HD void sc_halfsize(pv_halfk& h, const uint32_t k[8], uint32_t* stats = nullptr) {
@@ -310,7 +281,6 @@ PV_HD void sc_halfsize(pv_halfk& h, const uint32_t k[8], uint32_t* stats = nullp
         const bool act = !bad && ((r1[4] >> 3) | r1[5] | r1[6] | r1[7]) != 0;
         if (pv_wave_all(!act)) break;
         if (!act) continue;
-#if PV_SC_SPLIT_53
         // 53 leading bits (exact doubles), one division per quotient, Jebelean's conditions on the
         // sign-free cosequence (the same block as lp25519.h lp_halfsize, per lane)
         int w = 4;
@@ -364,54 +334,6 @@ PV_HD void sc_halfsize(pv_halfk& h, const uint32_t k[8], uint32_t* stats = nullp
         // rows n (A, B) and n + 1 (C, D): slot x holds the even row (P, -N), slot y the odd (-N, P)
         const int64_t A = (n & 1) ? -(int64_t)Ny : (int64_t)Px, B = (n & 1) ? (int64_t)Py : -(int64_t)Nx;
         const int64_t C = (n & 1) ? (int64_t)Px : -(int64_t)Ny, D = (n & 1) ? -(int64_t)Nx : (int64_t)Py;
-#else
-        // leading bits: xh = floor(r0 / 2^e), yh = floor(r1 / 2^e), 2^30 <= xh < 2^31 (r0 >= 2^131: w >= 4)
-        int w = 4;
-#pragma unroll
-        for (int i = 5; i < 8; i++) w = r0[i] ? i : w;
-        uint32_t a1 = 0, a0 = 0, b1 = 0, b0 = 0;
-#pragma unroll
-        for (int i = 4; i < 8; i++) {
-            a1 = i == w ? r0[i] : a1;
-            a0 = i == w ? r0[i - 1] : a0;
-            b1 = i == w ? r1[i] : b1;
-            b0 = i == w ? r1[i - 1] : b0;
-        }
-        const int s = 33 - (int)__builtin_clz(a1);  // (a1:a0) has 64 - clz bits; keep the top 31
-        const int32_t xh0 = (int32_t)((((uint64_t)a1 << 32) | a0) >> s);
-        const int32_t yh0 = (int32_t)((((uint64_t)b1 << 32) | b0) >> s);
-        // stop a block above 2^130: yh < 2^(130 - e), e = 32 (w - 1) + s (>= 100 here)
-        const int e = 32 * (w - 1) + s;
-        const int32_t ythr = e >= 130 ? 1 : (int32_t)(1u << (130 - e));
-        int32_t xh = xh0, yh = yh0, A = 1, B = 0, C = 0, D = 1;
-        bool go = true;
-        for (int it = 0; it < 24; it++) {
-            if (pv_wave_all(!go)) break;
-            if (!go) continue;
-            // Knuth's test: the quotient of (xh + A) / (yh + C) and of (xh + B) / (yh + D) agree
-            const int32_t n1 = xh + A, d1 = yh + C, n2 = xh + B, d2 = yh + D;
-            bool ok1, ok2;
-            const uint32_t q = pv_qdiv31(n1, d1, ok1);
-            const uint32_t q2 = pv_qdiv31(n2, d2, ok2);
-            if (!ok1 || !ok2 || q != q2) {
-                go = false;
-                continue;
-            }
-            const int64_t ny = (int64_t)xh - (int64_t)q * yh;
-            const int64_t nC = (int64_t)A - (int64_t)q * C, nD = (int64_t)B - (int64_t)q * D;
-            if (ny < ythr || nC >= 32768 || nC <= -32768 || nD >= 32768 || nD <= -32768) {
-                go = false;
-                continue;
-            }
-            A = C;
-            C = (int32_t)nC;
-            B = D;
-            D = (int32_t)nD;
-            xh = yh;
-            yh = (int32_t)ny;
-            if (stats) stats[1]++;
-        }
-#endif
         if (stats) stats[0]++;
         if (B == 0) {
             // no quotient could be settled from the leading bits: one exact step below

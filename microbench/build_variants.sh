@@ -1,6 +1,13 @@
 #!/bin/bash
 # Build engine variants (compile-time switches of csrc/pv_engine.hip) next to each other for A/B
-# timing on the GPU:
+# timing on the GPU. The switches that remain are the numeric tuning constants in #ifndef form
+# (PV_*_MINBLOCKS, PV_PREP_LDS_PAD, PV_SPARSE_*, PV_LP_CHAIN_BLOCKS, PV_KEY_SEED, PV_RANK_SUB,
+# PV_LATENCY_MAX, PV_KEYED_HINT_MIN, PV_SEG_STRIDE, PV_COMB_MIN_REQ, PV_FUSED_MIN_REQ, PV_ENC_SMALL_B,
+# PV_ENC16_MIN, PV_KC_*, PV_PIPE_*, PV_SIDE_GRID_PER_CU, and PV_BCOMB_W / PV_HALF_* / PV_ENC_BATCH_N in
+# the headers) and the diagnostic builds (PV_CLOCK_PROBE, PV_LAT_TRACE, PV_BOUNDS_CHECK,
+# PV_ENABLE_TEST_HOOKS). The variant switches of settled A/B experiments (kernel forms, priorities,
+# stream layouts) are gone: DESIGN.md "Variants tried and retired" lists them, their results and the
+# commit that still holds their code.
 #   microbench/build_variants.sh NAME "-DFLAG=.. ..." [NAME "FLAGS" ...]  -> microbench/variants/NAME.so
 # Only the engine is recompiled with the flags; the other objects come from the in-tree build
 # (make -C indy-plenum_amd first). Load one with PLENUM_AMD_LIB=microbench/variants/NAME.so

@@ -1,7 +1,7 @@
 // Latency of one lp_halfsize (the latency kernels' limb-parallel split of k, lp25519.h) on ONE wave,
-// as the signature wave runs it (development tool). Build with -DPV_LP_SPLIT_53=0 / 1 for the 31-bit
-// Knuth blocks / the 53-bit Jebelean blocks. Prints microseconds per split (s_memrealtime, 100 MHz)
-// and the mean block / quotient / exact-step counts.
+// as the signature wave runs it (development tool): 53-bit Lehmer blocks under Jebelean's conditions.
+// Prints microseconds per split (s_memrealtime, 100 MHz) and the mean block / quotient / exact-step
+// counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -65,8 +65,8 @@ int main() {
         CHECK(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_phase), sizeof ph));
         CHECK(hipMemcpy(&tt, dt, 8, hipMemcpyDeviceToHost));
         CHECK(hipMemcpy(o, dout, 16, hipMemcpyDeviceToHost));
-        printf("{\"split53\": %d, \"stats\": %d, \"us_per_split\": %.2f, \"blocks\": %.2f, \"block_quotients\": %.2f, \"exact_steps\": %.2f, \"acc\": %u, \"us_quot_mat_checks\": [%.2f, %.2f, %.2f]}\n",
-               PV_LP_SPLIT_53, ws, tt / 100.0 / nk, o[1] / (double)nk, o[2] / (double)nk, o[3] / (double)nk, o[0], ph[0] / 300.0 / nk, ph[1] / 300.0 / nk, ph[2] / 300.0 / nk);
+        printf("{\"split53\": 1, \"stats\": %d, \"us_per_split\": %.2f, \"blocks\": %.2f, \"block_quotients\": %.2f, \"exact_steps\": %.2f, \"acc\": %u, \"us_quot_mat_checks\": [%.2f, %.2f, %.2f]}\n",
+               ws, tt / 100.0 / nk, o[1] / (double)nk, o[2] / (double)nk, o[3] / (double)nk, o[0], ph[0] / 300.0 / nk, ph[1] / 300.0 / nk, ph[2] / 300.0 / nk);
     }
     return 0;
 }

@@ -361,7 +361,7 @@ int hc_sign_open_comb_kw16(const uint8_t* sm, uint64_t smlen, const uint8_t* pk)
     return use[0] && pv_words_equal(enc[0], in.R);
 }
 
-// The Straus path with [S]B from the wide comb (PV_STRAUS_WIDE_B): checks, -A, k, the [j](-A)
+// The full-length Straus path with [S]B from the wide comb: checks, -A, k, the [j](-A)
 // table, pv_comb_b_acc_w<16> over the radix-65536 host table, pv_straus_a_xyz (loop over k only,
 // then one addition of [S]B), encoding.
 int hc_sign_open_straus_wide16(const uint8_t* sm, uint64_t smlen, const uint8_t* pk) {
@@ -559,7 +559,7 @@ int hc_sign_open_straus_half16(const uint8_t* sm, uint64_t smlen, const uint8_t*
     pv_straus_ar_xyz(X, Y, Z, at, rt, dig, nw, [&](ge_p3& p) { p = accB; });
     // the LDS-staged loop the device runs (pv_straus_ar_xyz_staged) gives the same point
     pv_straus_ar_xyz_staged(X2, Y2, Z2, PvTabStage2<HostATab>{at, rt, 0, 0}, dig, nw, [&](ge_p3& p) { p = accB; });
-    // the device's fused epilogue (pv_msm_kernel, PV_MSM_FUSED_B): [k2 S]B's niels additions straight
+    // the device's fused epilogue (pv_msm_kernel): [k2 S]B's niels additions straight
     // into the loop's point (pv_comb_b_add_w) instead of one cached addition of accB
     fe X3, Y3, Z3;
     pv_straus_ar_xyz_addb(X3, Y3, Z3, at, rt, dig, nw, [&](ge_p3& acc) {
@@ -804,7 +804,7 @@ int hc_lp_sign_open_cached(const uint8_t* sm, uint64_t smlen, const uint8_t* pk)
     memcpy(in.S, buf.data() + 32, 32);
     memcpy(in.A, pk, 32);
     HostMsg mw{buf.data()};
-    // the cache build: key checks + table (pv_key_chain_quad_kernel / pv_key_fill_kernel)
+    // the cache build: key checks + table (pv_key_chain_lp_kernel / pv_key_fill_kernel)
     ge_p3 negA;
     const bool key_ok = pv_key_ok_negate(negA, in.A);
     std::vector<ge_p3> bases(PV_COMB_POS * PV_COMB_PTS);
@@ -891,7 +891,7 @@ int hc_lp_chain_check(const uint8_t* pk) {
     return bad;
 }
 
-// The chain as pv_key_chain_lp_kernel runs it with PV_CHAIN_PARTS = parts: lp_comb_chain_part per
+// The chain as pv_key_chain_lp_kernel runs it over `parts` launches of [lo, hi): lp_comb_chain_part per
 // part, every point stored as its 40 carried words, and each later part resuming from the stored
 // P_lo (lp_load_ext40). Returns the number of stored points that differ from pv_comb_chain's (as
 // affine points) or whose T is inconsistent.

@@ -89,7 +89,7 @@ def test_lp_invert(hc):
 
 
 def test_lp_invert_dual(hc):
-    """lp_invert<true> (the encode's default, PV_ENC_INV_DUAL): two values in rows 0, 1, repeated in
+    """lp_invert<true> (the form the encode's wave inversion uses): two values in rows 0, 1, repeated in
     rows 2, 3 (the wave tree's two products), 1 / z in every row."""
     rng = random.Random(43)
     h = A40()
@@ -230,8 +230,8 @@ def test_lp_key_chain_matches_per_lane_chain(hc, oracle):
 
 
 def test_lp_key_chain_in_parts(hc, oracle):
-    """The chain as the keyed launch runs it (PV_CHAIN_PARTS launches, each resuming from the previous
-    part's stored, carried P_lo) stores the same points as the per-lane chain, with consistent T,
+    """The chain kernel's [lo, hi) form (the keyed launch runs one part; in parts, each resumes from the
+    previous part's stored, carried P_lo) stores the same points as the per-lane chain, with consistent T,
     for 1, 2, 4 and 8 parts."""
     rng = random.Random(9)
     from vectors import ORDER8

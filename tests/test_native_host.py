@@ -344,7 +344,7 @@ def test_wide_cached_rows_vs_libsodium(hc, sodium, oracle):
 
 
 def test_straus_wide_b_vs_libsodium(hc, sodium, oracle):
-    """The Straus path as the device runs it with PV_STRAUS_WIDE_B: the loop over k's radix-16 digits
+    """The full-length Straus path with [S]B from the wide comb: the loop over k's radix-16 digits
     with the [j](-A) table only, then one addition of [S]B from pv_comb_b_acc_w -- every golden
     verdict and every adversarial class against libsodium."""
     from vectors import VectorGen

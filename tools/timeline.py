@@ -1,6 +1,6 @@
 """Kernel timeline of the last K engine steps from a rocprofv3 kernel trace (rocpd SQLite output).
 
-    python tools/timeline.py TRACE_DB [--steps K] [--first-kernel pv_key_insert_kernel]
+    python tools/timeline.py TRACE_DB [--steps K] [--first-kernel pv_key_insert_lds_kernel]
 
 A step starts at each launch of --first-kernel (the first kernel of a keyed chunk). Prints, per
 kernel of the last K steps, its queue/stream, start and end relative to the step's start (us) and
@@ -29,7 +29,7 @@ def main():
     q = next((c for c in ("stream_id", "queue_id", "queue") if c in cols), None)
     sel = "select name, start, end%s from kernels order by start" % (", " + q if q else "")
     rows = [(short(r[0]), int(r[1]), int(r[2]), r[3] if q else "") for r in con.execute(sel)]
-    starts = [i for i, r in enumerate(rows) if r[0].startswith(a.first_kernel)]  # also pv_key_insert_lds_kernel
+    starts = [i for i, r in enumerate(rows) if r[0].startswith(a.first_kernel)]  # a prefix: the default matches pv_key_insert_lds_kernel
     if not starts:
         raise SystemExit("no %s in the trace (columns: %s)" % (a.first_kernel, cols))
     if a.summary:
