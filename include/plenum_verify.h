@@ -276,6 +276,29 @@ int pv_key_cache_contains(const uint8_t* pk);
 int pv_key_cache_auto(uint32_t min_seen);
 int pv_key_cache_auto_stats(uint64_t* admitted, uint64_t* failed);
 
+/* Table reuse (on by default). The per-key comb tables a keyed chunk of more than 65,536 requests
+ * builds stay where they were built, in the workspace, and are listed in a device-side directory; a
+ * later chunk -- of the same call or of any later one -- that carries one of those keys reads its table
+ * instead of building it again. It costs no memory beyond the workspace (the table area holds 16,384
+ * tables whether they are kept or not), needs no put and no admission: a key's table is kept because a
+ * chunk needed it. A hit changes only where a table is read from: which keys get a table, which path a
+ * chunk takes and every verdict are what they are without it (the libsodium key checks ran when the
+ * table was built, and their result is kept with it). The node-side key cache takes precedence for the
+ * keys it holds. A chunk whose new tables do not fit below `capacity` empties the directory and builds
+ * all its tables, as every chunk does with reuse off. Chunks of at most 65,536 requests read listed
+ * tables and build the others in the scratch slots above the capacity; they list nothing.
+ *   pv_table_reuse(on, capacity)   on: 0 = every chunk builds its own tables. capacity: tables the
+ *                                  directory may list, clamped to [1, 16,384]; 0 keeps the current value
+ *                                  (default 14,336 = 16,384 less the 2,048 comb keys a chunk that lists
+ *                                  nothing can have). Turning reuse off or changing the capacity empties
+ *                                  the directory. Applies to every device of the process.
+ *   pv_table_reuse_stats(h, b, r)  tables read from the directory / built by chunks that went through
+ *                                  it / times a chunk emptied it, since pv_init. Synchronises the
+ *                                  device: for tests and tools.
+ * PV_TABLE_REUSE=0 in the environment at pv_init starts with reuse off. */
+int pv_table_reuse(int on, uint32_t capacity);
+int pv_table_reuse_stats(uint64_t* hits, uint64_t* built, uint64_t* resets);
+
 /* Batched base58 decode (Bitcoin alphabet, PyPI base58 2.x b58decode semantics: trailing ASCII
  * whitespace stripped, each leading '1' -> 0x00). Input: strings concatenated in `chars` with
  * n+1 offsets. Output: out[i * out_stride ...], out_len[i] bytes, status[i] = 0 ok, 1 invalid

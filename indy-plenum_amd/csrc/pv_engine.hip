@@ -84,6 +84,12 @@ static constexpr uint32_t PV_ALLCOMB_KEYS = 2048;
 static constexpr uint32_t PV_ALLCOMB_CHUNK = 262144;
 static constexpr uint32_t PV_XT_KEYS = 2048;      // tables shared by a pipelined call's sub-batches (1.35 GB)
 static constexpr uint32_t PV_XT_HASH = 4096;      // their hash table (>= 2 x keys)
+static constexpr uint32_t PV_DIR_HASH = 2 * PV_KEY_CAP;  // hash words of the resident-table directory (KeyWork::dir_*)
+// Slots the directory lists by default: the rest of ctab is scratch for the tables of a chunk that lists
+// nothing (at most PV_SPARSE_CHUNK requests). Such a chunk has at most PV_ALLCOMB_KEYS comb keys under
+// AUTO (all-comb, or PV_SPARSE_CHUNK / PV_COMB_MIN_REQ of them, or keys whose tables exist already). Only
+// forced PV_PATH_COMB (every key a comb key) can bring more misses than fit, and then resets the directory.
+static constexpr uint32_t PV_DIR_DEFAULT_CAP = PV_KEY_CAP - PV_ALLCOMB_KEYS;
 // An all-comb chunk of at most PV_SPARSE_CHUNK requests and at most PV_SPARSE_PER_KEY requests per key
 // on average builds only the table entries its digits use (comb.h pv_comb_fill_sparse; the need
 // masks are set by pv_comb_prep_req_kernel). A/B on MI355X (1,024 signers, device time,
@@ -313,6 +319,16 @@ struct Gate {
 //   key_cslot [stride] / comb_cslot [kcap]  node-side key cache slot of a key id / comb index: a key
 //            in the cache is a comb key whatever its request count, its T_A is the cache's table
 //            and the key stream (chain, fill) skips it
+//   comb_tslot [kcap]  slot of kw.ctab that holds (or will hold) the table of comb index j when it is
+//            not read from a cache: the allocator in pv_key_scan_kernel hands them out
+// Resident-table directory: the tables a dense chunk builds stay in ctab and are listed here, so a
+// later chunk that carries the same key reads its table instead of building it again. Nothing of it
+// lives on the host but an on/off flag, the capacity and a dirty bit.
+//   dir_htab [PV_DIR_HASH] open-addressing hash of listed slots (pv_kc_lookup with kw.seed: a hit
+//            compares the full 32-byte key), dir_keys [kcap][8], dir_flags [kcap] (libsodium key checks)
+//   dir_cnt  [2]  count: slots [0, count) are listed, nothing above them is; and the count the
+//            chunk's publish kernel stores once its tables are built and listed
+//   dir_stat [3]  u64 hits, built, resets
 // A key takes the comb path when it carries >= min_req requests of the chunk (the per-key table
 // costs about as much as ~50 requests save; 1 when the comb path is forced) and fewer than kcap
 // keys came before it; the rest -- singletons such as the adversarial keys of config 3 -- take the
@@ -344,6 +360,12 @@ struct KeyWork {
     uint64_t* sverdict;
     uint32_t* key_cslot;   // [stride] node-side key cache slot of key id (PV_EMPTY: not cached)
     uint32_t* comb_cslot;  // [kcap] the same per comb index: its table is read from the cache
+    uint32_t* comb_tslot;  // [kcap] ctab slot of comb index j (a table this chunk builds, or a resident one)
+    uint32_t* dir_htab;    // the resident-table directory (above)
+    uint32_t* dir_keys;
+    uint32_t* dir_flags;
+    uint32_t* dir_cnt;
+    unsigned long long* dir_stat;
     uint32_t* need;        // [PV_ALLCOMB_KEYS][32][5] needed |digit| bits per (comb index, position)
     const uint4* kc_tab;   // the cache's tables [cap][32][129][10] (keycache.h)
     const uint4* kc_ntab;  // the same divided by Z [cap][32][129][10] (comb.h pv_comb_row_to_affine), or null
@@ -362,9 +384,17 @@ struct KeyWork {
     uint32_t lat_choice;  // the scan picks latency vs keyed for this chunk (AUTO, device-buffer call)
     uint32_t seg_cap;     // key ids of segment s are s * seg_cap + [0, its counter)
     uint32_t dense_only;  // never fill sparsely (the tables outlive the chunk: pv_xtab_publish_kernel)
+    uint32_t dir_on;      // this chunk goes through the directory (probe, slot allocator)
+    uint32_t dir_cap;     // slots the directory may list (<= kcap)
+    uint32_t dir_pub;     // a dense chunk: its tables are whole and pv_dir_publish_kernel lists them
 };
 static constexpr uint32_t PV_EMPTY = 0xFFFFFFFFu;
 static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call's shared store (KeyWork::xt_*)
+static constexpr uint32_t PV_CSLOT_DIR = 0x20000000u;  // slot of kw.ctab listed in the resident-table directory
+// a key id's / comb index's cslot names a table of the node cache or the call store (never a directory hit)
+__host__ __device__ __forceinline__ bool pv_cslot_cached(uint32_t cslot) {
+    return cslot != PV_EMPTY && !(cslot & PV_CSLOT_DIR);
+}
 #ifndef PV_COMB_MIN_REQ
 #define PV_COMB_MIN_REQ 48
 #endif
@@ -808,9 +838,12 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_key_assign_kernel(uint64_t n, Key
 // Dedup 2b (only when the node-side key cache holds keys): every distinct key id looks its key up
 // in the cache (keycache.h); key_cslot[id] = its cache slot or PV_EMPTY. xt (hmask != 0 only for a
 // later sub-batch of a pipelined host call): a key the cache misses is looked up in the call's shared
-// table store next, a hit there giving its slot | PV_CSLOT_XT.
+// table store next, a hit there giving its slot | PV_CSLOT_XT. dir (hmask != 0 while table reuse is
+// on): a key both miss is looked up in the resident-table directory last, a hit there giving its
+// ctab slot | PV_CSLOT_DIR; such a hit says where the table is and nothing about the key's path.
 __global__ __launch_bounds__(PV_BLOCK) void pv_key_cache_probe_kernel(const uint8_t* __restrict__ pk, KeyWork kw,
-                                                                       PvKeyCacheView kc, PvKeyCacheView xt) {
+                                                                       PvKeyCacheView kc, PvKeyCacheView xt,
+                                                                       PvKeyCacheView dir) {
     const uint32_t id = blockIdx.x * PV_BLOCK + threadIdx.x;  // grid: PV_NSEG * seg_cap ids
     const uint32_t seg = id / kw.seg_cap;
     if (seg >= PV_NSEG || id - seg * kw.seg_cap >= kw.nkeys[PV_SEG_BASE + seg * PV_SEG_STRIDE]) return;
@@ -821,7 +854,36 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_key_cache_probe_kernel(const uint
         const uint32_t x = pv_kc_lookup(xt, A);
         if (x != PV_KC_EMPTY) s = x | PV_CSLOT_XT;
     }
+    if (s == PV_KC_EMPTY && dir.hmask) {
+        const uint32_t x = pv_kc_lookup(dir, A);
+        if (x != PV_KC_EMPTY) s = x | PV_CSLOT_DIR;
+    }
     kw.key_cslot[id] = s;
+}
+
+// Lists the tables a dense chunk built (comb keys without a cslot: the allocator gave each a ctab slot
+// above the directory's count) in the resident-table directory: key bytes and libsodium flag, then the
+// slot into the hash; the count moves up to what the scan computed. Runs on the main stream after the
+// chunk's comb kernel, so the tables are whole. A slot at or above the capacity stays unlisted.
+__global__ __launch_bounds__(PV_BLOCK) void pv_dir_publish_kernel(const uint8_t* __restrict__ pk, KeyWork kw) {
+    const uint32_t j = blockIdx.x * PV_BLOCK + threadIdx.x;
+    if (kw.nkeys[PV_SPLIT_LAT]) return;
+    if (j == 0) kw.dir_cnt[0] = kw.dir_cnt[1];
+    if (j >= kw.nkeys[PV_SPLIT_COMB_KEYS] || kw.comb_cslot[j] != PV_EMPTY) return;
+    const uint32_t s = kw.comb_tslot[j];
+    if (s >= kw.dir_cap) return;
+    uint32_t A[8];
+    pv_load_pk(A, pk, kw.key_owner[kw.comb_key[j]]);
+#pragma unroll
+    for (int q = 0; q < 8; q++) kw.dir_keys[8 * s + q] = A[q];
+    kw.dir_flags[s] = kw.key_flag[j];
+    __threadfence();  // the key bytes before the hash entry that names them
+    constexpr uint32_t hmask = PV_DIR_HASH - 1;
+    uint32_t h = pv_kc_hash(A, kw.seed) & hmask;
+    for (uint32_t probe = 0; probe <= hmask; probe++) {  // distinct keys, PV_DIR_HASH >= 2 x entries
+        if (atomicCAS(&kw.dir_htab[h], PV_KC_EMPTY, s) == PV_KC_EMPTY) return;
+        h = (h + 1) & hmask;
+    }
 }
 
 // Tables shared by the sub-batches of one pipelined host call (stage_and_launch): sub-batch 0 builds
@@ -906,7 +968,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
     // medium chunk with few distinct keys makes every key a comb key (PV_ALLCOMB_*)
     const bool all_comb = nk <= PV_ALLCOMB_KEYS && kw.chunk_n <= PV_ALLCOMB_CHUNK;
     auto is_cand = [&](uint32_t id, uint32_t c) {
-        return all_comb || c >= kw.min_req || (kw.kc_on && kw.key_cslot[id] != PV_EMPTY);
+        return all_comb || c >= kw.min_req || (kw.kc_on && pv_cslot_cached(kw.key_cslot[id]));
     };
     // up to 16k keys every count is loaded once, all loads in flight together (three dependent
     // passes of L2 reads took ~18 us at 7k keys); above that the passes re-read
@@ -928,28 +990,75 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
     }
     uint32_t ncand;
     const uint32_t jbase = pv_block_scan(cand, part, &ncand);
-    uint32_t cs = 0, ss = 0;
+    // nm / nh: this thread's comb keys with no table anywhere / with a resident one (directory hit)
+    uint32_t cs = 0, ss = 0, nm = 0, nh = 0;
     for (uint32_t v = lo, j = jbase; v < hi; v++) {
         const uint32_t id = vid(v);
         const uint32_t c = count(v, id);
-        if (is_cand(id, c) && j++ < kw.kcap) cs += c;
-        else ss += c;
+        if (is_cand(id, c) && j++ < kw.kcap) {
+            cs += c;
+            if (kw.dir_on) {
+                const uint32_t cslot = kw.key_cslot[id];
+                nm += cslot == PV_EMPTY ? 1u : 0u;
+                nh += cslot != PV_EMPTY && (cslot & PV_CSLOT_DIR) ? 1u : 0u;
+            }
+        } else {
+            ss += c;
+        }
     }
     uint32_t ctotal, stotal;
     uint32_t cc = pv_block_scan(cs, part, &ctotal);
     uint32_t sc = ctotal + pv_block_scan(ss, part, &stotal);
+    const bool lat = kw.lat_choice && !(nk <= PV_ALLCOMB_KEYS && 3u * nk <= kw.chunk_n);
+    // Slot allocator of the resident-table directory: miss number r builds into ctab slot count + r,
+    // above every listed slot. When the misses do not fit (a dense chunk: below the capacity, its
+    // tables get listed; any other: in the buffer, they are scratch) the chunk resets the directory:
+    // every comb key without a cached table is a miss and they take slots 0, 1, ...
+    uint32_t tnext = 0;  // this thread's next slot
+    bool dir_reset = false;
+    if (kw.dir_on) {
+        const uint32_t have = kw.dir_cnt[0];  // read by every thread before the scans' barriers, written after
+        uint32_t M, D;
+        const uint32_t mb = pv_block_scan(nm, part, &M);
+        const uint32_t hb = pv_block_scan(nh, part, &D);
+        dir_reset = !lat && have + M > (kw.dir_pub ? kw.dir_cap : kw.kcap);
+        tnext = dir_reset ? mb + hb : have + mb;
+        if (dir_reset)
+            for (uint32_t h = t; h < PV_DIR_HASH; h += PV_SCAN_THREADS) kw.dir_htab[h] = PV_KC_EMPTY;
+        if (t == 0) {
+            const uint32_t built = dir_reset ? M + D : M;
+            const uint32_t base = dir_reset ? 0u : have;
+            kw.dir_cnt[0] = base;
+            kw.dir_cnt[1] = kw.dir_pub && !lat ? min(base + built, kw.dir_cap) : base;
+            if (!lat) {
+                kw.dir_stat[0] += dir_reset ? 0u : D;
+                kw.dir_stat[1] += built;
+            }
+            kw.dir_stat[2] += dir_reset ? 1u : 0u;
+        }
+    }
     for (uint32_t v = lo, j = jbase; v < hi; v++) {
         const uint32_t id = vid(v);
         const uint32_t c = count(v, id);
         const bool cand_id = is_cand(id, c);
         if (cand_id && j < kw.kcap) {
-            const uint32_t cslot = kw.kc_on ? kw.key_cslot[id] : PV_EMPTY;
+            uint32_t cslot = kw.kc_on ? kw.key_cslot[id] : PV_EMPTY;
+            uint32_t tslot = j;  // no directory: comb index j builds into ctab[j]
+            if (kw.dir_on) {
+                const bool hit = cslot != PV_EMPTY && (cslot & PV_CSLOT_DIR);
+                if (hit && dir_reset) cslot = PV_EMPTY;  // rebuilt below the reset count
+                if (cslot == PV_EMPTY) tslot = tnext++;
+                else if (hit) tslot = cslot & ~PV_CSLOT_DIR;
+            }
             kw.key_cid[id] = j;
             kw.comb_key[j] = id;
             kw.comb_cslot[j] = cslot;
-            // a cached key's libsodium checks ran when its table was built (the chain skips it)
+            kw.comb_tslot[j] = tslot;
+            // a cached or resident key's libsodium checks ran when its table was built (the chain skips it)
             if (cslot != PV_EMPTY)
-                kw.key_flag[j] = (cslot & PV_CSLOT_XT) ? kw.xt_flags[cslot & ~PV_CSLOT_XT] : kc_flags[cslot];
+                kw.key_flag[j] = (cslot & PV_CSLOT_DIR)  ? kw.dir_flags[tslot]
+                                 : (cslot & PV_CSLOT_XT) ? kw.xt_flags[cslot & ~PV_CSLOT_XT]
+                                                         : kc_flags[cslot];
             kw.key_cursor[id] = cc;
             cc += c;
         } else {
@@ -964,7 +1073,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
         // AUTO's device-side choice for a 2,049..4,096-request batch of pv_verify_batch_device: the
         // rule pv_keyed_hint applies on the host (>= 3 requests per key, every key a comb key) now
         // that the dedup has counted the keys; otherwise the latency kernel runs after this chunk
-        kw.nkeys[PV_SPLIT_LAT] = kw.lat_choice && !(nk <= PV_ALLCOMB_KEYS && 3u * nk <= kw.chunk_n) ? 1u : 0u;
+        kw.nkeys[PV_SPLIT_LAT] = lat ? 1u : 0u;
         kw.nkeys[PV_SPLIT_COMB_KEYS] = min(ncand, kw.kcap);
         kw.nkeys[PV_SPLIT_SLOTS] = ctotal;
         kw.nkeys[PV_SPLIT_SPARSE] =
@@ -1153,7 +1262,7 @@ __global__ __launch_bounds__(64) void pv_key_chain_lp_kernel(const uint8_t* __re
     const LpLane c = LpLane::make();
     const LpConsts K = LpConsts::make(c);
     for (uint32_t id = blockIdx.x; id < nk; id += gridDim.x)
-        if (kw.comb_cslot[id] == PV_EMPTY) pv_key_chain_lp(pk, kw, id, c, K, lo, hi);  // cached: table ready
+        if (kw.comb_cslot[id] == PV_EMPTY) pv_key_chain_lp(pk, kw, id, c, K, lo, hi);  // cached or resident: table ready
 #endif
 }
 
@@ -1166,11 +1275,12 @@ __global__ __launch_bounds__(PV_BLOCK, PV_FILL_MINBLOCKS) void pv_key_fill_kerne
     const uint32_t items = kw.nkeys[PV_SPLIT_COMB_KEYS] * np * PV_COMB_BLOCKS;
     for (uint32_t it = blockIdx.x * PV_BLOCK + threadIdx.x; it < items; it += gridDim.x * PV_BLOCK) {
         const uint32_t id = it / (np * PV_COMB_BLOCKS);
-        if (kw.comb_cslot[id] != PV_EMPTY) continue;  // the key's table is in the node-side cache
+        if (kw.comb_cslot[id] != PV_EMPTY) continue;  // the key's table is in a cache or resident in ctab
         const int pos = lo + (int)((it / PV_COMB_BLOCKS) % np);
         const int b = it % PV_COMB_BLOCKS;
         const DevBasePts pts{DevBases{kw.bases + (uint64_t)id * PV_COMB_POS * PV_COMB_PTS * 10}, pos};
-        pv_comb_fill_block(DevCombRow{kw.ctab + ((uint64_t)id * PV_COMB_POS + pos) * PV_COMB_ENT * 10}, pts, b);
+        const uint64_t ts = kw.comb_tslot[id];
+        pv_comb_fill_block(DevCombRow{kw.ctab + (ts * PV_COMB_POS + pos) * PV_COMB_ENT * 10}, pts, b);
     }
 }
 
@@ -1197,8 +1307,8 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_key_fill_sparse_kernel(KeyWork kw
     }
     if (kw.comb_cslot[id] != PV_EMPTY) return;
     const DevBasePts pts{DevBases{kw.bases + (uint64_t)id * PV_COMB_POS * PV_COMB_PTS * 10}, pos};
-    pv_comb_fill_sparse(DevCombRow{kw.ctab + ((uint64_t)id * PV_COMB_POS + pos) * PV_COMB_ENT * 10}, pts,
-                        DevNeed{m});
+    const uint64_t ts = kw.comb_tslot[id];
+    pv_comb_fill_sparse(DevCombRow{kw.ctab + (ts * PV_COMB_POS + pos) * PV_COMB_ENT * 10}, pts, DevNeed{m});
 }
 
 // Key cache fill: comb index j of a put batch (tables built in the workspace by the chain / fill
@@ -1261,6 +1371,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_put_prep_kernel(KeyWork kw, ui
         kw.comb_key[j] = j;
         kw.key_owner[j] = j;
         kw.comb_cslot[j] = PV_EMPTY;
+        kw.comb_tslot[j] = j;
     }
 }
 
@@ -1518,15 +1629,16 @@ __device__ __forceinline__ void pv_comb_a_from(const Work& wk, const KeyWork& kw
                                                uint4* stg_wave) {
     const uint32_t id = kw.skey[i];  // comb index
     const uint32_t cslot = kw.comb_cslot[id];
-    const bool xt = cslot != PV_EMPTY && (cslot & PV_CSLOT_XT);
-    const uint4* ktab = cslot == PV_EMPTY ? kw.ctab + (uint64_t)id * PV_COMB_POS * PV_COMB_ENT * 10
-                        : xt ? kw.xt_tab + (uint64_t)(cslot & ~PV_CSLOT_XT) * PV_COMB_POS * PV_COMB_ENT * 10
-                             : kw.kc_tab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
+    const bool cached = pv_cslot_cached(cslot);  // else in kw.ctab: built by this chunk, or resident
+    const bool xt = cached && (cslot & PV_CSLOT_XT);
+    const uint4* ktab = !cached ? kw.ctab + (uint64_t)kw.comb_tslot[id] * PV_COMB_POS * PV_COMB_ENT * 10
+                        : xt    ? kw.xt_tab + (uint64_t)(cslot & ~PV_CSLOT_XT) * PV_COMB_POS * PV_COMB_ENT * 10
+                                : kw.kc_tab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
     const Soa qs(wk.q, 40, wk.stride);
     const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
     fe X, Y, Z;
     // a cached key with affine rows: additions without the Z1 Z2 product (comb.h pv_comb_row_to_affine)
-    const bool aff = cslot != PV_EMPTY && !xt && kw.kc_ntab;
+    const bool aff = cached && !xt && kw.kc_ntab;
     if (aff) ktab = kw.kc_ntab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
     pv_comb_a_xyz_staged(X, Y, Z, acc, DevCombStage{ktab, stg_wave, threadIdx.x & 63u, aff}, dig);
     if (kw.key_flag[id] == 0) wk.flags[i] = 0;
@@ -1878,6 +1990,11 @@ struct Ctx {
     KeyWork kw{};
     bool last_keyed = false;  // the most recent chunk ran the dedup / split kernels
     bool slots_dirty = true;  // the key hash table / need masks may hold entries (cleared before use)
+    // resident-table directory (KeyWork::dir_*): on/off, the slots it may list, and whether it has to be
+    // emptied before the next keyed chunk (first use, a control call, an enqueue failure in a keyed chunk)
+    bool dir_on = true;
+    uint32_t dir_cap = PV_DIR_DEFAULT_CAP;
+    bool dir_dirty = true;
     bool last_latency = false;  // the most recent launch took the latency path
     bool verdict_zeroed = false;  // the caller's verdict words are already 0 (pv_verify_batch)
     bool keyed_hint = false;      // pv_verify_batch saw few distinct keys: keyed path below PV_LATENCY_MAX
@@ -2231,7 +2348,15 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
         if (keyed) g_ctx.last_nkeys = g_ctx.kw.nkeys;
         KeyWork kw = g_ctx.kw;
         kw.min_req = g_ctx.path == PV_PATH_COMB ? 1u : (uint32_t)PV_COMB_MIN_REQ;
-        kw.kc_on = kc_active ? 1u : 0u;
+        // Table reuse: the chunk's keys are looked up in the resident-table directory as well, and the
+        // scan's allocator keeps what it builds off the listed slots. It decides where a table is read
+        // from and nothing else: kc_active, keyed and the scan's candidate rule do not see it. Sub-batch 0
+        // of a pipelined host call builds into the call's store, not into ctab: it stays outside.
+        const bool dir_use = g_ctx.dir_on && !g_ctx.xt_fill;
+        kw.kc_on = kc_active || dir_use ? 1u : 0u;
+        kw.dir_on = dir_use ? 1u : 0u;
+        kw.dir_cap = g_ctx.dir_cap;
+        kw.dir_pub = dir_use && m > PV_SPARSE_CHUNK ? 1u : 0u;  // direct_fill below: the tables are whole
         kw.chunk_n = (uint32_t)m;
         // a key-id segment holds the owners among its waves (every PV_NSEG-th wave of the chunk)
         kw.seg_cap = (uint32_t)((((m + 63) / 64) + PV_NSEG - 1) / PV_NSEG * 64);
@@ -2262,6 +2387,13 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                        PV_ERR_LAUNCH);
             }
             g_ctx.slots_dirty = true;  // until this chunk's unpermute kernel is enqueued
+            // the directory likewise: emptied here when it may be stale, stale until the chunk is enqueued
+            // whole. A chunk outside it builds into ctab[j], over whatever is listed.
+            if (dir_use && g_ctx.dir_dirty) {
+                PV_HIP(hipMemsetAsync(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4, stream), PV_ERR_LAUNCH);
+                PV_HIP(hipMemsetAsync(kw.dir_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);
+            }
+            if (!g_ctx.xt_fill) g_ctx.dir_dirty = true;
             // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
             if (PV_KEY_SEED > 0 && m > 16ull * PV_KEY_SEED) {  // small chunks: no contention worth a launch
                 const uint64_t ms = std::min<uint64_t>(m, PV_KEY_SEED);
@@ -2274,10 +2406,12 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             hipLaunchKernelGGL(pv_key_assign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
             PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-            if (kc_active) {
+            if (kc_active || dir_use) {
+                PvKeyCacheView dirv{kw.dir_htab, kw.dir_keys, kw.dir_flags, kw.ctab, dir_use ? PV_DIR_HASH - 1 : 0u,
+                                    kw.seed};
                 hipLaunchKernelGGL(pv_key_cache_probe_kernel, dim3((PV_NSEG * kw.seg_cap + PV_BLOCK - 1) / PV_BLOCK),
                                    dim3(PV_BLOCK), 0, stream, d_pk + 32 * c0,
-                                   kw, kcv, xtv);
+                                   kw, kcv, xtv, dirv);
                 PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             }
             gate = Gate{kw.nkeys, kw.slot_req};
@@ -2405,6 +2539,14 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                                    g_ctx.xt.flags);
                 PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             }
+            if (dir_use) {
+                if (kw.dir_pub) {  // list this chunk's tables for the chunks and calls that follow
+                    hipLaunchKernelGGL(pv_dir_publish_kernel, dim3((limit + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0,
+                                       stream, d_pk + 32 * c0, kw);
+                    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                }
+                g_ctx.dir_dirty = false;
+            }
             if (dev_choice) {  // runs only when the scan picked latency (the words were zeroed above)
                 rc = pv_latency_launch(d_sm, d_off + c0, m, d_pk + 32 * c0, g_ctx.d_bcomb, kc_view(),
                                        d_verdict + c0 / 64, true, stream, kw.nkeys + PV_SPLIT_LAT);
@@ -2481,6 +2623,16 @@ int lane_alloc_buffers(Work& w, KeyWork& kw) {
     PV_HIP(hipMalloc((void**)&kw.comb_cslot, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     PV_HIP(hipMalloc((void**)&kw.need, (uint64_t)PV_ALLCOMB_KEYS * PV_COMB_POS * 5 * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.comb_cslot, 0xFF, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.comb_tslot, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_htab, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_keys, (uint64_t)kw.kcap * 32), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_flags, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_cnt, 2 * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_stat, 3 * 8), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.comb_tslot, 0, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.dir_cnt, 0, 2 * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.dir_stat, 0, 3 * 8), PV_ERR_ALLOC);
     return PV_OK;
 }
 
@@ -2490,7 +2642,8 @@ void lane_free_buffers(Work& w, KeyWork& kw) {
                     (void*)kw.nkeys, (void*)kw.key_owner, (void*)kw.key_cid, (void*)kw.comb_key, (void*)kw.key_flag,
                     (void*)kw.bases, (void*)kw.ctab, (void*)kw.key_count, (void*)kw.key_cursor, (void*)kw.slot_req,
                     (void*)kw.req_pos, (void*)kw.skey, (void*)kw.sverdict, (void*)kw.key_cslot, (void*)kw.comb_cslot,
-                    (void*)kw.need})
+                    (void*)kw.need, (void*)kw.comb_tslot, (void*)kw.dir_htab, (void*)kw.dir_keys, (void*)kw.dir_flags,
+                    (void*)kw.dir_cnt, (void*)kw.dir_stat})
         if (p) (void)hipFree(p);
     w = Work{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     kw = KeyWork{};
@@ -2611,6 +2764,12 @@ int ctx_init_parts(int device) {
     PV_HIP(hipHostMalloc((void**)&g_ctx.h_zc_verdict, PV_ZC_MAX_REQ, hipHostMallocCoherent | hipHostMallocPortable),
            PV_ERR_ALLOC);
     if (const char* pad = getenv("PV_PREP_LDS_PAD")) g_ctx.prep_lds_pad = (uint32_t)atoi(pad);  // A/B knob
+    {  // PV_TABLE_REUSE=0: start with table reuse off (pv_table_reuse), every keyed chunk builds its tables
+        const char* tr = getenv("PV_TABLE_REUSE");
+        g_ctx.dir_on = !(tr && *tr == '0');
+        g_ctx.dir_cap = PV_DIR_DEFAULT_CAP;
+        g_ctx.dir_dirty = true;
+    }
     g_ctx.device = device;
     return PV_OK;
 }
@@ -2764,6 +2923,31 @@ int pv_set_path(int mode) {
         std::lock_guard<std::mutex> lk(g_mus[d]);
         g_ctxs[d].path = mode;
     }
+    return PV_OK;
+}
+
+int pv_table_reuse(int on, uint32_t capacity) {
+    const uint32_t cap = std::min<uint32_t>(capacity, PV_KEY_CAP);
+    for (int d = 0; d < PV_MAX_DEV; d++) {  // every device context of the process
+        std::lock_guard<std::mutex> lk(g_mus[d]);
+        Ctx& c = g_ctxs[d];
+        const bool want = on != 0;
+        if (want != c.dir_on || (cap && cap != c.dir_cap)) c.dir_dirty = true;  // emptied before its next use
+        c.dir_on = want;
+        if (cap) c.dir_cap = cap;
+    }
+    return PV_OK;
+}
+
+int pv_table_reuse_stats(uint64_t* hits, uint64_t* built, uint64_t* resets) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_table_reuse_stats: call pv_init first");
+    unsigned long long u[3] = {0, 0, 0};
+    PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpy(u, g_ctx.kw.dir_stat, sizeof(u), hipMemcpyDeviceToHost), PV_ERR_LAUNCH);
+    if (hits) *hits = u[0];
+    if (built) *built = u[1];
+    if (resets) *resets = u[2];
     return PV_OK;
 }
 
@@ -3725,6 +3909,11 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
     const char* fail_env = getenv("PV_TEST_FAIL_KC_PUT_BATCH");
     const long fail_batch = fail_env ? atol(fail_env) : -1;
     KeyWork kw = g_ctx.kw;
+    // the put builds comb index j's table in slot j of a scratch area: the part of ctab above the slots
+    // the resident-table directory may list when the batch fits there, else over the directory
+    constexpr uint64_t tab_q = (uint64_t)PV_COMB_POS * PV_COMB_ENT * 10;  // uint4 per table
+    uint4* const scratch_tab = g_ctx.kw.ctab + g_ctx.dir_cap * tab_q;
+    const uint32_t scratch_keys = kw.kcap - g_ctx.dir_cap;
     std::vector<uint8_t> lpk;
     std::vector<uint32_t> lslot;
     long batch = 0;
@@ -3750,6 +3939,12 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
         f0 = f;
         if (m == 0) continue;
         if (async && f0 < fresh.size()) return fail(PV_ERR_ARG, "kc_build_tables: asynchronous put above one batch");
+        if (g_ctx.dir_on && m <= scratch_keys) {
+            kw.ctab = scratch_tab;
+        } else {
+            kw.ctab = g_ctx.kw.ctab;
+            g_ctx.dir_dirty = true;
+        }
         PV_HIP(hipMemcpyAsync(k.d_put_pk, bpk, 32ull * m, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
         PV_HIP(hipMemcpyAsync(k.d_put_slot, bslot, (uint64_t)m * 4, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
         hipLaunchKernelGGL(pv_kc_put_prep_kernel, dim3((m + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0, s, kw, m);

@@ -81,6 +81,8 @@ SIGNATURES = {
     "pv_key_cache_contains": (ctypes.c_int, [ctypes.c_void_p]),
     "pv_key_cache_auto": (ctypes.c_int, [ctypes.c_uint32]),
     "pv_key_cache_auto_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pv_table_reuse": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32]),
+    "pv_table_reuse_stats": (ctypes.c_int, [_c_u64p, _c_u64p, _c_u64p]),
     "pv_last_zero_copy": (ctypes.c_int, []),
     "pv_init_devices": (ctypes.c_int, [ctypes.c_uint32]),
     "pv_verify_batch_multi_gpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -449,6 +451,23 @@ def last_split():
     last_path()
     v = [ctypes.c_uint32() for _ in range(3)]
     check(lib().pv_last_split(*[ctypes.byref(x) for x in v]), "pv_last_split")
+    return tuple(x.value for x in v)
+
+
+PV_TABLE_REUSE_CAP = 16384 - 2048  # default capacity of table reuse (csrc/pv_engine.hip PV_DIR_DEFAULT_CAP)
+
+
+def table_reuse(on=True, capacity=0):
+    """Keep the comb tables a large keyed chunk builds and read them in later chunks and calls
+    (pv_table_reuse; on by default). capacity: tables the engine may keep, 0 = unchanged."""
+    check(lib().pv_table_reuse(1 if on else 0, int(capacity)), "pv_table_reuse")
+
+
+def table_reuse_stats():
+    """(hits, built, resets) of table reuse since pv_init: tables read instead of built, tables built,
+    times the kept tables were dropped to make room. Synchronises the device."""
+    v = [ctypes.c_uint64() for _ in range(3)]
+    check(lib().pv_table_reuse_stats(*[ctypes.byref(x) for x in v]), "pv_table_reuse_stats")
     return tuple(x.value for x in v)
 
 

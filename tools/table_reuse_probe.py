@@ -1,0 +1,125 @@
+"""What table reuse (pv_table_reuse) costs when nothing recurs, and what a multi-chunk call gains.
+
+Two device-resident batches of 1,048,576 requests from disjoint sets of 1,024 signers (NYM-sized
+records, 16 signed messages per signer repeated). Three loops, each timed per call by the host clock
+around a sync, median of --calls calls after --warmup:
+
+  alternate  capacity 1,024, the two batches in turn: every call finds none of its keys, empties the
+             directory and builds all 1,024 tables, with the probe and the publish on top -- the price
+             of the mechanism when no signer recurs (compare with the same loop on a library without
+             reuse, or with PV_TABLE_REUSE=0)
+  recur      default capacity, one batch again and again: the steady state of recurring signers
+  multi      one call of 4 x 1,048,576 requests (four chunks of the same signers)
+
+Prints one JSON line. A library without pv_table_reuse (an older build) runs the same loops."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "indy-plenum_amd")]
+
+from plenum_amd import _native  # noqa: E402
+from oracle.libsodium_ref import LibSodium  # noqa: E402
+
+N = 1 << 20
+SIGNERS = 1024
+DISTINCT = 16
+MSG = 299
+
+
+def make_batch(ls, tag, reps=1):
+    rng = np.random.default_rng(tag)
+    sms, pks = [], []
+    for s in range(SIGNERS):
+        pk, sk = ls.seed_keypair(rng.bytes(32))
+        for _ in range(DISTINCT):
+            m = rng.bytes(MSG)
+            sms.append(ls.sign_detached(m, sk) + m)
+            pks.append(pk)
+    unit = len(sms)  # 16,384 records; repeated, so consecutive requests come from different signers
+    k = N // unit * reps
+    blob = np.frombuffer(b"".join(sms) * k, np.uint8)
+    pk = np.frombuffer(b"".join(pks) * k, np.uint8)
+    off = np.arange(unit * k + 1, dtype=np.uint64) * np.uint64(64 + MSG)
+    return blob, off, pk
+
+
+class Dev:
+    def __init__(self, L, blob, off, pk):
+        self.L, self.n = L, len(off) - 1
+        self.blob = self._put(np.concatenate([blob, np.zeros(_native.PV_BLOB_SLACK, np.uint8)]))
+        self.off, self.pk = self._put(off), self._put(pk)
+        self.words = (self.n + 63) // 64
+        self.ver = self._alloc(self.words * 8)
+
+    def _alloc(self, nbytes):
+        p = ctypes.c_void_p()
+        _native.check(self.L.pv_dev_alloc(ctypes.byref(p), nbytes), "pv_dev_alloc")
+        return p
+
+    def _put(self, a):
+        p = self._alloc(a.nbytes)
+        _native.check(self.L.pv_memcpy_h2d(p, a.ctypes.data, a.nbytes), "pv_memcpy_h2d")
+        return p
+
+    def call(self):
+        t0 = time.perf_counter()
+        _native.check(self.L.pv_verify_batch_device(self.blob, self.off, self.n, self.pk, self.ver, None),
+                      "pv_verify_batch_device")
+        _native.check(self.L.pv_sync(), "pv_sync")
+        return 1e3 * (time.perf_counter() - t0)
+
+    def valid(self):
+        out = np.zeros(self.words, np.uint64)
+        _native.check(self.L.pv_memcpy_d2h(out.ctypes.data, self.ver, out.nbytes), "pv_memcpy_d2h")
+        return int(np.unpackbits(out.view(np.uint8), bitorder="little")[:self.n].sum())
+
+
+def loop(devs, calls, warmup):
+    ts = []
+    for i in range(warmup + calls):
+        t = devs[i % len(devs)].call()
+        if i >= warmup:
+            ts.append(t)
+    return {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--no-multi", action="store_true")
+    a = ap.parse_args()
+    ls = LibSodium()
+    _native.ensure_device()
+    L = _native.lib()
+    has = hasattr(_native, "table_reuse")
+    A, B = Dev(L, *make_batch(ls, 1)), Dev(L, *make_batch(ls, 2))
+    out = {"lib": os.path.basename(_native.LIB_PATH), "table_reuse": has and os.environ.get("PV_TABLE_REUSE") != "0"}
+    if has:
+        _native.table_reuse(out["table_reuse"], SIGNERS)
+        s0 = _native.table_reuse_stats()
+    out["alternate"] = loop([A, B], a.calls, a.warmup)
+    if has:
+        out["alternate"]["hits_built_resets"] = [int(x - y) for x, y in zip(_native.table_reuse_stats(), s0)]
+        _native.table_reuse(out["table_reuse"], _native.PV_TABLE_REUSE_CAP)
+        s0 = _native.table_reuse_stats()
+    out["recur"] = loop([A], a.calls, a.warmup)
+    if has:
+        out["recur"]["hits_built_resets"] = [int(x - y) for x, y in zip(_native.table_reuse_stats(), s0)]
+    assert A.valid() == A.n and B.valid() == B.n
+    if not a.no_multi:
+        M = Dev(L, *make_batch(ls, 1, reps=4))
+        out["multi_4m"] = loop([M], max(5, a.calls // 2), 2)
+        assert M.valid() == M.n
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
