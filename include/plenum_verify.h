@@ -510,6 +510,96 @@ int pv_stream_create(void** stream);
 int pv_stream_destroy(void* stream);
 int pv_stream_sync(void* stream);
 
+/* The ledger's SHA-256 Merkle tree (RFC 6962 hashing as ledger/tree_hasher.py:16-28), batched. A tree
+ * is its size and its frontier (CompactMerkleTree.tree_size / .hashes, ledger/compact_merkle_tree.py:
+ * 73-79): one 32-byte hash per set bit of the size, the largest subtree first. Frontier hashes are
+ * opaque, so any size with popcount(size) hashes is a valid starting tree. Everything is byte-identical
+ * with the reference; a bad proof is never an error, it is a 0 verdict bit with a status.
+ *
+ *   pv_merkle_plan          host-only arithmetic (like pv_shard_plan) for n leaves appended to a tree of
+ *                           tree_size leaves: the node hashes the appends write to the hash store
+ *                           (ledger/compact_merkle_tree.py:131-136), popcount(tree_size + n) (the new
+ *                           frontier's length) and the sum of popcount(tree_size + i), i < n (the hashes
+ *                           of all audit paths). NULL out-pointers are skipped.
+ *   pv_merkle_append_batch  n sequential CompactMerkleTree.append calls (ledger/compact_merkle_tree.py:
+ *                           155-160 over _push_subtree :95-153), as plenum/common/ledger.py:75-100
+ *                           commitTxns and :129-143 treeWithAppliedTxns make them one transaction at a
+ *                           time; leaf i is data[off[i] : off[i+1]]. Host buffers, synchronous. Outputs
+ *                           (PvMerkleOut, every pointer may be NULL, which skips that output and its work):
+ *                             leaf_hash  the writeLeaf values, in order
+ *                             node_hash  the writeNode hashes, in hash-store order
+ *                             frontier   tree.hashes after the batch (popcount(tree_size + n) entries of
+ *                                        a 64-entry buffer, the rest zero), root = tree.root_hash
+ *                             roots      tree.root_hash after each leaf (:81-88)
+ *                             path       what append returned for each leaf (the frontier before it,
+ *                                        smallest subtree first), leaf i's hashes at [path_off[i],
+ *                                        path_off[i+1]) in 32-byte units; path and path_off go together
+ *                           n = 0 returns the input tree's frontier and root (the empty tree's root is
+ *                           SHA-256 of the empty string). Runs on the GPU, or in C++ on the host
+ *                           (pv_merkle_path) when no device is initialised or the batch is small, so it
+ *                           works without a GPU and never returns PV_ERR_NOT_INIT.
+ *   pv_merkle_append_batch_device
+ *                           the same on device buffers, enqueued on `stream` (NULL: the library's)
+ *                           without synchronising. Needs pv_init. d_frontier and every output pointer
+ *                           16-byte aligned; d_data readable to d_off[n] + PV_BLOB_SLACK, and from the
+ *                           4-byte boundary at or below d_data + d_off[0] (records are read as aligned
+ *                           32-bit words, so up to 3 bytes before the first record are touched; their
+ *                           values do not matter). n = 0 fills frontier, root and path_off[0] only.
+ *   pv_merkle_verify_inclusion_batch
+ *                           MerkleVerifier.verify_leaf_inclusion / verify_leaf_hash_inclusion
+ *                           (ledger/merkle_verifier.py:195-266 over :155-181) for n proofs: give either
+ *                           data and off (leaf i = data[off[i] : off[i+1]]) or leaf_hash[32 n]. Proof i is
+ *                           proof[32 proof_off[i] : 32 proof_off[i+1]], checked against root[32 i] for a
+ *                           tree of tree_size[i] leaves at leaf_index[i]. Verdict bit i (LSB-first) = 1 iff
+ *                           the reference returns True. status[i]: 0 compared, 1 tree_size <= leaf_index
+ *                           (the reference's ValueError), 2 proof too short, 3 proof too long.
+ *   pv_merkle_verify_inclusion_batch_device
+ *                           the same on device buffers (16-byte aligned hash arrays); verdicts as
+ *                           ceil(n / 64) 64-bit words like pv_verify_batch_device.
+ *   pv_merkle_chunk         leaves (or proofs) per device pass; larger batches are chained chunk by
+ *                           chunk through the frontier. 0 restores the default, 1,048,576; at most
+ *                           PV_MERKLE_CHUNK_MAX (the upper levels of a chunk run in one workgroup).
+ *   pv_merkle_path          PV_MERKLE_AUTO, PV_MERKLE_HOST, PV_MERKLE_DEVICE, for the two host-buffer entries.
+ *                           AUTO takes the host path without a device and below PV_MERKLE_AUTO_MIN leaves
+ *                           (PV_MERKLE_AUTO_MIN_PROOFS when per-leaf roots or paths are asked for,
+ *                           PV_MERKLE_AUTO_MIN_VERIFY proofs for the check): the smallest measured sizes
+ *                           at which the device path won by more than the run-to-run spread on one
+ *                           MI355X.
+ * Bad arguments (decreasing offsets, tree_size + n >= 2^48, no frontier for tree_size > 0, path without
+ * path_off) return PV_ERR_ARG before anything is launched. */
+#define PV_MERKLE_AUTO 0
+#define PV_MERKLE_HOST 1
+#define PV_MERKLE_DEVICE 2
+#define PV_MERKLE_AUTO_MIN 2048        /* appends: frontier / root / leaf and node hashes only */
+#define PV_MERKLE_AUTO_MIN_PROOFS 1024 /* appends with per-leaf roots or audit paths */
+#define PV_MERKLE_AUTO_MIN_VERIFY 512  /* the proof check */
+#define PV_MERKLE_CHUNK 1048576
+#define PV_MERKLE_CHUNK_MAX 16777216 /* 2^24: the largest chunk pv_merkle_chunk accepts */
+typedef struct {
+    uint8_t* leaf_hash;  /* [32 n] */
+    uint8_t* node_hash;  /* [32 n_nodes] */
+    uint8_t* frontier;   /* [32 * 64] */
+    uint8_t* root;       /* [32] */
+    uint8_t* roots;      /* [32 n] */
+    uint8_t* path;       /* [32 path_hashes] */
+    uint64_t* path_off;  /* [n + 1] */
+} PvMerkleOut;
+int pv_merkle_plan(uint64_t tree_size, uint64_t n, uint64_t* n_nodes, uint64_t* n_frontier, uint64_t* path_hashes);
+int pv_merkle_append_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off,
+                           uint64_t n, const PvMerkleOut* out);
+int pv_merkle_append_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
+                                  const uint64_t* d_off, uint64_t n, const PvMerkleOut* d_out, void* stream);
+int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, const uint8_t* leaf_hash,
+                                     const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* proof,
+                                     const uint64_t* proof_off, const uint8_t* root, uint64_t n, uint8_t* status,
+                                     uint8_t* verdict_bits);
+int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash,
+                                            const uint64_t* d_leaf_index, const uint64_t* d_tree_size,
+                                            const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
+                                            uint64_t n, uint8_t* d_status, uint64_t* d_verdict_words, void* stream);
+int pv_merkle_chunk(uint64_t leaves);
+int pv_merkle_path(int mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,148 @@
+// Host path of the batched Merkle append and audit-proof check: the same contract as the kernels of
+// pv_merkle.hip, in C++ over merkle_core.h (one source for the index arithmetic) and the host SHA-256
+// of signing_json.cpp. pv_merkle_append_batch takes it for small batches (a 3PC batch of ten
+// transactions must not pay kernel launches) and when no device is initialised.
+#include "merkle_host.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "merkle_core.h"
+#include "sha256_host.h"
+
+namespace {
+
+struct H32 {
+    uint8_t b[32];
+};
+
+constexpr unsigned MK_THREADS = 16;
+constexpr uint64_t MK_PER_THREAD = 2048;  // below this much work a thread is not worth starting
+
+// f(lo, hi) over [0, n) split over up to MK_THREADS threads
+template <class F>
+void parallel_for(uint64_t n, const F& f) {
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const uint64_t t = std::min<uint64_t>(std::min(MK_THREADS, hw), (n + MK_PER_THREAD - 1) / MK_PER_THREAD);
+    if (t <= 1) {
+        if (n) f(0, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (uint64_t k = 0; k < t; k++) th.emplace_back([&f, n, t, k] { f(n * k / t, n * (k + 1) / t); });
+    for (auto& x : th) x.join();
+}
+
+void hash_leaf(H32& out, const uint8_t* p, uint64_t len, std::vector<uint8_t>& buf) {
+    buf.resize(len + 1);
+    buf[0] = 0;
+    if (len) memcpy(buf.data() + 1, p, len);
+    pv_sha256_host(buf.data(), len + 1, out.b);
+}
+
+void hash_children(H32& out, const H32& l, const H32& r) {
+    uint8_t m[65];
+    m[0] = 1;
+    memcpy(m + 1, l.b, 32);
+    memcpy(m + 33, r.b, 32);
+    pv_sha256_host(m, 65, out.b);
+}
+
+}  // namespace
+
+void pv_merkle_host_append(uint64_t s, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                           const PvMerkleOut* out) {
+    const H32* oldf = reinterpret_cast<const H32*>(frontier);
+    uint64_t n_nodes, n_front, n_path;
+    pv_merkle_plan_core(s, n, &n_nodes, &n_front, &n_path);
+    std::vector<H32> leaf_own, node_own;
+    H32* leaf = reinterpret_cast<H32*>(out->leaf_hash);
+    H32* node = reinterpret_cast<H32*>(out->node_hash);
+    if (!leaf) {
+        leaf_own.resize(n);
+        leaf = leaf_own.data();
+    }
+    if (!node) {
+        node_own.resize(n_nodes);
+        node = node_own.data();
+    }
+    auto get = [&](const PvMerkleRef& r, H32& o) {
+        o = r.kind == PV_MK_OLD ? oldf[r.idx] : r.kind == PV_MK_LEAF ? leaf[r.idx] : node[r.idx];
+    };
+    auto hash = [](H32& o, const H32& l, const H32& r) { hash_children(o, l, r); };
+
+    parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+        std::vector<uint8_t> buf;
+        for (uint64_t i = lo; i < hi; i++) hash_leaf(leaf[i], data + off[i], off[i + 1] - off[i], buf);
+    });
+    // level h from level h - 1; the nodes of one level are independent
+    for (uint32_t h = 1; h <= PV_MERKLE_MAX_BITS && ((s + n) >> h) != (s >> h); h++) {
+        const uint64_t first = (s >> h) + 1, count = ((s + n) >> h) - (s >> h);
+        parallel_for(count, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t k = lo; k < hi; k++) {
+                const uint64_t u = (first + k) << h;
+                H32 l, r;
+                get(pv_merkle_node_ref(s, u - (1ull << (h - 1)), h - 1), l);
+                get(pv_merkle_node_ref(s, u, h - 1), r);
+                hash_children(node[pv_merkle_node_pos(u, h) - pv_merkle_node_count(s)], l, r);
+            }
+        });
+    }
+    const uint64_t t = s + n;
+    if (out->frontier) {
+        memset(out->frontier, 0, 32 * 64);
+        uint32_t k = pv_popc64(t);
+        for (uint64_t rest = t; rest; rest &= rest - 1)  // ascending bits fill from the back
+            get(pv_merkle_frontier_ref(s, t, (uint32_t)__builtin_ctzll(rest)), reinterpret_cast<H32*>(out->frontier)[--k]);
+    }
+    if (out->root) {
+        H32 acc;
+        if (t == 0) pv_sha256_host(acc.b, 0, acc.b);  // the empty string
+        else pv_merkle_fold_root(acc, s, t, get, hash);
+        memcpy(out->root, acc.b, 32);
+    }
+    if (out->path) {
+        const uint64_t base = pv_merkle_popc_sum(s);
+        parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; i++) {
+                const uint64_t at = pv_merkle_popc_sum(s + i) - base;
+                out->path_off[i] = at;
+                H32* dst = reinterpret_cast<H32*>(out->path) + at;
+                pv_merkle_audit_path(s, s + i, [&](uint32_t k, const PvMerkleRef& r) { get(r, dst[k]); });
+            }
+        });
+        out->path_off[n] = n_path;
+    }
+    if (out->roots)
+        parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; i++)
+                pv_merkle_fold_root(reinterpret_cast<H32*>(out->roots)[i], s, s + i + 1, get, hash);
+        });
+}
+
+void pv_merkle_host_verify(const uint8_t* data, const uint64_t* off, const uint8_t* leaf_hash,
+                           const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* proof,
+                           const uint64_t* proof_off, const uint8_t* root, uint64_t n, uint8_t* status,
+                           uint8_t* verdict_bits) {
+    std::vector<uint8_t> ok(n);
+    parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+        std::vector<uint8_t> buf;
+        for (uint64_t i = lo; i < hi; i++) {
+            H32 acc;
+            if (leaf_hash) memcpy(acc.b, leaf_hash + 32 * i, 32);
+            else hash_leaf(acc, data + off[i], off[i + 1] - off[i], buf);
+            const H32* p = reinterpret_cast<const H32*>(proof) + proof_off[i];
+            const uint32_t st = pv_merkle_path_check(
+                acc, leaf_index[i], tree_size[i], proof_off[i + 1] - proof_off[i],
+                [&](uint64_t k, H32& o) { o = p[k]; }, [](H32& o, const H32& l, const H32& r) { hash_children(o, l, r); });
+            status[i] = (uint8_t)st;
+            ok[i] = st == PV_MK_COMPARED && memcmp(acc.b, root + 32 * i, 32) == 0;
+        }
+    });
+    memset(verdict_bits, 0, (n + 7) / 8);
+    for (uint64_t i = 0; i < n; i++)
+        if (ok[i]) verdict_bits[i >> 3] |= (uint8_t)(1u << (i & 7));
+}

@@ -2875,6 +2875,7 @@ void pinned_cache_drain();
 extern "C" {
 void pv_shutdown(void) {
     pinned_cache_drain();  // freed pv_host_alloc blocks back to the system (live ones stay the caller's)
+    pv_merkle_shutdown();
     {
         std::lock_guard<std::mutex> lk(g_mg_mu);
         mg_destroy_comms();
@@ -4166,6 +4167,7 @@ int pv_stream_destroy(void* stream) {
         if (g_ctx.sg.last_stream == (hipStream_t)stream) g_ctx.sg.last_stream = nullptr;
     }
     pv_ingress_forget_stream(stream);
+    pv_merkle_forget_stream(stream);
     PV_HIP(hipStreamDestroy((hipStream_t)stream), PV_ERR_LAUNCH);
     return PV_OK;
 }

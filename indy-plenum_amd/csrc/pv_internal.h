@@ -12,6 +12,10 @@ hipStream_t pv_engine_stream();
 int pv_fail(int code, const std::string& msg);
 // A caller stream is being destroyed: the ingress workspace stops handing over through it.
 void pv_ingress_forget_stream(void* stream);
+// The same for the Merkle workspace (pv_merkle.hip), and its release in pv_shutdown (before the
+// device contexts go).
+void pv_merkle_forget_stream(void* stream);
+void pv_merkle_shutdown();
 // The latency path (pv_latency.hip): n requests on device buffers, verdict words written on `stream`.
 // run_if (device word, may be null): the kernel exits at once unless *run_if != 0 (AUTO's device-side
 // latency-vs-keyed choice).

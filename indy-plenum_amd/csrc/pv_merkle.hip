@@ -1,0 +1,669 @@
+// The ledger's SHA-256 Merkle tree on the GPU: n sequential CompactMerkleTree.append calls
+// (ledger/compact_merkle_tree.py:95-160) as one batch, and MerkleVerifier.verify_leaf_inclusion
+// (ledger/merkle_verifier.py:155-266) for a batch of proofs. Index arithmetic: merkle_core.h (shared with
+// the host path and the host-compiled check library); hashing: sha256.h.
+//
+// A batch of n leaves appended to a tree of size s needs no sequential walk (merkle_core.h): every hash
+// the reference would write or return is a leaf hash, an aligned node completed inside the batch, or an
+// entry of the input frontier. Per chunk of at most pv_merkle_chunk leaves:
+//   1. pv_merkle_leaf_kernel    one lane per leaf: SHA-256(0x00 || data) over variable-length records at
+//                               any byte offset (aligned 32-bit loads, funnel-shifted; no byte past the
+//                               record's last aligned word is read).
+//   2. pv_merkle_tile_kernel    one workgroup per tile of 1,024 leaves BY ABSOLUTE INDEX: heights 1..10 in
+//                               LDS, every new node also stored at its hash-store position.
+//      pv_merkle_upper_kernel   one workgroup, the same tile routine over heights 10 -> 20 -> 30 -> 40 -> 48
+//                               (few nodes); launched only when the chunk completes a node above height 10.
+//   3. pv_merkle_proof_kernel   (optional) one lane per leaf: its audit path gathered from the input
+//                               frontier, the new nodes and the leaf hashes, and the root after it.
+//   4. pv_merkle_finish_kernel  one wave: the frontier after the chunk (the next chunk's input) and its root.
+// and pv_merkle_verify_kernel, one lane per proof. Launches per chunk: at most five, whatever n is; no
+// host round trip between them.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/plenum_verify.h"
+#include "merkle_core.h"
+#include "merkle_host.h"
+#include "pv_internal.h"
+#include "sha256.h"
+
+namespace {
+
+constexpr int MK_BLOCK = 256;
+
+struct MkHash {
+    uint32_t w[8];  // digest words (sha256.h)
+};
+
+__device__ __forceinline__ MkHash mk_load(const uint32_t* p) {
+    const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
+    const uint32_t le[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    MkHash h;
+    sha256_words_from_le(h.w, le);
+    return h;
+}
+__device__ __forceinline__ void mk_store(uint32_t* p, const MkHash& h) {
+    reinterpret_cast<uint4*>(p)[0] =
+        make_uint4(pv_bswap32(h.w[0]), pv_bswap32(h.w[1]), pv_bswap32(h.w[2]), pv_bswap32(h.w[3]));
+    reinterpret_cast<uint4*>(p)[1] =
+        make_uint4(pv_bswap32(h.w[4]), pv_bswap32(h.w[5]), pv_bswap32(h.w[6]), pv_bswap32(h.w[7]));
+}
+__device__ __forceinline__ void mk_copy(uint32_t* dst, const uint32_t* src) {
+    reinterpret_cast<uint4*>(dst)[0] = reinterpret_cast<const uint4*>(src)[0];
+    reinterpret_cast<uint4*>(dst)[1] = reinterpret_cast<const uint4*>(src)[1];
+}
+__device__ __forceinline__ MkHash mk_children(const MkHash& l, const MkHash& r) {
+    MkHash o;
+    sha256_hash_children(o.w, l.w, r.w);
+    return o;
+}
+
+// The chunk's view of the tree: the input frontier, its leaf hashes and its new nodes (32-byte hashes,
+// 16-byte aligned).
+struct MkView {
+    uint64_t s, n;
+    const uint32_t* oldf;
+    const uint32_t* leaf;
+    const uint32_t* node;
+    __device__ __forceinline__ const uint32_t* at(const PvMerkleRef& r) const {
+        return (r.kind == PV_MK_OLD ? oldf : r.kind == PV_MK_LEAF ? leaf : node) + 8 * r.idx;
+    }
+};
+
+__device__ __forceinline__ MkHash mk_leaf_hash(const uint8_t* data, uint64_t len) {
+    MkHash h;
+    const PvRecordWords words(data, len);
+    sha256_prefixed<1>(h.w, 0u, len, words);
+    return h;
+}
+
+// ------------------------------------------------------------------------------------------ kernels
+
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_leaf_kernel(const uint8_t* __restrict__ data,
+                                                                  const uint64_t* __restrict__ off, uint64_t n,
+                                                                  uint32_t* __restrict__ leaf) {
+    const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t a = off[i], b = off[i + 1];
+    mk_store(leaf + 8 * i, mk_leaf_hash(data + a, b - a));
+}
+
+// Tile k of pass h0 (merkle_core.h): entries of height h0 into LDS, heights h0 + 1 .. h0 + 10 reduced in
+// place (node q of level l lives in the slot of its leftmost entry, q << l), each new node also stored
+// at its hash-store position. Called by every thread of the workgroup.
+__device__ __forceinline__ void mk_tile_reduce(uint32_t h0, uint64_t k, const MkView& v, uint32_t* node_out, uint4* lds) {
+    const uint64_t base = pv_merkle_node_count(v.s);
+    for (uint32_t e = threadIdx.x; e < PV_MERKLE_TILE; e += MK_BLOCK) {
+        const uint64_t u = ((k << PV_MERKLE_TILE_LOG) + e + 1) << h0;
+        if (pv_merkle_is_new(v.s, v.n, u)) {
+            const uint32_t* src = v.at(pv_merkle_node_ref(v.s, u, h0));
+            lds[2 * e] = reinterpret_cast<const uint4*>(src)[0];
+            lds[2 * e + 1] = reinterpret_cast<const uint4*>(src)[1];
+        }
+    }
+    __syncthreads();
+    for (uint32_t l = 1; l <= PV_MERKLE_TILE_LOG; l++) {
+        const uint32_t h = h0 + l;
+        if (h > PV_MERKLE_MAX_BITS) break;  // uniform
+        for (uint32_t q = threadIdx.x; q < (PV_MERKLE_TILE >> l); q += MK_BLOCK) {
+            const uint64_t u = ((k << PV_MERKLE_TILE_LOG) + ((uint64_t)(q + 1) << l)) << h0;
+            if (!pv_merkle_is_new(v.s, v.n, u)) continue;
+            const uint32_t ls = (2 * q) << (l - 1), rs = (2 * q + 1) << (l - 1);
+            // the left child ends at u - 2^(h-1): inside the old tree it is the input frontier's entry for bit h - 1
+            const bool left_new = u - (1ull << (h - 1)) > v.s;
+            const uint32_t* lp = left_new ? reinterpret_cast<const uint32_t*>(lds + 2 * ls)
+                                          : v.oldf + 8 * pv_popc64(v.s >> h);
+            const MkHash left = mk_load(lp), right = mk_load(reinterpret_cast<const uint32_t*>(lds + 2 * rs));
+            const MkHash out = mk_children(left, right);
+            mk_store(reinterpret_cast<uint32_t*>(lds + 2 * ls), out);
+            mk_store(node_out + 8 * (pv_merkle_node_pos(u, h) - base), out);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_tile_kernel(MkView v, uint64_t tile_first, uint32_t* node_out) {
+    __shared__ uint4 lds[2 * PV_MERKLE_TILE];
+    mk_tile_reduce(0, tile_first + blockIdx.x, v, node_out, lds);
+}
+
+// Heights above 10: one workgroup walks the passes h0 = 10, 20, ... while the chunk completes a node above
+// h0; a pass reads the nodes of height h0 the previous pass (or the tile kernel) stored.
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_upper_kernel(MkView v, uint32_t* node_out) {
+    __shared__ uint4 lds[2 * PV_MERKLE_TILE];
+    for (uint32_t h0 = PV_MERKLE_TILE_LOG; h0 < PV_MERKLE_MAX_BITS && pv_merkle_any_above(v.s, v.n, h0);
+         h0 += PV_MERKLE_TILE_LOG) {
+        uint64_t first, count;
+        pv_merkle_tiles(v.s, v.n, h0, &first, &count);
+        for (uint64_t k = 0; k < count; k++) {
+            mk_tile_reduce(h0, first + k, v, node_out, lds);
+            __syncthreads();
+        }
+        __threadfence_block();  // the next pass reads this pass's stores
+    }
+}
+
+// One lane per leaf i of the chunk (appended at size t = s + i): path (may be null) receives its audit
+// path at path[32 (path_off[i] - poff_base)...], path_off[i] = poff_base + hashes of the chunk's earlier
+// leaves; roots (may be null) the root after the leaf.
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_proof_kernel(MkView v, uint32_t* __restrict__ path,
+                                                                   uint64_t* __restrict__ path_off,
+                                                                   uint64_t poff_base, uint32_t* __restrict__ roots) {
+    const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    if (i >= v.n) return;
+    const uint64_t t = v.s + i;
+    if (path) {
+        const uint64_t at = pv_merkle_popc_sum(t) - pv_merkle_popc_sum(v.s);
+        path_off[i] = poff_base + at;
+        if (i == v.n - 1) path_off[v.n] = poff_base + at + pv_popc64(t);
+        uint32_t* dst = path + 8 * at;
+        pv_merkle_audit_path(v.s, t, [&](uint32_t k, const PvMerkleRef& r) { mk_copy(dst + 8 * k, v.at(r)); });
+    }
+    if (roots) {
+        MkHash acc;
+        pv_merkle_fold_root(
+            acc, v.s, t + 1, [&](const PvMerkleRef& r, MkHash& o) { o = mk_load(v.at(r)); },
+            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+        mk_store(roots + 8 * i, acc);
+    }
+}
+
+// One wave: the frontier of size s + n (largest subtree first, the rest of the 64 entries zero) and, if
+// asked for, its root (n = 0: the input tree's).
+__global__ __launch_bounds__(64) void pv_merkle_finish_kernel(MkView v, uint32_t* __restrict__ frontier,
+                                                              uint32_t* __restrict__ root) {
+    const uint64_t t = v.s + v.n;
+    const uint32_t lane = threadIdx.x, m = pv_popc64(t);
+    // entry `lane` is the lane-th set bit of t from the top
+    uint64_t rest = t;
+    for (uint32_t k = 0; k < m - 1 - lane && lane < m; k++) rest &= rest - 1;  // drop the m - 1 - lane lowest bits
+    if (lane < m) {
+        mk_copy(frontier + 8 * lane, v.at(pv_merkle_frontier_ref(v.s, t, (uint32_t)__builtin_ctzll(rest))));
+    } else {
+        reinterpret_cast<uint4*>(frontier + 8 * lane)[0] = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4*>(frontier + 8 * lane)[1] = make_uint4(0, 0, 0, 0);
+    }
+    if (root && lane == 0 && t == 0) {  // the empty tree: SHA-256 of the empty string
+        const MkHash empty{{0xe3b0c442u, 0x98fc1c14u, 0x9afbf4c8u, 0x996fb924u, 0x27ae41e4u, 0x649b934cu, 0xa495991bu, 0x7852b855u}};
+        mk_store(root, empty);
+    } else if (root && lane == 0) {
+        MkHash acc;
+        pv_merkle_fold_root(
+            acc, v.s, t, [&](const PvMerkleRef& r, MkHash& o) { o = mk_load(v.at(r)); },
+            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+        mk_store(root, acc);
+    }
+}
+
+// One lane per proof; verdict word w bit b = proof 64 w + b (one ballot per wave).
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
+    const uint8_t* __restrict__ data, const uint64_t* __restrict__ off, const uint32_t* __restrict__ leaf_hash,
+    const uint64_t* __restrict__ leaf_index, const uint64_t* __restrict__ tree_size, const uint32_t* __restrict__ proof,
+    const uint64_t* __restrict__ proof_off, const uint32_t* __restrict__ root, uint64_t n, uint8_t* __restrict__ status,
+    uint64_t* __restrict__ verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    bool ok = false;
+    if (i < n) {
+        MkHash acc;
+        if (leaf_hash) {
+            acc = mk_load(leaf_hash + 8 * i);
+        } else {
+            const uint64_t a = off[i], b = off[i + 1];
+            acc = mk_leaf_hash(data + a, b - a);
+        }
+        const uint64_t p0 = proof_off[i], plen = proof_off[i + 1] - p0;
+        const uint32_t st = pv_merkle_path_check(
+            acc, leaf_index[i], tree_size[i], plen, [&](uint64_t k, MkHash& o) { o = mk_load(proof + 8 * (p0 + k)); },
+            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+        status[i] = (uint8_t)st;
+        if (st == PV_MK_COMPARED) {
+            const MkHash want = mk_load(root + 8 * i);
+            uint32_t diff = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) diff |= acc.w[k] ^ want.w[k];
+            ok = diff == 0;
+        }
+    }
+    const uint64_t word = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && i < n) verdict[i >> 6] = word;
+}
+
+// --------------------------------------------------------------------------------------------- host
+
+#define MK_HIP(call, code)                                                                          \
+    do {                                                                                            \
+        hipError_t e_ = (call);                                                                     \
+        if (e_ != hipSuccess) return pv_fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// The Merkle code's own workspace: allocated on first use (an engine that never hashes a leaf holds
+// nothing), freed by pv_shutdown, handed over between caller streams by an event as the signing
+// workspace is. Launches are serialised on g_mk_mu.
+struct MkWork {
+    uint32_t* leaf = nullptr;  // a chunk's leaf hashes / new nodes when the caller does not take them
+    uint64_t leaf_cap = 0;
+    uint32_t* node = nullptr;
+    uint64_t node_cap = 0;
+    uint32_t* front = nullptr;  // three frontiers of 64 hashes: two for chunk chaining, one for a host entry's input
+    uint8_t* d_in = nullptr;    // host entries: staged inputs and outputs of one chunk
+    uint64_t d_in_cap = 0;
+    uint8_t* d_out = nullptr;
+    uint64_t d_out_cap = 0;
+    hipEvent_t ev_done = nullptr;
+    hipStream_t last_stream = nullptr;
+};
+MkWork g_mk;
+std::mutex g_mk_mu;
+uint64_t g_mk_chunk = PV_MERKLE_CHUNK;
+int g_mk_path = PV_MERKLE_AUTO;
+constexpr uint64_t MK_CHUNK_BYTES = 1ull << 30;  // a host-entry chunk also ends at this many data bytes
+constexpr uint64_t MK_FRONT_BYTES = 64 * 32;
+
+uint64_t mk_up(uint64_t x) { return (x + 255) & ~255ull; }
+
+template <class T>
+int mk_grow(T*& p, uint64_t& cap, uint64_t want) {
+    if (want <= cap) return PV_OK;
+    if (p) (void)hipFree(p);  // synchronises: no launch still reads the old block
+    p = nullptr;
+    cap = 0;
+    MK_HIP(hipMalloc((void**)&p, want), PV_ERR_ALLOC);
+    cap = want;
+    return PV_OK;
+}
+
+// The hand-over: `stream` waits for the workspace's last user. Caller holds g_mk_mu.
+int mk_begin(hipStream_t stream) {
+    if (!g_mk.front) MK_HIP(hipMalloc((void**)&g_mk.front, 3 * MK_FRONT_BYTES), PV_ERR_ALLOC);
+    if (!g_mk.ev_done) MK_HIP(hipEventCreateWithFlags(&g_mk.ev_done, hipEventDisableTiming), PV_ERR_NO_DEVICE);
+    if (g_mk.last_stream && g_mk.last_stream != stream) MK_HIP(hipStreamWaitEvent(stream, g_mk.ev_done, 0), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+int mk_end(hipStream_t stream) {
+    MK_HIP(hipEventRecord(g_mk.ev_done, stream), PV_ERR_LAUNCH);
+    g_mk.last_stream = stream;
+    return PV_OK;
+}
+uint32_t* mk_front(int which) { return g_mk.front + which * (MK_FRONT_BYTES / 4); }
+
+struct MkChunkOut {  // device pointers, null = not wanted
+    uint32_t* leaf;
+    uint32_t* node;
+    uint32_t* roots;
+    uint32_t* path;
+    uint64_t* path_off;
+    uint64_t poff_base;
+    uint32_t* root;
+};
+
+// One chunk: m > 0 leaves (d_off[0..m] into d_data) appended at size s with input frontier d_fin; the
+// frontier after it goes to d_fout. Caller holds g_mk_mu and ran mk_begin.
+int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uint64_t* d_off, uint64_t m,
+             const MkChunkOut& o, uint32_t* d_fout, hipStream_t stream) {
+    uint64_t n_nodes, n_front, n_path;
+    pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
+    uint32_t* leaf = o.leaf;
+    uint32_t* node = o.node;
+    int rc;
+    if (!leaf) {
+        if ((rc = mk_grow(g_mk.leaf, g_mk.leaf_cap, std::max<uint64_t>(m, 4096) * 32))) return rc;
+        leaf = g_mk.leaf;
+    }
+    if (!node) {
+        if ((rc = mk_grow(g_mk.node, g_mk.node_cap, (std::max<uint64_t>(m, 4096) + 64) * 32))) return rc;  // n_nodes < m + 48
+        node = g_mk.node;
+    }
+    const MkView v{s, m, d_fin, leaf, node};
+    const unsigned grid = (unsigned)((m + MK_BLOCK - 1) / MK_BLOCK);
+    hipLaunchKernelGGL(pv_merkle_leaf_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, d_data, d_off, m, leaf);
+    MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    if (n_nodes) {
+        uint64_t first, count;
+        pv_merkle_tiles(s, m, 0, &first, &count);
+        hipLaunchKernelGGL(pv_merkle_tile_kernel, dim3((unsigned)count), dim3(MK_BLOCK), 0, stream, v, first, node);
+        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        if (pv_merkle_any_above(s, m, PV_MERKLE_TILE_LOG)) {
+            hipLaunchKernelGGL(pv_merkle_upper_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, v, node);
+            MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        }
+    }
+    if (o.path || o.roots) {
+        hipLaunchKernelGGL(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
+                           o.poff_base, o.roots);
+        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    }
+    hipLaunchKernelGGL(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
+    MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+int mk_check_out(const PvMerkleOut* out, const char* who) {
+    if (!out) return pv_fail(PV_ERR_ARG, std::string(who) + ": null output struct");
+    if ((out->path != nullptr) != (out->path_off != nullptr))
+        return pv_fail(PV_ERR_ARG, std::string(who) + ": path and path_off go together");
+    return PV_OK;
+}
+bool mk_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// Device buffers, n > 0, on `stream`. Caller holds g_mk_mu.
+int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, const uint64_t* d_off, uint64_t n,
+               const PvMerkleOut& out, hipStream_t stream) {
+    int rc = mk_begin(stream);
+    if (rc) return rc;
+    const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
+    int cur = 0;
+    const uint32_t* fin = reinterpret_cast<const uint32_t*>(d_frontier);
+    if (n == 0) {  // the input tree's frontier and root
+        const MkView v{s0, 0, fin, nullptr, nullptr};
+        hipLaunchKernelGGL(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, mk_front(0),
+                           reinterpret_cast<uint32_t*>(out.root));
+        if (hipGetLastError() != hipSuccess) rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: launch failed");
+        if (out.path_off && hipMemsetAsync(out.path_off, 0, 8, stream) != hipSuccess)  // path_off[0] = 0, as the host path
+            rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: path_off[0] store failed");
+        fin = mk_front(0);
+    }
+    for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += g_mk_chunk) {
+        const uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0), s = s0 + c0;
+        const bool is_last = c0 + m == n;
+        const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
+        const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(out.leaf_hash + 32 * c0) : nullptr,
+                           out.node_hash ? reinterpret_cast<uint32_t*>(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0))
+                                         : nullptr,
+                           out.roots ? reinterpret_cast<uint32_t*>(out.roots + 32 * c0) : nullptr,
+                           out.path ? reinterpret_cast<uint32_t*>(out.path + 32 * pbase) : nullptr,
+                           out.path ? out.path_off + c0 : nullptr,
+                           pbase,
+                           is_last ? reinterpret_cast<uint32_t*>(out.root) : nullptr};
+        rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream);
+        fin = mk_front(cur);
+        cur ^= 1;
+    }
+    if (rc == PV_OK && out.frontier)
+        if (hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: frontier copy failed");
+    const int rc2 = mk_end(stream);
+    return rc ? rc : rc2;
+}
+
+// The device path of the host entry: chunk by chunk through the staging blocks. Arguments validated, n > 0.
+int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                         const PvMerkleOut& out) {
+    const hipStream_t st = pv_engine_stream();
+    int rc = mk_begin(st);
+    if (rc) return rc;
+    auto run = [&]() -> int {
+        const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
+        if (s0) MK_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        const uint32_t* fin = mk_front(2);
+        int cur = 0;
+        std::vector<uint64_t> rebased;
+        for (uint64_t c0 = 0; c0 < n;) {
+            uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0);
+            if (off[c0 + m] - off[c0] > MK_CHUNK_BYTES) {  // the byte bound: the longest prefix within it, at least one leaf
+                const uint64_t* e = std::upper_bound(off + c0 + 1, off + c0 + m + 1, off[c0] + MK_CHUNK_BYTES);
+                m = std::max<uint64_t>(1, (uint64_t)(e - (off + c0)) - 1);
+            }
+            const uint64_t s = s0 + c0, base = off[c0], bytes = off[c0 + m] - base;
+            const bool is_last = c0 + m == n;
+            uint64_t n_nodes, n_front, n_path;
+            pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
+            // inputs: [offsets, rebased][data + slack]; outputs: [leaf][node][roots][path_off][path][root]
+            const uint64_t i_off = 0, i_data = mk_up((m + 1) * 8), i_total = i_data + mk_up(bytes + PV_BLOB_SLACK);
+            const uint64_t o_leaf = 0, o_node = o_leaf + (out.leaf_hash ? mk_up(32 * m) : 0),
+                           o_roots = o_node + (out.node_hash ? mk_up(32 * n_nodes) : 0),
+                           o_poff = o_roots + (out.roots ? mk_up(32 * m) : 0),
+                           o_path = o_poff + (out.path ? mk_up(8 * (m + 1)) : 0),
+                           o_root = o_path + (out.path ? mk_up(32 * n_path) : 0), o_total = o_root + 256;
+            int rc;
+            if ((rc = mk_grow(g_mk.d_in, g_mk.d_in_cap, i_total)) || (rc = mk_grow(g_mk.d_out, g_mk.d_out_cap, o_total)))
+                return rc;
+            rebased.resize(m + 1);
+            for (uint64_t i = 0; i <= m; i++) rebased[i] = off[c0 + i] - base;
+            MK_HIP(hipMemcpyAsync(g_mk.d_in + i_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+            if (bytes) MK_HIP(hipMemcpyAsync(g_mk.d_in + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+            uint8_t* d = g_mk.d_out;
+            const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
+            const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(d + o_leaf) : nullptr,
+                               out.node_hash ? reinterpret_cast<uint32_t*>(d + o_node) : nullptr,
+                               out.roots ? reinterpret_cast<uint32_t*>(d + o_roots) : nullptr,
+                               out.path ? reinterpret_cast<uint32_t*>(d + o_path) : nullptr,
+                               out.path ? reinterpret_cast<uint64_t*>(d + o_poff) : nullptr,
+                               pbase,
+                               is_last && out.root ? reinterpret_cast<uint32_t*>(d + o_root) : nullptr};
+            if ((rc = mk_chunk(s, fin, g_mk.d_in + i_data, reinterpret_cast<const uint64_t*>(g_mk.d_in + i_off), m, o,
+                               mk_front(cur), st)))
+                return rc;
+            fin = mk_front(cur);
+            cur ^= 1;
+            if (out.leaf_hash)
+                MK_HIP(hipMemcpyAsync(out.leaf_hash + 32 * c0, d + o_leaf, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            if (out.node_hash && n_nodes)
+                MK_HIP(hipMemcpyAsync(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0), d + o_node, 32 * n_nodes,
+                                      hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            if (out.roots)
+                MK_HIP(hipMemcpyAsync(out.roots + 32 * c0, d + o_roots, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            if (out.path) {
+                MK_HIP(hipMemcpyAsync(out.path_off + c0, d + o_poff, 8 * (m + 1), hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                if (n_path)
+                    MK_HIP(hipMemcpyAsync(out.path + 32 * pbase, d + o_path, 32 * n_path, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            }
+            if (is_last) {
+                if (out.root) MK_HIP(hipMemcpyAsync(out.root, d + o_root, 32, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                if (out.frontier) MK_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            }
+            MK_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);  // the staging blocks are free for the next chunk
+            c0 += m;
+        }
+        return PV_OK;
+    };
+    rc = run();
+    const int rc2 = mk_end(st);
+    return rc ? rc : rc2;
+}
+
+int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash, const uint64_t* d_index,
+                      const uint64_t* d_size, const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
+                      uint64_t n, uint8_t* d_status, uint64_t* d_verdict, hipStream_t stream) {
+    const uint64_t chunk = (g_mk_chunk + 63) & ~63ull;  // whole verdict words per chunk
+    for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint64_t m = std::min<uint64_t>(chunk, n - c0);
+        hipLaunchKernelGGL(pv_merkle_verify_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
+                           stream, d_data, d_off ? d_off + c0 : nullptr,
+                           d_leaf_hash ? reinterpret_cast<const uint32_t*>(d_leaf_hash + 32 * c0) : nullptr, d_index + c0,
+                           d_size + c0, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off + c0,
+                           reinterpret_cast<const uint32_t*>(d_root + 32 * c0), m, d_status + c0, d_verdict + c0 / 64);
+        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    }
+    return PV_OK;
+}
+
+bool mk_monotone(const uint64_t* o, uint64_t k) {
+    for (uint64_t i = 0; i < k; i++)
+        if (o[i + 1] < o[i]) return false;
+    return true;
+}
+
+}  // namespace
+
+void pv_merkle_forget_stream(void* stream) {
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    if (g_mk.last_stream == (hipStream_t)stream) g_mk.last_stream = nullptr;
+}
+
+void pv_merkle_shutdown() {
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    for (void* p : {(void*)g_mk.leaf, (void*)g_mk.node, (void*)g_mk.front, (void*)g_mk.d_in, (void*)g_mk.d_out})
+        if (p) (void)hipFree(p);
+    if (g_mk.ev_done) (void)hipEventDestroy(g_mk.ev_done);
+    g_mk = MkWork();
+}
+
+extern "C" {
+
+int pv_merkle_plan(uint64_t tree_size, uint64_t n, uint64_t* n_nodes, uint64_t* n_frontier, uint64_t* path_hashes) {
+    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_plan: tree_size + n must stay below 2^48");
+    uint64_t a, b, c;
+    pv_merkle_plan_core(tree_size, n, &a, &b, &c);
+    if (n_nodes) *n_nodes = a;
+    if (n_frontier) *n_frontier = b;
+    if (path_hashes) *path_hashes = c;
+    return PV_OK;
+}
+
+int pv_merkle_chunk(uint64_t leaves) {
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    if (leaves > PV_MERKLE_CHUNK_MAX) return pv_fail(PV_ERR_ARG, "pv_merkle_chunk: more than 2^24 leaves");
+    g_mk_chunk = leaves ? leaves : PV_MERKLE_CHUNK;
+    return PV_OK;
+}
+
+int pv_merkle_path(int mode) {
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    if (mode != PV_MERKLE_AUTO && mode != PV_MERKLE_HOST && mode != PV_MERKLE_DEVICE)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_path: unknown mode");
+    g_mk_path = mode;
+    return PV_OK;
+}
+
+int pv_merkle_append_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off,
+                           uint64_t n, const PvMerkleOut* out) {
+    int rc = mk_check_out(out, "pv_merkle_append_batch");
+    if (rc) return rc;
+    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: tree_size + n must stay below 2^48");
+    if (tree_size > 0 && !frontier) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: a tree of size > 0 needs its frontier");
+    if (n > 0) {
+        if (!off) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null offsets");
+        if (!mk_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: offsets must be non-decreasing");
+        if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null data");
+    }
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    const bool have_dev = pv_engine_stream() != nullptr;
+    if (g_mk_path == PV_MERKLE_DEVICE && !have_dev)
+        return pv_fail(PV_ERR_NO_DEVICE, "pv_merkle_append_batch: the device path is forced and no device is initialised");
+    const uint64_t auto_min = out->roots || out->path ? PV_MERKLE_AUTO_MIN_PROOFS : PV_MERKLE_AUTO_MIN;
+    const bool device = n > 0 && have_dev && (g_mk_path == PV_MERKLE_DEVICE || (g_mk_path == PV_MERKLE_AUTO && n >= auto_min));
+    if (!device) {
+        lk.unlock();  // the host path shares no workspace: CPU-only callers run side by side
+        pv_merkle_host_append(tree_size, frontier, data, off, n, out);
+        return PV_OK;
+    }
+    return mk_host_entry_device(tree_size, frontier, data, off, n, *out);
+}
+
+int pv_merkle_append_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
+                                  const uint64_t* d_off, uint64_t n, const PvMerkleOut* d_out, void* stream) {
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_merkle_append_batch_device: call pv_init first");
+    int rc = mk_check_out(d_out, "pv_merkle_append_batch_device");
+    if (rc) return rc;
+    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: tree_size + n must stay below 2^48");
+    if (tree_size > 0 && !d_frontier)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: a tree of size > 0 needs its frontier");
+    if (n > 0 && (!d_data || !d_off)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: null pointer");
+    for (const void* p : {(const void*)d_frontier, (const void*)d_out->leaf_hash, (const void*)d_out->node_hash,
+                          (const void*)d_out->frontier, (const void*)d_out->root, (const void*)d_out->roots,
+                          (const void*)d_out->path})
+        if (mk_misaligned(p)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: hash arrays must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, stream ? (hipStream_t)stream : pv_engine_stream());
+}
+
+int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, const uint8_t* leaf_hash,
+                                     const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* proof,
+                                     const uint64_t* proof_off, const uint8_t* root, uint64_t n, uint8_t* status,
+                                     uint8_t* verdict_bits) {
+    if (n == 0) return PV_OK;
+    if (!leaf_index || !tree_size || !proof_off || !root || !status || !verdict_bits)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: null pointer");
+    if ((leaf_hash != nullptr) == (off != nullptr))
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: give either data and off, or leaf_hash");
+    if (off && (!mk_monotone(off, n) || (!data && off[n] != off[0])))
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: offsets must be non-decreasing over a data blob");
+    if (!mk_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: proof offsets must be non-decreasing over a proof array");
+    if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: more than 2^32 - 1 proofs");
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    const bool have_dev = pv_engine_stream() != nullptr;
+    if (g_mk_path == PV_MERKLE_DEVICE && !have_dev)
+        return pv_fail(PV_ERR_NO_DEVICE, "pv_merkle_verify_inclusion_batch: the device path is forced and no device is initialised");
+    if (!(have_dev && (g_mk_path == PV_MERKLE_DEVICE || (g_mk_path == PV_MERKLE_AUTO && n >= PV_MERKLE_AUTO_MIN_VERIFY)))) {
+        lk.unlock();
+        pv_merkle_host_verify(data, off, leaf_hash, leaf_index, tree_size, proof, proof_off, root, n, status, verdict_bits);
+        return PV_OK;
+    }
+    const hipStream_t st = pv_engine_stream();
+    int rc = mk_begin(st);
+    if (rc) return rc;
+    auto run = [&]() -> int {
+        // staged whole: [leaf off | leaf hashes][index][size][proof off, rebased][root][data + slack | -][proof]; out: [status][words]
+        const uint64_t dbase = off ? off[0] : 0, dbytes = off ? off[n] - dbase : 0;
+        const uint64_t pbase = proof_off[0], phashes = proof_off[n] - pbase;
+        const uint64_t i_leaf = 0, i_index = mk_up(off ? (n + 1) * 8 : 32 * n), i_size = i_index + mk_up(8 * n),
+                       i_poff = i_size + mk_up(8 * n), i_root = i_poff + mk_up(8 * (n + 1)),
+                       i_data = i_root + mk_up(32 * n), i_proof = i_data + (off ? mk_up(dbytes + PV_BLOB_SLACK) : 0),
+                       i_total = i_proof + mk_up(32 * phashes + 32);
+        const uint64_t o_status = 0, o_words = mk_up(n), o_total = o_words + mk_up((n + 63) / 64 * 8);
+        int rc;
+        if ((rc = mk_grow(g_mk.d_in, g_mk.d_in_cap, i_total)) || (rc = mk_grow(g_mk.d_out, g_mk.d_out_cap, o_total))) return rc;
+        uint8_t* d = g_mk.d_in;
+        // every copy on st; the temporaries live until the synchronisation below
+        std::vector<uint64_t> loff(off ? n + 1 : 0), poff(n + 1);
+        auto h2d = [&](uint64_t at, const void* src, uint64_t bytes) {
+            return bytes ? hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+        };
+        if (off) {
+            for (uint64_t i = 0; i <= n; i++) loff[i] = off[i] - dbase;
+            MK_HIP(h2d(i_leaf, loff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
+            MK_HIP(h2d(i_data, data + dbase, dbytes), PV_ERR_LAUNCH);
+        } else {
+            MK_HIP(h2d(i_leaf, leaf_hash, 32 * n), PV_ERR_LAUNCH);
+        }
+        for (uint64_t i = 0; i <= n; i++) poff[i] = proof_off[i] - pbase;
+        MK_HIP(h2d(i_poff, poff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
+        MK_HIP(h2d(i_index, leaf_index, 8 * n), PV_ERR_LAUNCH);
+        MK_HIP(h2d(i_size, tree_size, 8 * n), PV_ERR_LAUNCH);
+        MK_HIP(h2d(i_root, root, 32 * n), PV_ERR_LAUNCH);
+        MK_HIP(h2d(i_proof, proof + 32 * pbase, 32 * phashes), PV_ERR_LAUNCH);
+        if ((rc = mk_verify_enqueue(off ? d + i_data : nullptr, off ? reinterpret_cast<const uint64_t*>(d + i_leaf) : nullptr,
+                                    off ? nullptr : d + i_leaf, reinterpret_cast<const uint64_t*>(d + i_index),
+                                    reinterpret_cast<const uint64_t*>(d + i_size), d + i_proof,
+                                    reinterpret_cast<const uint64_t*>(d + i_poff), d + i_root, n, g_mk.d_out + o_status,
+                                    reinterpret_cast<uint64_t*>(g_mk.d_out + o_words), st)))
+            return rc;
+        MK_HIP(hipMemcpyAsync(status, g_mk.d_out + o_status, n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        MK_HIP(hipMemcpyAsync(verdict_bits, g_mk.d_out + o_words, (n + 7) / 8, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        MK_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+        return PV_OK;
+    };
+    rc = run();
+    const int rc2 = mk_end(st);
+    return rc ? rc : rc2;
+}
+
+int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash,
+                                            const uint64_t* d_leaf_index, const uint64_t* d_tree_size,
+                                            const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
+                                            uint64_t n, uint8_t* d_status, uint64_t* d_verdict_words, void* stream) {
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_merkle_verify_inclusion_batch_device: call pv_init first");
+    if (n == 0) return PV_OK;
+    if (!d_leaf_index || !d_tree_size || !d_proof || !d_proof_off || !d_root || !d_status || !d_verdict_words)
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: null pointer");
+    if ((d_leaf_hash != nullptr) == (d_off != nullptr) || (d_off && !d_data))
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: give either data and off, or leaf_hash");
+    if (mk_misaligned(d_leaf_hash) || mk_misaligned(d_proof) || mk_misaligned(d_root))
+        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: hash arrays must be 16-byte aligned");
+    if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: more than 2^32 - 1 proofs");
+    std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
+    return mk_verify_enqueue(d_data, d_off, d_leaf_hash, d_leaf_index, d_tree_size, d_proof, d_proof_off, d_root, n, d_status,
+                             d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+}
+
+}  // extern "C"

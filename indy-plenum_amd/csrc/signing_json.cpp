@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/plenum_verify.h"
+#include "sha256_host.h"
 
 int pv_fail(int code, const std::string& msg);  // pv_engine.hip
 
@@ -820,6 +821,8 @@ void plan_one(const Doc& d, uint32_t root, bool plugins, PlanOut& o) {
 }
 
 }  // namespace
+
+void pv_sha256_host(const uint8_t* data, size_t len, uint8_t out[32]) { sha256(data, len, out); }
 
 extern "C" int pv_wire_plan(const char* json, const uint64_t* off, uint64_t n, const char* plugin_fields, int threads,
                             PvWirePlan* P) {

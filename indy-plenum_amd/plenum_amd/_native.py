@@ -15,7 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PLENUM_AMD_LIB", os.path.join(_HERE, "libplenum_verify.so"))
 
 PV_OK = 0
+PV_ERR_NO_DEVICE = -1
 PV_ERR_ARG = -4
+PV_ERR_NOT_INIT = -5
 PV_BLOB_SLACK = 256
 PV_ABI_VERSION = 1
 PV_SIGN_CHUNK = 262144  # messages per launch inside pv_sign_batch (csrc/pv_engine.hip PV_SIGN_CHUNK)
@@ -106,6 +108,17 @@ SIGNATURES = {
                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
     "pv_sign_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_merkle_plan": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _c_u64p, _c_u64p, _c_u64p]),
+    "pv_merkle_append_batch": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p]),
+    "pv_merkle_append_batch_device": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_merkle_verify_inclusion_batch": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                                ctypes.c_void_p]),
+    "pv_merkle_verify_inclusion_batch_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_merkle_chunk": (ctypes.c_int, [ctypes.c_uint64]),
+    "pv_merkle_path": (ctypes.c_int, [ctypes.c_int]),
 }
 
 
@@ -569,3 +582,124 @@ class KeyCache:
             raise ValueError("keys must be 32 bytes each")
         return bool(lib().pv_key_cache_contains(_ptr(b)))
 
+
+
+# ------------------------------------------------------------------------------------------ Merkle
+PV_MERKLE_AUTO, PV_MERKLE_HOST, PV_MERKLE_DEVICE = 0, 1, 2
+PV_MERKLE_AUTO_MIN = 2048   # include/plenum_verify.h: AUTO takes the device path from this many leaves
+PV_MERKLE_AUTO_MIN_PROOFS = 1024  # the same when per-leaf roots or audit paths are asked for
+PV_MERKLE_AUTO_MIN_VERIFY = 512  # proofs from which AUTO checks on the device
+PV_MERKLE_CHUNK = 1048576
+MERKLE_OUTPUTS = ("leaf_hash", "node_hash", "frontier", "root", "roots", "path")
+
+
+class PvMerkleOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("leaf_hash", "node_hash", "frontier", "root", "roots", "path", "path_off")]
+
+
+def merkle_plan(tree_size, n):
+    """(new node hashes, frontier length after, hashes of all audit paths) of n appends to tree_size leaves."""
+    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib().pv_merkle_plan(tree_size, n, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "pv_merkle_plan")
+    return a.value, b.value, c.value
+
+
+def merkle_chunk(leaves=0):
+    check(lib().pv_merkle_chunk(leaves), "pv_merkle_chunk")
+
+
+_merkle_mode = PV_MERKLE_AUTO
+_merkle_no_device = False  # a device was looked for once and none is visible
+
+
+def merkle_path(mode=PV_MERKLE_AUTO):
+    global _merkle_mode
+    check(lib().pv_merkle_path(mode), "pv_merkle_path")
+    _merkle_mode = mode
+
+
+def _merkle_device_ready(n, auto_min):
+    """Bind a GPU only for a call that will take the device path (mode DEVICE, or AUTO at or above its
+    threshold): a process that only hashes small batches, or runs where no GPU is visible, never builds
+    the verification engine's context; the library's host path serves it. The look for a device happens once."""
+    global _merkle_no_device
+    if _device is not None or _merkle_no_device or _merkle_mode == PV_MERKLE_HOST:
+        return
+    if _merkle_mode == PV_MERKLE_AUTO and n < auto_min:
+        return
+    try:
+        ensure_device()
+    except NativeUnavailable:
+        _merkle_no_device = True
+
+
+def merkle_append(tree_size, frontier, blob, off, want=MERKLE_OUTPUTS):
+    """n sequential CompactMerkleTree.append calls as one pv_merkle_append_batch: leaf i = blob[off[i]:off[i+1]]
+    appended to the tree (tree_size, frontier = tree.hashes joined). Returns a dict of the outputs named in
+    `want` (uint8 arrays; "path" also brings "path_off", uint64 in hash units)."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = off.shape[0] - 1
+    _merkle_device_ready(n, PV_MERKLE_AUTO_MIN_PROOFS if "roots" in want or "path" in want else PV_MERKLE_AUTO_MIN)
+    if n < 0:
+        raise ValueError("merkle_append: offsets must hold n + 1 entries")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    if int(off[n]) > blob.size:
+        raise ValueError("merkle_append: offsets reach past the blob")
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    front = np.frombuffer(bytes(frontier) or b"\0", dtype=np.uint8)
+    if tree_size and front.size != 32 * bin(tree_size).count("1"):
+        raise ValueError("merkle_append: the frontier must hold popcount(tree_size) hashes")
+    n_nodes, _, n_path = merkle_plan(tree_size, n)
+    res, out = {}, PvMerkleOut()
+    shapes = {"leaf_hash": (n, 32), "node_hash": (n_nodes, 32), "frontier": (64, 32), "root": (32,), "roots": (n, 32),
+              "path": (n_path, 32)}
+    keep = []  # an empty output still passes a non-null pointer, so it counts as wanted
+    for k in want:
+        res[k] = np.zeros(shapes[k], np.uint8)
+        keep.append(res[k] if res[k].size else np.zeros(32, np.uint8))
+        setattr(out, k, keep[-1].ctypes.data)
+    if "path" in want:
+        res["path_off"] = np.zeros(n + 1, np.uint64)
+        out.path_off = res["path_off"].ctypes.data
+    check(lib().pv_merkle_append_batch(tree_size, _ptr(front) if tree_size else None, _ptr(blob), _ptr(off), n,
+                                       ctypes.byref(out)), "pv_merkle_append_batch")
+    if "frontier" in res:
+        res["frontier"] = res["frontier"][:bin(tree_size + n).count("1")]
+    return res
+
+
+def merkle_verify_inclusion(leaf_index, tree_size, proofs, roots, leaves=None, leaf_hashes=None):
+    """MerkleVerifier.verify_leaf_inclusion (leaves) / verify_leaf_hash_inclusion (leaf_hashes) for n proofs:
+    proofs[i] a list of 32-byte hashes, roots[i] 32 bytes. Returns (verdicts bool[n], status uint8[n])."""
+    n = len(proofs)
+    _merkle_device_ready(n, PV_MERKLE_AUTO_MIN_VERIFY)
+    if n == 0:
+        return np.zeros(0, bool), np.zeros(0, np.uint8)
+    if (leaves is None) == (leaf_hashes is None):
+        raise ValueError("merkle_verify_inclusion: give either leaves or leaf_hashes")
+    poff = np.zeros(n + 1, np.uint64)
+    np.cumsum([len(p) for p in proofs], out=poff[1:])
+    pbuf = np.frombuffer(b"".join(b"".join(p) for p in proofs) or bytes(32), dtype=np.uint8)
+    if pbuf.size != 32 * int(poff[n]) and int(poff[n]):
+        raise ValueError("merkle_verify_inclusion: proof hashes must be 32 bytes each")
+    rbuf = np.frombuffer(b"".join(roots), dtype=np.uint8)
+    if rbuf.size != 32 * n:
+        raise ValueError("merkle_verify_inclusion: roots must be 32 bytes each")
+    idx = np.ascontiguousarray(leaf_index, dtype=np.uint64)
+    size = np.ascontiguousarray(tree_size, dtype=np.uint64)
+    data = doff = lh = None
+    if leaves is not None:
+        data, doff = _blob(leaves)
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+    else:
+        lh = np.frombuffer(b"".join(leaf_hashes), dtype=np.uint8)
+        if lh.size != 32 * n:
+            raise ValueError("merkle_verify_inclusion: leaf hashes must be 32 bytes each")
+    status, bits = np.zeros(n, np.uint8), np.zeros((n + 7) // 8, np.uint8)
+    check(lib().pv_merkle_verify_inclusion_batch(
+        _ptr(data) if data is not None else None, _ptr(doff) if doff is not None else None,
+        _ptr(lh) if lh is not None else None, _ptr(idx), _ptr(size), _ptr(pbuf), _ptr(poff), _ptr(rbuf), n, _ptr(status),
+        _ptr(bits)), "pv_merkle_verify_inclusion_batch")
+    return np.unpackbits(bits, count=n, bitorder="little").view(bool), status

@@ -163,3 +163,20 @@ class InvalidNodeOp(InvalidNodeMsg):
 
 class InvalidClientMsgType(InvalidClientRequest):
     pass
+
+
+# ledger/error.py:44-70 (the Merkle verifier's errors) and ledger/util.py:64
+class LedgerError(Exception):
+    """Exceptions raised by the ledger's verification code (the reference's ledger.error.Error)."""
+
+
+class VerifyError(LedgerError):
+    """Some expected property of the input cannot be verified."""
+
+
+class ProofError(VerifyError):
+    """A cryptographic proof is not valid."""
+
+
+class ConsistencyVerificationFailed(Exception):
+    pass
