@@ -600,6 +600,68 @@ int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_
 int pv_merkle_chunk(uint64_t leaves);
 int pv_merkle_path(int mode);
 
+/* ---- The state trie: batched PruningState.set with SHA3-256 node hashing ----
+ * The state's Patricia trie (state/trie/pruning_trie.py) is canonical and its store content-addressed
+ * and never pruned (state/db/persistent_db.py:26-30), so n sequential Trie.update calls
+ * (pruning_trie.py:1006-1027) equal one pass that builds the final trie and hashes every new node once.
+ *   pv_sha3_256_batch        SHA3-256 of n records data[off[i] .. off[i + 1]) -> out[32 i]. Host buffers;
+ *                            on the device or the host path as pv_trie_path says.
+ *   pv_sha3_256_batch_device the same on device buffers, enqueued on `stream` (null = the library's), no
+ *                            synchronise: d_data readable to d_off[n] rounded up to 8 bytes, d_out 8-byte
+ *                            aligned. PV_ERR_NOT_INIT without pv_init.
+ *   pv_trie_update_batch     the trie under `root` (32 bytes; the blank root = the empty trie) overlaid
+ *                            with n sets key i -> value i (values as the trie stores them: PruningState
+ *                            passes rlp([value])), a later entry of a key winning. `known` holds the
+ *                            existing nodes the caller has fetched: known_hash[32 k] and their RLP
+ *                            known_blob[known_off[k] .. known_off[k + 1]). Returns
+ *                              PV_OK                out->root, and the new nodes (every node on a touched
+ *                                                   path, deepest first, the root last): node i has hash
+ *                                                   node_hash[32 i] and RLP node_blob[node_off[i] ..
+ *                                                   + node_len[i]); n_nodes and blob_bytes say how many;
+ *                              PV_TRIE_NEED_NODES   the update reaches existing nodes that `known` lacks:
+ *                                                   out->n_missing hashes in out->missing (as many as
+ *                                                   missing_cap holds); fetch them, add them to `known`
+ *                                                   and call again. Nothing is called back and no caller
+ *                                                   pointer is kept;
+ *                              PV_TRIE_NEED_SPACE   node_cap or blob_cap is too small: n_nodes and
+ *                                                   blob_bytes hold what is needed;
+ *                              PV_ERR_DECODE        a known node is not a well-formed trie node;
+ *                              PV_ERR_ARG           null pointers, decreasing offsets, a key above 65,535
+ *                                                   bytes, a value that is empty or not below 2^24 bytes.
+ *                            n = 0 returns the input root and no nodes. out->launches and
+ *                            out->tail_records report how the device path ran (0 on the host path).
+ *   pv_trie_path             PV_TRIE_AUTO, PV_TRIE_HOST, PV_TRIE_DEVICE for the two host-buffer entries.
+ *                            AUTO hashes on the host without a device and below PV_TRIE_AUTO_MIN records;
+ *                            DEVICE without an initialised device returns PV_ERR_NO_DEVICE. */
+#define PV_TRIE_NEED_NODES 1
+#define PV_TRIE_NEED_SPACE 2
+#define PV_TRIE_AUTO 0
+#define PV_TRIE_HOST 1
+#define PV_TRIE_DEVICE 2
+#define PV_TRIE_AUTO_MIN 352 /* records (nodes to hash) from which AUTO takes the device path */
+typedef struct {
+    uint8_t* root;       /* [32] */
+    uint8_t* node_hash;  /* [32 node_cap] */
+    uint64_t node_cap;
+    uint8_t* node_blob;  /* [blob_cap] */
+    uint64_t blob_cap;
+    uint64_t* node_off;  /* [node_cap] */
+    uint64_t* node_len;  /* [node_cap] */
+    uint8_t* missing;    /* [32 missing_cap] */
+    uint64_t missing_cap;
+    uint64_t n_nodes;    /* written */
+    uint64_t blob_bytes;
+    uint64_t n_missing;
+    uint64_t launches;
+    uint64_t tail_records;
+} PvTrieOut;
+int pv_sha3_256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* out);
+int pv_sha3_256_batch_device(const uint8_t* d_data, const uint64_t* d_off, uint64_t n, uint8_t* d_out, void* stream);
+int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const uint8_t* known_blob,
+                         const uint64_t* known_off, uint64_t n_known, const uint8_t* key_blob, const uint64_t* key_off,
+                         const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, PvTrieOut* out);
+int pv_trie_path(int mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2876,6 +2876,7 @@ extern "C" {
 void pv_shutdown(void) {
     pinned_cache_drain();  // freed pv_host_alloc blocks back to the system (live ones stay the caller's)
     pv_merkle_shutdown();
+    pv_trie_shutdown();
     {
         std::lock_guard<std::mutex> lk(g_mg_mu);
         mg_destroy_comms();
@@ -4168,6 +4169,7 @@ int pv_stream_destroy(void* stream) {
     }
     pv_ingress_forget_stream(stream);
     pv_merkle_forget_stream(stream);
+    pv_trie_forget_stream(stream);
     PV_HIP(hipStreamDestroy((hipStream_t)stream), PV_ERR_LAUNCH);
     return PV_OK;
 }

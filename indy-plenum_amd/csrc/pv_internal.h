@@ -16,6 +16,9 @@ void pv_ingress_forget_stream(void* stream);
 // device contexts go).
 void pv_merkle_forget_stream(void* stream);
 void pv_merkle_shutdown();
+// The same pair for the state-trie workspace (pv_trie.hip).
+void pv_trie_forget_stream(void* stream);
+void pv_trie_shutdown();
 // The latency path (pv_latency.hip): n requests on device buffers, verdict words written on `stream`.
 // run_if (device word, may be null): the kernel exits at once unless *run_if != 0 (AUTO's device-side
 // latency-vs-keyed choice).

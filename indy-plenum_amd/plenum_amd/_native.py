@@ -18,6 +18,7 @@ PV_OK = 0
 PV_ERR_NO_DEVICE = -1
 PV_ERR_ARG = -4
 PV_ERR_NOT_INIT = -5
+PV_ERR_DECODE = -7
 PV_BLOB_SLACK = 256
 PV_ABI_VERSION = 1
 PV_SIGN_CHUNK = 262144  # messages per launch inside pv_sign_batch (csrc/pv_engine.hip PV_SIGN_CHUNK)
@@ -119,6 +120,12 @@ SIGNATURES = {
                                                                                        ctypes.c_void_p, ctypes.c_void_p]),
     "pv_merkle_chunk": (ctypes.c_int, [ctypes.c_uint64]),
     "pv_merkle_path": (ctypes.c_int, [ctypes.c_int]),
+    "pv_sha3_256_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "pv_sha3_256_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "pv_trie_update_batch": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_uint64, ctypes.c_void_p]),
+    "pv_trie_path": (ctypes.c_int, [ctypes.c_int]),
 }
 
 
@@ -703,3 +710,119 @@ def merkle_verify_inclusion(leaf_index, tree_size, proofs, roots, leaves=None, l
         _ptr(lh) if lh is not None else None, _ptr(idx), _ptr(size), _ptr(pbuf), _ptr(poff), _ptr(rbuf), n, _ptr(status),
         _ptr(bits)), "pv_merkle_verify_inclusion_batch")
     return np.unpackbits(bits, count=n, bitorder="little").view(bool), status
+
+
+# -------------------------------------------------------------------------------------- state trie
+PV_TRIE_NEED_NODES, PV_TRIE_NEED_SPACE = 1, 2
+PV_TRIE_AUTO, PV_TRIE_HOST, PV_TRIE_DEVICE = 0, 1, 2
+PV_TRIE_AUTO_MIN = 352  # include/plenum_verify.h: records from which AUTO hashes on the device
+PV_TRIE_MAX_KEY, PV_TRIE_MAX_VALUE = 65535, (1 << 24) - 1
+
+
+class PvTrieOut(ctypes.Structure):
+    _fields_ = [("root", ctypes.c_void_p), ("node_hash", ctypes.c_void_p), ("node_cap", ctypes.c_uint64),
+                ("node_blob", ctypes.c_void_p), ("blob_cap", ctypes.c_uint64), ("node_off", ctypes.c_void_p),
+                ("node_len", ctypes.c_void_p), ("missing", ctypes.c_void_p), ("missing_cap", ctypes.c_uint64),
+                ("n_nodes", ctypes.c_uint64), ("blob_bytes", ctypes.c_uint64), ("n_missing", ctypes.c_uint64),
+                ("launches", ctypes.c_uint64), ("tail_records", ctypes.c_uint64)]
+
+
+_trie_mode = PV_TRIE_AUTO
+_trie_no_device = False
+trie_last = {"launches": 0, "tail_records": 0, "nodes": 0, "rounds": 0}  # how the last trie_update ran
+
+
+def trie_path(mode=PV_TRIE_AUTO):
+    global _trie_mode
+    check(lib().pv_trie_path(mode), "pv_trie_path")
+    _trie_mode = mode
+
+
+def _trie_device_ready(work):
+    """As _merkle_device_ready: a GPU is bound only by a call that will hash on it."""
+    global _trie_no_device
+    if _device is not None or _trie_no_device or _trie_mode == PV_TRIE_HOST:
+        return
+    if _trie_mode == PV_TRIE_AUTO and work < PV_TRIE_AUTO_MIN:
+        return
+    try:
+        ensure_device()
+    except NativeUnavailable:
+        _trie_no_device = True
+
+
+def sha3_256_batch(blob, off):
+    """SHA3-256 of the records blob[off[i]:off[i+1]] -> uint8 array (n, 32), one pv_sha3_256_batch."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = off.shape[0] - 1
+    if n < 0:
+        raise ValueError("sha3_256_batch: offsets must hold n + 1 entries")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    if n and int(off[n]) > blob.size:
+        raise ValueError("sha3_256_batch: offsets reach past the blob")
+    _trie_device_ready(n)
+    out = np.zeros((n, 32), np.uint8)
+    if n:
+        check(lib().pv_sha3_256_batch(_ptr(blob if blob.size else np.zeros(1, np.uint8)), _ptr(off), n, _ptr(out)),
+              "pv_sha3_256_batch")
+    return out
+
+
+def trie_update_raw(root, known_hashes, known_rlps, keys, values, node_cap=None, blob_cap=None, missing_cap=None):
+    """One pv_trie_update_batch. Returns (rc, root bytes, [(hash, rlp)], [missing hashes], PvTrieOut)."""
+    n, k = len(keys), len(known_hashes)
+    kb, ko = _blob(keys)
+    vb, vo = _blob(values)
+    nb, no = _blob(known_rlps)
+    nh = np.frombuffer(b"".join(known_hashes) or bytes(32), np.uint8)
+    if nh.size != 32 * max(k, 1):
+        raise ValueError("trie_update: known hashes must be 32 bytes each")
+    if node_cap is None:
+        node_cap = 2 * n + k + 16
+    if blob_cap is None:
+        blob_cap = int(nb.size) + int(kb.size) + int(vb.size) + 640 * n + 80 * k + 1024
+    if missing_cap is None:
+        missing_cap = 16 * n + 16
+    rootbuf = np.zeros(32, np.uint8)
+    hashes = np.zeros((max(node_cap, 1), 32), np.uint8)
+    nblob = np.zeros(max(blob_cap, 1), np.uint8)
+    noff, nlen = np.zeros(max(node_cap, 1), np.uint64), np.zeros(max(node_cap, 1), np.uint64)
+    miss = np.zeros((max(missing_cap, 1), 32), np.uint8)
+    out = PvTrieOut(rootbuf.ctypes.data, hashes.ctypes.data, node_cap, nblob.ctypes.data, blob_cap, noff.ctypes.data,
+                    nlen.ctypes.data, miss.ctypes.data, missing_cap)
+    rc = lib().pv_trie_update_batch(bytes(root), _ptr(nh), _ptr(nb), _ptr(no), k, _ptr(kb), _ptr(ko), _ptr(vb), _ptr(vo),
+                                    n, ctypes.byref(out))
+    nodes, missing = [], []
+    if rc == PV_OK:
+        data = nblob.tobytes()
+        nodes = [(hashes[i].tobytes(), data[int(noff[i]):int(noff[i]) + int(nlen[i])]) for i in range(out.n_nodes)]
+    elif rc == PV_TRIE_NEED_NODES:
+        missing = [miss[i].tobytes() for i in range(min(out.n_missing, missing_cap))]
+    return rc, rootbuf.tobytes(), nodes, missing, out
+
+
+def trie_update(root, fetch, keys, values):
+    """The trie under `root` overlaid with keys[i] -> values[i] (values as the trie stores them), as one call
+    chain: pv_trie_update_batch says which existing nodes it lacks, fetch(hash) -> RLP brings them, until none
+    are missing. Returns (new root, [(hash, rlp)] of every new node, the root last)."""
+    n = len(keys)
+    _trie_device_ready(2 * n)  # at least a node per set; the library decides by the real count
+    known = {}
+    caps = {}
+    rounds = 0
+    while True:
+        rounds += 1
+        hs = list(known)
+        rc, new_root, nodes, missing, out = trie_update_raw(root, hs, [known[h] for h in hs], keys, values, **caps)
+        if rc == PV_TRIE_NEED_NODES:
+            if out.n_missing > len(missing):  # more than the list held: a larger list, the same round again
+                caps["missing_cap"] = int(out.n_missing)
+            for h in missing:
+                known[h] = bytes(fetch(h))
+            continue
+        if rc == PV_TRIE_NEED_SPACE:
+            caps["node_cap"], caps["blob_cap"] = int(out.n_nodes), int(out.blob_bytes)
+            continue
+        check(rc, "pv_trie_update_batch")
+        trie_last.update(launches=int(out.launches), tail_records=int(out.tail_records), nodes=len(nodes), rounds=rounds)
+        return new_root, nodes
