@@ -299,6 +299,24 @@ int pv_key_cache_auto_stats(uint64_t* admitted, uint64_t* failed);
 int pv_table_reuse(int on, uint32_t capacity);
 int pv_table_reuse_stats(uint64_t* hits, uint64_t* built, uint64_t* resets);
 
+/* Affine rows for resident tables (on by default; it needs table reuse). A chunk of more than 65,536
+ * requests that reads a listed table whose key passed libsodium's key checks, when such a chunk has read
+ * it once before (the table's second hit), converts that table, after its own kernels have read it, to
+ * affine rows in place: every entry divided by its Z with one inversion per 33 entries. Every later
+ * chunk, of any size, then adds from it with 7 field multiplications and 128 bytes per addition instead
+ * of 8 and 160. Verdicts do not change. A table that large chunks do not come back for twice is never
+ * converted (converting 1,024 tables costs what ten warm 1M-request chunks save); at most 1,024 tables are converted behind one chunk, the rest on their next hit; a
+ * table that is rebuilt (a reset, a control call, a key-cache put over the directory) starts in cached
+ * form again.
+ *   pv_table_affine(on)              0 = resident tables stay as built. Switching empties the directory.
+ *                                    Applies to every device of the process.
+ *   pv_table_affine_stats(c, r)      tables converted / tables read in affine form by chunks that went
+ *                                    through the directory, since pv_init. Synchronises the device: for
+ *                                    tests and tools.
+ * PV_TABLE_AFFINE=0 in the environment at pv_init starts with it off. */
+int pv_table_affine(int on);
+int pv_table_affine_stats(uint64_t* converted, uint64_t* affine_reads);
+
 /* Batched base58 decode (Bitcoin alphabet, PyPI base58 2.x b58decode semantics: trailing ASCII
  * whitespace stripped, each leading '1' -> 0x00). Input: strings concatenated in `chars` with
  * n+1 offsets. Output: out[i * out_stride ...], out_len[i] bytes, status[i] = 0 ok, 1 invalid

@@ -352,6 +352,52 @@ PV_HD void pv_comb_row_to_affine(const Src& src, const Dst& dst) {
     }
 }
 
+// The same conversion IN PLACE, for a resident table (pv_dir_affine_kernel): the source's own words
+// 20..29 are the Z2 the backward pass still needs, so the running products are parked outside the row,
+// in scr (scr.store(k, f) / scr.load(k, f), k = 0 .. d1 - d0 - 1). Entries [d0, d1) of the row with one
+// inversion of their own, so a row can be cut into segments that convert side by side; the output is
+// canonical, hence the same words whatever the cut, and equal to pv_comb_row_to_affine's.
+// row.load_z2(d, z) reads words 20..29 of entry d, row.load(d, c) the whole entry,
+// row.store_affine(d, ypx, ymx, xy2d) writes it back with words 20..29 zero.
+static constexpr int PV_AFF_SEGS = 4;    // segments per row (pv_dir_affine_kernel: one thread each)
+static constexpr int PV_AFF_SEG = 33;    // entries per segment: 4 x 33 >= PV_COMB_ENT, the last has 30
+static_assert(PV_AFF_SEGS * PV_AFF_SEG >= PV_COMB_ENT, "segments cover the row");
+template <class Row, class Scr>
+PV_HD void pv_comb_row_to_affine_inplace(const Row& row, const Scr& scr, int d0, int d1) {
+    fe prod;
+    fe_1(prod);
+    for (int d = d0; d < d1; d++) {
+        fe z2;
+        row.load_z2(d, z2);
+        fe_mul(prod, prod, z2);
+        scr.store(d - d0, prod);
+    }
+    fe inv;
+    fe_invert(inv, prod);
+    for (int d = d1 - 1; d >= d0; d--) {
+        ge_cached c;
+        row.load(d, c);
+        fe zi, zi2, t, ypx, ymx, xy2d;
+        if (d > d0) {
+            fe prev;
+            scr.load(d - d0 - 1, prev);
+            fe_mul(zi, inv, prev);  // 1 / Z2_d
+        } else {
+            fe_copy(zi, inv);
+        }
+        fe_mul(inv, inv, c.Z2);
+        fe_add(t, zi, zi);  // 1 / Z_d
+        fe_carry(zi2, t);
+        fe_mul(t, c.YplusX, zi2);
+        fe_canonical(ypx, t);
+        fe_mul(t, c.YminusX, zi2);
+        fe_canonical(ymx, t);
+        fe_mul(t, c.T2d, zi2);
+        fe_canonical(xy2d, t);
+        row.store_affine(d, ypx, ymx, xy2d);
+    }
+}
+
 // Staging over plain Rows objects (host tests): stage() remembers the entry, staged() reads it.
 template <class ARows>
 struct PvRowsStageA {

@@ -325,10 +325,24 @@ struct Gate {
 // later chunk that carries the same key reads its table instead of building it again. Nothing of it
 // lives on the host but an on/off flag, the capacity and a dirty bit.
 //   dir_htab [PV_DIR_HASH] open-addressing hash of listed slots (pv_kc_lookup with kw.seed: a hit
-//            compares the full 32-byte key), dir_keys [kcap][8], dir_flags [kcap] (libsodium key checks)
+//            compares the full 32-byte key), dir_keys [kcap][8], dir_flags [kcap]: bit 0 (PV_KF_OK) the
+//            libsodium key checks passed, bit 1 (PV_KF_AFF) the slot's rows are affine, bit 2 (PV_KF_HIT)
+//            a dense chunk has read the slot once already (both below)
 //   dir_cnt  [2]  count: slots [0, count) are listed, nothing above them is; and the count the
 //            chunk's publish kernel stores once its tables are built and listed
-//   dir_stat [3]  u64 hits, built, resets
+//   dir_stat [5]  u64 hits, built, resets, tables converted to affine rows, tables read in affine form
+// Affine rows: a dense chunk (dir_pub) that hits a listed table whose key passed the checks marks the
+// slot PV_KF_HIT; the next dense chunk that hits it -- the table's second hit: converting 1,024 tables
+// costs as much as ten warm 1M-request chunks save, so a table that comes back once is left alone --
+// queues the slot in aff_list; pv_dir_affine_kernel converts those tables in place behind the chunk's comb kernels
+// (comb.h pv_comb_row_to_affine_inplace) and sets PV_KF_AFF, and every later chunk reads them in affine
+// form. The scan copies dir_flags into key_flag for a hit; key_flag of a key the chunk
+// builds comes from the chain kernel and has bit 0 only. PV_KF_AFF and PV_KF_HIT are cleared wherever a
+// slot is rebuilt, because a rebuilt slot is listed again only by pv_dir_publish_kernel, which stores bit 0
+// alone: after a reset by the scan, after dir_dirty emptied the directory (a control call, an enqueue
+// failure, a key-cache put that ran over the directory), and for the tables built above the count.
+//   aff_list [PV_AFF_CAP] slots queued by this chunk's scan;  aff_cnt [1] how many it queued (may exceed
+//            the cap: the rest wait for their next hit);  aff_scr  the conversion's parked Z2 products
 // A key takes the comb path when it carries >= min_req requests of the chunk (the per-key table
 // costs about as much as ~50 requests save; 1 when the comb path is forced) and fewer than kcap
 // keys came before it; the rest -- singletons such as the adversarial keys of config 3 -- take the
@@ -366,6 +380,9 @@ struct KeyWork {
     uint32_t* dir_flags;
     uint32_t* dir_cnt;
     unsigned long long* dir_stat;
+    uint32_t* aff_list;    // affine-row conversion queue (above)
+    uint32_t* aff_cnt;
+    uint32_t* aff_scr;
     uint32_t* need;        // [PV_ALLCOMB_KEYS][32][5] needed |digit| bits per (comb index, position)
     const uint4* kc_tab;   // the cache's tables [cap][32][129][10] (keycache.h)
     const uint4* kc_ntab;  // the same divided by Z [cap][32][129][10] (comb.h pv_comb_row_to_affine), or null
@@ -387,7 +404,12 @@ struct KeyWork {
     uint32_t dir_on;      // this chunk goes through the directory (probe, slot allocator)
     uint32_t dir_cap;     // slots the directory may list (<= kcap)
     uint32_t dir_pub;     // a dense chunk: its tables are whole and pv_dir_publish_kernel lists them
+    uint32_t aff_conv;    // a dense chunk with pv_table_affine on: its scan queues hit tables for conversion
 };
+static constexpr uint32_t PV_KF_OK = 1u;   // key_flag / dir_flags: libsodium's key checks passed
+static constexpr uint32_t PV_KF_AFF = 2u;  // the table's rows are affine (a directory hit only)
+static constexpr uint32_t PV_KF_HIT = 4u;  // a dense chunk has hit the table before: its next dense hit converts it
+static constexpr uint32_t PV_AFF_CAP = 1024;  // tables one chunk converts (aff_scr: 165 KB each, 173 MB)
 static constexpr uint32_t PV_EMPTY = 0xFFFFFFFFu;
 static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call's shared store (KeyWork::xt_*)
 static constexpr uint32_t PV_CSLOT_DIR = 0x20000000u;  // slot of kw.ctab listed in the resident-table directory
@@ -876,7 +898,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_dir_publish_kernel(const uint8_t*
     pv_load_pk(A, pk, kw.key_owner[kw.comb_key[j]]);
 #pragma unroll
     for (int q = 0; q < 8; q++) kw.dir_keys[8 * s + q] = A[q];
-    kw.dir_flags[s] = kw.key_flag[j];
+    kw.dir_flags[s] = kw.key_flag[j] & PV_KF_OK;  // a table this chunk built: cached form, PV_KF_AFF and PV_KF_HIT clear
     __threadfence();  // the key bytes before the hash entry that names them
     constexpr uint32_t hmask = PV_DIR_HASH - 1;
     uint32_t h = pv_kc_hash(A, kw.seed) & hmask;
@@ -901,7 +923,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_xtab_publish_kernel(const uint8_t
     pv_load_pk(A, pk, kw.key_owner[kw.comb_key[j]]);
 #pragma unroll
     for (int q = 0; q < 8; q++) keys[8 * j + q] = A[q];
-    flags[j] = kw.key_flag[j];
+    flags[j] = kw.key_flag[j] & PV_KF_OK;
     __threadfence();  // the key bytes before the hash entry that names them
     uint32_t h = pv_kc_hash(A, seed) & hmask;
     for (uint32_t probe = 0; probe <= hmask; probe++) {  // distinct keys, hmask + 1 >= 2 x entries
@@ -1017,6 +1039,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
     uint32_t tnext = 0;  // this thread's next slot
     bool dir_reset = false;
     if (kw.dir_on) {
+        if (t == 0) kw.aff_cnt[0] = 0;  // the queue below fills after the scans' barriers
         const uint32_t have = kw.dir_cnt[0];  // read by every thread before the scans' barriers, written after
         uint32_t M, D;
         const uint32_t mb = pv_block_scan(nm, part, &M);
@@ -1037,6 +1060,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
             kw.dir_stat[2] += dir_reset ? 1u : 0u;
         }
     }
+    uint32_t na = 0;  // this thread's directory hits whose rows are affine
     for (uint32_t v = lo, j = jbase; v < hi; v++) {
         const uint32_t id = vid(v);
         const uint32_t c = count(v, id);
@@ -1055,10 +1079,26 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
             kw.comb_cslot[j] = cslot;
             kw.comb_tslot[j] = tslot;
             // a cached or resident key's libsodium checks ran when its table was built (the chain skips it)
-            if (cslot != PV_EMPTY)
-                kw.key_flag[j] = (cslot & PV_CSLOT_DIR)  ? kw.dir_flags[tslot]
-                                 : (cslot & PV_CSLOT_XT) ? kw.xt_flags[cslot & ~PV_CSLOT_XT]
-                                                         : kc_flags[cslot];
+            if (cslot != PV_EMPTY) {
+                const uint32_t f = (cslot & PV_CSLOT_DIR)  ? kw.dir_flags[tslot]
+                                   : (cslot & PV_CSLOT_XT) ? kw.xt_flags[cslot & ~PV_CSLOT_XT]
+                                                           : kc_flags[cslot];
+                kw.key_flag[j] = f;  // a directory hit: every bit, the comb kernels read PV_KF_AFF rows as affine
+                if ((cslot & PV_CSLOT_DIR) && !lat) {
+                    na += f & PV_KF_AFF ? 1u : 0u;
+                    // a dense chunk's hit on a checked key's cached-form table: the first is remembered in the
+                    // slot (this thread alone handles the key), the second queues it: converted behind the
+                    // chunk's comb kernels
+                    if (kw.aff_conv && (f & (PV_KF_OK | PV_KF_AFF)) == PV_KF_OK) {
+                        if (!(f & PV_KF_HIT)) {
+                            kw.dir_flags[tslot] = f | PV_KF_HIT;
+                        } else {
+                            const uint32_t q = atomicAdd(&kw.aff_cnt[0], 1u);
+                            if (q < PV_AFF_CAP) kw.aff_list[q] = tslot;
+                        }
+                    }
+                }
+            }
             kw.key_cursor[id] = cc;
             cc += c;
         } else {
@@ -1068,6 +1108,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
         }
         if (cand_id) j++;
     }
+    if (na) atomicAdd(&kw.dir_stat[4], (unsigned long long)na);
     if (t == 0) {
         kw.nkeys[PV_SPLIT_KEYS] = nk;  // distinct keys (pv_last_path)
         // AUTO's device-side choice for a 2,049..4,096-request batch of pv_verify_batch_device: the
@@ -1327,7 +1368,7 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_scatter_kernel(const uint4* __
         tab[dst + t] = ctab[src + t];
     if (blockIdx.x == 0 && threadIdx.x < 8) {
         keys[8 * slots[j] + threadIdx.x] = reinterpret_cast<const uint32_t*>(pk)[8 * j + threadIdx.x];
-        if (threadIdx.x == 0) flags[slots[j]] = key_flag[j];
+        if (threadIdx.x == 0) flags[slots[j]] = key_flag[j] & PV_KF_OK;
     }
 }
 
@@ -1360,6 +1401,66 @@ __global__ __launch_bounds__(64) void pv_kc_affine_kernel(const uint4* __restric
     const uint64_t slot = slots[t / PV_COMB_POS], pos = t % PV_COMB_POS;
     pv_comb_row_to_affine(DevCachedRowSrc{tab + (slot * PV_COMB_POS + pos) * PV_COMB_ENT * 10},
                           DevAffineRowDst{atab + (slot * PV_COMB_POS + pos) * PV_COMB_ENT * 10});
+}
+
+// Resident tables to affine rows, in place (comb.h pv_comb_row_to_affine_inplace): the slots this
+// chunk's scan queued (aff_list, aff_cnt: device-side, so the launch is fixed -- PV_AFF_CAP workgroups,
+// each leaving at once when its index is past the count, as the chain's do for resident keys). One
+// workgroup per table, one thread per (position, segment of 33 entries); the parked products go to
+// aff_scr [workgroup][33][10][128], one word per thread and step, coalesced. Runs on the main stream
+// after every kernel of the chunk that reads ctab and before any of the next chunk, so no reader sees
+// a table half converted; PV_KF_AFF is set once the whole table is written (fence, barrier, flag), the
+// order pv_dir_publish_kernel keeps between a key's bytes and its hash entry.
+struct DevAffineRow {
+    uint4* r;  // [129][10]
+    __device__ __forceinline__ void load(int d, ge_cached& c) const { DevCachedRowSrc{r}.load(d, c); }
+    __device__ __forceinline__ void load_z2(int d, fe& z) const {
+        const uint4 a = r[d * 10 + 5], b = r[d * 10 + 6], c = r[d * 10 + 7];
+        const uint32_t w[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y};
+#pragma unroll
+        for (int q = 0; q < 10; q++) z.v[q] = w[q];
+    }
+    __device__ __forceinline__ void store_affine(int d, const fe& ypx, const fe& ymx, const fe& xy2d) const {
+        uint4* e = r + d * 10;
+        e[0] = make_uint4(ypx.v[0], ypx.v[1], ypx.v[2], ypx.v[3]);
+        e[1] = make_uint4(ypx.v[4], ypx.v[5], ypx.v[6], ypx.v[7]);
+        e[2] = make_uint4(ypx.v[8], ypx.v[9], ymx.v[0], ymx.v[1]);
+        e[3] = make_uint4(ymx.v[2], ymx.v[3], ymx.v[4], ymx.v[5]);
+        e[4] = make_uint4(ymx.v[6], ymx.v[7], ymx.v[8], ymx.v[9]);
+        e[5] = make_uint4(0u, 0u, 0u, 0u);
+        e[6] = make_uint4(0u, 0u, 0u, 0u);
+        e[7] = make_uint4(0u, 0u, xy2d.v[0], xy2d.v[1]);
+        e[8] = make_uint4(xy2d.v[2], xy2d.v[3], xy2d.v[4], xy2d.v[5]);
+        e[9] = make_uint4(xy2d.v[6], xy2d.v[7], xy2d.v[8], xy2d.v[9]);
+    }
+};
+static constexpr uint32_t PV_AFF_THREADS = PV_COMB_POS * PV_AFF_SEGS;  // 128: one table per workgroup
+struct DevAffineScr {
+    uint32_t* z;  // this thread's column of [33][10][PV_AFF_THREADS]
+    __device__ __forceinline__ void store(int k, const fe& f) const {
+#pragma unroll
+        for (int q = 0; q < 10; q++) z[(uint32_t)(k * 10 + q) * PV_AFF_THREADS] = f.v[q];
+    }
+    __device__ __forceinline__ void load(int k, fe& f) const {
+#pragma unroll
+        for (int q = 0; q < 10; q++) f.v[q] = z[(uint32_t)(k * 10 + q) * PV_AFF_THREADS];
+    }
+};
+__global__ __launch_bounds__(PV_AFF_THREADS) void pv_dir_affine_kernel(KeyWork kw) {
+    // a chunk that took the latency choice or reset the directory queued nothing
+    if (blockIdx.x >= min(kw.aff_cnt[0], PV_AFF_CAP)) return;
+    const uint64_t slot = kw.aff_list[blockIdx.x];  // < dir_cnt <= kcap: a listed slot the scan read from the hash
+    const uint32_t pos = threadIdx.x / PV_AFF_SEGS, seg = threadIdx.x % PV_AFF_SEGS;
+    const int d0 = (int)seg * PV_AFF_SEG, d1 = min(d0 + PV_AFF_SEG, PV_COMB_ENT);
+    pv_comb_row_to_affine_inplace(
+        DevAffineRow{kw.ctab + (slot * PV_COMB_POS + pos) * PV_COMB_ENT * 10},
+        DevAffineScr{kw.aff_scr + (uint64_t)blockIdx.x * PV_AFF_SEG * 10 * PV_AFF_THREADS + threadIdx.x}, d0, d1);
+    __threadfence();  // the rows before the bit that says they are affine
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        kw.dir_flags[slot] |= PV_KF_AFF;
+        atomicAdd(&kw.dir_stat[3], 1ull);
+    }
 }
 
 // Key cache put: the workspace set up for m keys given in order (d_put_pk[j] is comb index j's key):
@@ -1511,7 +1612,7 @@ __device__ __forceinline__ void pv_comb_bw_acc(ge_p3& acc, const uint4* bcomb, c
 }
 // A slot whose [k](-A) was added in the niels loop: projective Q to q rows 0..29 and the key's flag.
 __device__ __forceinline__ void pv_comb_store_q(const Work& wk, const KeyWork& kw, uint32_t i, const ge_p3& acc) {
-    if (kw.key_flag[kw.skey[i]] == 0) wk.flags[i] = 0;
+    if ((kw.key_flag[kw.skey[i]] & PV_KF_OK) == 0) wk.flags[i] = 0;
     const Soa qs(wk.q, 40, wk.stride);
 #pragma unroll
     for (int q = 0; q < 10; q++) {
@@ -1638,10 +1739,13 @@ __device__ __forceinline__ void pv_comb_a_from(const Work& wk, const KeyWork& kw
     const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
     fe X, Y, Z;
     // a cached key with affine rows: additions without the Z1 Z2 product (comb.h pv_comb_row_to_affine)
-    const bool aff = cached && !xt && kw.kc_ntab;
-    if (aff) ktab = kw.kc_ntab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
+    // so has a resident table that pv_dir_affine_kernel converted in place (PV_KF_AFF from the directory)
+    const uint32_t kf = kw.key_flag[id];
+    const bool kc_aff = cached && !xt && kw.kc_ntab;
+    const bool aff = kc_aff || (!cached && (kf & PV_KF_AFF));
+    if (kc_aff) ktab = kw.kc_ntab + (uint64_t)cslot * PV_COMB_POS * PV_COMB_ENT * 10;
     pv_comb_a_xyz_staged(X, Y, Z, acc, DevCombStage{ktab, stg_wave, threadIdx.x & 63u, aff}, dig);
-    if (kw.key_flag[id] == 0) wk.flags[i] = 0;
+    if ((kf & PV_KF_OK) == 0) wk.flags[i] = 0;
 #pragma unroll
     for (int q = 0; q < 10; q++) {
         qs.st(q, i, X.v[q]);
@@ -1670,7 +1774,7 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_a_kerne
     const uint32_t i = pv_xcd_block() * PV_BLOCK + threadIdx.x;  // slot
     if (i >= gate.ncomb()) return;
     if (pv_kw_rows(kw, i)) {  // pv_comb_b_kernel added [k](-A) from the key's wide rows: Q is in q rows 0..29
-        if (kw.key_flag[kw.skey[i]] == 0) wk.flags[i] = 0;
+        if ((kw.key_flag[kw.skey[i]] & PV_KF_OK) == 0) wk.flags[i] = 0;
         return;
     }
     __shared__ uint4 stg[PV_BLOCK / 64][10][64];
@@ -1995,6 +2099,7 @@ struct Ctx {
     bool dir_on = true;
     uint32_t dir_cap = PV_DIR_DEFAULT_CAP;
     bool dir_dirty = true;
+    bool aff_on = true;  // dense chunks convert the resident tables they hit to affine rows (pv_table_affine)
     bool last_latency = false;  // the most recent launch took the latency path
     bool verdict_zeroed = false;  // the caller's verdict words are already 0 (pv_verify_batch)
     bool keyed_hint = false;      // pv_verify_batch saw few distinct keys: keyed path below PV_LATENCY_MAX
@@ -2357,6 +2462,7 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
         kw.dir_on = dir_use ? 1u : 0u;
         kw.dir_cap = g_ctx.dir_cap;
         kw.dir_pub = dir_use && m > PV_SPARSE_CHUNK ? 1u : 0u;  // direct_fill below: the tables are whole
+        kw.aff_conv = kw.dir_pub && g_ctx.aff_on ? 1u : 0u;
         kw.chunk_n = (uint32_t)m;
         // a key-id segment holds the owners among its waves (every PV_NSEG-th wave of the chunk)
         kw.seg_cap = (uint32_t)((((m + 63) / 64) + PV_NSEG - 1) / PV_NSEG * 64);
@@ -2545,6 +2651,10 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                                        stream, d_pk + 32 * c0, kw);
                     PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
                 }
+                if (kw.aff_conv) {  // the listed tables this chunk hit: affine rows for the chunks that follow
+                    hipLaunchKernelGGL(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
+                    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                }
                 g_ctx.dir_dirty = false;
             }
             if (dev_choice) {  // runs only when the scan picked latency (the words were zeroed above)
@@ -2628,11 +2738,15 @@ int lane_alloc_buffers(Work& w, KeyWork& kw) {
     PV_HIP(hipMalloc((void**)&kw.dir_keys, (uint64_t)kw.kcap * 32), PV_ERR_ALLOC);
     PV_HIP(hipMalloc((void**)&kw.dir_flags, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     PV_HIP(hipMalloc((void**)&kw.dir_cnt, 2 * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_stat, 3 * 8), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.dir_stat, 5 * 8), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.aff_list, (uint64_t)PV_AFF_CAP * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.aff_cnt, 4), PV_ERR_ALLOC);
+    PV_HIP(hipMalloc((void**)&kw.aff_scr, (uint64_t)PV_AFF_CAP * PV_AFF_SEG * 10 * PV_AFF_THREADS * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.aff_cnt, 0, 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.comb_tslot, 0, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_cnt, 0, 2 * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMemset(kw.dir_stat, 0, 3 * 8), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.dir_stat, 0, 5 * 8), PV_ERR_ALLOC);
     return PV_OK;
 }
 
@@ -2643,7 +2757,7 @@ void lane_free_buffers(Work& w, KeyWork& kw) {
                     (void*)kw.bases, (void*)kw.ctab, (void*)kw.key_count, (void*)kw.key_cursor, (void*)kw.slot_req,
                     (void*)kw.req_pos, (void*)kw.skey, (void*)kw.sverdict, (void*)kw.key_cslot, (void*)kw.comb_cslot,
                     (void*)kw.need, (void*)kw.comb_tslot, (void*)kw.dir_htab, (void*)kw.dir_keys, (void*)kw.dir_flags,
-                    (void*)kw.dir_cnt, (void*)kw.dir_stat})
+                    (void*)kw.dir_cnt, (void*)kw.dir_stat, (void*)kw.aff_list, (void*)kw.aff_cnt, (void*)kw.aff_scr})
         if (p) (void)hipFree(p);
     w = Work{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     kw = KeyWork{};
@@ -2769,6 +2883,8 @@ int ctx_init_parts(int device) {
         g_ctx.dir_on = !(tr && *tr == '0');
         g_ctx.dir_cap = PV_DIR_DEFAULT_CAP;
         g_ctx.dir_dirty = true;
+        const char* ta = getenv("PV_TABLE_AFFINE");  // PV_TABLE_AFFINE=0: resident tables stay in cached form
+        g_ctx.aff_on = !(ta && *ta == '0');
     }
     g_ctx.device = device;
     return PV_OK;
@@ -2950,6 +3066,28 @@ int pv_table_reuse_stats(uint64_t* hits, uint64_t* built, uint64_t* resets) {
     if (hits) *hits = u[0];
     if (built) *built = u[1];
     if (resets) *resets = u[2];
+    return PV_OK;
+}
+
+int pv_table_affine(int on) {
+    for (int d = 0; d < PV_MAX_DEV; d++) {  // every device context of the process
+        std::lock_guard<std::mutex> lk(g_mus[d]);
+        Ctx& c = g_ctxs[d];
+        const bool want = on != 0;
+        if (want != c.aff_on) c.dir_dirty = true;  // emptied before its next use: never half in one regime
+        c.aff_on = want;
+    }
+    return PV_OK;
+}
+
+int pv_table_affine_stats(uint64_t* converted, uint64_t* affine_reads) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_table_affine_stats: call pv_init first");
+    unsigned long long u[5] = {0, 0, 0, 0, 0};
+    PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpy(u, g_ctx.kw.dir_stat, sizeof(u), hipMemcpyDeviceToHost), PV_ERR_LAUNCH);
+    if (converted) *converted = u[3];
+    if (affine_reads) *affine_reads = u[4];
     return PV_OK;
 }
 

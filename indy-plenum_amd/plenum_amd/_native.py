@@ -86,6 +86,8 @@ SIGNATURES = {
     "pv_key_cache_auto_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "pv_table_reuse": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32]),
     "pv_table_reuse_stats": (ctypes.c_int, [_c_u64p, _c_u64p, _c_u64p]),
+    "pv_table_affine": (ctypes.c_int, [ctypes.c_int]),
+    "pv_table_affine_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
     "pv_last_zero_copy": (ctypes.c_int, []),
     "pv_init_devices": (ctypes.c_int, [ctypes.c_uint32]),
     "pv_verify_batch_multi_gpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -488,6 +490,20 @@ def table_reuse_stats():
     times the kept tables were dropped to make room. Synchronises the device."""
     v = [ctypes.c_uint64() for _ in range(3)]
     check(lib().pv_table_reuse_stats(*[ctypes.byref(x) for x in v]), "pv_table_reuse_stats")
+    return tuple(x.value for x in v)
+
+
+def table_affine(on=True):
+    """Convert the kept tables a large keyed chunk reads to affine rows for the chunks that follow
+    (pv_table_affine; on by default). Switching empties the kept tables."""
+    check(lib().pv_table_affine(1 if on else 0), "pv_table_affine")
+
+
+def table_affine_stats():
+    """(converted, affine_reads) since pv_init: kept tables converted to affine rows, and kept tables
+    read in that form. Synchronises the device."""
+    v = [ctypes.c_uint64() for _ in range(2)]
+    check(lib().pv_table_affine_stats(*[ctypes.byref(x) for x in v]), "pv_table_affine_stats")
     return tuple(x.value for x in v)
 
 

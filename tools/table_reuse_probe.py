@@ -10,8 +10,14 @@ around a sync, median of --calls calls after --warmup:
              reuse, or with PV_TABLE_REUSE=0)
   recur      default capacity, one batch again and again: the steady state of recurring signers
   multi      one call of 4 x 1,048,576 requests (four chunks of the same signers)
+  twice      capacity 1,024, three batches of disjoint signers in the order A A B B C C: every set is
+             built, hit once and replaced, so with affine rows on (pv_table_affine) each hit converts
+             1,024 tables that are never read again -- the promotion's worst case. Reported apart: the
+             calls that build (first of a pair) and the calls that hit (second); the conversion's own
+             time is the second's median less the same figure with PV_TABLE_AFFINE=0
 
-Prints one JSON line. A library without pv_table_reuse (an older build) runs the same loops."""
+Prints one JSON line. A library without pv_table_reuse or pv_table_affine (an older build) runs the
+same loops."""
 import argparse
 import ctypes
 import json
@@ -90,11 +96,25 @@ def loop(devs, calls, warmup):
     return {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
 
+def loop_pairs(devs, rounds, warmup_rounds):
+    """devs in the order A A B B C C ...: medians of all calls, of the first and of the second of a pair."""
+    first, second = [], []
+    for r in range(warmup_rounds + rounds):
+        for i, d in enumerate(devs):
+            t = d.call()
+            if r >= warmup_rounds:
+                (second if i % 2 else first).append(t)
+    med = lambda v: round(float(np.median(v)), 4)  # noqa: E731
+    return {"median_ms": med(first + second), "first_ms": med(first), "second_ms": med(second),
+            "second_min_ms": round(min(second), 4), "second_max_ms": round(max(second), 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--no-multi", action="store_true")
+    ap.add_argument("--no-twice", action="store_true")
     a = ap.parse_args()
     ls = LibSodium()
     _native.ensure_device()
@@ -102,6 +122,9 @@ def main():
     has = hasattr(_native, "table_reuse")
     A, B = Dev(L, *make_batch(ls, 1)), Dev(L, *make_batch(ls, 2))
     out = {"lib": os.path.basename(_native.LIB_PATH), "table_reuse": has and os.environ.get("PV_TABLE_REUSE") != "0"}
+    has_aff = hasattr(_native, "table_affine")
+    out["table_affine"] = has_aff and os.environ.get("PV_TABLE_AFFINE") != "0"
+    a0 = _native.table_affine_stats() if has_aff else None
     if has:
         _native.table_reuse(out["table_reuse"], SIGNERS)
         s0 = _native.table_reuse_stats()
@@ -114,6 +137,19 @@ def main():
     if has:
         out["recur"]["hits_built_resets"] = [int(x - y) for x, y in zip(_native.table_reuse_stats(), s0)]
     assert A.valid() == A.n and B.valid() == B.n
+    if has_aff:
+        out["recur"]["converted_affine_reads"] = [int(x - y) for x, y in zip(_native.table_affine_stats(), a0)]
+    if not a.no_twice:
+        C = Dev(L, *make_batch(ls, 3))
+        if has:
+            _native.table_reuse(out["table_reuse"], SIGNERS)
+        a0 = _native.table_affine_stats() if has_aff else None
+        out["twice"] = loop_pairs([A, A, B, B, C, C], max(3, a.calls // 4), 1)
+        if has_aff:
+            out["twice"]["converted_affine_reads"] = [int(x - y) for x, y in zip(_native.table_affine_stats(), a0)]
+        if has:
+            _native.table_reuse(out["table_reuse"], _native.PV_TABLE_REUSE_CAP)
+        assert A.valid() == A.n and B.valid() == B.n and C.valid() == C.n
     if not a.no_multi:
         M = Dev(L, *make_batch(ls, 1, reps=4))
         out["multi_4m"] = loop([M], max(5, a.calls // 2), 2)
