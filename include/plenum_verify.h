@@ -680,6 +680,63 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
                          const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, PvTrieOut* out);
 int pv_trie_path(int mode);
 
+/* ---- State proofs: batched verification with SHA3-256 proof-node hashing ----
+ * PruningState.verify_state_proof (state/pruning_state.py:113-122 over pruning_trie.py:1100-1119) for many
+ * queries at once. A proof is a pool of node records (each one node's RLP); a query names its proof, a root,
+ * a key and the value expected as the trie stores it (PruningState passes rlp([value])), length 0 expecting
+ * the key's absence. Several queries may share one proof (verify_state_proof_multi, prefix proofs).
+ *   pv_trie_verify_proofs         host buffers; one status byte per query:
+ *                                   PV_PROOF_ACCEPT / PV_PROOF_REJECT   what the reference's call returns;
+ *                                   PV_PROOF_DEFER    the library does not decide: a record of the query's
+ *                                                     proof is not canonical RLP (the reference decodes
+ *                                                     leniently and hashes its own re-encoding), or a node
+ *                                                     the walk visits is not a well-formed trie node. The
+ *                                                     caller runs its sequential method.
+ *                                 On the device or the host path as pv_trie_path says; AUTO takes the device
+ *                                 from PV_TRIE_PROOF_AUTO_MIN records on. PV_ERR_ARG: a null pointer,
+ *                                 decreasing offsets, query_proof[i] >= n_proofs, a proof of more than
+ *                                 PV_PROOF_MAX_NODES records, a key above 65,535 bytes, a value not below 2^24.
+ *   pv_trie_verify_proofs_device  the same on device buffers (d_in is a host struct of device pointers),
+ *                                 two launches enqueued on `stream` (null = the library's), no synchronise.
+ *                                 d_node_hash: 32 n_nodes bytes of scratch, 8-byte aligned; node_blob readable
+ *                                 to its last record's end rounded up to 8 bytes. Nothing the host cannot see
+ *                                 is validated: a query whose indices or sizes are out of range gets
+ *                                 PV_PROOF_DEFER and reads nothing. PV_ERR_NOT_INIT without pv_init.
+ *   pv_trie_proof_split           host only: n_proofs serialized proofs ser[ser_off[p] .. ser_off[p + 1]), each
+ *                                 the RLP list of its nodes, split into records in place: node i is
+ *                                 ser[node_off[i] .. + node_len[i]), proof p has the records proof_first[p] ..
+ *                                 proof_first[p + 1]. The list prefixes lie between the records, hence the
+ *                                 lengths. proof_ok[p] = 0 (and no records) for a proof whose outer list is not
+ *                                 canonical RLP: the caller defers it. node_off holds node_cap + 1 entries
+ *                                 (the last one closes the array, as PvProofIn's), node_len node_cap.
+ *                                 *n_nodes is the count needed; records beyond node_cap are not written
+ *                                 (PV_TRIE_NEED_SPACE). */
+#define PV_PROOF_REJECT 0
+#define PV_PROOF_ACCEPT 1
+#define PV_PROOF_DEFER 2
+#define PV_PROOF_MAX_NODES 1024   /* records per proof */
+#define PV_TRIE_PROOF_AUTO_MIN 259 /* proof records from which AUTO takes the device path */
+typedef struct {
+    const uint8_t* node_blob;
+    const uint64_t* node_off;    /* n_nodes + 1: record i starts at node_off[i] */
+    uint64_t n_nodes;
+    const uint64_t* proof_first; /* n_proofs + 1: first record of proof p */
+    uint64_t n_proofs;
+    const uint32_t* query_proof; /* n_queries: which proof */
+    const uint8_t* root;         /* 32 n_queries */
+    const uint8_t* key_blob;
+    const uint64_t* key_off;     /* n_queries + 1 */
+    const uint8_t* val_blob;
+    const uint64_t* val_off;     /* n_queries + 1; length 0 = expect absence */
+    uint64_t n_queries;
+    const uint64_t* node_len;    /* null: record i ends at node_off[i + 1]; else n_nodes lengths (records
+                                    with bytes between them, as pv_trie_proof_split leaves them) */
+} PvProofIn;
+int pv_trie_verify_proofs(const PvProofIn* in, uint8_t* status);
+int pv_trie_verify_proofs_device(const PvProofIn* d_in, uint8_t* d_status, uint8_t* d_node_hash, void* stream);
+int pv_trie_proof_split(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,
+                        uint64_t* node_off, uint64_t* node_len, uint64_t node_cap, uint64_t* n_nodes, uint8_t* proof_ok);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 //                         barrier between depths (as pv_merkle_upper_kernel for the upper Merkle
 //                         levels): a long, thin top of the trie costs no launches.
 // and pv_sha3_blob_kernel, the primitive on its own: records in a blob plus offsets, at any alignment.
+// Further down, the read path: pv_proof_node_kernel and pv_proof_walk_kernel verify batches of state proofs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -20,6 +21,7 @@
 #include "../../include/plenum_verify.h"
 #include "keccak.h"
 #include "pv_internal.h"
+#include "trie_core.h"
 #include "trie_host.h"
 
 namespace {
@@ -69,6 +71,59 @@ __global__ __launch_bounds__(TR_BLOCK) void pv_sha3_blob_kernel(const uint8_t* _
     sha3_256(d, len, PvKeccakWords(data + a, len));
 #pragma unroll
     for (int k = 0; k < 4; k++) out[4 * i + k] = d[k];
+}
+
+// State proofs: two launches on one stream, ordered by the stream alone.
+//   pv_proof_node_kernel  one lane per proof record: its SHA3-256, absorbed as pv_sha3_blob_kernel absorbs
+//                         it, and one flag byte, 1 when the record is not canonical RLP all the way down
+//                         (tr_rlp_canonical: byte loads inside the record, four named list ends, no stack);
+//   pv_proof_walk_kernel  one lane per query: PV_PROOF_DEFER when a record of its proof is flagged, else
+//                         tr_proof_walk on the RLP bytes in place, the node behind a reference found by a
+//                         linear scan of the proof's digests.
+// Neither trusts an index it reads from device memory: a record whose offsets decrease is flagged, a query
+// whose proof, record range or key and value offsets are out of range is deferred without a read.
+__global__ __launch_bounds__(TR_BLOCK) void pv_proof_node_kernel(const uint8_t* __restrict__ blob,
+                                                                 const uint64_t* __restrict__ off,
+                                                                 const uint64_t* __restrict__ lens, uint64_t n,
+                                                                 uint64_t* __restrict__ digest, uint8_t* __restrict__ flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t a = off[i];
+    uint64_t len;
+    bool bad = false;
+    if (lens) {
+        len = lens[i];
+    } else {
+        const uint64_t b = off[i + 1];
+        bad = b < a;
+        len = bad ? 0 : b - a;
+    }
+    uint64_t d[4];
+    sha3_256(d, len, PvKeccakWords(blob + a, len));
+#pragma unroll
+    for (int k = 0; k < 4; k++) digest[4 * i + k] = d[k];
+    flag[i] = bad || !tr_rlp_canonical(blob + a, len) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(TR_BLOCK) void pv_proof_walk_kernel(const PvProofIn in, const uint64_t* __restrict__ digest,
+                                                                 const uint8_t* __restrict__ flag,
+                                                                 uint8_t* __restrict__ status) {
+    const uint64_t i = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (i >= in.n_queries) return;
+    uint8_t st = PV_PROOF_DEFER;
+    const uint64_t p = in.query_proof[i];
+    if (p < in.n_proofs) {
+        const uint64_t first = in.proof_first[p], last = in.proof_first[p + 1];
+        const uint64_t ka = in.key_off[i], kb = in.key_off[i + 1], va = in.val_off[i], vb = in.val_off[i + 1];
+        if (first <= last && last <= in.n_nodes && last - first <= PV_PROOF_MAX_NODES && ka <= kb && va <= vb) {
+            bool clean = true;
+            for (uint64_t j = first; j < last; j++) clean &= flag[j] == 0;
+            if (clean)
+                st = (uint8_t)tr_proof_walk(in.node_blob, in.node_off, in.node_len, digest, first, last - first,
+                                            in.root + 32 * i, in.key_blob + ka, kb - ka, in.val_blob + va, vb - va);
+        }
+    }
+    status[i] = st;
 }
 
 // --------------------------------------------------------------------------------------------- host
@@ -178,6 +233,95 @@ int tr_choose(uint64_t work, const char* who, bool* device) {
         return pv_fail(PV_ERR_NO_DEVICE, std::string(who) + ": the device path is forced and no device is initialised");
     *device = work > 0 && have_dev && (g_tr_path == PV_TRIE_DEVICE || (g_tr_path == PV_TRIE_AUTO && work >= PV_TRIE_AUTO_MIN));
     return PV_OK;
+}
+
+// Both proof launches for device buffers. Caller holds g_tr_mu.
+int tr_proof_enqueue(const PvProofIn& d, uint64_t* d_digest, uint8_t* d_flag, uint8_t* d_status, hipStream_t st) {
+    if (d.n_nodes) {
+        hipLaunchKernelGGL(pv_proof_node_kernel, dim3((unsigned)((d.n_nodes + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
+                           st, d.node_blob, d.node_off, d.node_len, d.n_nodes, d_digest, d_flag);
+        TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    }
+    hipLaunchKernelGGL(pv_proof_walk_kernel, dim3((unsigned)((d.n_queries + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
+                       d, (const uint64_t*)d_digest, (const uint8_t*)d_flag, d_status);
+    TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+// The host-buffer entry's device path: every array staged into the workspace, offsets rebased to the
+// bytes that are copied, statuses copied back. Caller holds g_tr_mu and has validated `in`.
+int tr_proof_device(const PvProofIn& in, uint8_t* status) {
+    const hipStream_t st = pv_engine_stream();
+    int rc = tr_begin(st);
+    if (rc) return rc;
+    auto run = [&]() -> int {
+        const uint64_t nn = in.n_nodes, np = in.n_proofs, nq = in.n_queries;
+        uint64_t lo = ~0ull, hi = 0;  // the span of the node blob the records lie in
+        for (uint64_t i = 0; i < nn; i++) {
+            const uint64_t len = in.node_len ? in.node_len[i] : in.node_off[i + 1] - in.node_off[i];
+            lo = std::min(lo, in.node_off[i]);
+            hi = std::max(hi, in.node_off[i] + len);
+        }
+        if (nn == 0) lo = hi = 0;
+        const uint64_t kbase = in.key_off[0], kbytes = in.key_off[nq] - kbase, vbase = in.val_off[0],
+                       vbytes = in.val_off[nq] - vbase;
+        std::vector<uint64_t> noff(nn + 1), koff(nq + 1), voff(nq + 1);
+        for (uint64_t i = 0; i < nn; i++) noff[i] = in.node_off[i] - lo;
+        noff[nn] = in.node_len ? hi - lo : in.node_off[nn] - lo;
+        for (uint64_t i = 0; i <= nq; i++) {
+            koff[i] = in.key_off[i] - kbase;
+            voff[i] = in.val_off[i] - vbase;
+        }
+        uint64_t at = 0;
+        auto seg = [&](uint64_t bytes) {
+            const uint64_t a = at;
+            at += tr_up(bytes ? bytes : 1);
+            return a;
+        };
+        const uint64_t i_noff = seg(8 * (nn + 1)), i_nlen = seg(in.node_len ? 8 * nn : 0), i_pf = seg(8 * (np + 1)),
+                       i_koff = seg(8 * (nq + 1)), i_voff = seg(8 * (nq + 1)), i_qp = seg(4 * nq), i_root = seg(32 * nq),
+                       i_key = seg(kbytes), i_val = seg(vbytes), i_blob = seg(hi - lo + 8);
+        const uint64_t o_flag = tr_up(32 * nn + 1), o_status = o_flag + tr_up(nn + 1);
+        int rc;
+        if ((rc = tr_grow(g_tr.d_in, g_tr.d_in_cap, at)) || (rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, o_status + tr_up(nq))))
+            return rc;
+        auto put = [&](uint64_t where, const void* src, uint64_t bytes) -> hipError_t {
+            return bytes ? hipMemcpyAsync(g_tr.d_in + where, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+        };
+        TR_HIP(put(i_noff, noff.data(), 8 * (nn + 1)), PV_ERR_LAUNCH);
+        if (in.node_len) TR_HIP(put(i_nlen, in.node_len, 8 * nn), PV_ERR_LAUNCH);
+        TR_HIP(put(i_pf, in.proof_first, 8 * (np + 1)), PV_ERR_LAUNCH);
+        TR_HIP(put(i_koff, koff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
+        TR_HIP(put(i_voff, voff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
+        TR_HIP(put(i_qp, in.query_proof, 4 * nq), PV_ERR_LAUNCH);
+        TR_HIP(put(i_root, in.root, 32 * nq), PV_ERR_LAUNCH);
+        TR_HIP(put(i_key, kbytes ? in.key_blob + kbase : nullptr, kbytes), PV_ERR_LAUNCH);
+        TR_HIP(put(i_val, vbytes ? in.val_blob + vbase : nullptr, vbytes), PV_ERR_LAUNCH);
+        TR_HIP(put(i_blob, hi > lo ? in.node_blob + lo : nullptr, hi - lo), PV_ERR_LAUNCH);
+        auto u64p = [&](uint64_t where) { return reinterpret_cast<const uint64_t*>(g_tr.d_in + where); };
+        PvProofIn d;
+        d.node_blob = g_tr.d_in + i_blob;
+        d.node_off = u64p(i_noff);
+        d.n_nodes = nn;
+        d.proof_first = u64p(i_pf);
+        d.n_proofs = np;
+        d.query_proof = reinterpret_cast<const uint32_t*>(g_tr.d_in + i_qp);
+        d.root = g_tr.d_in + i_root;
+        d.key_blob = g_tr.d_in + i_key;
+        d.key_off = u64p(i_koff);
+        d.val_blob = g_tr.d_in + i_val;
+        d.val_off = u64p(i_voff);
+        d.n_queries = nq;
+        d.node_len = in.node_len ? u64p(i_nlen) : nullptr;
+        if ((rc = tr_proof_enqueue(d, reinterpret_cast<uint64_t*>(g_tr.d_out), g_tr.d_out + o_flag, g_tr.d_out + o_status, st)))
+            return rc;
+        TR_HIP(hipMemcpyAsync(status, g_tr.d_out + o_status, nq, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        TR_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+        return PV_OK;
+    };
+    rc = run();
+    const int rc2 = tr_end(st);
+    return rc ? rc : rc2;
 }
 
 }  // namespace
@@ -315,6 +459,54 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
     }
     memcpy(out->root, out->node_hash + 32 * (nr - 1), 32);  // the root is the last record
     return PV_OK;
+}
+
+int pv_trie_verify_proofs(const PvProofIn* in, uint8_t* status) {
+    if (!in) return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs: null input struct");
+    if (in->n_queries == 0) return PV_OK;
+    if (!status) return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs: null status");
+    const char* why = nullptr;
+    if (pv_proof_check_args(*in, &why)) return pv_fail(PV_ERR_ARG, std::string("pv_trie_verify_proofs: ") + why);
+    std::unique_lock<std::mutex> lk(g_tr_mu);
+    const bool have_dev = pv_engine_stream() != nullptr;
+    if (g_tr_path == PV_TRIE_DEVICE && !have_dev)
+        return pv_fail(PV_ERR_NO_DEVICE, "pv_trie_verify_proofs: the device path is forced and no device is initialised");
+    if (have_dev && (g_tr_path == PV_TRIE_DEVICE || (g_tr_path == PV_TRIE_AUTO && in->n_nodes >= PV_TRIE_PROOF_AUTO_MIN)))
+        return tr_proof_device(*in, status);
+    lk.unlock();  // the host path shares no workspace
+    pv_proof_host(*in, status);
+    return PV_OK;
+}
+
+int pv_trie_verify_proofs_device(const PvProofIn* d_in, uint8_t* d_status, uint8_t* d_node_hash, void* stream) {
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_trie_verify_proofs_device: call pv_init first");
+    if (!d_in) return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: null input struct");
+    if (d_in->n_queries == 0) return PV_OK;
+    if (!d_status || !d_in->proof_first || !d_in->query_proof || !d_in->root || !d_in->key_off || !d_in->val_off ||
+        !d_in->key_blob || !d_in->val_blob || (d_in->n_nodes && (!d_in->node_off || !d_in->node_blob || !d_node_hash)))
+        return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: null pointer");
+    if (reinterpret_cast<uintptr_t>(d_node_hash) & 7u)
+        return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: d_node_hash must be 8-byte aligned");
+    if ((d_in->n_nodes >> 31) || (d_in->n_queries >> 31) || (d_in->n_proofs >> 31))
+        return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: more than 2^31 - 1 records, proofs or queries");
+    const hipStream_t st = stream ? (hipStream_t)stream : pv_engine_stream();
+    std::lock_guard<std::mutex> lk(g_tr_mu);
+    int rc = tr_begin(st);  // the flags live in the workspace: handed over from the stream that used it last
+    if (rc) return rc;
+    if (!(rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, tr_up(d_in->n_nodes + 1))))
+        rc = tr_proof_enqueue(*d_in, reinterpret_cast<uint64_t*>(d_node_hash), g_tr.d_out, d_status, st);
+    const int rc2 = tr_end(st);
+    return rc ? rc : rc2;
+}
+
+int pv_trie_proof_split(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,
+                        uint64_t* node_off, uint64_t* node_len, uint64_t node_cap, uint64_t* n_nodes, uint8_t* proof_ok) {
+    if (!proof_first || !n_nodes) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null pointer");
+    if (n_proofs && (!ser_off || !proof_ok || !tr_monotone(ser_off, n_proofs)))
+        return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null pointer or decreasing offsets");
+    if (n_proofs && !ser && ser_off[n_proofs] != ser_off[0]) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null proofs");
+    if (!node_off || (node_cap && !node_len)) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: a capacity without its array");
+    return pv_proof_split_host(ser, ser_off, n_proofs, proof_first, node_off, node_len, node_cap, n_nodes, proof_ok);
 }
 
 }  // extern "C"

@@ -13,6 +13,9 @@
 // has 32 bytes or more, and its RLP itself below that (pruning_trie.py:339-340). So every node to hash
 // is laid out in one arena, 64-bit aligned, with a 32-byte hole where each hashed child's digest goes,
 // and the hashing (keccak.h here, pv_trie.hip on the device) runs depth by depth, deepest first.
+//
+// At the end of the file, the host side of state-proof verification: splitting serialized proofs into
+// records, the argument checks of the host-buffer entry, and the host path of the two stages.
 #include "trie_host.h"
 
 #include <string.h>
@@ -460,6 +463,100 @@ void pv_trie_host_hash(uint8_t* arena, const PvTrieRec* recs, uint64_t n, uint8_
         });
         i0 = i1;
     }
+}
+
+// ---------------------------------------------------------------------------------- state proofs
+
+int pv_proof_check_args(const PvProofIn& in, const char** err) {
+    auto bad = [&](const char* why) {
+        *err = why;
+        return PV_ERR_ARG;
+    };
+    auto monotone = [](const uint64_t* o, uint64_t k) {
+        for (uint64_t i = 0; i < k; i++)
+            if (o[i + 1] < o[i]) return false;
+        return true;
+    };
+    if (!in.proof_first || !in.query_proof || !in.root || !in.key_off || !in.val_off || !in.node_off)
+        return bad("null pointer");
+    if ((in.n_nodes >> 31) || (in.n_queries >> 31) || (in.n_proofs >> 31)) return bad("more than 2^31 - 1 records, proofs or queries");
+    if (!monotone(in.proof_first, in.n_proofs) || !monotone(in.key_off, in.n_queries) || !monotone(in.val_off, in.n_queries) ||
+        (!in.node_len && !monotone(in.node_off, in.n_nodes)))
+        return bad("offsets must be non-decreasing");
+    if (in.proof_first[in.n_proofs] > in.n_nodes) return bad("proof_first reaches past the records");
+    for (uint64_t p = 0; p < in.n_proofs; p++)
+        if (in.proof_first[p + 1] - in.proof_first[p] > PV_PROOF_MAX_NODES) return bad("a proof of more than 1,024 records");
+    bool bytes = false;
+    for (uint64_t i = 0; i < in.n_nodes && !bytes; i++) bytes = in.node_len ? in.node_len[i] != 0 : in.node_off[i + 1] != in.node_off[i];
+    if (bytes && !in.node_blob) return bad("null node blob");
+    if ((!in.key_blob && in.key_off[in.n_queries] != in.key_off[0]) || (!in.val_blob && in.val_off[in.n_queries] != in.val_off[0]))
+        return bad("null key or value blob");
+    for (uint64_t i = 0; i < in.n_queries; i++) {
+        if (in.query_proof[i] >= in.n_proofs) return bad("a query names a proof that is not there");
+        if (in.key_off[i + 1] - in.key_off[i] > PV_TRIE_MAX_KEY) return bad("a key is longer than 65,535 bytes");
+        if (in.val_off[i + 1] - in.val_off[i] > PV_TRIE_MAX_VALUE) return bad("a value is not below 2^24 bytes");
+    }
+    return PV_OK;
+}
+
+void pv_proof_host(const PvProofIn& in, uint8_t* status) {
+    std::vector<uint64_t> digest(4 * in.n_nodes + 1);
+    std::vector<uint8_t> flag(in.n_nodes + 1);  // 1: the record is not canonical RLP
+    parallel_for(in.n_nodes, [&](uint64_t lo, uint64_t hi) {
+        std::vector<uint64_t> buf;
+        for (uint64_t i = lo; i < hi; i++) {
+            const uint64_t len = in.node_len ? in.node_len[i] : in.node_off[i + 1] - in.node_off[i];
+            const uint8_t* p = in.node_blob + in.node_off[i];
+            buf.assign(len / 8 + 1, 0);  // aligned and whole words: what the word reader loads
+            if (len) memcpy(buf.data(), p, len);
+            sha3_256(&digest[4 * i], len, PvKeccakWords(reinterpret_cast<const uint8_t*>(buf.data()), len));
+            flag[i] = tr_rlp_canonical(p, len) ? 0 : 1;
+        }
+    });
+    // queries are cheap next to records: a thread per 128 of them as well
+    parallel_for(in.n_queries, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            const uint64_t first = in.proof_first[in.query_proof[i]], count = in.proof_first[in.query_proof[i] + 1] - first;
+            bool clean = true;
+            for (uint64_t j = first; j < first + count; j++) clean &= flag[j] == 0;
+            status[i] = !clean ? (uint8_t)TR_PROOF_DEFER
+                               : (uint8_t)tr_proof_walk(in.node_blob, in.node_off, in.node_len, digest.data(), first, count,
+                                                        in.root + 32 * i, in.key_blob + in.key_off[i],
+                                                        in.key_off[i + 1] - in.key_off[i], in.val_blob + in.val_off[i],
+                                                        in.val_off[i + 1] - in.val_off[i]);
+        }
+    });
+}
+
+int pv_proof_split_host(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,
+                        uint64_t* node_off, uint64_t* node_len, uint64_t node_cap, uint64_t* n_nodes, uint8_t* proof_ok) {
+    uint64_t n = 0;
+    for (uint64_t p = 0; p < n_proofs; p++) {
+        proof_first[p] = n;
+        proof_ok[p] = 0;
+        const uint8_t* a = ser + ser_off[p];
+        const uint8_t* b = ser + ser_off[p + 1];
+        TrItem top, it;
+        if (!tr_rlp_item(a, b, &top) || !top.list || top.raw + top.raw_len != b) continue;
+        bool ok = true;
+        uint64_t k = 0;
+        for (const uint8_t* q = top.p; q < b; q += it.raw_len, k++)
+            if (!(ok = tr_rlp_item(q, b, &it))) break;
+        if (!ok) continue;
+        proof_ok[p] = 1;
+        for (const uint8_t* q = top.p; q < b; q += it.raw_len, n++) {
+            tr_rlp_item(q, b, &it);
+            if (n < node_cap) {
+                node_off[n] = (uint64_t)(q - ser);
+                node_len[n] = it.raw_len;
+            }
+        }
+    }
+    proof_first[n_proofs] = n;
+    *n_nodes = n;
+    if (n > node_cap) return PV_TRIE_NEED_SPACE;
+    node_off[n] = n_proofs ? ser_off[n_proofs] : 0;  // n + 1 entries, as PvProofIn's
+    return PV_OK;
 }
 
 void pv_sha3_host_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* out) {

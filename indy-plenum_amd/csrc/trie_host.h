@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/plenum_verify.h"
+
 // One node to hash: arena[off .. off + len) is its RLP (off a multiple of 8), its digest goes to
 // arena[hole .. hole + 32) in its parent's record (PV_TRIE_NO_HOLE: the root). Records are ordered
 // deepest first; `next` is the index of the first record of the next shallower depth.
@@ -51,6 +53,15 @@ int pv_trie_host_build(const PvTrieIn& in, PvTriePlan* plan, std::string* err);
 void pv_trie_host_hash(uint8_t* arena, const PvTrieRec* recs, uint64_t n, uint8_t* hashes);
 // SHA3-256 of n records data[off[i] .. off[i + 1]) to out[32 i], on up to 16 threads.
 void pv_sha3_host_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* out);
+
+// State proofs on the host path: SHA3-256 and tr_rlp_canonical of every record, then tr_proof_walk of
+// every query (trie_core.h), each on up to 16 threads. Arguments are validated by the caller.
+void pv_proof_host(const PvProofIn& in, uint8_t* status);
+// pv_trie_proof_split (plenum_verify.h) once its pointers are checked.
+int pv_proof_split_host(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,
+                        uint64_t* node_off, uint64_t* node_len, uint64_t node_cap, uint64_t* n_nodes, uint8_t* proof_ok);
+// PV_OK, or PV_ERR_ARG with *err set: the checks of pv_trie_verify_proofs on host-readable arguments.
+int pv_proof_check_args(const PvProofIn& in, const char** err);
 
 extern const uint8_t PV_TRIE_BLANK_ROOT[32];
 

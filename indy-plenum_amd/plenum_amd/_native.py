@@ -128,6 +128,10 @@ SIGNATURES = {
     "pv_trie_update_batch": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64] + [ctypes.c_void_p] * 4
                              + [ctypes.c_uint64, ctypes.c_void_p]),
     "pv_trie_path": (ctypes.c_int, [ctypes.c_int]),
+    "pv_trie_verify_proofs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_trie_verify_proofs_device": (ctypes.c_int, [ctypes.c_void_p] * 4),
+    "pv_trie_proof_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 3
+                            + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -754,12 +758,12 @@ def trie_path(mode=PV_TRIE_AUTO):
     _trie_mode = mode
 
 
-def _trie_device_ready(work):
+def _trie_device_ready(work, auto_min=PV_TRIE_AUTO_MIN):
     """As _merkle_device_ready: a GPU is bound only by a call that will hash on it."""
     global _trie_no_device
     if _device is not None or _trie_no_device or _trie_mode == PV_TRIE_HOST:
         return
-    if _trie_mode == PV_TRIE_AUTO and work < PV_TRIE_AUTO_MIN:
+    if _trie_mode == PV_TRIE_AUTO and work < auto_min:
         return
     try:
         ensure_device()
@@ -842,3 +846,88 @@ def trie_update(root, fetch, keys, values):
         check(rc, "pv_trie_update_batch")
         trie_last.update(launches=int(out.launches), tail_records=int(out.tail_records), nodes=len(nodes), rounds=rounds)
         return new_root, nodes
+
+
+# ------------------------------------------------------------------------------------- state proofs
+PV_PROOF_REJECT, PV_PROOF_ACCEPT, PV_PROOF_DEFER = 0, 1, 2
+PV_PROOF_MAX_NODES = 1024
+PV_TRIE_PROOF_AUTO_MIN = 259  # include/plenum_verify.h: proof records from which AUTO takes the device path
+
+
+class PvProofIn(ctypes.Structure):
+    _fields_ = [("node_blob", ctypes.c_void_p), ("node_off", ctypes.c_void_p), ("n_nodes", ctypes.c_uint64),
+                ("proof_first", ctypes.c_void_p), ("n_proofs", ctypes.c_uint64), ("query_proof", ctypes.c_void_p),
+                ("root", ctypes.c_void_p), ("key_blob", ctypes.c_void_p), ("key_off", ctypes.c_void_p),
+                ("val_blob", ctypes.c_void_p), ("val_off", ctypes.c_void_p), ("n_queries", ctypes.c_uint64),
+                ("node_len", ctypes.c_void_p)]
+
+
+# how the last trie_verify_proofs_raw ran: records hashed, queries, queries deferred, kernel launches (0: host path)
+proof_last = {"nodes": 0, "queries": 0, "deferred": 0, "launches": 0}
+
+
+def trie_proof_split(sers):
+    """One pv_trie_proof_split over serialized proofs (each the RLP list of its nodes): (blob, proof_first,
+    node_off, node_len, ok). Record i is blob[node_off[i]:node_off[i] + node_len[i]], proof p has the records
+    proof_first[p] .. proof_first[p + 1]; ok[p] = 0 for a proof whose outer list is not canonical RLP."""
+    n = len(sers)
+    blob, off = _blob(sers)
+    first, ok = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8)
+    cap = max(16, int(blob.size) // 32)
+    while True:
+        node_off, node_len, count = np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint64), ctypes.c_uint64()
+        rc = lib().pv_trie_proof_split(_ptr(blob), _ptr(off), n, _ptr(first), _ptr(node_off), _ptr(node_len), cap,
+                                       ctypes.byref(count), _ptr(ok))
+        if rc != PV_TRIE_NEED_SPACE:
+            break
+        cap = int(count.value)
+    check(rc, "pv_trie_proof_split")
+    k = int(count.value)
+    return blob, first, node_off[:k + 1], node_len[:k], ok[:n]
+
+
+def trie_verify_proofs_raw(node_blob, node_off, node_len, proof_first, query_proof, roots, key_blob, key_off, val_blob,
+                           val_off):
+    """One pv_trie_verify_proofs on arrays laid out as PvProofIn says (node_len None: record i ends at
+    node_off[i + 1]). Returns the uint8 status per query."""
+    u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64)  # noqa: E731
+    u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)  # noqa: E731
+    node_blob, node_off, proof_first = u8(node_blob), u64(node_off), u64(proof_first)
+    node_len = u64(node_len) if node_len is not None else None
+    query_proof = np.ascontiguousarray(query_proof, dtype=np.uint32)
+    roots, key_blob, key_off, val_blob, val_off = u8(roots), u8(key_blob), u64(key_off), u8(val_blob), u64(val_off)
+    nn, npf, nq = node_off.shape[0] - 1, proof_first.shape[0] - 1, query_proof.shape[0]
+    if nn < 0 or npf < 0 or key_off.shape[0] != nq + 1 or val_off.shape[0] != nq + 1 or roots.size != 32 * nq or \
+            (node_len is not None and node_len.shape[0] != nn):
+        raise ValueError("trie_verify_proofs: array sizes do not fit together")
+    ends = node_off[:-1] + node_len if node_len is not None else node_off[1:]
+    if (nn and int(ends.max()) > node_blob.size) or (nq and (int(key_off[nq]) > key_blob.size or int(val_off[nq]) > val_blob.size)):
+        raise ValueError("trie_verify_proofs: offsets reach past a blob")
+    status = np.zeros(nq, np.uint8)
+    if nq == 0:
+        return status
+    _trie_device_ready(nn, PV_TRIE_PROOF_AUTO_MIN)
+    pad = lambda a: a if a.size else np.zeros(1, np.uint8)  # noqa: E731
+    keep = [pad(node_blob), pad(key_blob), pad(val_blob), pad(roots)]
+    arg = PvProofIn(keep[0].ctypes.data, node_off.ctypes.data, nn, proof_first.ctypes.data, npf, query_proof.ctypes.data,
+                    keep[3].ctypes.data, keep[1].ctypes.data, key_off.ctypes.data, keep[2].ctypes.data, val_off.ctypes.data,
+                    nq, node_len.ctypes.data if node_len is not None else None)
+    check(lib().pv_trie_verify_proofs(ctypes.byref(arg), _ptr(status)), "pv_trie_verify_proofs")
+    device = _device is not None and (_trie_mode == PV_TRIE_DEVICE or (_trie_mode == PV_TRIE_AUTO and nn >= PV_TRIE_PROOF_AUTO_MIN))
+    proof_last.update(nodes=nn, queries=nq, deferred=int((status == PV_PROOF_DEFER).sum()),
+                      launches=(2 if nn else 1) if device else 0)
+    return status
+
+
+def trie_verify_proofs(blob, off, lens, node_idx, proof_first, query_proof, roots, keys, values):
+    """pv_trie_verify_proofs over the records node_idx picks out of (blob, off, lens): lens None means record i
+    ends at off[i + 1]. proof_first indexes node_idx; roots, keys and values are lists of bytes, one per query."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint64) if lens is not None else np.diff(off)
+    idx = np.ascontiguousarray(node_idx, dtype=np.int64)
+    node_off = np.concatenate([off[:-1][idx], np.zeros(1, np.uint64)]) if off.size else np.zeros(1, np.uint64)
+    kb, ko = _blob(keys)
+    vb, vo = _blob(values)
+    blob = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob
+    return trie_verify_proofs_raw(blob, node_off, lens[idx], proof_first, query_proof,
+                                  np.frombuffer(b"".join(roots), np.uint8), kb, ko, vb, vo)

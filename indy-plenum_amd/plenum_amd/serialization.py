@@ -9,7 +9,10 @@ parent path), which must be preserved for signature compatibility:
   level 0 only); other iterables -> items joined by ","; None -> ""; anything else -> str(obj);
   a value outside (str, int, float, list, dict, None) -> Exception("invalid type found ...").
 """
+import base64
 from collections.abc import Iterable
+
+from .base58 import b58decode, b58encode
 
 _ACCEPTED = (str, int, float, list, dict, type(None))
 
@@ -53,3 +56,29 @@ signing_serializer = SigningSerializer()
 def serialize_msg_for_signing(msg, topLevelKeysToIgnore=None):
     """UTF-8 bytes of ``msg`` in signing form (serialization.py:27-36)."""
     return signing_serializer.serialize(msg, topLevelKeysToIgnore=topLevelKeysToIgnore)
+
+
+class Base58Serializer:
+    """bytes <-> base58 text (common/serializers/base58_serializer.py), over the package's own base58."""
+
+    def serialize(self, data, fields=None, toBytes=False):
+        return b58encode(data).decode("utf-8")
+
+    def deserialize(self, data, fields=None):
+        return b58decode(data)
+
+
+class Base64Serializer:
+    """bytes <-> base64 bytes (common/serializers/base64_serializer.py)."""
+
+    def serialize(self, data, fields=None, toBytes=False):
+        return base64.b64encode(data)
+
+    def deserialize(self, data, fields=None):
+        return base64.b64decode(data)
+
+
+# The wire form of a state proof (common/serializers/serialization.py:18-20): the root hash in base58, the
+# serialized proof nodes (PruningState.generate_state_proof(..., serialize=True)) in base64.
+state_roots_serializer = Base58Serializer()
+proof_nodes_serializer = Base64Serializer()

@@ -14,8 +14,26 @@ call chain for a whole batch.
                                      catch-up check)
 
 The batch calls go through libplenum_verify (pv_trie_update_batch): the structure in C++ on the host, the
-SHA3-256 of every new node on the GPU or, for small batches and without one, on host threads. Not here:
-remove / delete, state proofs, prefix iteration, persistent stores."""
+SHA3-256 of every new node on the GPU or, for small batches and without one, on host threads.
+
+State proofs (pruning_trie.py:1043-1170, pruning_state.py:104-128): generate_state_proof and its prefix form,
+verify_state_proof and verify_state_proof_multi, and for many proofs at once
+
+    Trie.verify_spv_proof_batch(items)             n x Trie.verify_spv_proof
+    PruningState.verify_state_proof_batch(items)   n x PruningState.verify_state_proof
+    PruningState.generate_state_proof_batch(keys)  n x generate_state_proof, one decoded-node cache
+
+The batch verification goes through pv_trie_verify_proofs: one SHA3-256 per proof node and one walk per query,
+on the GPU or on host threads. The library answers ACCEPT, REJECT or DEFER per query; a deferred query (a proof
+record that is not canonical RLP, a malformed node on the path) goes through the sequential method here, which
+decodes as leniently as the reference does. Generation hashes nothing (the nodes come out of a content-addressed
+store) and stays in Python.
+
+Node order of a generated proof: the hashed nodes below the root in the order the walk loaded them, each once,
+then the root last. (The reference returns the nodes below the root in a set's order; the root is last there too.)
+An embedded node (RLP under 32 bytes) travels inside its parent and is no proof node of its own.
+
+Not here: remove / delete, prefix iteration, persistent stores."""
 import hashlib
 
 from . import _native
@@ -76,6 +94,35 @@ def rlp_decode(data):
             out.append(x)
         return out, b
     return item(0)[0]
+
+
+def _lenient_prefix(data, pos):
+    """(is_list, payload length, payload start) of the prefix at pos, nothing checked: a length field cut short
+    by the end of the data counts the bytes that are there."""
+    b0 = data[pos]
+    if b0 < 0x80:
+        return False, 1, pos
+    is_list = b0 >= 0xC0
+    v = b0 - (0xC0 if is_list else 0x80)
+    if v < 56:
+        return is_list, v, pos + 1
+    start = pos + 1 + v - 55
+    return is_list, int.from_bytes(data[pos + 1:start], "big"), start
+
+
+def rlp_decode_lenient(data):
+    """What the reference's proof deserializer (state/util/fast_rlp.py:34-71) makes of `data`: no bounds, no
+    minimal-length and no trailing-byte checks. A list runs to the end of the bytes it was given, whatever its
+    length field says; an item that runs past them is cut off there. IndexError on empty input."""
+    is_list, n, pos = _lenient_prefix(data, 0)
+    if not is_list:
+        return bytes(data[pos:pos + n])
+    out = []
+    while pos < len(data):
+        _, n, start = _lenient_prefix(data, pos)
+        out.append(rlp_decode_lenient(data[pos:start + n]))
+        pos = start + n
+    return out
 
 
 BLANK_ROOT = sha3(rlp_encode(BLANK_NODE))
@@ -241,6 +288,257 @@ class Trie:
         self._walk(node or self.root_node, [], out)
         return out
 
+    # -------------------------------------------------------------------------------------- proofs
+    def _recorder(self, cache=None):
+        """(load, seen): load(ref) is _load that notes every node it fetches by hash in `seen`, an insertion-
+        ordered {RLP: node}. Recording is local to the call that asked for it; `cache` ({hash: (RLP, node)})
+        lets several calls share the decoding."""
+        seen = {}
+
+        def load(ref):
+            if ref == BLANK_NODE or isinstance(ref, list):
+                return ref
+            hit = cache.get(ref) if cache is not None else None
+            if hit is None:
+                enc = bytes(self._db.get(ref))
+                hit = (enc, rlp_decode(enc))
+                if cache is not None:
+                    cache[bytes(ref)] = hit
+            seen.setdefault(hit[0], hit[1])
+            return hit[1]
+        return load, seen
+
+    @staticmethod
+    def _get_with(node, path, load):
+        """_get over load(ref), with the reference's answer for a list that is no node (pruning_trie.py:359-407:
+        neither 2 nor 17 items gives None, which equals no expected value)."""
+        while True:
+            if node == BLANK_NODE:
+                return BLANK_NODE
+            if len(node) == 17:
+                if not path:
+                    return node[16]
+                node, path = load(node[path[0]]), path[1:]
+                continue
+            if len(node) != 2:
+                return None
+            cur, term = hp_unpack(node[0])
+            if term:
+                return node[1] if cur == path else BLANK_NODE
+            if path[:len(cur)] != cur:
+                return BLANK_NODE
+            node, path = load(node[1]), path[len(cur):]
+
+    @staticmethod
+    def _last_node_for_prefix(node, prefix, seen_prefix, load):
+        """The node below which every key with `prefix` lies (pruning_trie.py:409-458); seen_prefix collects the
+        nibbles consumed above it, not the node's own path."""
+        while True:
+            if node == BLANK_NODE:
+                return BLANK_NODE
+            if len(node) == 17:
+                if not prefix:
+                    return node
+                seen_prefix.append(prefix[0])
+                node, prefix = load(node[prefix[0]]), prefix[1:]
+                continue
+            cur, term = hp_unpack(node[0])
+            if term or len(prefix) <= len(cur):
+                return node if cur[:len(prefix)] == prefix else BLANK_NODE
+            if prefix[:len(cur)] != cur:
+                return BLANK_NODE
+            seen_prefix.extend(cur)
+            node, prefix = load(node[1]), prefix[len(cur):]
+
+    def _collect(self, node, prefix, out, load):
+        """_walk over load(ref): {nibble tuple: raw value} of everything below node."""
+        if node == BLANK_NODE:
+            return
+        if len(node) == 17:
+            for i in range(16):
+                self._collect(load(node[i]), prefix + [i], out, load)
+            if node[16]:
+                out[tuple(prefix)] = node[16]
+            return
+        cur, term = hp_unpack(node[0])
+        if term:
+            out[tuple(prefix + cur)] = node[1]
+        else:
+            self._collect(load(node[1]), prefix + cur, out, load)
+
+    def produce_spv_proof(self, key, root=None, get_value=False, _cache=None):
+        """The nodes fetched by hash on key's path below `root` (a node; default the current root), in the order
+        loaded, each once. The root itself is not among them. With get_value: (nodes, the raw stored value or None)."""
+        root = root if root is not None else self.root_node
+        load, seen = self._recorder(_cache)
+        rv = self._get_with(root, bin_to_nibbles(_to_bytes(key, "Key")), load)
+        nodes = list(seen.values())
+        return (nodes, rv if rv != BLANK_NODE else None) if get_value else nodes
+
+    def produce_spv_proof_for_keys_with_prefix(self, key_prfx, root=None, get_value=False, _cache=None):
+        """The nodes fetched by hash on the way to the prefix and in the whole subtree below it. With get_value:
+        (nodes, {full key: raw stored value})."""
+        root = root if root is not None else self.root_node
+        load, seen = self._recorder(_cache)
+        seen_prefix = []
+        node = self._last_node_for_prefix(root, bin_to_nibbles(_to_bytes(key_prfx, "Key")), seen_prefix, load)
+        found = {}
+        self._collect(node, [], found, load)
+        nodes = list(seen.values())
+        if not get_value:
+            return nodes
+        values = {}
+        for k, v in found.items():
+            nib = seen_prefix + list(k)
+            values[nibbles_to_bin(nib[1:] if len(nib) % 2 else nib)] = v
+        return nodes, values
+
+    def _generate_state_proof(self, path, func, root, serialize, **kw):
+        root = root if root is not None else self.root_node
+        rv = func(path, root, **kw)
+        has_val = isinstance(rv, tuple)
+        nodes = rv[0] if has_val else rv
+        nodes.append(list(root) if isinstance(root, list) else root)  # the root last; b'' for the blank root
+        if serialize:
+            nodes = self.serialize_proof(nodes)
+        return (nodes, rv[1]) if has_val else nodes
+
+    def generate_state_proof(self, key, root=None, serialize=False, get_value=False, _cache=None):
+        return self._generate_state_proof(key, self.produce_spv_proof, root, serialize, get_value=get_value, _cache=_cache)
+
+    def generate_state_proof_for_keys_with_prefix(self, key_prfx, root=None, serialize=False, get_value=False):
+        return self._generate_state_proof(key_prfx, self.produce_spv_proof_for_keys_with_prefix, root, serialize,
+                                          get_value=get_value)
+
+    @staticmethod
+    def serialize_proof(proof_nodes):
+        return rlp_encode(proof_nodes)
+
+    @staticmethod
+    def deserialize_proof(ser_proof):
+        return rlp_decode_lenient(bytes(ser_proof))
+
+    @staticmethod
+    def get_new_trie_with_proof_nodes(proof_nodes):
+        """A trie over a fresh store holding every proof node under the SHA3-256 of its (re-)encoding."""
+        trie = Trie(KeyValueStorageInMemory())
+        for node in proof_nodes:
+            enc = rlp_encode(node)
+            trie._db.put(sha3(enc), enc)
+        return trie
+
+    @staticmethod
+    def verify_spv_proof(root, key, value, proof_nodes, serialized=False):
+        """Does the trie under the root hash `root` hold `value` (as stored; b'' = nothing) for `key`, by these
+        nodes alone? Deserializing and storing the nodes may raise; everything after gives False."""
+        if serialized:
+            proof_nodes = Trie.deserialize_proof(proof_nodes)
+        trie = Trie.get_new_trie_with_proof_nodes(proof_nodes)
+        try:
+            trie.root_hash = root
+            return trie._get_with(trie.root_node, bin_to_nibbles(_to_bytes(key, "Key")), trie._load) == value
+        except Exception:
+            return False
+
+    @staticmethod
+    def verify_spv_proof_multi(root, key_values, proof_nodes, serialized=False):
+        """verify_spv_proof for every key -> value of `key_values` against one pool of nodes."""
+        if serialized:
+            proof_nodes = Trie.deserialize_proof(proof_nodes)
+        trie = Trie.get_new_trie_with_proof_nodes(proof_nodes)
+        try:
+            trie.root_hash = root
+            for k, v in key_values.items():
+                if trie._get_with(trie.root_node, bin_to_nibbles(_to_bytes(k, "Key")), trie._load) != v:
+                    return False
+            return True
+        except Exception:
+            return False
+
+    @staticmethod
+    def _proof_statuses(queries, proofs, serialized):
+        """The library's status per query, or None where Python decides alone. queries: (proof index, root, key,
+        value); proofs: per proof the list of nodes or, serialized, the bytes. None for a root that is not 32
+        bytes or blank, a key or value that is no byte string or above the library's limits, a proof of more
+        than 1,024 nodes, one whose nodes cannot be encoded and a serialized one whose outer list is not
+        canonical RLP."""
+        out = [None] * len(queries)
+        records = [None] * len(proofs)  # per proof: (start, end) into node_off, once it is known to be usable
+        blob, off, lens = b"", [], None
+        if serialized:
+            try:
+                sers = [bytes(p) for p in proofs]
+            except TypeError:
+                return out
+            blob, first, off, lens, ok = _native.trie_proof_split(sers)
+            for p in range(len(proofs)):
+                if ok[p] and first[p + 1] - first[p] <= _native.PV_PROOF_MAX_NODES:
+                    records[p] = (int(first[p]), int(first[p + 1]))
+        else:
+            parts, at = [], 0
+            for p, nodes in enumerate(proofs):
+                try:
+                    encs = [rlp_encode(n) for n in nodes]
+                except Exception:
+                    continue  # the sequential method raises what it raises
+                if len(encs) > _native.PV_PROOF_MAX_NODES:
+                    continue
+                records[p] = (len(off), len(off) + len(encs))
+                for e in encs:
+                    off.append(at)
+                    at += len(e)
+                parts += encs
+            off.append(at)
+            blob = b"".join(parts)
+        sent, proof_of, first = [], {}, [0]
+        node_idx = []
+        roots, keys, vals, qp = [], [], [], []
+        for i, (p, root, key, value) in enumerate(queries):
+            if records[p] is None or not isinstance(root, (bytes, bytearray)) or len(root) != 32 or root == BLANK_ROOT:
+                continue
+            if isinstance(key, str):
+                key = key.encode()
+            if not isinstance(key, (bytes, bytearray)) or not isinstance(value, (bytes, bytearray)):
+                continue
+            if len(key) > _native.PV_TRIE_MAX_KEY or len(value) > _native.PV_TRIE_MAX_VALUE:
+                continue
+            if p not in proof_of:
+                proof_of[p] = len(first) - 1
+                node_idx.extend(range(*records[p]))
+                first.append(len(node_idx))
+            sent.append(i)
+            qp.append(proof_of[p])
+            roots.append(bytes(root))
+            keys.append(bytes(key))
+            vals.append(bytes(value))
+        if sent:
+            status = _native.trie_verify_proofs(blob, off, lens, node_idx, first, qp, roots, keys, vals)
+            for i, s in zip(sent, status):
+                out[i] = int(s)
+        return out
+
+    @staticmethod
+    def verify_spv_proof_batch(items, serialized=False):
+        """[verify_spv_proof(root, key, value, proof_nodes, serialized) for each of items], the hashing and the
+        walks as one library call. What the library defers or cannot take goes through the sequential method,
+        which may raise as it does on its own."""
+        items = list(items)
+        status = Trie._proof_statuses([(i, r, k, v) for i, (r, k, v, _) in enumerate(items)], [it[3] for it in items],
+                                      serialized)
+        return [Trie.verify_spv_proof(r, k, v, pn, serialized) if s is None or s == _native.PV_PROOF_DEFER
+                else s == _native.PV_PROOF_ACCEPT for s, (r, k, v, pn) in zip(status, items)]
+
+    @staticmethod
+    def verify_spv_proof_multi_batch(root, key_values, proof_nodes, serialized=False):
+        """verify_spv_proof_multi as one proof with many queries in one library call."""
+        if key_values:
+            status = Trie._proof_statuses([(0, root, k, v) for k, v in key_values.items()], [proof_nodes], serialized)
+            if _native.PV_PROOF_REJECT in status:
+                return False  # that pair alone makes the sequential answer False
+            if all(s == _native.PV_PROOF_ACCEPT for s in status):
+                return True
+        return Trie.verify_spv_proof_multi(root, key_values, proof_nodes, serialized)
+
     # -------------------------------------------------------------------------------------- update
     def _leaf_ref(self, path, value):
         return self._ref([hp_pack(path, True), value])
@@ -383,8 +681,47 @@ class PruningState:
         if val:
             return self.get_decoded(val)
 
+    def get_all_leaves_for_root_hash(self, root_hash):
+        return self._trie.to_dict(self._hash_to_node(root_hash))
+
     def remove(self, key):
         self._trie.delete(key)
+
+    # -------------------------------------------------------------------------------------- proofs
+    def generate_state_proof(self, key, root=None, serialize=False, get_value=False):
+        """The proof for `key` under `root` (a node, as get_head_by_hash gives it; default the head): the hashed
+        nodes on its path in the order loaded, then the root. serialize: as one RLP list. get_value: with the
+        raw stored value (rlp([value])) or None."""
+        return self._trie.generate_state_proof(key, root, serialize, get_value=get_value)
+
+    def generate_state_proof_for_keys_with_prefix(self, key_prfx, root=None, serialize=False, get_value=False):
+        return self._trie.generate_state_proof_for_keys_with_prefix(key_prfx, root, serialize, get_value=get_value)
+
+    def generate_state_proof_batch(self, keys, root=None, serialize=False, get_value=False):
+        """[generate_state_proof(key, root, serialize, get_value) for key in keys]; a node that several paths
+        share (the top of the trie) is fetched and decoded once for the call."""
+        cache = {}
+        return [self._trie.generate_state_proof(k, root, serialize, get_value=get_value, _cache=cache) for k in keys]
+
+    @staticmethod
+    def encode_kv_for_verification(key, value):
+        return key.encode() if isinstance(key, str) else key, rlp_encode([value]) if value is not None else b""
+
+    @staticmethod
+    def verify_state_proof(root, key, value, proof_nodes, serialized=False):
+        key, value = PruningState.encode_kv_for_verification(key, value)
+        return Trie.verify_spv_proof(root, key, value, proof_nodes, serialized)
+
+    @staticmethod
+    def verify_state_proof_multi(root, key_values, proof_nodes, serialized=False):
+        encoded = dict(PruningState.encode_kv_for_verification(k, v) for k, v in key_values.items())
+        return Trie.verify_spv_proof_multi_batch(root, encoded, proof_nodes, serialized)
+
+    @staticmethod
+    def verify_state_proof_batch(items, serialized=False):
+        """[verify_state_proof(root, key, value, proof_nodes, serialized) for each of items] as one library call."""
+        return Trie.verify_spv_proof_batch(
+            [(r,) + PruningState.encode_kv_for_verification(k, v) + (pn,) for r, k, v, pn in items], serialized)
 
     def commit(self, rootHash=None, rootNode=None):
         if rootNode:
