@@ -2084,11 +2084,9 @@ struct Ctx {
     hipEvent_t ev_prep_done = nullptr;        // comb_prep done: need masks ready (main -> fstream)
     hipStream_t sstream = nullptr;           // Straus-path slots of a split chunk, overlapped
     hipEvent_t ev_straus_done = nullptr;     // their q / flags written (sstream -> main)
-    // Workspace hand-over between callers' streams: every launch ends by recording ev_launch_done
-    // on its stream; a launch on a DIFFERENT stream first makes its stream wait for it, so two
-    // batches enqueued on two caller streams never share the workspace at the same time.
-    hipEvent_t ev_launch_done = nullptr;
-    hipStream_t last_stream = nullptr;
+    // Workspace hand-over between callers' streams (workspace.h): every launch ends by recording it on
+    // its stream, and a launch on a DIFFERENT stream first makes its stream wait for it.
+    PvHandover hand;
     uint32_t* d_btab = nullptr;
     Work work{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     KeyWork kw{};
@@ -2112,12 +2110,9 @@ struct Ctx {
     uint32_t prep_lds_pad = PV_PREP_LDS_PAD;  // dynamic LDS per comb_prep workgroup (occupancy cap)
     int path = PV_PATH_AUTO;
     // host-entry staging
-    uint8_t* h_stage = nullptr;  // pinned
-    uint64_t h_stage_cap = 0;
-    uint8_t* d_stage = nullptr;
-    uint64_t d_stage_cap = 0;
-    uint64_t* h_ver = nullptr;  // pinned verdict words of the pipelined host-buffer form
-    uint64_t h_ver_cap = 0;
+    PvPinnedBuf h_stage;
+    PvDevBuf d_stage;
+    PvPinnedBuf h_ver;  // verdict words of the pipelined host-buffer form
     // pipelined host-buffer form: H2D of sub-batch j on cstream, its kernels on `stream` after ev_copy[j]
     hipStream_t cstream = nullptr;
     hipEvent_t ev_cstart = nullptr;  // the engine stream's work so far (cstream waits: staging reuse)
@@ -2183,26 +2178,20 @@ struct Ctx {
     uint8_t* h_zc_verdict = nullptr;
     bool last_zero_copy = false;  // the most recent pv_verify_batch took the zero-copy form
     // pv_verify_batch_multi_gpu: this device's gathered verdict words (device) and their host copy
-    uint64_t* d_mg = nullptr;
-    uint64_t d_mg_words = 0;
-    uint64_t* h_mg = nullptr;
-    uint64_t h_mg_words = 0;
+    PvDevBuf d_mg;
+    PvPinnedBuf h_mg;
     const uint32_t* last_nkeys = nullptr;  // split counters of the most recent keyed chunk
     // Signing workspace (pv_sign_*), its own: the expanded keys (a mod L || prefix, 64 B per signer), the
     // host entries' copies of the secret keys / seeds (pinned and device) and their chunk staging. Handed
-    // over between callers' streams like the verification workspace (ev_done / last_stream). The secret
-    // parts are overwritten before a call returns (device entry: behind its kernels, on its stream).
+    // over between callers' streams like the verification workspace. The secret parts are overwritten
+    // before a call returns (device entry: behind its kernels, on its stream).
     struct {
-        uint4* d_keys = nullptr;
-        uint64_t keys_cap = 0;  // signers
-        uint8_t* d_sk = nullptr;
-        uint8_t* h_sk = nullptr;
-        uint64_t d_sk_cap = 0, h_sk_cap = 0;  // bytes
-        uint8_t* d_stage = nullptr;
-        uint8_t* h_stage = nullptr;
-        uint64_t d_cap = 0, h_cap = 0;  // bytes
-        hipEvent_t ev_done = nullptr;
-        hipStream_t last_stream = nullptr;
+        PvDevBuf d_keys;
+        PvDevBuf d_sk;
+        PvPinnedBuf h_sk;
+        PvDevBuf d_stage;
+        PvPinnedBuf h_stage;
+        PvHandover hand;
     } sg;
 };
 
@@ -2234,12 +2223,6 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-#define PV_HIP(call, code)                                                                     \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) return fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 PvKeyCacheView kc_view() {
     auto& k = g_ctx.kc;
@@ -2304,21 +2287,9 @@ int kc_upload_htab(hipStream_t s, uint32_t* hbuf = nullptr) {
 int kc_auto_after_batch(const uint8_t* pk, uint64_t n, hipStream_t s, const uint8_t* vb, const uint64_t* hver);
 
 int ensure_stage(uint64_t host_bytes, uint64_t dev_bytes) {
-    if (host_bytes > g_ctx.h_stage_cap) {
-        if (g_ctx.h_stage) (void)hipHostFree(g_ctx.h_stage);
-        g_ctx.h_stage = nullptr;
-        const uint64_t cap = std::max<uint64_t>(host_bytes, 1 << 20);
-        PV_HIP(hipHostMalloc((void**)&g_ctx.h_stage, cap, hipHostMallocPortable), PV_ERR_ALLOC);
-        g_ctx.h_stage_cap = cap;
-    }
-    if (dev_bytes > g_ctx.d_stage_cap) {
-        if (g_ctx.d_stage) (void)hipFree(g_ctx.d_stage);
-        g_ctx.d_stage = nullptr;
-        const uint64_t cap = std::max<uint64_t>(dev_bytes, 1 << 20);
-        PV_HIP(hipMalloc((void**)&g_ctx.d_stage, cap), PV_ERR_ALLOC);
-        g_ctx.d_stage_cap = cap;
-    }
-    return PV_OK;
+    if (host_bytes)
+        if (int rc = g_ctx.h_stage.grow(std::max<uint64_t>(host_bytes, 1 << 20), hipHostMallocPortable)) return rc;
+    return dev_bytes ? g_ctx.d_stage.grow(std::max<uint64_t>(dev_bytes, 1 << 20)) : PV_OK;
 }
 
 int ensure_events(int count) {
@@ -2351,12 +2322,11 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
 int launch(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
            hipStream_t stream) {
     if (n == 0) return PV_OK;
-    if (g_ctx.last_stream && g_ctx.last_stream != stream)
-        PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_launch_done, 0), PV_ERR_LAUNCH);
-    int rc = launch_chunks(d_sm, d_off, n, d_pk, d_verdict, stream);
+    int rc = g_ctx.hand.begin(stream);
+    if (rc) return rc;
+    rc = launch_chunks(d_sm, d_off, n, d_pk, d_verdict, stream);
     // recorded even after a failed enqueue: whatever did get enqueued is covered
-    PV_HIP(hipEventRecord(g_ctx.ev_launch_done, stream), PV_ERR_LAUNCH);
-    g_ctx.last_stream = stream;
+    if (int rc2 = g_ctx.hand.end(stream)) return rc2;
     return rc;
 }
 
@@ -2792,7 +2762,7 @@ int ctx_init_parts(int device) {
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_prep_done, evf), PV_ERR_NO_DEVICE);
     PV_HIP(hipStreamCreateWithFlags(&g_ctx.sstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
     PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_straus_done, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_launch_done, evf), PV_ERR_NO_DEVICE);
+    if (int rc = g_ctx.hand.ensure()) return rc;
     {
         // the host path's copy stream at the greatest priority: the runtime keeps such streams on hardware
         // queues of their own instead of round-robin over GPU_MAX_HW_QUEUES (4) with the engine's streams,
@@ -2910,11 +2880,11 @@ void ctx_free() {
     (void)hipSetDevice(g_ctx.device);
     if (g_ctx.comm) ncclCommDestroy(g_ctx.comm);
     if (g_ctx.h_zc_verdict) (void)hipHostFree(g_ctx.h_zc_verdict);
-    if (g_ctx.d_mg) (void)hipFree(g_ctx.d_mg);
-    if (g_ctx.h_mg) (void)hipHostFree(g_ctx.h_mg);
+    g_ctx.d_mg.release();
+    g_ctx.h_mg.release();
     kc_free();
-    if (g_ctx.h_stage) (void)hipHostFree(g_ctx.h_stage);
-    if (g_ctx.d_stage) (void)hipFree(g_ctx.d_stage);
+    g_ctx.h_stage.release();
+    g_ctx.d_stage.release();
     if (g_ctx.d_btab) (void)hipFree(g_ctx.d_btab);
     lane_free_buffers(g_ctx.work, g_ctx.kw);
     if (g_ctx.d_bcomb) (void)hipFree(g_ctx.d_bcomb);
@@ -2930,19 +2900,18 @@ void ctx_free() {
     if (g_ctx.ev_prep_done) (void)hipEventDestroy(g_ctx.ev_prep_done);
     if (g_ctx.sstream) (void)hipStreamDestroy(g_ctx.sstream);
     if (g_ctx.ev_straus_done) (void)hipEventDestroy(g_ctx.ev_straus_done);
-    if (g_ctx.ev_launch_done) (void)hipEventDestroy(g_ctx.ev_launch_done);
+    g_ctx.hand.destroy();
     if (g_ctx.cstream) (void)hipStreamDestroy(g_ctx.cstream);
     if (g_ctx.ev_cstart) (void)hipEventDestroy(g_ctx.ev_cstart);
     for (hipEvent_t e : g_ctx.ev_copy) (void)hipEventDestroy(e);
-    if (g_ctx.h_ver) (void)hipHostFree(g_ctx.h_ver);
+    g_ctx.h_ver.release();
     for (void* p : {(void*)g_ctx.xt.htab, (void*)g_ctx.xt.keys, (void*)g_ctx.xt.flags, (void*)g_ctx.xt.tab})
         if (p) (void)hipFree(p);
     if (g_ctx.kc.ev_async) (void)hipEventDestroy(g_ctx.kc.ev_async);
-    for (void* p : {(void*)g_ctx.sg.d_keys, (void*)g_ctx.sg.d_sk, (void*)g_ctx.sg.d_stage})
-        if (p) (void)hipFree(p);
-    if (g_ctx.sg.h_sk) (void)hipHostFree(g_ctx.sg.h_sk);
-    if (g_ctx.sg.h_stage) (void)hipHostFree(g_ctx.sg.h_stage);
-    if (g_ctx.sg.ev_done) (void)hipEventDestroy(g_ctx.sg.ev_done);
+    for (PvDevBuf* b : {&g_ctx.sg.d_keys, &g_ctx.sg.d_sk, &g_ctx.sg.d_stage}) b->release();
+    g_ctx.sg.h_sk.release();
+    g_ctx.sg.h_stage.release();
+    g_ctx.sg.hand.destroy();
     g_ctx = Ctx();
 }
 
@@ -2991,6 +2960,7 @@ void pinned_cache_drain();
 extern "C" {
 void pv_shutdown(void) {
     pinned_cache_drain();  // freed pv_host_alloc blocks back to the system (live ones stay the caller's)
+    pv_ingress_shutdown();
     pv_merkle_shutdown();
     pv_trie_shutdown();
     {
@@ -3224,17 +3194,13 @@ static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t 
 // sm_off[0..n] non-decreasing (the host-buffer entries refuse anything else before touching the
 // device); large batches are checked in slices on the calling context's copy workers.
 static bool offsets_nondecreasing(const uint64_t* off, uint64_t n) {
-    auto ok = [off](uint64_t a, uint64_t b) {
-        uint64_t bad = 0;
-        for (uint64_t i = a; i < b; i++) bad |= off[i + 1] < off[i];
-        return bad == 0;
-    };
-    if (n < (1u << 17)) return ok(0, n);
+    if (n < (1u << 17)) return pv_offsets_monotone(off, n);
     pvhost::CopyPool& pool = cur_pool();
     const unsigned k = std::max(1u, pool.threads());
     std::atomic<bool> good{true};
     pool.run(k, [&](unsigned t) {
-        if (!ok(n * t / k, n * (t + 1) / k)) good = false;
+        const uint64_t a = n * t / k, b = n * (t + 1) / k;
+        if (!pv_offsets_monotone(off + a, b - a)) good = false;
     });
     return good.load();
 }
@@ -3285,7 +3251,7 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
             int rc = ensure_stage(n * stride, 0);
             if (rc) return rc;
             uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
-            uint8_t* slots = g_ctx.h_stage;
+            uint8_t* slots = g_ctx.h_stage.p;
             memset(vb, 0xFF, n);  // pending: the host spins on these bytes instead of a stream sync
             auto fill_at = [&](uint8_t* base, uint64_t a, uint64_t b) {
                 for (uint64_t i = a; i < b; i++) {
@@ -3309,16 +3275,14 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
                 cur_pool().run(k, [&](unsigned t) { fill_at(slots, n * t / k, n * (t + 1) / k); });
             }
             hipStream_t s = g_ctx.stream;
-            if (g_ctx.last_stream && g_ctx.last_stream != s)
-                PV_HIP(hipStreamWaitEvent(s, g_ctx.ev_launch_done, 0), PV_ERR_LAUNCH);
+            if ((rc = g_ctx.hand.begin(s))) return rc;
             g_ctx.last_latency = true;
             g_ctx.last_keyed = false;
             g_ctx.last_dev_choice = false;
             g_ctx.last_zero_copy = true;
             rc = one ? pv_latency_launch_zc_one(one_slot, (uint32_t)stride, g_ctx.d_bcomb, kc_view(), vb, s)
                      : pv_latency_launch_zc(slots, (uint32_t)stride, n, g_ctx.d_bcomb, kc_view(), vb, s);
-            PV_HIP(hipEventRecord(g_ctx.ev_launch_done, s), PV_ERR_LAUNCH);
-            g_ctx.last_stream = s;
+            if (int rc2 = g_ctx.hand.end(s)) return rc2;
             if (rc) {
                 (void)hipStreamSynchronize(s);
                 return rc;
@@ -3381,17 +3345,6 @@ static int ensure_xtab() {
     return PV_OK;
 }
 
-static int ensure_hver(uint64_t bytes) {
-    if (bytes <= g_ctx.h_ver_cap) return PV_OK;
-    if (g_ctx.h_ver) (void)hipHostFree(g_ctx.h_ver);
-    g_ctx.h_ver = nullptr;
-    g_ctx.h_ver_cap = 0;
-    const uint64_t cap = std::max<uint64_t>(bytes, 64 << 10);
-    PV_HIP(hipHostMalloc((void**)&g_ctx.h_ver, cap, hipHostMallocPortable), PV_ERR_ALLOC);
-    g_ctx.h_ver_cap = cap;
-    return PV_OK;
-}
-
 // The copy form of a host-buffer batch on the calling thread's context: moves the keys, offsets and
 // records to the device staging area and enqueues the verification on the context's stream. d_out:
 // where the verdict words go (nullptr = the staging area's own verdict section); *dver / *hver receive
@@ -3445,8 +3398,8 @@ static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t 
     hipStream_t s = c.stream;
     int rc = ensure_stage(all_pin ? 0 : total, total);
     if (rc) return rc;
-    uint8_t* h = c.h_stage;
-    uint8_t* d = c.d_stage;
+    uint8_t* h = c.h_stage.p;
+    uint8_t* d = c.d_stage.p;
     uint64_t* dver = reinterpret_cast<uint64_t*>(d + pk_bytes + off_bytes);
     uint8_t* dblob = d + pk_bytes + off_bytes + v_bytes;
     auto finish_piece = [&](uint64_t lo, uint64_t hi) -> int {
@@ -3489,7 +3442,7 @@ static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t 
         *hver_out = reinterpret_cast<uint64_t*>(h + pk_bytes + off_bytes);
         return PV_OK;
     }
-    if ((rc = ensure_hver(v_bytes))) return rc;
+    if ((rc = c.h_ver.grow(std::max<uint64_t>(v_bytes, 64 << 10), hipHostMallocPortable))) return rc;
     while (c.ev_copy.size() < np) {
         hipEvent_t e;
         PV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PV_ERR_LAUNCH);
@@ -3505,7 +3458,7 @@ static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t 
     // the copy stream starts after everything enqueued so far (the previous users of the staging area)
     PV_HIP(hipEventRecord(c.ev_cstart, s), PV_ERR_LAUNCH);
     PV_HIP(hipStreamWaitEvent(cs, c.ev_cstart, 0), PV_ERR_LAUNCH);
-    if (c.last_stream && c.last_stream != s) PV_HIP(hipStreamWaitEvent(cs, c.ev_launch_done, 0), PV_ERR_LAUNCH);
+    if ((rc = c.hand.wait(cs, s))) return rc;
     // sub-batch j = requests [lo(j), lo(j + 1))
     auto lo_of = [&](uint64_t j) -> uint64_t { return bnd[std::min<uint64_t>(j, np)]; };
     pvhost::CopyPool& pool = cur_pool();
@@ -3600,7 +3553,7 @@ static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t 
         for (hipEvent_t e : tev) (void)hipEventDestroy(e);
     }
     *dver_out = dver;
-    *hver_out = c.h_ver;
+    *hver_out = c.h_ver.as<uint64_t>();
     return PV_OK;
 }
 
@@ -3810,21 +3763,14 @@ int pv_verify_batch_multi_gpu(const uint8_t* sm, const uint64_t* sm_off, uint64_
                 auto run = [&]() -> int {
                     PV_HIP(hipSetDevice(d), PV_ERR_NO_DEVICE);
                     Ctx& c = g_ctx;
-                    const uint64_t need = (uint64_t)G * wpr;
-                    if (c.d_mg_words < need) {
-                        if (c.d_mg) (void)hipFree(c.d_mg);
-                        c.d_mg = nullptr;
-                        c.d_mg_words = 0;
-                        PV_HIP(hipMalloc((void**)&c.d_mg, need * 8), PV_ERR_ALLOC);
-                        c.d_mg_words = need;
-                    }
-                    if (c.last_stream && c.last_stream != c.stream)
-                        PV_HIP(hipStreamWaitEvent(c.stream, c.ev_launch_done, 0), PV_ERR_LAUNCH);
-                    PV_HIP(hipMemsetAsync(c.d_mg + (uint64_t)r * wpr, 0, wpr * 8, c.stream), PV_ERR_LAUNCH);
+                    int rc;
+                    if ((rc = c.d_mg.grow((uint64_t)G * wpr * 8)) || (rc = c.hand.begin(c.stream))) return rc;
+                    uint64_t* slot = c.d_mg.as<uint64_t>() + (uint64_t)r * wpr;
+                    PV_HIP(hipMemsetAsync(slot, 0, wpr * 8, c.stream), PV_ERR_LAUNCH);
                     const uint64_t lo = b[r], hi = b[r + 1];
                     if (hi == lo) return PV_OK;
                     uint64_t *dv = nullptr, *hv = nullptr;
-                    return stage_and_launch(sm, sm_off + lo, hi - lo, pk + 32 * lo, c.d_mg + (uint64_t)r * wpr, &dv, &hv);
+                    return stage_and_launch(sm, sm_off + lo, hi - lo, pk + 32 * lo, slot, &dv, &hv);
                 };
                 if ((rcs[r] = run()) != PV_OK) errs[r] = g_err;
             });
@@ -3840,7 +3786,7 @@ int pv_verify_batch_multi_gpu(const uint8_t* sm, const uint64_t* sm_off, uint64_
     ncclResult_t nr = ncclGroupStart();
     for (int r = 0; r < G && nr == ncclSuccess; r++) {
         Ctx& c = g_ctxs[g_mg.devs[r]];
-        nr = ncclAllGather(c.d_mg + (uint64_t)r * wpr, c.d_mg, wpr, ncclUint64, g_mg.comms[r], c.stream);
+        nr = ncclAllGather(c.d_mg.as<uint64_t>() + (uint64_t)r * wpr, c.d_mg.p, wpr, ncclUint64, g_mg.comms[r], c.stream);
     }
     const ncclResult_t ne = ncclGroupEnd();
     if (nr == ncclSuccess) nr = ne;
@@ -3849,17 +3795,11 @@ int pv_verify_batch_multi_gpu(const uint8_t* sm, const uint64_t* sm_off, uint64_
     (void)hipGetDevice(&cur);
     rc = PV_OK;
     if (nr != ncclSuccess) rc = fail(PV_ERR_COMM, std::string("ncclAllGather: ") + ncclGetErrorString(nr));
-    if (rc == PV_OK && c0.h_mg_words < (uint64_t)G * wpr) {
-        if (c0.h_mg) (void)hipHostFree(c0.h_mg);
-        c0.h_mg = nullptr;
-        c0.h_mg_words = 0;
-        if (hipSetDevice(c0.device) != hipSuccess ||
-            hipHostMalloc((void**)&c0.h_mg, (uint64_t)G * wpr * 8, hipHostMallocPortable) != hipSuccess)
-            rc = fail(PV_ERR_ALLOC, "pv_verify_batch_multi_gpu: pinned verdict buffer");
-        else
-            c0.h_mg_words = (uint64_t)G * wpr;
-    }
-    if (rc == PV_OK && hipMemcpyAsync(c0.h_mg, c0.d_mg, (uint64_t)G * wpr * 8, hipMemcpyDeviceToHost, c0.stream) != hipSuccess)
+    const uint64_t gbytes = (uint64_t)G * wpr * 8;
+    if (rc == PV_OK && c0.h_mg.cap < gbytes &&
+        (hipSetDevice(c0.device) != hipSuccess || c0.h_mg.grow(gbytes, hipHostMallocPortable) != PV_OK))
+        rc = fail(PV_ERR_ALLOC, "pv_verify_batch_multi_gpu: pinned verdict buffer");
+    if (rc == PV_OK && hipMemcpyAsync(c0.h_mg.p, c0.d_mg.p, gbytes, hipMemcpyDeviceToHost, c0.stream) != hipSuccess)
         rc = fail(PV_ERR_LAUNCH, "pv_verify_batch_multi_gpu: verdict copy");
     for (int r = 0; r < G; r++) {
         Ctx& c = g_ctxs[g_mg.devs[r]];
@@ -3871,7 +3811,7 @@ int pv_verify_batch_multi_gpu(const uint8_t* sm, const uint64_t* sm_off, uint64_
     if (rc) return rc;
     for (int r = 0; r < G; r++) {  // shard r's words start at bit b[r] (a multiple of 64)
         const uint64_t lo = b[r], hi = b[r + 1];
-        if (hi > lo) memcpy(verdict_bits + lo / 8, c0.h_mg + (uint64_t)r * wpr, (hi - lo + 7) / 8);
+        if (hi > lo) memcpy(verdict_bits + lo / 8, c0.h_mg.p + (uint64_t)r * wpr * 8, (hi - lo + 7) / 8);
     }
     return PV_OK;
 }
@@ -3963,7 +3903,7 @@ int ordered_copy(void* dst, const void* src, uint64_t bytes, hipMemcpyKind kind)
         return PV_OK;
     }
     hipStream_t s = g_ctx.stream;
-    if (g_ctx.last_stream && g_ctx.last_stream != s) PV_HIP(hipStreamWaitEvent(s, g_ctx.ev_launch_done, 0), PV_ERR_LAUNCH);
+    if (int rc = g_ctx.hand.begin(s)) return rc;
     PV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s), PV_ERR_LAUNCH);
     PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
     return PV_OK;
@@ -4045,7 +3985,7 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
                            bool async) {
     auto& k = g_ctx.kc;
     hipStream_t s = g_ctx.stream;
-    if (g_ctx.last_stream && g_ctx.last_stream != s) PV_HIP(hipStreamWaitEvent(s, g_ctx.ev_launch_done, 0), PV_ERR_LAUNCH);
+    if (int rc = g_ctx.hand.begin(s)) return rc;
     const char* fail_env = getenv("PV_TEST_FAIL_KC_PUT_BATCH");
     const long fail_batch = fail_env ? atol(fail_env) : -1;
     KeyWork kw = g_ctx.kw;
@@ -4147,7 +4087,7 @@ static int kc_fold_hits() {
 }
 
 // pv_key_cache_put under g_mu. async (automatic admission): at most kcap new keys, nothing waited
-// for (pinned staging; the hash-table upload and ev_launch_done are stream-ordered after the build).
+// for (pinned staging; the hash-table upload and the hand-over event are stream-ordered after the build).
 static int kc_put_locked(const uint8_t* pks, uint64_t n, bool async) {
     auto& k = g_ctx.kc;
     if (async) {
@@ -4223,8 +4163,7 @@ static int kc_put_locked(const uint8_t* pks, uint64_t n, bool async) {
     } else {
         rc = kc_upload_htab(g_ctx.stream);
     }
-    PV_HIP(hipEventRecord(g_ctx.ev_launch_done, g_ctx.stream), PV_ERR_LAUNCH);
-    g_ctx.last_stream = g_ctx.stream;
+    if (int rc2 = g_ctx.hand.end(g_ctx.stream)) return rc2;
     k.broken = rc != PV_OK;  // a complete upload also repairs an earlier failed one
     return rc;
 }
@@ -4302,8 +4241,8 @@ int pv_stream_destroy(void* stream) {
     {
         // a later launch must not wait on an event of a destroyed stream
         std::lock_guard<std::mutex> lk(g_mu);
-        if (g_ctx.last_stream == (hipStream_t)stream) g_ctx.last_stream = nullptr;
-        if (g_ctx.sg.last_stream == (hipStream_t)stream) g_ctx.sg.last_stream = nullptr;
+        g_ctx.hand.forget((hipStream_t)stream);
+        g_ctx.sg.hand.forget((hipStream_t)stream);
     }
     pv_ingress_forget_stream(stream);
     pv_merkle_forget_stream(stream);
@@ -4321,47 +4260,18 @@ int pv_stream_sync(void* stream) {
 // ---------------------------------------------------------------------------------------- signing
 namespace {
 
-template <class T>
-int sg_grow_dev(T*& p, uint64_t& cap, uint64_t want) {
-    if (want <= cap) return PV_OK;
-    if (p) (void)hipFree(p);  // synchronises: no launch still reads the old block
-    p = nullptr;
-    cap = 0;
-    PV_HIP(hipMalloc((void**)&p, want), PV_ERR_ALLOC);
-    cap = want;
-    return PV_OK;
-}
-int sg_grow_host(uint8_t*& p, uint64_t& cap, uint64_t want) {
-    if (want <= cap) return PV_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    PV_HIP(hipHostMalloc((void**)&p, want, hipHostMallocDefault), PV_ERR_ALLOC);
-    cap = want;
-    return PV_OK;
-}
-uint64_t sg_up(uint64_t x) { return (x + 255) & ~255ull; }
-
 // Room for `signers` expanded keys, and the hand-over: `stream` waits for the workspace's last user.
 // Caller holds g_mu.
 int sg_begin(uint64_t signers, hipStream_t stream) {
     auto& g = g_ctx.sg;
-    if (signers > g.keys_cap) {
-        uint64_t bytes = g.keys_cap * 64;
-        const int rc = sg_grow_dev(g.d_keys, bytes, std::max<uint64_t>(signers, 4096) * 64);
-        g.keys_cap = bytes / 64;
-        if (rc) return rc;
-    }
-    if (!g.ev_done) PV_HIP(hipEventCreateWithFlags(&g.ev_done, hipEventDisableTiming), PV_ERR_NO_DEVICE);
-    if (g.last_stream && g.last_stream != stream) PV_HIP(hipStreamWaitEvent(stream, g.ev_done, 0), PV_ERR_LAUNCH);
-    return PV_OK;
+    if (int rc = g.d_keys.grow(std::max<uint64_t>(signers, 4096) * 64)) return rc;
+    return g.hand.begin(stream);
 }
 // The expanded keys are overwritten behind the kernels that read them, and the workspace released.
 int sg_end(uint64_t signers, hipStream_t stream) {
     auto& g = g_ctx.sg;
-    const hipError_t e = hipMemsetAsync(g.d_keys, 0, signers * 64, stream);
-    PV_HIP(hipEventRecord(g.ev_done, stream), PV_ERR_LAUNCH);
-    g.last_stream = stream;
+    const hipError_t e = hipMemsetAsync(g.d_keys.p, 0, signers * 64, stream);
+    if (int rc = g.hand.end(stream)) return rc;
     if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: key scrub: ") + hipGetErrorString(e));
     return PV_OK;
 }
@@ -4369,7 +4279,7 @@ int sg_end(uint64_t signers, hipStream_t stream) {
 int sg_keys(const uint8_t* d_seeds, uint32_t seed_q, uint64_t signers, uint8_t* d_pk, hipStream_t stream) {
     const unsigned grid = (unsigned)((signers + PV_BLOCK - 1) / PV_BLOCK);
     PV_LAUNCH_BC2(pv_sign_keys_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, reinterpret_cast<const uint4*>(d_seeds),
-                  seed_q, signers, g_ctx.sg.d_keys, reinterpret_cast<uint4*>(d_pk), g_ctx.d_bc2);
+                  seed_q, signers, g_ctx.sg.d_keys.as<uint4>(), reinterpret_cast<uint4*>(d_pk), g_ctx.d_bc2);
     PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     return PV_OK;
 }
@@ -4378,7 +4288,7 @@ int sg_chunk(const uint8_t* d_msg, const uint64_t* d_off, uint64_t m, const uint
              const uint32_t* d_idx, uint64_t idx_base, uint8_t* d_sig, hipStream_t stream) {
     const unsigned grid = (unsigned)((m + PV_BLOCK - 1) / PV_BLOCK);
     PV_LAUNCH_BC2(pv_sign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_msg, d_off, m,
-                  reinterpret_cast<const uint4*>(d_sk), g_ctx.sg.d_keys, n_signers, d_idx, idx_base,
+                  reinterpret_cast<const uint4*>(d_sk), g_ctx.sg.d_keys.as<uint4>(), n_signers, d_idx, idx_base,
                   reinterpret_cast<uint4*>(d_sig), g_ctx.d_bc2);
     PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     return PV_OK;
@@ -4402,9 +4312,9 @@ int sg_enqueue(const uint8_t* d_msg, const uint64_t* d_off, uint64_t n, const ui
 // and, once that is done, in pinned memory.
 int sg_scrub_secrets(uint64_t bytes, hipStream_t stream) {
     auto& g = g_ctx.sg;
-    hipError_t e = g.d_sk ? hipMemsetAsync(g.d_sk, 0, std::min(bytes, g.d_sk_cap), stream) : hipSuccess;
+    hipError_t e = g.d_sk.p ? hipMemsetAsync(g.d_sk.p, 0, std::min(bytes, g.d_sk.cap), stream) : hipSuccess;
     const hipError_t e2 = hipStreamSynchronize(stream);
-    if (g.h_sk) memset(g.h_sk, 0, std::min(bytes, g.h_sk_cap));
+    if (g.h_sk.p) memset(g.h_sk.p, 0, std::min(bytes, g.h_sk.cap));
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: secret scrub: ") + hipGetErrorString(e));
     return PV_OK;
@@ -4440,43 +4350,47 @@ int pv_sign_batch(const uint8_t* msg, const uint64_t* msg_off, uint64_t n, const
         return fail(PV_ERR_ARG, "pv_sign_batch: no signers, or more than 2^32 - 1 items");
     if (!signer_idx && n_signers != n) return fail(PV_ERR_ARG, "pv_sign_batch: without signer_idx, n_signers must equal n");
     // everything the kernels index with is validated, so a bad argument is an error and never a fault
-    for (uint64_t i = 0; i < n; i++) {
-        if (msg_off[i + 1] < msg_off[i]) return fail(PV_ERR_ARG, "pv_sign_batch: offsets must be non-decreasing");
-        if (signer_idx && signer_idx[i] >= n_signers) return fail(PV_ERR_ARG, "pv_sign_batch: signer index out of range");
-    }
+    // (of a bad offset and a bad signer index, the one at the earlier item is reported; the offset at a tie)
+    uint64_t bad_idx = n;
+    for (uint64_t i = 0; i < n && signer_idx && bad_idx == n; i++)
+        if (signer_idx[i] >= n_signers) bad_idx = i;
+    if (!pv_offsets_monotone(msg_off, std::min(bad_idx + 1, n)))
+        return fail(PV_ERR_ARG, "pv_sign_batch: offsets must be non-decreasing");
+    if (bad_idx < n) return fail(PV_ERR_ARG, "pv_sign_batch: signer index out of range");
     if (!msg && msg_off[n] != msg_off[0]) return fail(PV_ERR_ARG, "pv_sign_batch: null message blob");
     auto& g = g_ctx.sg;
     const hipStream_t s = g_ctx.stream;
     const uint64_t sk_bytes = n_signers * 64;
     int rc;
-    if ((rc = sg_grow_host(g.h_sk, g.h_sk_cap, sk_bytes)) || (rc = sg_grow_dev(g.d_sk, g.d_sk_cap, sk_bytes)) ||
+    if ((rc = g.h_sk.grow(sk_bytes, hipHostMallocDefault)) || (rc = g.d_sk.grow(sk_bytes)) ||
         (rc = sg_begin(n_signers, s)))
         return rc;
-    memcpy(g.h_sk, sk, sk_bytes);
+    memcpy(g.h_sk.p, sk, sk_bytes);
     auto run = [&]() -> int {
-        PV_HIP(hipMemcpyAsync(g.d_sk, g.h_sk, sk_bytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        int rc = sg_keys(g.d_sk, 4, n_signers, nullptr, s);
+        PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, sk_bytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+        int rc = sg_keys(g.d_sk.p, 4, n_signers, nullptr, s);
         for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK) {
             // chunk staging: [offsets, rebased][signer indices][signatures][message bytes + slack]
             const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
             const uint64_t base = msg_off[c0], mbytes = msg_off[c0 + m] - base;
-            const uint64_t o_off = 0, o_idx = o_off + sg_up((m + 1) * 8), o_sig = o_idx + sg_up(m * 4),
-                           o_msg = o_sig + sg_up(m * 64), total = o_msg + sg_up(mbytes + PV_BLOB_SLACK);
-            if ((rc = sg_grow_host(g.h_stage, g.h_cap, total)) || (rc = sg_grow_dev(g.d_stage, g.d_cap, total))) break;
-            uint64_t* ho = reinterpret_cast<uint64_t*>(g.h_stage + o_off);
+            PvLayout l;
+            const uint64_t o_off = l.add((m + 1) * 8), o_idx = l.add(m * 4), o_sig = l.add(m * 64),
+                           o_msg = l.add(mbytes + PV_BLOB_SLACK), total = l.at;
+            if ((rc = g.h_stage.grow(total, hipHostMallocDefault)) || (rc = g.d_stage.grow(total))) break;
+            uint64_t* ho = reinterpret_cast<uint64_t*>(g.h_stage.p + o_off);
             for (uint64_t i = 0; i <= m; i++) ho[i] = msg_off[c0 + i] - base;
-            if (signer_idx) memcpy(g.h_stage + o_idx, signer_idx + c0, m * 4);
-            if (mbytes) memcpy(g.h_stage + o_msg, msg + base, mbytes);
-            PV_HIP(hipMemcpyAsync(g.d_stage, g.h_stage, o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            if (signer_idx) memcpy(g.h_stage.p + o_idx, signer_idx + c0, m * 4);
+            if (mbytes) memcpy(g.h_stage.p + o_msg, msg + base, mbytes);
+            PV_HIP(hipMemcpyAsync(g.d_stage.p, g.h_stage.p, o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
             if (mbytes)
-                PV_HIP(hipMemcpyAsync(g.d_stage + o_msg, g.h_stage + o_msg, mbytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            if ((rc = sg_chunk(g.d_stage + o_msg, reinterpret_cast<const uint64_t*>(g.d_stage + o_off), m, g.d_sk,
-                               n_signers, signer_idx ? reinterpret_cast<const uint32_t*>(g.d_stage + o_idx) : nullptr,
-                               c0, g.d_stage + o_sig, s)))
+                PV_HIP(hipMemcpyAsync(g.d_stage.p + o_msg, g.h_stage.p + o_msg, mbytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            if ((rc = sg_chunk(g.d_stage.p + o_msg, reinterpret_cast<const uint64_t*>(g.d_stage.p + o_off), m, g.d_sk.p,
+                               n_signers, signer_idx ? reinterpret_cast<const uint32_t*>(g.d_stage.p + o_idx) : nullptr,
+                               c0, g.d_stage.p + o_sig, s)))
                 break;
-            PV_HIP(hipMemcpyAsync(g.h_stage + o_sig, g.d_stage + o_sig, m * 64, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
+            PV_HIP(hipMemcpyAsync(g.h_stage.p + o_sig, g.d_stage.p + o_sig, m * 64, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
             PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-            memcpy(sig_out + 64 * c0, g.h_stage + o_sig, m * 64);
+            memcpy(sig_out + 64 * c0, g.h_stage.p + o_sig, m * 64);
         }
         return rc;
     };
@@ -4496,24 +4410,24 @@ int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uin
     const hipStream_t s = g_ctx.stream;
     const uint64_t cm = std::min<uint64_t>(PV_SIGN_CHUNK, n);
     int rc;
-    if ((rc = sg_grow_host(g.h_sk, g.h_sk_cap, cm * 32)) || (rc = sg_grow_dev(g.d_sk, g.d_sk_cap, cm * 32)) ||
-        (rc = sg_grow_host(g.h_stage, g.h_cap, cm * 32)) || (rc = sg_grow_dev(g.d_stage, g.d_cap, cm * 32)) ||
+    if ((rc = g.h_sk.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_sk.grow(cm * 32)) ||
+        (rc = g.h_stage.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_stage.grow(cm * 32)) ||
         (rc = sg_begin(cm, s)))
         return rc;
     auto run = [&]() -> int {
         for (uint64_t c0 = 0; c0 < n; c0 += PV_SIGN_CHUNK) {
             const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
-            memcpy(g.h_sk, seeds + 32 * c0, m * 32);
-            PV_HIP(hipMemcpyAsync(g.d_sk, g.h_sk, m * 32, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            const int rc = sg_keys(g.d_sk, 2, m, g.d_stage, s);
+            memcpy(g.h_sk.p, seeds + 32 * c0, m * 32);
+            PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, m * 32, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            const int rc = sg_keys(g.d_sk.p, 2, m, g.d_stage.p, s);
             if (rc) return rc;
-            PV_HIP(hipMemcpyAsync(g.h_stage, g.d_stage, m * 32, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
+            PV_HIP(hipMemcpyAsync(g.h_stage.p, g.d_stage.p, m * 32, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
             PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
             for (uint64_t i = 0; i < m; i++) {
-                if (pk_out) memcpy(pk_out + 32 * (c0 + i), g.h_stage + 32 * i, 32);
+                if (pk_out) memcpy(pk_out + 32 * (c0 + i), g.h_stage.p + 32 * i, 32);
                 if (sk_out) {
                     memcpy(sk_out + 64 * (c0 + i), seeds + 32 * (c0 + i), 32);
-                    memcpy(sk_out + 64 * (c0 + i) + 32, g.h_stage + 32 * i, 32);
+                    memcpy(sk_out + 64 * (c0 + i) + 32, g.h_stage.p + 32 * i, 32);
                 }
             }
         }

@@ -453,76 +453,37 @@ __global__ __launch_bounds__(ING_BLOCK) void pv_ing_assemble_kernel(
 
 // ------------------------------------------------------------------------------------------ host
 
+// The ingress workspace (workspace.h): allocated on first use, freed by pv_shutdown, handed over between
+// caller streams by an event. Launches are serialised on g_ing_mu.
 struct IngWork {
-    uint64_t n_cap = 0, sig_cap = 0, blob_cap = 0;
-    uint4* sigfix = nullptr;
-    uint4* pk = nullptr;
-    uint32_t* siginfo = nullptr;
-    uint64_t* rec_len = nullptr;
-    uint64_t* local = nullptr;
-    uint64_t* off = nullptr;
-    uint64_t* tile_sum = nullptr;
-    uint32_t* overrun = nullptr;
-    uint4* kpk = nullptr;
-    uint8_t* kstatus = nullptr;
-    uint8_t* blob = nullptr;
+    PvDevBuf sigfix, pk, siginfo, rec_len, local, off, tile_sum;  // per verification
+    PvDevBuf overrun;
+    PvDevBuf kpk, kstatus;  // per signer
+    PvDevBuf blob;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    // workspace hand-over between callers' streams (as the engine's ev_launch_done)
-    hipEvent_t ev_done = nullptr;
-    hipStream_t last_stream = nullptr;
+    PvHandover hand;
     // host-entry staging (pv_ingress_verify)
-    uint8_t* h_stage = nullptr;
-    uint64_t h_cap = 0;
-    uint8_t* d_stage = nullptr;
-    uint64_t d_cap = 0;
+    PvPinnedBuf h_stage;
+    PvDevBuf d_stage;
 };
 
 IngWork g_ing;
 std::mutex g_ing_mu;
 
-#define ING_HIP(call, code)                                                                         \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return pv_fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-int regrow(T*& p, uint64_t bytes) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    ING_HIP(hipMalloc((void**)&p, std::max<uint64_t>(bytes, 256)), PV_ERR_ALLOC);
-    return PV_OK;
-}
-
 int ensure_work(uint64_t n, uint64_t nsig, uint64_t blob_bytes) {
     int rc;
-    if (n > g_ing.n_cap) {
-        const uint64_t c = std::max<uint64_t>(n, 1 << 16);
-        const uint64_t tiles = (c + SCAN_TILE - 1) / SCAN_TILE;
-        if ((rc = regrow(g_ing.sigfix, c * 96)) || (rc = regrow(g_ing.pk, c * 32)) ||
-            (rc = regrow(g_ing.siginfo, c * 4)) || (rc = regrow(g_ing.rec_len, c * 8)) ||
-            (rc = regrow(g_ing.local, c * 8)) || (rc = regrow(g_ing.off, (c + 1) * 8)) ||
-            (rc = regrow(g_ing.tile_sum, tiles * 8)))
-            return rc;
-        g_ing.n_cap = c;
-    }
-    if (!g_ing.overrun && (rc = regrow(g_ing.overrun, 256))) return rc;
-    if (nsig > g_ing.sig_cap) {
-        const uint64_t c = std::max<uint64_t>(nsig, 1 << 12);
-        if ((rc = regrow(g_ing.kpk, c * 32)) || (rc = regrow(g_ing.kstatus, c))) return rc;
-        g_ing.sig_cap = c;
-    }
-    if (blob_bytes > g_ing.blob_cap) {
-        const uint64_t c = std::max<uint64_t>(blob_bytes, 1 << 20);
-        if ((rc = regrow(g_ing.blob, c + PV_BLOB_SLACK))) return rc;
-        g_ing.blob_cap = c;
-    }
-    if (!g_ing.ev0) {
-        ING_HIP(hipEventCreate(&g_ing.ev0), PV_ERR_NO_DEVICE);
-        ING_HIP(hipEventCreate(&g_ing.ev1), PV_ERR_NO_DEVICE);
-        ING_HIP(hipEventCreateWithFlags(&g_ing.ev_done, hipEventDisableTiming), PV_ERR_NO_DEVICE);
-    }
+    uint64_t c = std::max<uint64_t>(n, 1 << 16);
+    const uint64_t tiles = (c + SCAN_TILE - 1) / SCAN_TILE;
+    if ((rc = g_ing.sigfix.grow(c * 96)) || (rc = g_ing.pk.grow(c * 32)) || (rc = g_ing.siginfo.grow(c * 4)) ||
+        (rc = g_ing.rec_len.grow(c * 8)) || (rc = g_ing.local.grow(c * 8)) || (rc = g_ing.off.grow((c + 1) * 8)) ||
+        (rc = g_ing.tile_sum.grow(std::max<uint64_t>(tiles * 8, 256))) || (rc = g_ing.overrun.grow(256)))
+        return rc;
+    c = std::max<uint64_t>(nsig, 1 << 12);
+    if ((rc = g_ing.kpk.grow(c * 32)) || (rc = g_ing.kstatus.grow(c))) return rc;
+    if ((rc = g_ing.blob.grow(std::max<uint64_t>(blob_bytes, 1 << 20) + PV_BLOB_SLACK))) return rc;
+    if (!g_ing.ev0) PV_HIP(hipEventCreate(&g_ing.ev0), PV_ERR_NO_DEVICE);
+    if (!g_ing.ev1) PV_HIP(hipEventCreate(&g_ing.ev1), PV_ERR_NO_DEVICE);
     return PV_OK;
 }
 
@@ -543,12 +504,11 @@ int ingress_device(const uint8_t* sig_chars, const uint64_t* sig_off, const uint
     const uint64_t cap = 96 * n + msg_bytes_total;
     int rc = ensure_work(n, nsig, cap);
     if (rc) return rc;
-    if (g_ing.last_stream && g_ing.last_stream != s) ING_HIP(hipStreamWaitEvent(s, g_ing.ev_done, 0), PV_ERR_LAUNCH);
+    if ((rc = g_ing.hand.begin(s))) return rc;
     rc = ingress_enqueue(sig_chars, sig_off, msg_idx, signer_idx, n, msg, msg_off, nmsg, cap, idr_chars, idr_off,
                          vk_chars, vk_off, vk_present, nsig, status, verdict, s);
-    ING_HIP(hipEventRecord(g_ing.ev_done, s), PV_ERR_LAUNCH);
-    g_ing.last_stream = s;
-    return rc;
+    const int rc2 = g_ing.hand.end(s);  // also after a failed enqueue: whatever did get enqueued is covered
+    return rc ? rc : rc2;
 }
 
 int ingress_enqueue(const uint8_t* sig_chars, const uint64_t* sig_off, const uint32_t* msg_idx,
@@ -556,40 +516,54 @@ int ingress_enqueue(const uint8_t* sig_chars, const uint64_t* sig_off, const uin
                     uint64_t cap, const uint8_t* idr_chars, const uint64_t* idr_off, const uint8_t* vk_chars,
                     const uint64_t* vk_off, const uint8_t* vk_present, uint64_t nsig, uint8_t* status,
                     uint64_t* verdict, hipStream_t s) {
-    ING_HIP(hipEventRecord(g_ing.ev0, s), PV_ERR_LAUNCH);
+    uint4 *const sigfix = g_ing.sigfix.as<uint4>(), *const pk = g_ing.pk.as<uint4>(), *const kpk = g_ing.kpk.as<uint4>();
+    uint32_t *const siginfo = g_ing.siginfo.as<uint32_t>(), *const overrun = g_ing.overrun.as<uint32_t>();
+    uint64_t *const rec_len = g_ing.rec_len.as<uint64_t>(), *const local = g_ing.local.as<uint64_t>(),
+             *const off = g_ing.off.as<uint64_t>(), *const tile_sum = g_ing.tile_sum.as<uint64_t>();
+    uint8_t *const kstatus = g_ing.kstatus.p, *const blob = g_ing.blob.p;
+    PV_HIP(hipEventRecord(g_ing.ev0, s), PV_ERR_LAUNCH);
     if (nsig > 0) {
         hipLaunchKernelGGL(pv_ing_signer_kernel, dim3((unsigned)((nsig + ING_BLOCK - 1) / ING_BLOCK)), dim3(ING_BLOCK),
-                           0, s, idr_chars, idr_off, vk_chars, vk_off, vk_present, nsig, g_ing.kpk, g_ing.kstatus);
-        ING_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                           0, s, idr_chars, idr_off, vk_chars, vk_off, vk_present, nsig, kpk, kstatus);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     }
     const unsigned grid = (unsigned)((n + ING_BLOCK - 1) / ING_BLOCK);
     hipLaunchKernelGGL(pv_ing_sig_kernel, dim3(grid), dim3(ING_BLOCK), 0, s, sig_chars, sig_off, msg_idx, signer_idx,
-                       n, msg_off, nmsg, g_ing.kpk, g_ing.kstatus, nsig, g_ing.sigfix, g_ing.pk, g_ing.siginfo,
-                       g_ing.rec_len, status);
-    ING_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                       n, msg_off, nmsg, kpk, kstatus, nsig, sigfix, pk, siginfo, rec_len, status);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(pv_ing_scan_tiles_kernel, dim3((unsigned)tiles), dim3(ING_BLOCK), 0, s, g_ing.rec_len, n,
-                       g_ing.local, g_ing.tile_sum);
-    ING_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-    hipLaunchKernelGGL(pv_ing_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, s, g_ing.tile_sum, tiles, n, g_ing.off, cap,
-                       g_ing.overrun);
-    ING_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    hipLaunchKernelGGL(pv_ing_scan_tiles_kernel, dim3((unsigned)tiles), dim3(ING_BLOCK), 0, s, rec_len, n, local,
+                       tile_sum);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    hipLaunchKernelGGL(pv_ing_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, s, tile_sum, tiles, n, off, cap, overrun);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     const uint64_t athreads = n * ASM_LANES;
     hipLaunchKernelGGL(pv_ing_assemble_kernel, dim3((unsigned)((athreads + ING_BLOCK - 1) / ING_BLOCK)),
-                       dim3(ING_BLOCK), 0, s, n, g_ing.local, g_ing.tile_sum, g_ing.rec_len, g_ing.siginfo,
-                       reinterpret_cast<const uint8_t*>(g_ing.sigfix), msg_idx, msg, msg_off, g_ing.overrun, g_ing.blob,
-                       g_ing.off, status);
-    ING_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-    ING_HIP(hipEventRecord(g_ing.ev1, s), PV_ERR_LAUNCH);
+                       dim3(ING_BLOCK), 0, s, n, local, tile_sum, rec_len, siginfo, g_ing.sigfix.p, msg_idx, msg, msg_off,
+                       overrun, blob, off, status);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_HIP(hipEventRecord(g_ing.ev1, s), PV_ERR_LAUNCH);
     g_ing.timed = true;
-    return pv_verify_batch_device(g_ing.blob, g_ing.off, n, reinterpret_cast<const uint8_t*>(g_ing.pk), verdict, s);
+    return pv_verify_batch_device(blob, off, n, g_ing.pk.p, verdict, s);
 }
 
 }  // namespace
 
 void pv_ingress_forget_stream(void* stream) {
     std::lock_guard<std::mutex> lk(g_ing_mu);
-    if (g_ing.last_stream == (hipStream_t)stream) g_ing.last_stream = nullptr;
+    g_ing.hand.forget((hipStream_t)stream);
+}
+
+void pv_ingress_shutdown() {
+    std::lock_guard<std::mutex> lk(g_ing_mu);
+    for (PvDevBuf* b : {&g_ing.sigfix, &g_ing.pk, &g_ing.siginfo, &g_ing.rec_len, &g_ing.local, &g_ing.off, &g_ing.tile_sum,
+                        &g_ing.overrun, &g_ing.kpk, &g_ing.kstatus, &g_ing.blob, &g_ing.d_stage})
+        b->release();
+    g_ing.h_stage.release();
+    if (g_ing.ev0) (void)hipEventDestroy(g_ing.ev0);
+    if (g_ing.ev1) (void)hipEventDestroy(g_ing.ev1);
+    g_ing.hand.destroy();
+    g_ing = IngWork();
 }
 
 extern "C" {
@@ -615,9 +589,9 @@ int pv_ingress_verify_device(const char* d_sig_chars, const uint64_t* d_sig_off,
 
 int pv_ingress_front_ms(double* ms) {
     if (!g_ing.timed) return pv_fail(PV_ERR_NOT_INIT, "pv_ingress_front_ms: no ingress call yet");
-    ING_HIP(hipEventSynchronize(g_ing.ev1), PV_ERR_LAUNCH);
+    PV_HIP(hipEventSynchronize(g_ing.ev1), PV_ERR_LAUNCH);
     float t = 0;
-    ING_HIP(hipEventElapsedTime(&t, g_ing.ev0, g_ing.ev1), PV_ERR_LAUNCH);
+    PV_HIP(hipEventElapsedTime(&t, g_ing.ev0, g_ing.ev1), PV_ERR_LAUNCH);
     if (ms) *ms = t;
     return PV_OK;
 }
@@ -634,13 +608,8 @@ int pv_ingress_verify(const char* sig_chars, const uint64_t* sig_off, const uint
     if (n_signers > 0 && (!idr_chars || !idr_off || !vk_chars || !vk_off || !vk_present))
         return pv_fail(PV_ERR_ARG, "pv_ingress_verify: null signer pointer");
     // validate everything the kernels index with, so a bad argument is an error and never a fault
-    auto monotone = [](const uint64_t* o, uint64_t k) {
-        for (uint64_t i = 0; i < k; i++)
-            if (o[i + 1] < o[i]) return false;
-        return true;
-    };
-    if (!monotone(sig_off, n) || !monotone(msg_off, n_msgs) || (n_signers && (!monotone(idr_off, n_signers) ||
-                                                                              !monotone(vk_off, n_signers))))
+    if (!pv_offsets_monotone(sig_off, n) || !pv_offsets_monotone(msg_off, n_msgs) ||
+        (n_signers && (!pv_offsets_monotone(idr_off, n_signers) || !pv_offsets_monotone(vk_off, n_signers))))
         return pv_fail(PV_ERR_ARG, "pv_ingress_verify: offsets must be non-decreasing");
     uint64_t mtotal = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -651,39 +620,18 @@ int pv_ingress_verify(const char* sig_chars, const uint64_t* sig_off, const uint
     std::lock_guard<std::mutex> lk(g_ing_mu);
     // staging: [sig_off][msg_off][idr_off][vk_off] u64, [msg_idx][signer_idx] u32, [vk_present][status],
     // [verdict words], then the byte blobs; every section 256-B aligned
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t b_sigoff = up((n + 1) * 8), b_msgoff = up((n_msgs + 1) * 8);
-    const uint64_t b_idroff = up((n_signers + 1) * 8), b_vkoff = b_idroff;
-    const uint64_t b_idx = up(n * 4), b_vkp = up(n_signers + 1), b_status = up(n), b_ver = up((n + 63) / 64 * 8);
     const uint64_t sig_base = sig_off[0], msg_base = n_msgs ? msg_off[0] : 0;
-    const uint64_t b_sig = up(sig_off[n] - sig_base + 8), b_msg = up((n_msgs ? msg_off[n_msgs] - msg_base : 0) + 8);
     const uint64_t idr_base = n_signers ? idr_off[0] : 0, vk_base = n_signers ? vk_off[0] : 0;
-    const uint64_t b_idr = up((n_signers ? idr_off[n_signers] - idr_base : 0) + 8);
-    const uint64_t b_vk = up((n_signers ? vk_off[n_signers] - vk_base : 0) + 8);
-    const uint64_t total = b_sigoff + b_msgoff + b_idroff + b_vkoff + 2 * b_idx + b_vkp + b_status + b_ver + b_sig +
-                           b_msg + b_idr + b_vk;
-    if (total > g_ing.h_cap) {
-        if (g_ing.h_stage) (void)hipHostFree(g_ing.h_stage);
-        g_ing.h_stage = nullptr;
-        ING_HIP(hipHostMalloc((void**)&g_ing.h_stage, total, hipHostMallocDefault), PV_ERR_ALLOC);
-        g_ing.h_cap = total;
-    }
-    if (total > g_ing.d_cap) {
-        int rc = regrow(g_ing.d_stage, total);
-        if (rc) return rc;
-        g_ing.d_cap = total;
-    }
-    uint8_t* h = g_ing.h_stage;
-    uint64_t at = 0;
-    auto sec = [&](uint64_t bytes) {
-        const uint64_t p = at;
-        at += bytes;
-        return p;
-    };
-    const uint64_t o_sigoff = sec(b_sigoff), o_msgoff = sec(b_msgoff), o_idroff = sec(b_idroff),
-                   o_vkoff = sec(b_vkoff), o_midx = sec(b_idx), o_sidx = sec(b_idx), o_vkp = sec(b_vkp),
-                   o_status = sec(b_status), o_ver = sec(b_ver), o_sig = sec(b_sig), o_msg = sec(b_msg),
-                   o_idr = sec(b_idr), o_vk = sec(b_vk);
+    PvLayout l;
+    const uint64_t o_sigoff = l.add((n + 1) * 8), o_msgoff = l.add((n_msgs + 1) * 8), o_idroff = l.add((n_signers + 1) * 8),
+                   o_vkoff = l.add((n_signers + 1) * 8), o_midx = l.add(n * 4), o_sidx = l.add(n * 4),
+                   o_vkp = l.add(n_signers + 1), o_status = l.add(n), o_ver = l.add((n + 63) / 64 * 8),
+                   o_sig = l.add(sig_off[n] - sig_base + 8), o_msg = l.add((n_msgs ? msg_off[n_msgs] - msg_base : 0) + 8),
+                   o_idr = l.add((n_signers ? idr_off[n_signers] - idr_base : 0) + 8),
+                   o_vk = l.add((n_signers ? vk_off[n_signers] - vk_base : 0) + 8), total = l.at;
+    int rc;
+    if ((rc = g_ing.h_stage.grow(total, hipHostMallocDefault)) || (rc = g_ing.d_stage.grow(total))) return rc;
+    uint8_t* h = g_ing.h_stage.p;
     auto rebase = [&](uint64_t o, const uint64_t* src, uint64_t k, uint64_t base) {
         uint64_t* d = reinterpret_cast<uint64_t*>(h + o);
         for (uint64_t i = 0; i <= k; i++) d[i] = src[i] - base;
@@ -701,19 +649,19 @@ int pv_ingress_verify(const char* sig_chars, const uint64_t* sig_off, const uint
     memcpy(h + o_sidx, signer_idx, n * 4);
     memcpy(h + o_sig, sig_chars + sig_base, sig_off[n] - sig_base);
     if (n_msgs) memcpy(h + o_msg, msg + msg_base, msg_off[n_msgs] - msg_base);
-    uint8_t* d = g_ing.d_stage;
+    uint8_t* d = g_ing.d_stage.p;
     const hipStream_t s = pv_engine_stream();
-    ING_HIP(hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-    ING_HIP(hipMemcpyAsync(d + o_sig, h + o_sig, total - o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-    int rc = ingress_device(d + o_sig, reinterpret_cast<const uint64_t*>(d + o_sigoff),
-                            reinterpret_cast<const uint32_t*>(d + o_midx), reinterpret_cast<const uint32_t*>(d + o_sidx),
-                            n, d + o_msg, reinterpret_cast<const uint64_t*>(d + o_msgoff), n_msgs, mtotal, d + o_idr,
-                            reinterpret_cast<const uint64_t*>(d + o_idroff), d + o_vk,
-                            reinterpret_cast<const uint64_t*>(d + o_vkoff), d + o_vkp, n_signers, d + o_status,
-                            reinterpret_cast<uint64_t*>(d + o_ver), s);
+    PV_HIP(hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpyAsync(d + o_sig, h + o_sig, total - o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+    rc = ingress_device(d + o_sig, reinterpret_cast<const uint64_t*>(d + o_sigoff),
+                        reinterpret_cast<const uint32_t*>(d + o_midx), reinterpret_cast<const uint32_t*>(d + o_sidx), n,
+                        d + o_msg, reinterpret_cast<const uint64_t*>(d + o_msgoff), n_msgs, mtotal, d + o_idr,
+                        reinterpret_cast<const uint64_t*>(d + o_idroff), d + o_vk,
+                        reinterpret_cast<const uint64_t*>(d + o_vkoff), d + o_vkp, n_signers, d + o_status,
+                        reinterpret_cast<uint64_t*>(d + o_ver), s);
     if (rc) return rc;
-    ING_HIP(hipMemcpyAsync(h + o_status, d + o_status, b_status + b_ver, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-    ING_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpyAsync(h + o_status, d + o_status, o_sig - o_status, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
+    PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
     memcpy(status, h + o_status, n);
     memcpy(verdict_bits, h + o_ver, (n + 7) / 8);
     return PV_OK;

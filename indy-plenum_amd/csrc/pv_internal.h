@@ -6,17 +6,17 @@
 
 #include <string>
 
+#include "workspace.h"  // pv_fail, PV_HIP and what the workspaces below are made of
+
 // The library's main stream (valid after pv_init).
 hipStream_t pv_engine_stream();
-// Records `msg` as the calling thread's pv_last_error() and returns `code`.
-int pv_fail(int code, const std::string& msg);
-// A caller stream is being destroyed: the ingress workspace stops handing over through it.
+// The workspaces outside pv_engine.hip (ingress, Merkle, state trie), each with the same pair of hooks:
+// pv_stream_destroy tells it that a caller stream is going (its hand-over forgets the stream), and
+// pv_shutdown releases it before the device contexts go.
 void pv_ingress_forget_stream(void* stream);
-// The same for the Merkle workspace (pv_merkle.hip), and its release in pv_shutdown (before the
-// device contexts go).
+void pv_ingress_shutdown();
 void pv_merkle_forget_stream(void* stream);
 void pv_merkle_shutdown();
-// The same pair for the state-trie workspace (pv_trie.hip).
 void pv_trie_forget_stream(void* stream);
 void pv_trie_shutdown();
 // The latency path (pv_latency.hip): n requests on device buffers, verdict words written on `stream`.

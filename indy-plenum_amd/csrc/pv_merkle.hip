@@ -236,27 +236,14 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
 
 // --------------------------------------------------------------------------------------------- host
 
-#define MK_HIP(call, code)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return pv_fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // The Merkle code's own workspace: allocated on first use (an engine that never hashes a leaf holds
-// nothing), freed by pv_shutdown, handed over between caller streams by an event as the signing
-// workspace is. Launches are serialised on g_mk_mu.
+// nothing), freed by pv_shutdown, handed over between caller streams by an event (workspace.h).
+// Launches are serialised on g_mk_mu.
 struct MkWork {
-    uint32_t* leaf = nullptr;  // a chunk's leaf hashes / new nodes when the caller does not take them
-    uint64_t leaf_cap = 0;
-    uint32_t* node = nullptr;
-    uint64_t node_cap = 0;
-    uint32_t* front = nullptr;  // three frontiers of 64 hashes: two for chunk chaining, one for a host entry's input
-    uint8_t* d_in = nullptr;    // host entries: staged inputs and outputs of one chunk
-    uint64_t d_in_cap = 0;
-    uint8_t* d_out = nullptr;
-    uint64_t d_out_cap = 0;
-    hipEvent_t ev_done = nullptr;
-    hipStream_t last_stream = nullptr;
+    PvDevBuf leaf, node;   // a chunk's leaf hashes / new nodes when the caller does not take them
+    PvDevBuf front;        // three frontiers of 64 hashes: two for chunk chaining, one for a host entry's input
+    PvDevBuf d_in, d_out;  // host entries: staged inputs and outputs of one chunk
+    PvHandover hand;
 };
 MkWork g_mk;
 std::mutex g_mk_mu;
@@ -265,32 +252,12 @@ int g_mk_path = PV_MERKLE_AUTO;
 constexpr uint64_t MK_CHUNK_BYTES = 1ull << 30;  // a host-entry chunk also ends at this many data bytes
 constexpr uint64_t MK_FRONT_BYTES = 64 * 32;
 
-uint64_t mk_up(uint64_t x) { return (x + 255) & ~255ull; }
-
-template <class T>
-int mk_grow(T*& p, uint64_t& cap, uint64_t want) {
-    if (want <= cap) return PV_OK;
-    if (p) (void)hipFree(p);  // synchronises: no launch still reads the old block
-    p = nullptr;
-    cap = 0;
-    MK_HIP(hipMalloc((void**)&p, want), PV_ERR_ALLOC);
-    cap = want;
-    return PV_OK;
-}
-
 // The hand-over: `stream` waits for the workspace's last user. Caller holds g_mk_mu.
 int mk_begin(hipStream_t stream) {
-    if (!g_mk.front) MK_HIP(hipMalloc((void**)&g_mk.front, 3 * MK_FRONT_BYTES), PV_ERR_ALLOC);
-    if (!g_mk.ev_done) MK_HIP(hipEventCreateWithFlags(&g_mk.ev_done, hipEventDisableTiming), PV_ERR_NO_DEVICE);
-    if (g_mk.last_stream && g_mk.last_stream != stream) MK_HIP(hipStreamWaitEvent(stream, g_mk.ev_done, 0), PV_ERR_LAUNCH);
-    return PV_OK;
+    if (int rc = g_mk.front.grow(3 * MK_FRONT_BYTES)) return rc;
+    return g_mk.hand.begin(stream);
 }
-int mk_end(hipStream_t stream) {
-    MK_HIP(hipEventRecord(g_mk.ev_done, stream), PV_ERR_LAUNCH);
-    g_mk.last_stream = stream;
-    return PV_OK;
-}
-uint32_t* mk_front(int which) { return g_mk.front + which * (MK_FRONT_BYTES / 4); }
+uint32_t* mk_front(int which) { return g_mk.front.as<uint32_t>() + which * (MK_FRONT_BYTES / 4); }
 
 struct MkChunkOut {  // device pointers, null = not wanted
     uint32_t* leaf;
@@ -312,34 +279,34 @@ int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uin
     uint32_t* node = o.node;
     int rc;
     if (!leaf) {
-        if ((rc = mk_grow(g_mk.leaf, g_mk.leaf_cap, std::max<uint64_t>(m, 4096) * 32))) return rc;
-        leaf = g_mk.leaf;
+        if ((rc = g_mk.leaf.grow(std::max<uint64_t>(m, 4096) * 32))) return rc;
+        leaf = g_mk.leaf.as<uint32_t>();
     }
     if (!node) {
-        if ((rc = mk_grow(g_mk.node, g_mk.node_cap, (std::max<uint64_t>(m, 4096) + 64) * 32))) return rc;  // n_nodes < m + 48
-        node = g_mk.node;
+        if ((rc = g_mk.node.grow((std::max<uint64_t>(m, 4096) + 64) * 32))) return rc;  // n_nodes < m + 48
+        node = g_mk.node.as<uint32_t>();
     }
     const MkView v{s, m, d_fin, leaf, node};
     const unsigned grid = (unsigned)((m + MK_BLOCK - 1) / MK_BLOCK);
     hipLaunchKernelGGL(pv_merkle_leaf_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, d_data, d_off, m, leaf);
-    MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     if (n_nodes) {
         uint64_t first, count;
         pv_merkle_tiles(s, m, 0, &first, &count);
         hipLaunchKernelGGL(pv_merkle_tile_kernel, dim3((unsigned)count), dim3(MK_BLOCK), 0, stream, v, first, node);
-        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
         if (pv_merkle_any_above(s, m, PV_MERKLE_TILE_LOG)) {
             hipLaunchKernelGGL(pv_merkle_upper_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, v, node);
-            MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
         }
     }
     if (o.path || o.roots) {
         hipLaunchKernelGGL(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
                            o.poff_base, o.roots);
-        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     }
     hipLaunchKernelGGL(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
-    MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     return PV_OK;
 }
 
@@ -387,7 +354,7 @@ int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, co
     if (rc == PV_OK && out.frontier)
         if (hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToDevice, stream) != hipSuccess)
             rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: frontier copy failed");
-    const int rc2 = mk_end(stream);
+    const int rc2 = g_mk.hand.end(stream);
     return rc ? rc : rc2;
 }
 
@@ -399,7 +366,7 @@ int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* da
     if (rc) return rc;
     auto run = [&]() -> int {
         const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
-        if (s0) MK_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        if (s0) PV_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
         const uint32_t* fin = mk_front(2);
         int cur = 0;
         std::vector<uint64_t> rebased;
@@ -414,20 +381,18 @@ int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* da
             uint64_t n_nodes, n_front, n_path;
             pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
             // inputs: [offsets, rebased][data + slack]; outputs: [leaf][node][roots][path_off][path][root]
-            const uint64_t i_off = 0, i_data = mk_up((m + 1) * 8), i_total = i_data + mk_up(bytes + PV_BLOB_SLACK);
-            const uint64_t o_leaf = 0, o_node = o_leaf + (out.leaf_hash ? mk_up(32 * m) : 0),
-                           o_roots = o_node + (out.node_hash ? mk_up(32 * n_nodes) : 0),
-                           o_poff = o_roots + (out.roots ? mk_up(32 * m) : 0),
-                           o_path = o_poff + (out.path ? mk_up(8 * (m + 1)) : 0),
-                           o_root = o_path + (out.path ? mk_up(32 * n_path) : 0), o_total = o_root + 256;
+            PvLayout li, lo;  // the sections of an output the caller does not take stay empty
+            const uint64_t i_off = li.add((m + 1) * 8), i_data = li.add(bytes + PV_BLOB_SLACK);
+            const uint64_t o_leaf = out.leaf_hash ? lo.add(32 * m) : 0, o_node = out.node_hash ? lo.add(32 * n_nodes) : 0,
+                           o_roots = out.roots ? lo.add(32 * m) : 0, o_poff = out.path ? lo.add(8 * (m + 1)) : 0,
+                           o_path = out.path ? lo.add(32 * n_path) : 0, o_root = lo.add(32);
             int rc;
-            if ((rc = mk_grow(g_mk.d_in, g_mk.d_in_cap, i_total)) || (rc = mk_grow(g_mk.d_out, g_mk.d_out_cap, o_total)))
-                return rc;
+            if ((rc = g_mk.d_in.grow(li.at)) || (rc = g_mk.d_out.grow(lo.at))) return rc;
             rebased.resize(m + 1);
             for (uint64_t i = 0; i <= m; i++) rebased[i] = off[c0 + i] - base;
-            MK_HIP(hipMemcpyAsync(g_mk.d_in + i_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-            if (bytes) MK_HIP(hipMemcpyAsync(g_mk.d_in + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-            uint8_t* d = g_mk.d_out;
+            PV_HIP(hipMemcpyAsync(g_mk.d_in.p + i_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+            if (bytes) PV_HIP(hipMemcpyAsync(g_mk.d_in.p + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+            uint8_t* d = g_mk.d_out.p;
             const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
             const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(d + o_leaf) : nullptr,
                                out.node_hash ? reinterpret_cast<uint32_t*>(d + o_node) : nullptr,
@@ -436,34 +401,34 @@ int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* da
                                out.path ? reinterpret_cast<uint64_t*>(d + o_poff) : nullptr,
                                pbase,
                                is_last && out.root ? reinterpret_cast<uint32_t*>(d + o_root) : nullptr};
-            if ((rc = mk_chunk(s, fin, g_mk.d_in + i_data, reinterpret_cast<const uint64_t*>(g_mk.d_in + i_off), m, o,
+            if ((rc = mk_chunk(s, fin, g_mk.d_in.p + i_data, reinterpret_cast<const uint64_t*>(g_mk.d_in.p + i_off), m, o,
                                mk_front(cur), st)))
                 return rc;
             fin = mk_front(cur);
             cur ^= 1;
             if (out.leaf_hash)
-                MK_HIP(hipMemcpyAsync(out.leaf_hash + 32 * c0, d + o_leaf, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                PV_HIP(hipMemcpyAsync(out.leaf_hash + 32 * c0, d + o_leaf, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
             if (out.node_hash && n_nodes)
-                MK_HIP(hipMemcpyAsync(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0), d + o_node, 32 * n_nodes,
+                PV_HIP(hipMemcpyAsync(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0), d + o_node, 32 * n_nodes,
                                       hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
             if (out.roots)
-                MK_HIP(hipMemcpyAsync(out.roots + 32 * c0, d + o_roots, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                PV_HIP(hipMemcpyAsync(out.roots + 32 * c0, d + o_roots, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
             if (out.path) {
-                MK_HIP(hipMemcpyAsync(out.path_off + c0, d + o_poff, 8 * (m + 1), hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                PV_HIP(hipMemcpyAsync(out.path_off + c0, d + o_poff, 8 * (m + 1), hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
                 if (n_path)
-                    MK_HIP(hipMemcpyAsync(out.path + 32 * pbase, d + o_path, 32 * n_path, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                    PV_HIP(hipMemcpyAsync(out.path + 32 * pbase, d + o_path, 32 * n_path, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
             }
             if (is_last) {
-                if (out.root) MK_HIP(hipMemcpyAsync(out.root, d + o_root, 32, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-                if (out.frontier) MK_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                if (out.root) PV_HIP(hipMemcpyAsync(out.root, d + o_root, 32, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+                if (out.frontier) PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
             }
-            MK_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);  // the staging blocks are free for the next chunk
+            PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);  // the staging blocks are free for the next chunk
             c0 += m;
         }
         return PV_OK;
     };
     rc = run();
-    const int rc2 = mk_end(st);
+    const int rc2 = g_mk.hand.end(st);
     return rc ? rc : rc2;
 }
 
@@ -478,30 +443,22 @@ int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_
                            d_leaf_hash ? reinterpret_cast<const uint32_t*>(d_leaf_hash + 32 * c0) : nullptr, d_index + c0,
                            d_size + c0, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off + c0,
                            reinterpret_cast<const uint32_t*>(d_root + 32 * c0), m, d_status + c0, d_verdict + c0 / 64);
-        MK_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     }
     return PV_OK;
-}
-
-bool mk_monotone(const uint64_t* o, uint64_t k) {
-    for (uint64_t i = 0; i < k; i++)
-        if (o[i + 1] < o[i]) return false;
-    return true;
 }
 
 }  // namespace
 
 void pv_merkle_forget_stream(void* stream) {
     std::lock_guard<std::mutex> lk(g_mk_mu);
-    if (g_mk.last_stream == (hipStream_t)stream) g_mk.last_stream = nullptr;
+    g_mk.hand.forget((hipStream_t)stream);
 }
 
 void pv_merkle_shutdown() {
     std::lock_guard<std::mutex> lk(g_mk_mu);
-    for (void* p : {(void*)g_mk.leaf, (void*)g_mk.node, (void*)g_mk.front, (void*)g_mk.d_in, (void*)g_mk.d_out})
-        if (p) (void)hipFree(p);
-    if (g_mk.ev_done) (void)hipEventDestroy(g_mk.ev_done);
-    g_mk = MkWork();
+    for (PvDevBuf* b : {&g_mk.leaf, &g_mk.node, &g_mk.front, &g_mk.d_in, &g_mk.d_out}) b->release();
+    g_mk.hand.destroy();
 }
 
 extern "C" {
@@ -541,7 +498,7 @@ int pv_merkle_append_batch(uint64_t tree_size, const uint8_t* frontier, const ui
     if (tree_size > 0 && !frontier) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: a tree of size > 0 needs its frontier");
     if (n > 0) {
         if (!off) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null offsets");
-        if (!mk_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: offsets must be non-decreasing");
+        if (!pv_offsets_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: offsets must be non-decreasing");
         if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null data");
     }
     std::unique_lock<std::mutex> lk(g_mk_mu);
@@ -585,9 +542,9 @@ int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, c
         return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: null pointer");
     if ((leaf_hash != nullptr) == (off != nullptr))
         return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: give either data and off, or leaf_hash");
-    if (off && (!mk_monotone(off, n) || (!data && off[n] != off[0])))
+    if (off && (!pv_offsets_monotone(off, n) || (!data && off[n] != off[0])))
         return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: offsets must be non-decreasing over a data blob");
-    if (!mk_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
+    if (!pv_offsets_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
         return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: proof offsets must be non-decreasing over a proof array");
     if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: more than 2^32 - 1 proofs");
     std::unique_lock<std::mutex> lk(g_mk_mu);
@@ -606,14 +563,14 @@ int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, c
         // staged whole: [leaf off | leaf hashes][index][size][proof off, rebased][root][data + slack | -][proof]; out: [status][words]
         const uint64_t dbase = off ? off[0] : 0, dbytes = off ? off[n] - dbase : 0;
         const uint64_t pbase = proof_off[0], phashes = proof_off[n] - pbase;
-        const uint64_t i_leaf = 0, i_index = mk_up(off ? (n + 1) * 8 : 32 * n), i_size = i_index + mk_up(8 * n),
-                       i_poff = i_size + mk_up(8 * n), i_root = i_poff + mk_up(8 * (n + 1)),
-                       i_data = i_root + mk_up(32 * n), i_proof = i_data + (off ? mk_up(dbytes + PV_BLOB_SLACK) : 0),
-                       i_total = i_proof + mk_up(32 * phashes + 32);
-        const uint64_t o_status = 0, o_words = mk_up(n), o_total = o_words + mk_up((n + 63) / 64 * 8);
+        PvLayout li, lo;
+        const uint64_t i_leaf = li.add(off ? (n + 1) * 8 : 32 * n), i_index = li.add(8 * n), i_size = li.add(8 * n),
+                       i_poff = li.add(8 * (n + 1)), i_root = li.add(32 * n),
+                       i_data = off ? li.add(dbytes + PV_BLOB_SLACK) : 0, i_proof = li.add(32 * phashes + 32);
+        const uint64_t o_status = lo.add(n), o_words = lo.add((n + 63) / 64 * 8);
         int rc;
-        if ((rc = mk_grow(g_mk.d_in, g_mk.d_in_cap, i_total)) || (rc = mk_grow(g_mk.d_out, g_mk.d_out_cap, o_total))) return rc;
-        uint8_t* d = g_mk.d_in;
+        if ((rc = g_mk.d_in.grow(li.at)) || (rc = g_mk.d_out.grow(lo.at))) return rc;
+        uint8_t* d = g_mk.d_in.p;
         // every copy on st; the temporaries live until the synchronisation below
         std::vector<uint64_t> loff(off ? n + 1 : 0), poff(n + 1);
         auto h2d = [&](uint64_t at, const void* src, uint64_t bytes) {
@@ -621,30 +578,30 @@ int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, c
         };
         if (off) {
             for (uint64_t i = 0; i <= n; i++) loff[i] = off[i] - dbase;
-            MK_HIP(h2d(i_leaf, loff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
-            MK_HIP(h2d(i_data, data + dbase, dbytes), PV_ERR_LAUNCH);
+            PV_HIP(h2d(i_leaf, loff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
+            PV_HIP(h2d(i_data, data + dbase, dbytes), PV_ERR_LAUNCH);
         } else {
-            MK_HIP(h2d(i_leaf, leaf_hash, 32 * n), PV_ERR_LAUNCH);
+            PV_HIP(h2d(i_leaf, leaf_hash, 32 * n), PV_ERR_LAUNCH);
         }
         for (uint64_t i = 0; i <= n; i++) poff[i] = proof_off[i] - pbase;
-        MK_HIP(h2d(i_poff, poff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
-        MK_HIP(h2d(i_index, leaf_index, 8 * n), PV_ERR_LAUNCH);
-        MK_HIP(h2d(i_size, tree_size, 8 * n), PV_ERR_LAUNCH);
-        MK_HIP(h2d(i_root, root, 32 * n), PV_ERR_LAUNCH);
-        MK_HIP(h2d(i_proof, proof + 32 * pbase, 32 * phashes), PV_ERR_LAUNCH);
+        PV_HIP(h2d(i_poff, poff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
+        PV_HIP(h2d(i_index, leaf_index, 8 * n), PV_ERR_LAUNCH);
+        PV_HIP(h2d(i_size, tree_size, 8 * n), PV_ERR_LAUNCH);
+        PV_HIP(h2d(i_root, root, 32 * n), PV_ERR_LAUNCH);
+        PV_HIP(h2d(i_proof, proof + 32 * pbase, 32 * phashes), PV_ERR_LAUNCH);
         if ((rc = mk_verify_enqueue(off ? d + i_data : nullptr, off ? reinterpret_cast<const uint64_t*>(d + i_leaf) : nullptr,
                                     off ? nullptr : d + i_leaf, reinterpret_cast<const uint64_t*>(d + i_index),
                                     reinterpret_cast<const uint64_t*>(d + i_size), d + i_proof,
-                                    reinterpret_cast<const uint64_t*>(d + i_poff), d + i_root, n, g_mk.d_out + o_status,
-                                    reinterpret_cast<uint64_t*>(g_mk.d_out + o_words), st)))
+                                    reinterpret_cast<const uint64_t*>(d + i_poff), d + i_root, n, g_mk.d_out.p + o_status,
+                                    reinterpret_cast<uint64_t*>(g_mk.d_out.p + o_words), st)))
             return rc;
-        MK_HIP(hipMemcpyAsync(status, g_mk.d_out + o_status, n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        MK_HIP(hipMemcpyAsync(verdict_bits, g_mk.d_out + o_words, (n + 7) / 8, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        MK_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(status, g_mk.d_out.p + o_status, n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(verdict_bits, g_mk.d_out.p + o_words, (n + 7) / 8, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
         return PV_OK;
     };
     rc = run();
-    const int rc2 = mk_end(st);
+    const int rc2 = g_mk.hand.end(st);
     return rc ? rc : rc2;
 }
 

@@ -128,54 +128,17 @@ __global__ __launch_bounds__(TR_BLOCK) void pv_proof_walk_kernel(const PvProofIn
 
 // --------------------------------------------------------------------------------------------- host
 
-#define TR_HIP(call, code)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return pv_fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // The trie code's own workspace: allocated on first use (an engine that never touches a trie holds
-// nothing), freed by pv_shutdown, handed over between caller streams by an event as the Merkle
-// workspace is. Launches are serialised on g_tr_mu.
+// nothing), freed by pv_shutdown, handed over between caller streams by an event (workspace.h).
+// Launches are serialised on g_tr_mu.
 struct TrWork {
-    uint8_t* d_in = nullptr;  // the arena and its records, or a blob and its offsets
-    uint64_t d_in_cap = 0;
-    uint8_t* d_out = nullptr;  // digests
-    uint64_t d_out_cap = 0;
-    hipEvent_t ev_done = nullptr;
-    hipStream_t last_stream = nullptr;
+    PvDevBuf d_in;   // the arena and its records, or a blob and its offsets
+    PvDevBuf d_out;  // digests
+    PvHandover hand;
 };
 TrWork g_tr;
 std::mutex g_tr_mu;
 int g_tr_path = PV_TRIE_AUTO;
-
-uint64_t tr_up(uint64_t x) { return (x + 255) & ~255ull; }
-
-int tr_grow(uint8_t*& p, uint64_t& cap, uint64_t want) {
-    if (want <= cap) return PV_OK;
-    if (p) (void)hipFree(p);  // synchronises: no launch still reads the old block
-    p = nullptr;
-    cap = 0;
-    TR_HIP(hipMalloc((void**)&p, want), PV_ERR_ALLOC);
-    cap = want;
-    return PV_OK;
-}
-int tr_begin(hipStream_t stream) {
-    if (!g_tr.ev_done) TR_HIP(hipEventCreateWithFlags(&g_tr.ev_done, hipEventDisableTiming), PV_ERR_NO_DEVICE);
-    if (g_tr.last_stream && g_tr.last_stream != stream) TR_HIP(hipStreamWaitEvent(stream, g_tr.ev_done, 0), PV_ERR_LAUNCH);
-    return PV_OK;
-}
-int tr_end(hipStream_t stream) {
-    TR_HIP(hipEventRecord(g_tr.ev_done, stream), PV_ERR_LAUNCH);
-    g_tr.last_stream = stream;
-    return PV_OK;
-}
-
-bool tr_monotone(const uint64_t* o, uint64_t k) {
-    for (uint64_t i = 0; i < k; i++)
-        if (o[i + 1] < o[i]) return false;
-    return true;
-}
 
 // The launches for nr records on device buffers. Caller holds g_tr_mu.
 int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs, uint64_t nr, uint64_t* d_hashes,
@@ -184,7 +147,7 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
         if (nr - i0 <= TR_TAIL_MAX) {
             hipLaunchKernelGGL(pv_sha3_tail_kernel, dim3(1), dim3(TR_BLOCK), 0, st, d_arena, d_recs, (uint32_t)i0,
                                (uint32_t)nr, d_hashes);
-            TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             ++*launches;
             *tail_records = nr - i0;
             break;
@@ -192,7 +155,7 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
         const uint64_t i1 = recs[i0].next, count = i1 - i0;
         hipLaunchKernelGGL(pv_sha3_batch_kernel, dim3((unsigned)((count + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
                            d_arena, d_recs, (uint32_t)i0, (uint32_t)count, d_hashes);
-        TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
         ++*launches;
         i0 = i1;
     }
@@ -202,27 +165,27 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
 // arena and records staged whole, hashed, copied back: arena -> blob, digests -> hashes
 int tr_device_hash(PvTriePlan& plan, uint8_t* blob, uint8_t* hashes, uint64_t* launches, uint64_t* tail_records) {
     const hipStream_t st = pv_engine_stream();
-    int rc = tr_begin(st);
+    int rc = g_tr.hand.begin(st);
     if (rc) return rc;
     auto run = [&]() -> int {
-        const uint64_t nr = plan.recs.size(), i_recs = tr_up(plan.arena_bytes);
+        const uint64_t nr = plan.recs.size(), i_recs = pv_up256(plan.arena_bytes);
         int rc;
-        if ((rc = tr_grow(g_tr.d_in, g_tr.d_in_cap, i_recs + tr_up(nr * sizeof(PvTrieRec)))) ||
-            (rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, tr_up(32 * nr))))
+        if ((rc = g_tr.d_in.grow(i_recs + pv_up256(nr * sizeof(PvTrieRec)))) ||
+            (rc = g_tr.d_out.grow(pv_up256(32 * nr))))
             return rc;
-        TR_HIP(hipMemcpyAsync(g_tr.d_in, plan.arena.data(), plan.arena_bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        TR_HIP(hipMemcpyAsync(g_tr.d_in + i_recs, plan.recs.data(), nr * sizeof(PvTrieRec), hipMemcpyHostToDevice, st),
+        PV_HIP(hipMemcpyAsync(g_tr.d_in.p, plan.arena.data(), plan.arena_bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(g_tr.d_in.p + i_recs, plan.recs.data(), nr * sizeof(PvTrieRec), hipMemcpyHostToDevice, st),
                PV_ERR_LAUNCH);
-        if ((rc = tr_enqueue(g_tr.d_in, reinterpret_cast<const PvTrieRec*>(g_tr.d_in + i_recs), plan.recs.data(), nr,
-                             reinterpret_cast<uint64_t*>(g_tr.d_out), st, launches, tail_records)))
+        if ((rc = tr_enqueue(g_tr.d_in.p, reinterpret_cast<const PvTrieRec*>(g_tr.d_in.p + i_recs), plan.recs.data(), nr,
+                             reinterpret_cast<uint64_t*>(g_tr.d_out.p), st, launches, tail_records)))
             return rc;
-        TR_HIP(hipMemcpyAsync(blob, g_tr.d_in, plan.arena_bytes, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        TR_HIP(hipMemcpyAsync(hashes, g_tr.d_out, 32 * nr, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        TR_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(blob, g_tr.d_in.p, plan.arena_bytes, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(hashes, g_tr.d_out.p, 32 * nr, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
         return PV_OK;
     };
     rc = run();
-    const int rc2 = tr_end(st);
+    const int rc2 = g_tr.hand.end(st);
     return rc ? rc : rc2;
 }
 
@@ -240,11 +203,11 @@ int tr_proof_enqueue(const PvProofIn& d, uint64_t* d_digest, uint8_t* d_flag, ui
     if (d.n_nodes) {
         hipLaunchKernelGGL(pv_proof_node_kernel, dim3((unsigned)((d.n_nodes + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
                            st, d.node_blob, d.node_off, d.node_len, d.n_nodes, d_digest, d_flag);
-        TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     }
     hipLaunchKernelGGL(pv_proof_walk_kernel, dim3((unsigned)((d.n_queries + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
                        d, (const uint64_t*)d_digest, (const uint8_t*)d_flag, d_status);
-    TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     return PV_OK;
 }
 
@@ -252,7 +215,7 @@ int tr_proof_enqueue(const PvProofIn& d, uint64_t* d_digest, uint8_t* d_flag, ui
 // bytes that are copied, statuses copied back. Caller holds g_tr_mu and has validated `in`.
 int tr_proof_device(const PvProofIn& in, uint8_t* status) {
     const hipStream_t st = pv_engine_stream();
-    int rc = tr_begin(st);
+    int rc = g_tr.hand.begin(st);
     if (rc) return rc;
     auto run = [&]() -> int {
         const uint64_t nn = in.n_nodes, np = in.n_proofs, nq = in.n_queries;
@@ -272,55 +235,50 @@ int tr_proof_device(const PvProofIn& in, uint8_t* status) {
             koff[i] = in.key_off[i] - kbase;
             voff[i] = in.val_off[i] - vbase;
         }
-        uint64_t at = 0;
-        auto seg = [&](uint64_t bytes) {
-            const uint64_t a = at;
-            at += tr_up(bytes ? bytes : 1);
-            return a;
-        };
-        const uint64_t i_noff = seg(8 * (nn + 1)), i_nlen = seg(in.node_len ? 8 * nn : 0), i_pf = seg(8 * (np + 1)),
-                       i_koff = seg(8 * (nq + 1)), i_voff = seg(8 * (nq + 1)), i_qp = seg(4 * nq), i_root = seg(32 * nq),
-                       i_key = seg(kbytes), i_val = seg(vbytes), i_blob = seg(hi - lo + 8);
-        const uint64_t o_flag = tr_up(32 * nn + 1), o_status = o_flag + tr_up(nn + 1);
+        PvLayout li;
+        const uint64_t i_noff = li.add(8 * (nn + 1)), i_nlen = li.add(in.node_len ? 8 * nn : 0),
+                       i_pf = li.add(8 * (np + 1)), i_koff = li.add(8 * (nq + 1)), i_voff = li.add(8 * (nq + 1)),
+                       i_qp = li.add(4 * nq), i_root = li.add(32 * nq), i_key = li.add(kbytes), i_val = li.add(vbytes),
+                       i_blob = li.add(hi - lo + 8);
+        const uint64_t o_flag = pv_up256(32 * nn + 1), o_status = o_flag + pv_up256(nn + 1);
         int rc;
-        if ((rc = tr_grow(g_tr.d_in, g_tr.d_in_cap, at)) || (rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, o_status + tr_up(nq))))
-            return rc;
+        if ((rc = g_tr.d_in.grow(li.at)) || (rc = g_tr.d_out.grow(o_status + pv_up256(nq)))) return rc;
+        uint8_t *const din = g_tr.d_in.p, *const dout = g_tr.d_out.p;
         auto put = [&](uint64_t where, const void* src, uint64_t bytes) -> hipError_t {
-            return bytes ? hipMemcpyAsync(g_tr.d_in + where, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+            return bytes ? hipMemcpyAsync(din + where, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
         };
-        TR_HIP(put(i_noff, noff.data(), 8 * (nn + 1)), PV_ERR_LAUNCH);
-        if (in.node_len) TR_HIP(put(i_nlen, in.node_len, 8 * nn), PV_ERR_LAUNCH);
-        TR_HIP(put(i_pf, in.proof_first, 8 * (np + 1)), PV_ERR_LAUNCH);
-        TR_HIP(put(i_koff, koff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
-        TR_HIP(put(i_voff, voff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
-        TR_HIP(put(i_qp, in.query_proof, 4 * nq), PV_ERR_LAUNCH);
-        TR_HIP(put(i_root, in.root, 32 * nq), PV_ERR_LAUNCH);
-        TR_HIP(put(i_key, kbytes ? in.key_blob + kbase : nullptr, kbytes), PV_ERR_LAUNCH);
-        TR_HIP(put(i_val, vbytes ? in.val_blob + vbase : nullptr, vbytes), PV_ERR_LAUNCH);
-        TR_HIP(put(i_blob, hi > lo ? in.node_blob + lo : nullptr, hi - lo), PV_ERR_LAUNCH);
-        auto u64p = [&](uint64_t where) { return reinterpret_cast<const uint64_t*>(g_tr.d_in + where); };
+        PV_HIP(put(i_noff, noff.data(), 8 * (nn + 1)), PV_ERR_LAUNCH);
+        if (in.node_len) PV_HIP(put(i_nlen, in.node_len, 8 * nn), PV_ERR_LAUNCH);
+        PV_HIP(put(i_pf, in.proof_first, 8 * (np + 1)), PV_ERR_LAUNCH);
+        PV_HIP(put(i_koff, koff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
+        PV_HIP(put(i_voff, voff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
+        PV_HIP(put(i_qp, in.query_proof, 4 * nq), PV_ERR_LAUNCH);
+        PV_HIP(put(i_root, in.root, 32 * nq), PV_ERR_LAUNCH);
+        PV_HIP(put(i_key, kbytes ? in.key_blob + kbase : nullptr, kbytes), PV_ERR_LAUNCH);
+        PV_HIP(put(i_val, vbytes ? in.val_blob + vbase : nullptr, vbytes), PV_ERR_LAUNCH);
+        PV_HIP(put(i_blob, hi > lo ? in.node_blob + lo : nullptr, hi - lo), PV_ERR_LAUNCH);
+        auto u64p = [&](uint64_t where) { return reinterpret_cast<const uint64_t*>(din + where); };
         PvProofIn d;
-        d.node_blob = g_tr.d_in + i_blob;
+        d.node_blob = din + i_blob;
         d.node_off = u64p(i_noff);
         d.n_nodes = nn;
         d.proof_first = u64p(i_pf);
         d.n_proofs = np;
-        d.query_proof = reinterpret_cast<const uint32_t*>(g_tr.d_in + i_qp);
-        d.root = g_tr.d_in + i_root;
-        d.key_blob = g_tr.d_in + i_key;
+        d.query_proof = reinterpret_cast<const uint32_t*>(din + i_qp);
+        d.root = din + i_root;
+        d.key_blob = din + i_key;
         d.key_off = u64p(i_koff);
-        d.val_blob = g_tr.d_in + i_val;
+        d.val_blob = din + i_val;
         d.val_off = u64p(i_voff);
         d.n_queries = nq;
         d.node_len = in.node_len ? u64p(i_nlen) : nullptr;
-        if ((rc = tr_proof_enqueue(d, reinterpret_cast<uint64_t*>(g_tr.d_out), g_tr.d_out + o_flag, g_tr.d_out + o_status, st)))
-            return rc;
-        TR_HIP(hipMemcpyAsync(status, g_tr.d_out + o_status, nq, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        TR_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+        if ((rc = tr_proof_enqueue(d, reinterpret_cast<uint64_t*>(dout), dout + o_flag, dout + o_status, st))) return rc;
+        PV_HIP(hipMemcpyAsync(status, dout + o_status, nq, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
         return PV_OK;
     };
     rc = run();
-    const int rc2 = tr_end(st);
+    const int rc2 = g_tr.hand.end(st);
     return rc ? rc : rc2;
 }
 
@@ -328,15 +286,14 @@ int tr_proof_device(const PvProofIn& in, uint8_t* status) {
 
 void pv_trie_forget_stream(void* stream) {
     std::lock_guard<std::mutex> lk(g_tr_mu);
-    if (g_tr.last_stream == (hipStream_t)stream) g_tr.last_stream = nullptr;
+    g_tr.hand.forget((hipStream_t)stream);
 }
 
 void pv_trie_shutdown() {
     std::lock_guard<std::mutex> lk(g_tr_mu);
-    for (void* p : {(void*)g_tr.d_in, (void*)g_tr.d_out})
-        if (p) (void)hipFree(p);
-    if (g_tr.ev_done) (void)hipEventDestroy(g_tr.ev_done);
-    g_tr = TrWork();
+    g_tr.d_in.release();
+    g_tr.d_out.release();
+    g_tr.hand.destroy();
 }
 
 extern "C" {
@@ -352,7 +309,7 @@ int pv_trie_path(int mode) {
 int pv_sha3_256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* out) {
     if (n == 0) return PV_OK;
     if (!off || !out) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: null pointer");
-    if (!tr_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: offsets must be non-decreasing");
+    if (!pv_offsets_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: offsets must be non-decreasing");
     if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: null data");
     if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: more than 2^31 - 1 records");
     std::unique_lock<std::mutex> lk(g_tr_mu);
@@ -365,28 +322,28 @@ int pv_sha3_256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint
         return PV_OK;
     }
     const hipStream_t st = pv_engine_stream();
-    if ((rc = tr_begin(st))) return rc;
+    if ((rc = g_tr.hand.begin(st))) return rc;
     auto run = [&]() -> int {
         // staged whole: [offsets, rebased][data, to a whole word]
-        const uint64_t base = off[0], bytes = off[n] - base, i_data = tr_up(8 * (n + 1));
+        const uint64_t base = off[0], bytes = off[n] - base, i_data = pv_up256(8 * (n + 1));
         int rc;
-        if ((rc = tr_grow(g_tr.d_in, g_tr.d_in_cap, i_data + tr_up(bytes + 8))) ||
-            (rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, tr_up(32 * n))))
+        if ((rc = g_tr.d_in.grow(i_data + pv_up256(bytes + 8))) ||
+            (rc = g_tr.d_out.grow(pv_up256(32 * n))))
             return rc;
         std::vector<uint64_t> rebased(n + 1);
         for (uint64_t i = 0; i <= n; i++) rebased[i] = off[i] - base;
-        TR_HIP(hipMemcpyAsync(g_tr.d_in, rebased.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        if (bytes) TR_HIP(hipMemcpyAsync(g_tr.d_in + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(g_tr.d_in.p, rebased.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        if (bytes) PV_HIP(hipMemcpyAsync(g_tr.d_in.p + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
         hipLaunchKernelGGL(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
-                           g_tr.d_in + i_data, reinterpret_cast<const uint64_t*>(g_tr.d_in), n,
-                           reinterpret_cast<uint64_t*>(g_tr.d_out));
-        TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        TR_HIP(hipMemcpyAsync(out, g_tr.d_out, 32 * n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        TR_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+                           g_tr.d_in.p + i_data, reinterpret_cast<const uint64_t*>(g_tr.d_in.p), n,
+                           reinterpret_cast<uint64_t*>(g_tr.d_out.p));
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(out, g_tr.d_out.p, 32 * n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
         return PV_OK;
     };
     rc = run();
-    const int rc2 = tr_end(st);
+    const int rc2 = g_tr.hand.end(st);
     return rc ? rc : rc2;
 }
 
@@ -398,7 +355,7 @@ int pv_sha3_256_batch_device(const uint8_t* d_data, const uint64_t* d_off, uint6
     if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch_device: more than 2^31 - 1 records");
     hipLaunchKernelGGL(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
                        stream ? (hipStream_t)stream : pv_engine_stream(), d_data, d_off, n, reinterpret_cast<uint64_t*>(d_out));
-    TR_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
     return PV_OK;
 }
 
@@ -412,10 +369,10 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
         return PV_OK;
     }
     if (!key_off || !val_off || !val_blob) return pv_fail(PV_ERR_ARG, "pv_trie_update_batch: null keys or values");
-    if (!tr_monotone(key_off, n) || !tr_monotone(val_off, n))
+    if (!pv_offsets_monotone(key_off, n) || !pv_offsets_monotone(val_off, n))
         return pv_fail(PV_ERR_ARG, "pv_trie_update_batch: offsets must be non-decreasing");
     if (!key_blob && key_off[n] != key_off[0]) return pv_fail(PV_ERR_ARG, "pv_trie_update_batch: null key blob");
-    if (n_known && (!known_hash || !known_blob || !known_off || !tr_monotone(known_off, n_known)))
+    if (n_known && (!known_hash || !known_blob || !known_off || !pv_offsets_monotone(known_off, n_known)))
         return pv_fail(PV_ERR_ARG, "pv_trie_update_batch: known nodes need hashes, a blob and non-decreasing offsets");
     if ((out->node_cap && (!out->node_hash || !out->node_off || !out->node_len)) || (out->blob_cap && !out->node_blob) ||
         (out->missing_cap && !out->missing))
@@ -491,18 +448,18 @@ int pv_trie_verify_proofs_device(const PvProofIn* d_in, uint8_t* d_status, uint8
         return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: more than 2^31 - 1 records, proofs or queries");
     const hipStream_t st = stream ? (hipStream_t)stream : pv_engine_stream();
     std::lock_guard<std::mutex> lk(g_tr_mu);
-    int rc = tr_begin(st);  // the flags live in the workspace: handed over from the stream that used it last
+    int rc = g_tr.hand.begin(st);  // the flags live in the workspace: handed over from the stream that used it last
     if (rc) return rc;
-    if (!(rc = tr_grow(g_tr.d_out, g_tr.d_out_cap, tr_up(d_in->n_nodes + 1))))
-        rc = tr_proof_enqueue(*d_in, reinterpret_cast<uint64_t*>(d_node_hash), g_tr.d_out, d_status, st);
-    const int rc2 = tr_end(st);
+    if (!(rc = g_tr.d_out.grow(pv_up256(d_in->n_nodes + 1))))
+        rc = tr_proof_enqueue(*d_in, reinterpret_cast<uint64_t*>(d_node_hash), g_tr.d_out.p, d_status, st);
+    const int rc2 = g_tr.hand.end(st);
     return rc ? rc : rc2;
 }
 
 int pv_trie_proof_split(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,
                         uint64_t* node_off, uint64_t* node_len, uint64_t node_cap, uint64_t* n_nodes, uint8_t* proof_ok) {
     if (!proof_first || !n_nodes) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null pointer");
-    if (n_proofs && (!ser_off || !proof_ok || !tr_monotone(ser_off, n_proofs)))
+    if (n_proofs && (!ser_off || !proof_ok || !pv_offsets_monotone(ser_off, n_proofs)))
         return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null pointer or decreasing offsets");
     if (n_proofs && !ser && ser_off[n_proofs] != ser_off[0]) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: null proofs");
     if (!node_off || (node_cap && !node_len)) return pv_fail(PV_ERR_ARG, "pv_trie_proof_split: a capacity without its array");

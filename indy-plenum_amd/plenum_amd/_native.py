@@ -193,6 +193,16 @@ def ensure_device(device=None):
     return _device
 
 
+def shutdown():
+    """pv_shutdown: every device context and workspace is released, and the binding forgets what it had
+    bound, so the next call that needs a GPU runs pv_init again. Path settings (set_path, merkle_path,
+    trie_path) are the library's and stay."""
+    global _device, _multi_devices, _merkle_no_device, _trie_no_device
+    lib().pv_shutdown()
+    _device = _multi_devices = None
+    _merkle_no_device = _trie_no_device = False
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 

@@ -1,0 +1,75 @@
+// A stand-in for <hip/hip_runtime.h> that lets workspace_check.cpp compile csrc/workspace.h with g++ and
+// no GPU: allocations over malloc, events and streams as small integers, a log of every runtime call and
+// a switch that makes the k-th allocation from now on fail.
+#ifndef STUB_HIP_RUNTIME_H
+#define STUB_HIP_RUNTIME_H
+
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <string>
+#include <vector>
+
+enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
+inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "out of memory (stub)"; }
+
+typedef struct StubEvent* hipEvent_t;    // never dereferenced: (hipEvent_t)id
+typedef struct StubStream* hipStream_t;  // the same
+constexpr unsigned hipHostMallocDefault = 0, hipHostMallocPortable = 1, hipEventDisableTiming = 2;
+
+struct StubCall {
+    std::string name;  // "hipMalloc", "hipStreamWaitEvent", ...
+    uintptr_t a, b;    // bytes and flags / stream and event / the pointer freed
+};
+struct StubState {
+    std::vector<StubCall> log;
+    int fail_in = 0;  // > 0: the fail_in-th allocation from now fails
+    uint64_t dev_allocs = 0, dev_frees = 0, host_allocs = 0, host_frees = 0, events = 0, events_destroyed = 0;
+};
+inline StubState& stub() {
+    static StubState s;
+    return s;
+}
+inline hipError_t stub_alloc(const char* name, void** p, size_t bytes, unsigned flags, uint64_t& count) {
+    stub().log.push_back({name, bytes, flags});
+    if (stub().fail_in > 0 && --stub().fail_in == 0) return hipErrorOutOfMemory;
+    *p = malloc(bytes);
+    count++;
+    return hipSuccess;
+}
+inline hipError_t hipMalloc(void** p, size_t bytes) { return stub_alloc("hipMalloc", p, bytes, 0, stub().dev_allocs); }
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned flags) {
+    return stub_alloc("hipHostMalloc", p, bytes, flags, stub().host_allocs);
+}
+inline hipError_t hipFree(void* p) {
+    stub().log.push_back({"hipFree", (uintptr_t)p, 0});
+    stub().dev_frees++;
+    free(p);
+    return hipSuccess;
+}
+inline hipError_t hipHostFree(void* p) {
+    stub().log.push_back({"hipHostFree", (uintptr_t)p, 0});
+    stub().host_frees++;
+    free(p);
+    return hipSuccess;
+}
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
+    *e = (hipEvent_t)(uintptr_t)(++stub().events);
+    stub().log.push_back({"hipEventCreateWithFlags", (uintptr_t)*e, flags});
+    return hipSuccess;
+}
+inline hipError_t hipEventDestroy(hipEvent_t e) {
+    stub().log.push_back({"hipEventDestroy", (uintptr_t)e, 0});
+    stub().events_destroyed++;
+    return hipSuccess;
+}
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    stub().log.push_back({"hipEventRecord", (uintptr_t)s, (uintptr_t)e});
+    return hipSuccess;
+}
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    stub().log.push_back({"hipStreamWaitEvent", (uintptr_t)s, (uintptr_t)e});
+    return hipSuccess;
+}
+
+#endif  // STUB_HIP_RUNTIME_H

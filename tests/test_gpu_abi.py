@@ -215,3 +215,79 @@ def test_dedup_lds_table_overflow(native, sodium):
         native.set_path(native.PV_PATH_AUTO)
     assert np.array_equal(got, want), np.nonzero(got != want)[0][:10]
     assert split == (4096, 4096, n), split
+
+
+# pv_shutdown releases every workspace (ingress, Merkle, state trie, signing, verification) and a second
+# pv_init starts from nothing: run in a child process, so this session's library state stays as it is.
+_REINIT_CHILD = r"""
+import hashlib, json
+import numpy as np
+from plenum_amd import _native as N
+from oracle.libsodium_ref import LibSodium
+from oracle.base58_ref import b58encode
+import merkle_ref
+from test_gpu_ingress import expected, signer_forms
+
+sod, rng = LibSodium(), np.random.default_rng(41)
+signers = signer_forms(sod, rng, 4)
+idrs, vks, sks = [s[0] for s in signers], [s[1] for s in signers], [s[2] for s in signers]
+msgs = [rng.bytes(int(rng.integers(1, 200))) for _ in range(4)]
+raw = [sod.sign_detached(m, sk) for m, sk in zip(msgs, sks)]
+raw[2] = raw[2][:5] + bytes([raw[2][5] ^ 1]) + raw[2][6:]  # one tampered
+sigs = [b58encode(s) for s in raw]
+blob, off = merkle_ref.pack(msgs, lead=3)
+sk_table = np.frombuffer(b"".join(sks), np.uint8).reshape(4, 64)
+pks = np.ascontiguousarray(sk_table[:, 32:])
+sm_blob, sm_off = N._blob([s + m for s, m in zip(raw, msgs)])
+
+
+def five():
+    N.merkle_path(N.PV_MERKLE_DEVICE)
+    N.trie_path(N.PV_TRIE_DEVICE)
+    st, v = N.ingress_verify(sigs, msgs, [0, 1, 2, 3], [0, 1, 2, 3], idrs, vks)
+    mk = N.merkle_append(0, b"", blob, off)
+    out = {"ingress": [st.tolist(), v.tolist()],
+           "merkle": {k: mk[k].tobytes().hex() for k in sorted(mk)},
+           "sha3": N.sha3_256_batch(blob, off).tobytes().hex(),
+           "sign": N.sign_batch(blob, off, sk_table).tobytes().hex(),
+           "verify": N.verify_sm_batch(sm_blob, sm_off, pks).tolist()}
+    return out
+
+
+N.ensure_device()
+before = five()
+N.shutdown()
+N.ensure_device()
+after = five()
+w_st, w_v = expected(sod, N, sigs, msgs, [0, 1, 2, 3], [0, 1, 2, 3], idrs, vks)
+w_mk = merkle_ref.append_all(0, [], msgs)
+path_off = np.zeros(5, np.uint64)
+np.cumsum([len(p) for p in w_mk["paths"]], out=path_off[1:])
+w_mk = {"leaf_hash": b"".join(w_mk["leaf_hash"]), "node_hash": b"".join(w_mk["node_hash"]),
+        "frontier": b"".join(w_mk["frontier"]), "root": w_mk["root"], "roots": b"".join(w_mk["roots"]),
+        "path": b"".join(b"".join(p) for p in w_mk["paths"]), "path_off": path_off.tobytes()}
+want = {"ingress": [w_st.tolist(), w_v.tolist()],
+        "merkle": {k: v.hex() for k, v in w_mk.items()},
+        "sha3": b"".join(hashlib.sha3_256(m).digest() for m in msgs).hex(),
+        "sign": b"".join(sod.sign_detached(m, sk) for m, sk in zip(msgs, sks)).hex(),
+        "verify": [sod.sign_open_ok(s + m, pk.tobytes()) for s, m, pk in zip(raw, msgs, pks)]}
+print(json.dumps({"before": before, "after": after, "want": want}))
+"""
+
+
+def test_shutdown_then_init_again(sodium):
+    """pv_init, one 4-item call each of pv_ingress_verify, pv_merkle_append_batch and pv_sha3_256_batch (device
+    paths forced), pv_sign_batch and pv_verify_batch; pv_shutdown; pv_init; the same five calls: byte-identical
+    outputs before and after, equal to libsodium, hashlib and the Merkle restatement."""
+    import subprocess
+    import sys
+    root = os.path.dirname(HERE)
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([root, os.path.join(root, "indy-plenum_amd"), HERE, env.get("PYTHONPATH", "")])
+    r = subprocess.run([sys.executable, "-c", _REINIT_CHILD], cwd=root, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["before"] == out["after"]
+    for k, want in out["want"].items():
+        assert out["after"][k] == want, k
+    assert out["want"]["verify"] == [True, True, False, True] and out["want"]["ingress"][1] == [True, True, False, True]

@@ -1,0 +1,58 @@
+"""The shared pieces of the device workspaces (indy-plenum_amd/csrc/workspace.h: grow-only device and
+pinned buffers, the event hand-over between caller streams, the 256-byte staging layout, the offsets
+check), compiled with g++ against a stub HIP runtime (tests/native/stub_hip) that logs every call and can
+fail an allocation. Built with AddressSanitizer and UBSan and run as a stand-alone program. CPU only."""
+import json
+import os
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "workspace_check.cpp")
+STUB = os.path.join(HERE, "native", "stub_hip")
+HDR = os.path.join(HERE, "..", "indy-plenum_amd", "csrc", "workspace.h")
+BIN = os.path.join(HERE, "native", "workspace_check")
+
+
+@pytest.fixture(scope="module")
+def report():
+    deps = [SRC, HDR, os.path.join(STUB, "hip", "hip_runtime.h")]
+    if not os.path.exists(BIN) or os.path.getmtime(BIN) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                               "-fno-sanitize-recover=undefined", "-Wall", "-Werror", "-I", STUB, "-o", BIN, SRC])
+    out = subprocess.run([BIN], check=True, capture_output=True, text=True, timeout=60).stdout
+    return json.loads(out)
+
+
+def _group(report, name, at_least):
+    checks = {k: v for k, v in report.items() if k.startswith(name + ".")}
+    assert len(checks) >= at_least, sorted(checks)
+    assert all(v is True for v in checks.values()), {k: v for k, v in checks.items() if v is not True}
+
+
+def test_device_buffer_is_empty_after_a_failed_grow(report):
+    """grow(want <= cap) makes no runtime call; a failed grow returns PV_ERR_ALLOC and leaves p == nullptr
+    and cap == 0, so the next grow of any size allocates again; release twice is harmless; allocations
+    equal frees."""
+    _group(report, "dev", 13)
+
+
+def test_pinned_buffer_is_empty_after_a_failed_grow(report):
+    """The same for pinned memory, and the hipHostMalloc flags arrive unchanged."""
+    _group(report, "pinned", 13)
+
+
+def test_hand_over_waits_only_for_another_stream(report):
+    """Read from the stub's call log: no wait on the first use or on the stream that used the workspace
+    last, exactly one wait (on the waiting stream, for the recorded event) otherwise; a forgotten stream is
+    never waited for; destroy, then begin, recreates the event."""
+    _group(report, "hand", 15)
+
+
+def test_layout_sections_are_aligned_and_disjoint(report):
+    _group(report, "layout", 5)
+
+
+def test_offsets_monotone(report):
+    _group(report, "monotone", 6)
