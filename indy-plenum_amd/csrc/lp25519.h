@@ -420,7 +420,7 @@ LP_FN lu lp_pow22523(const LpLane& c, const lu& z) {
 }
 
 // z^(p - 2) = 1 / z in every row at once (fe_invert's chain: z^(2^250 - 1), five squarings, times
-// z^11). The encode kernel inverts the wave's cross-lane products with it (pv_engine.hip PvWaveInvert):
+// z^11). The encode kernel inverts the wave's cross-lane products with it (pv_engine_dev.h PvWaveInvert):
 // a chain of limb-parallel products, ~300 cycles each (fewer with DUAL: two values, five column terms
 // per lane), instead of each lane's own chain of 101-instruction squarings.
 template <bool DUAL = false>

@@ -1,4 +1,8 @@
-// libplenum_verify: MI355X batch Ed25519 verification engine (kernels + device-side C ABI).
+// libplenum_verify: MI355X batch Ed25519 verification engine: the verification kernels, the device
+// context (pv_ctx.h Ctx: lifecycle, launch, control and statistics entries), the node-side key cache and
+// the device-buffer entry. The rest of the engine lives beside it: signing in pv_sign.hip, the
+// host-buffer entries in pv_host.hip, RCCL and in-process multi-GPU in pv_multi.hip, the latency path in
+// pv_latency.hip; the device types they share are pv_engine_dev.h.
 //
 // One lane per request, 256-thread workgroups, two workgroups per CU (2 waves/SIMD: measured
 // v_mad_u64_u32 throughput saturates at >= 2 waves/SIMD, profiles/r01_isa_rates.jsonl). The grid is
@@ -20,34 +24,23 @@
 #include <list>
 #include <unordered_map>
 #include <mutex>
-#include <chrono>
 #include <atomic>
 #include <random>
-#include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <thread>
 #include <string>
 #include <vector>
 
 #include "btable.h"
-#include "copy_pool.h"
-#include "kc_admit.h"
 #include "comb.h"
 #include "keycache.h"
 #include "lp25519.h"
 #include "verify_core.h"
-#include "sign_core.h"
+#include "pv_engine_dev.h"
+#include "pv_ctx.h"
 #include "pv_internal.h"
 #include "../../include/plenum_verify.h"
 #include "../../include/plenum_verify_test.h"
-
-static constexpr int PV_BLOCK = 256;
-// an integer from the environment (A/B knobs read once at first use), or dflt
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e && *e ? atoi(e) : dflt;
-}
 
 #ifndef PV_COMB_A_MINBLOCKS
 #define PV_COMB_A_MINBLOCKS 3
@@ -62,34 +55,6 @@ static int env_int(const char* name, int dflt) {
 #ifndef PV_PREP_MINBLOCKS
 #define PV_PREP_MINBLOCKS 2  // Straus prep (decompression + SHA-512 + recoding)
 #endif
-// Dynamic LDS requested by every pv_comb_prep_req_kernel workgroup, unused: it caps the kernel's residency
-// so that the key chain, launched beside it on the key stream, finds a wave slot on every SIMD at
-// once instead of waiting for prep workgroups to retire (env PV_PREP_LDS_PAD overrides at pv_init).
-// 41,984 B: 3 workgroups per CU (126 KB of the 160 KB), 3 prep waves per SIMD leave the chain's wave a
-// slot from the start -- A/B (profiles/r04/ab_pad.txt): chain 0.40 -> 0.31 ms in-step, comb kernel
-// starts 0.83 -> 0.79 ms, step -2 %; 54 KB (2 per CU) slows the prep more than it helps
-#ifndef PV_PREP_LDS_PAD
-#define PV_PREP_LDS_PAD 41984
-#endif
-static constexpr uint64_t PV_CHUNK = 1ull << 20;  // requests per launch sequence (workspace ~1.8 GB)
-static constexpr uint32_t PV_KEY_CAP = 16384;     // distinct keys the comb tables hold (10.8 GB)
-// AUTO: chunks above the latency path's range go keyed (dedup, then comb keys / Straus side). At
-// medium sizes (4k-256k requests) the Straus side's one-lane latency (~0.9 ms) is paid by the whole
-// launch as soon as it has any request, so a chunk with few distinct keys makes EVERY key a comb
-// key (PV_ALLCOMB_*): tools/latency_probe.py on MI355X, 1,024 signers, device time per call --
-// 10k requests 0.77 ms all-comb vs 0.91 Straus, 32k 0.76 vs 0.95 (and 1.02 split at >= 48 requests
-// per key); bounded so the fill never exceeds 2,048 keys' tables (~0.5 ms).
-static constexpr uint64_t PV_KEYED_MIN = 4097;
-static constexpr uint32_t PV_ALLCOMB_KEYS = 2048;
-static constexpr uint32_t PV_ALLCOMB_CHUNK = 262144;
-static constexpr uint32_t PV_XT_KEYS = 2048;      // tables shared by a pipelined call's sub-batches (1.35 GB)
-static constexpr uint32_t PV_XT_HASH = 4096;      // their hash table (>= 2 x keys)
-static constexpr uint32_t PV_DIR_HASH = 2 * PV_KEY_CAP;  // hash words of the resident-table directory (KeyWork::dir_*)
-// Slots the directory lists by default: the rest of ctab is scratch for the tables of a chunk that lists
-// nothing (at most PV_SPARSE_CHUNK requests). Such a chunk has at most PV_ALLCOMB_KEYS comb keys under
-// AUTO (all-comb, or PV_SPARSE_CHUNK / PV_COMB_MIN_REQ of them, or keys whose tables exist already). Only
-// forced PV_PATH_COMB (every key a comb key) can bring more misses than fit, and then resets the directory.
-static constexpr uint32_t PV_DIR_DEFAULT_CAP = PV_KEY_CAP - PV_ALLCOMB_KEYS;
 // An all-comb chunk of at most PV_SPARSE_CHUNK requests and at most PV_SPARSE_PER_KEY requests per key
 // on average builds only the table entries its digits use (comb.h pv_comb_fill_sparse; the need
 // masks are set by pv_comb_prep_req_kernel). A/B on MI355X (1,024 signers, device time,
@@ -119,14 +84,6 @@ static constexpr uint32_t PV_DIR_DEFAULT_CAP = PV_KEY_CAP - PV_ALLCOMB_KEYS;
 #define PV_RANK_SUB 8
 #endif
 static_assert((PV_RANK_SUB & (PV_RANK_SUB - 1)) == 0, "PV_RANK_SUB must be a power of two");
-#ifndef PV_LATENCY_MAX
-#define PV_LATENCY_MAX 4096  // AUTO: batches up to this size take the latency path (pv_latency.hip)
-#endif
-// AUTO picks latency vs keyed by key repeats from this size up to PV_LATENCY_MAX (pv_keyed_hint on
-// the host, the dedup's lat_choice on the device)
-#ifndef PV_KEYED_HINT_MIN
-#define PV_KEYED_HINT_MIN 2049
-#endif
 
 // ---------------------------------------------------------------------------------------- device
 
@@ -212,16 +169,6 @@ struct DevATab {
 // Digit rows, one coalesced load each time a loop enters a new group of windows. Rows 0..7: |k1|
 // (Straus path, radix 16) or k (comb path, radix 256); rows 8..: the signed radix-2^W digits of k2 S
 // (Straus) or S (comb) for the wide fixed-base comb.
-// Radix of the wide fixed-base comb chosen at pv_init: PV_BC2_W (24: 10.7 GB of HBM) or, when that
-// allocation fails (or PV_FORCE_BCOMB16 is set), W = 16 over the radix-65536 comb T_B the latency
-// path already holds (the same layout and digits: comb.h). Kernels that recode or read S's digits
-// are instantiated for both.
-template <int W>
-struct Bc2 {
-    static constexpr int POS = (253 + W - 1) / W;
-    static constexpr uint32_t ENT = (1u << (W - 1)) + 1u;
-};
-static_assert(Bc2<16>::ENT == PV_BCOMB_ENT && Bc2<16>::POS == PV_BCOMB_POS, "W = 16 is the radix-65536 comb");
 // Straus path: rows PV_K2_ROW.. hold k2's radix-16 digits, row PV_NW_ROW the lane's window count
 static constexpr int PV_K2_ROW = 8 + (Bc2<16>::POS > PV_BC2_POS ? Bc2<16>::POS : PV_BC2_POS);
 static constexpr int PV_NW_ROW = PV_K2_ROW + 8;
@@ -237,205 +184,10 @@ struct DevDigits {
     __device__ __forceinline__ int fb(int j) const { return (int)d.ld(8 + j, slot); }
 };
 
-// Request bytes at an arbitrary byte offset: aligned dword loads + v_alignbyte_b32 funnel shifts.
-struct DevMsg {
-    const uint32_t* ap;  // rec rounded down to 4 bytes
-    uint32_t sh;         // rec & 3
-    __device__ __forceinline__ uint32_t dw(uint64_t i) const {
-        return __builtin_amdgcn_alignbyte(ap[i + 1], ap[i], sh);
-    }
-    // little-endian bytes [8q, 8q + 8) of the record
-    __device__ __forceinline__ uint64_t operator()(uint64_t q) const {
-        return ((uint64_t)dw(2 * q + 1) << 32) | dw(2 * q);
-    }
-};
-
-// Per-request intermediate state between the kernels (SoA, coalesced per wave):
-//   atab  [n / 64][18][64][10] uint4        Straus path: cached [j](+-A) and [j](-R'), j = 0..8 (DevATab)
-//   digits[PV_DIGIT_ROWS][n] uint32          see DevDigits
-//   flags [n] uint32                        1 = every libsodium pre-check passed
-//   q     [40][n] uint32                    projective Q = (X, Y, Z) from the msm kernel (rows 0..29);
-//                                           the comb path's [S]B half parks an extended point here
-struct Work {
-    uint4* atab;
-    uint32_t* digits;
-    uint32_t* flags;
-    uint32_t* q;
-    uint4* qb;        // not read by any kernel (kept: dropping it moves the kernel-argument layout)
-    uint64_t stride;  // chunk capacity (requests)
-    uint4* aos;       // per REQUEST comb-prep results, PrepAos<W>::Q uint4 each (pv_comb_prep_req_kernel)
-};
-
-// How a chunk's requests are split between the two arithmetic paths, decided ON THE DEVICE by the
-// dedup/sort kernels (no host round trip). split == nullptr: the Straus path was forced (or the
-// chunk is too small for dedup to pay) -- no key kernels ran and slot == request. Otherwise the
-// requests are in key-sorted slot order, the first split[PV_SPLIT_SLOTS] slots belong to keys
-// that take the comb path and the remaining slots take the Straus path (request = slot_req[slot]).
-static constexpr int PV_SPLIT_KEYS = 0;        // distinct keys in the chunk
-static constexpr int PV_SPLIT_COMB_KEYS = 1;   // keys given a comb table
-static constexpr int PV_SPLIT_SLOTS = 2;       // requests (slots) of those keys
-static constexpr int PV_SPLIT_SPARSE = 3;      // 1: the comb tables are filled sparsely (small chunk)
-static constexpr int PV_SPLIT_LAT = 4;         // 1: the dedup chose the latency path for this chunk
-static constexpr uint32_t PV_SPLIT_WORDS = 8;  // counters cleared per keyed chunk
-static constexpr uint32_t PV_NSEG = 8;         // key-id segments (pv_key_assign_kernel)
-// segment g's id counter: word PV_SEG_BASE + g * PV_SEG_STRIDE of the split buffer, one counter per
-// 1 KB so that the segments' atomics land on different memory channels (same-line counters
-// serialise like one)
-#ifndef PV_SEG_STRIDE
-#define PV_SEG_STRIDE 256
-#endif
-static constexpr uint32_t PV_SEG_BASE = 256;
-static constexpr uint32_t PV_SPLIT_ALLOC_WORDS = PV_SEG_BASE + PV_NSEG * PV_SEG_STRIDE;
-struct Gate {
-    const uint32_t* split;
-    const uint32_t* slot_req;
-    __device__ __forceinline__ bool keyed() const { return split != nullptr; }
-    // the dedup handed this chunk to the latency path (pv_key_scan_kernel, lat_choice): every
-    // kernel of the throughput paths exits at once, the unpermute kernel only cleans up
-    __device__ __forceinline__ bool off() const { return split != nullptr && split[PV_SPLIT_LAT] != 0u; }
-    // Straus-path kernels loop over 256-slot tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...;
-    // split, the tiles are taken from the END of the slot range (where the Straus slots are) and a
-    // small grid strides over them, so the first tile with no Straus slot ends the loop and no
-    // flood of empty workgroups competes with the comb kernels for CUs.
-    __device__ __forceinline__ uint32_t stile(uint32_t t, uint32_t ntiles) const { return split ? ntiles - 1 - t : t; }
-    __device__ __forceinline__ uint32_t ncomb() const { return split ? split[PV_SPLIT_SLOTS] : 0u; }
-    // request of a Straus-path slot
-    __device__ __forceinline__ uint32_t req(uint32_t i) const { return split ? slot_req[i] : i; }
-};
-
-// Keyed workspace (comb.h). The hash table maps a 32-byte key to the index of the first request
-// that carried it; slot_id gives the dense key id of an owned slot (ids < chunk size).
-//   slot     [H] u32   owner request index, PV_EMPTY = free
-//   slot_id  [H] u32   dense key id of an owned slot
-//   slot_cnt [PV_RANK_SUB][H]  requests carrying the key per sub-table (request workgroup mod
-//            PV_RANK_SUB); the assign kernel replaces each nonzero count by its offset in the key
-//   req_key  [stride]  the request's hash slot;         req_rank [stride] its rank in its sub-table
-//   nkeys    [3]       PV_SPLIT_* counters (see Gate)
-//   key_owner[stride]  a request carrying key id
-//   key_cid  [stride]  comb index of key id (PV_EMPTY: its requests take the Straus path)
-//   comb_key [kcap]    key id of comb index j;  key_flag [kcap]  libsodium key checks passed
-//   bases    [kcap][32][4][10] uint4 [256^i](-A) and its [16], [32], [64] multiples, extended
-//   ctab     [kcap][32][129][10] uint4  T_A, cached form
-//   key_cslot [stride] / comb_cslot [kcap]  node-side key cache slot of a key id / comb index: a key
-//            in the cache is a comb key whatever its request count, its T_A is the cache's table
-//            and the key stream (chain, fill) skips it
-//   comb_tslot [kcap]  slot of kw.ctab that holds (or will hold) the table of comb index j when it is
-//            not read from a cache: the allocator in pv_key_scan_kernel hands them out
-// Resident-table directory: the tables a dense chunk builds stay in ctab and are listed here, so a
-// later chunk that carries the same key reads its table instead of building it again. Nothing of it
-// lives on the host but an on/off flag, the capacity and a dirty bit.
-//   dir_htab [PV_DIR_HASH] open-addressing hash of listed slots (pv_kc_lookup with kw.seed: a hit
-//            compares the full 32-byte key), dir_keys [kcap][8], dir_flags [kcap]: bit 0 (PV_KF_OK) the
-//            libsodium key checks passed, bit 1 (PV_KF_AFF) the slot's rows are affine, bit 2 (PV_KF_HIT)
-//            a dense chunk has read the slot once already (both below)
-//   dir_cnt  [2]  count: slots [0, count) are listed, nothing above them is; and the count the
-//            chunk's publish kernel stores once its tables are built and listed
-//   dir_stat [5]  u64 hits, built, resets, tables converted to affine rows, tables read in affine form
-// Affine rows: a dense chunk (dir_pub) that hits a listed table whose key passed the checks marks the
-// slot PV_KF_HIT; the next dense chunk that hits it -- the table's second hit: converting 1,024 tables
-// costs as much as ten warm 1M-request chunks save, so a table that comes back once is left alone --
-// queues the slot in aff_list; pv_dir_affine_kernel converts those tables in place behind the chunk's comb kernels
-// (comb.h pv_comb_row_to_affine_inplace) and sets PV_KF_AFF, and every later chunk reads them in affine
-// form. The scan copies dir_flags into key_flag for a hit; key_flag of a key the chunk
-// builds comes from the chain kernel and has bit 0 only. PV_KF_AFF and PV_KF_HIT are cleared wherever a
-// slot is rebuilt, because a rebuilt slot is listed again only by pv_dir_publish_kernel, which stores bit 0
-// alone: after a reset by the scan, after dir_dirty emptied the directory (a control call, an enqueue
-// failure, a key-cache put that ran over the directory), and for the tables built above the count.
-//   aff_list [PV_AFF_CAP] slots queued by this chunk's scan;  aff_cnt [1] how many it queued (may exceed
-//            the cap: the rest wait for their next hit);  aff_scr  the conversion's parked Z2 products
-// A key takes the comb path when it carries >= min_req requests of the chunk (the per-key table
-// costs about as much as ~50 requests save; 1 when the comb path is forced) and fewer than kcap
-// keys came before it; the rest -- singletons such as the adversarial keys of config 3 -- take the
-// Straus path in the same launch.
-// Key-sorted processing order ("slots"): after dedup the requests of each key occupy a contiguous
-// range of slots, comb keys first, so consecutive lanes and waves read the same key's table rows
-// (L2-resident) instead of 1,024 keys' tables at random:
-//   key_count[stride], key_cursor[stride]  requests per key id, then the key's first slot
-//   slot_req [stride]                   slot -> request index;  req_pos [stride] request -> slot
-//   skey     [stride]                   slot -> comb index;     sverdict [stride / 64] slot verdicts
-struct KeyWork {
-    uint32_t* slot;
-    uint32_t* slot_id;
-    uint32_t* slot_cnt;
-    uint32_t* req_key;
-    uint32_t* req_rank;
-    uint32_t* nkeys;
-    uint32_t* key_owner;
-    uint32_t* key_cid;
-    uint32_t* comb_key;
-    uint32_t* key_flag;
-    uint4* bases;
-    uint4* ctab;
-    uint32_t* key_count;
-    uint32_t* key_cursor;
-    uint32_t* slot_req;
-    uint32_t* req_pos;
-    uint32_t* skey;
-    uint64_t* sverdict;
-    uint32_t* key_cslot;   // [stride] node-side key cache slot of key id (PV_EMPTY: not cached)
-    uint32_t* comb_cslot;  // [kcap] the same per comb index: its table is read from the cache
-    uint32_t* comb_tslot;  // [kcap] ctab slot of comb index j (a table this chunk builds, or a resident one)
-    uint32_t* dir_htab;    // the resident-table directory (above)
-    uint32_t* dir_keys;
-    uint32_t* dir_flags;
-    uint32_t* dir_cnt;
-    unsigned long long* dir_stat;
-    uint32_t* aff_list;    // affine-row conversion queue (above)
-    uint32_t* aff_cnt;
-    uint32_t* aff_scr;
-    uint32_t* need;        // [PV_ALLCOMB_KEYS][32][5] needed |digit| bits per (comb index, position)
-    const uint4* kc_tab;   // the cache's tables [cap][32][129][10] (keycache.h)
-    const uint4* kc_ntab;  // the same divided by Z [cap][32][129][10] (comb.h pv_comb_row_to_affine), or null
-    const uint4* kc_wtab;  // radix-65536 rows of slots < kc_wcap [kc_wcap][16][32897][8] (comb.h PV_KW_*), or null
-    uint32_t kc_wcap;
-    // a later sub-batch of a pipelined host call with a non-empty node cache: the keys the node cache
-    // misses are looked up in the call's shared store too; a hit there is slot | PV_CSLOT_XT
-    const uint32_t* xt_flags;
-    const uint4* xt_tab;
-    uint32_t hmask;
-    uint32_t kcap;
-    uint32_t seed;
-    uint32_t min_req;
-    uint32_t kc_on;    // this launch consults the key cache (pv_key_cache_probe_kernel ran)
-    uint32_t chunk_n;  // requests in this chunk
-    uint32_t lat_choice;  // the scan picks latency vs keyed for this chunk (AUTO, device-buffer call)
-    uint32_t seg_cap;     // key ids of segment s are s * seg_cap + [0, its counter)
-    uint32_t dense_only;  // never fill sparsely (the tables outlive the chunk: pv_xtab_publish_kernel)
-    uint32_t dir_on;      // this chunk goes through the directory (probe, slot allocator)
-    uint32_t dir_cap;     // slots the directory may list (<= kcap)
-    uint32_t dir_pub;     // a dense chunk: its tables are whole and pv_dir_publish_kernel lists them
-    uint32_t aff_conv;    // a dense chunk with pv_table_affine on: its scan queues hit tables for conversion
-};
-static constexpr uint32_t PV_KF_OK = 1u;   // key_flag / dir_flags: libsodium's key checks passed
-static constexpr uint32_t PV_KF_AFF = 2u;  // the table's rows are affine (a directory hit only)
-static constexpr uint32_t PV_KF_HIT = 4u;  // a dense chunk has hit the table before: its next dense hit converts it
-static constexpr uint32_t PV_AFF_CAP = 1024;  // tables one chunk converts (aff_scr: 165 KB each, 173 MB)
-static constexpr uint32_t PV_EMPTY = 0xFFFFFFFFu;
-static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call's shared store (KeyWork::xt_*)
-static constexpr uint32_t PV_CSLOT_DIR = 0x20000000u;  // slot of kw.ctab listed in the resident-table directory
-// a key id's / comb index's cslot names a table of the node cache or the call store (never a directory hit)
-__host__ __device__ __forceinline__ bool pv_cslot_cached(uint32_t cslot) {
-    return cslot != PV_EMPTY && !(cslot & PV_CSLOT_DIR);
-}
 #ifndef PV_COMB_MIN_REQ
 #define PV_COMB_MIN_REQ 48
 #endif
 
-// LDS-DMA staging of one table entry per lane (comb.h, the staged comb loops). An entry of Q uint4 is
-// fetched by Q global_load_lds_dwordx4, each writing 1 KiB = 16 B x 64 lanes of the wave's staging
-// area, laid out [q][lane] so that reading it back is one conflict-free ds_read_b128 per q.
-// pv_glds16_row: Q pieces of 16 B from g[0..Q) to l[q * 64 + lane] (a wave's [q][lane] staging area). The
-// instruction's immediate offset (16 q) applies to BOTH the global and the LDS address, so the LDS
-// base of piece q is moved back by the same 16 q bytes (M0 is set per instruction anyway): all Q
-// loads then share ONE 64-bit global address instead of Q 64-bit adds per staged entry.
-template <int Q, int q = 0>
-__device__ __forceinline__ void pv_glds16_row(const uint4* g, uint4* l) {
-    if constexpr (q < Q) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(l + q * 64 - q), 16, 16 * q, 0);
-        pv_glds16_row<Q, q + 1>(g, l);
-    }
-}
 // A 10-piece entry whose pieces 5 and 6 (words 20..27) are skipped on lanes with `skip` (affine comb rows:
 // their Z2 words are not read). Lanes that skip leave those pieces of their staging column stale.
 __device__ __forceinline__ void pv_glds16_row10_skip56(const uint4* g, uint4* l, bool skip) {
@@ -448,33 +200,6 @@ __device__ __forceinline__ void pv_glds16_row10_skip56(const uint4* g, uint4* l,
     }
     pv_glds16_row<10, 7>(g, l);
 }
-// the LDS reads of the previous staged entry must be complete before its buffer is refilled
-__device__ __forceinline__ void pv_lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// Wide fixed-base comb rows (comb.h PV_BC2_*): row j = entries 0..PV_BC2_ENT-1 of [d 2^(W j)] B,
-// 8 uint4 each, LDS-staged like DevCombStage; 64-bit entry index (the table is ~10.7 GB at W = 24).
-template <uint32_t ENT>
-struct DevB2Stage {
-    const uint4* base;
-    uint4* lds;
-    uint32_t lane;
-    __device__ __forceinline__ void stage(int j, int d) const {
-        const uint4* e = base + ((uint64_t)j * ENT + (uint32_t)d) * (PV_BCOMB_STRIDE / 4);
-        pv_lds_reads_done();
-        pv_glds16_row<PV_BCOMB_STRIDE / 4>(e, lds);
-    }
-    __device__ __forceinline__ void staged(int part, uint32_t w[20]) const {
-#pragma unroll
-        for (int q = 0; q < (part ? 3 : 5); q++) {
-            const uint4 v = lds[(5 * part + q) * 64 + lane];
-            const int lim = part ? 10 : 20;
-            if (4 * q < lim) w[4 * q] = v.x;
-            if (4 * q + 1 < lim) w[4 * q + 1] = v.y;
-            if (4 * q + 2 < lim) w[4 * q + 2] = v.z;
-            if (4 * q + 3 < lim) w[4 * q + 3] = v.w;
-        }
-    }
-};
 
 __device__ __forceinline__ void pv_load_pk(uint32_t A[8], const uint8_t* pk, uint32_t i) {
     const uint4* p4 = reinterpret_cast<const uint4*>(pk + 32 * (uint64_t)i);
@@ -1908,55 +1633,6 @@ struct DevEncSink {
         if (l == 0 && r0 < n) verdict[r0 >> 6] = bits;
     }
 };
-// The encode's one inversion per lane done by the whole wave: the 64 lanes' products are multiplied
-// pairwise across lanes (xor partners 32, 16, 8, 4, 2) down to two products, one per lane residue mod 2,
-// which are inverted at once in limb-parallel form (lp_invert<true>: rows 0, 1 the two products, repeated
-// in rows 2, 3, and five column terms per lane, a shorter dependent chain per product), and the inverses
-// walked back down the same tree (one product per level). Where every lane ran its own ~27k-instruction
-// exponentiation chain (the chain's latency was most of the kernel's time), the wave now runs ~265
-// limb-parallel products. Every lane of the wave must be active (pv_encode_kernel: all lanes run the batch).
-__device__ __forceinline__ void pv_shfl_xor_fe(fe& o, const fe& a, int m) {
-#pragma unroll
-    for (int k = 0; k < 10; k++) o.v[k] = __shfl_xor(a.v[k], m);
-}
-struct PvWaveInvert {
-    __device__ void operator()(fe& x) const {
-#if LP_DEVICE
-        constexpr int LV = 5;         // tree levels
-        constexpr uint32_t RES = 1u;  // lane residue a row's product covers
-        const uint32_t lane = threadIdx.x & 63u;
-        constexpr int M[5] = {32, 16, 8, 4, 2};
-        fe p[LV + 1], q;
-        p[0] = x;
-#pragma unroll
-        for (int i = 0; i < LV; i++) {
-            pv_shfl_xor_fe(q, p[i], M[i]);
-            fe_mul(p[i + 1], p[i], q);
-        }
-        const LpLane c = LpLane::make();
-        const int src = (int)((lane >> 4) & RES);
-        fe inv;
-        // row r (lanes 16 r + k) gets limb k of lane (r & RES)'s product
-        uint32_t z = 0;
-#pragma unroll
-        for (int k = 0; k < 10; k++) {
-            const uint32_t t = __shfl(p[LV].v[k], src);
-            z = (lane & 15u) == (uint32_t)k ? t : z;
-        }
-        const lu zi = lp_invert<true>(c, lu(z));
-#pragma unroll
-        for (int k = 0; k < 10; k++) inv.v[k] = __shfl(static_cast<uint32_t>(zi), (int)(16u * (lane & RES)) + k);
-#pragma unroll
-        for (int i = LV - 1; i >= 0; i--) {
-            pv_shfl_xor_fe(q, p[i], M[i]);
-            fe_mul(inv, inv, q);
-        }
-        x = inv;
-#else
-        fe_invert(x, x);
-#endif
-    }
-};
 
 template <int B>
 __global__ __launch_bounds__(PV_BLOCK, 2) void pv_encode_kernel(const uint8_t* __restrict__ sm,
@@ -1978,262 +1654,16 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_encode_kernel(const uint8_t* _
                                                         comb ? kw.slot_req : nullptr, w, l, n}, PvWaveInvert{});
 }
 
-// ---------------------------------------------------------------------------------------- signing
-// Batch Ed25519 signing (sign_core.h: the arithmetic, and why it is NOT side-channel hardened). One
-// lane per item, wave64; every lane of a wave stays active to the end (the LDS staging of the comb
-// entries and the wave-wide inversion need whole waves), a lane past the batch or with a bad signer
-// index repeats the last item's work and stores nothing / zeros.
-static constexpr uint64_t PV_SIGN_CHUNK = 262144;  // messages (or seeds) per launch
-
-__device__ __forceinline__ void pv_ld8(uint32_t o[8], const uint4* p) {
-    const uint4 a = p[0], b = p[1];
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-__device__ __forceinline__ void pv_st8(uint4* p, const uint32_t v[8], bool keep = true) {
-    p[0] = keep ? make_uint4(v[0], v[1], v[2], v[3]) : make_uint4(0, 0, 0, 0);
-    p[1] = keep ? make_uint4(v[4], v[5], v[6], v[7]) : make_uint4(0, 0, 0, 0);
-}
-
-// Per signer: key expansion of the seed at seeds[i * seed_q] (seed_q = 2: packed seeds; 4: the seed
-// half of 64-byte secret keys) to keys[4 i ..] = a mod L || prefix. With pk_out (the keypair entry,
-// kernel-uniform) also A = encode([a]B) to pk_out[2 i ..].
-template <int W>
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_sign_keys_kernel(const uint4* __restrict__ seeds, uint32_t seed_q,
-                                                                    uint64_t n, uint4* __restrict__ keys,
-                                                                    uint4* __restrict__ pk_out,
-                                                                    const uint4* __restrict__ bcomb) {
-    const uint64_t i0 = (uint64_t)blockIdx.x * PV_BLOCK + threadIdx.x;
-    const bool in = i0 < n;
-    const uint64_t i = in ? i0 : n - 1;
-    uint32_t seed[8], a[8], prefix[8];
-    pv_ld8(seed, seeds + i * seed_q);
-    pv_sign_expand(a, prefix, seed);
-    if (in) {
-        pv_st8(keys + 4 * i, a);
-        pv_st8(keys + 4 * i + 2, prefix);
-    }
-    if (!pk_out) return;
-    __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    ge_p3 acc;
-    pv_sign_base_mult<W, Bc2<W>::POS>(acc, a, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u});
-    uint32_t enc[8];
-    pv_sign_encode(enc, acc, in, PvWaveInvert{});
-    if (in) pv_st8(pk_out + 2 * i, enc);
-}
-
-// Per message r of a chunk: signer s = sidx ? sidx[r] : idx_base + r; nonce hash, [r]B from the wide
-// comb, R by the wave's shared inversion, second hash over the key bytes as given (sk[s][32:64]), S, and
-// the 64-byte signature as four uint4 stores. s >= n_signers: 64 zero bytes.
-template <int W>
-__global__ __launch_bounds__(PV_BLOCK, 2) void pv_sign_kernel(const uint8_t* __restrict__ msg,
-                                                               const uint64_t* __restrict__ off, uint64_t n,
-                                                               const uint4* __restrict__ sk,
-                                                               const uint4* __restrict__ keys, uint64_t n_signers,
-                                                               const uint32_t* __restrict__ sidx, uint64_t idx_base,
-                                                               uint4* __restrict__ sig_out,
-                                                               const uint4* __restrict__ bcomb) {
-    const uint32_t r0 = blockIdx.x * PV_BLOCK + threadIdx.x;
-    const bool in = r0 < n;
-    const uint32_t r = in ? r0 : (uint32_t)n - 1;  // whole waves stay in step
-    const uint64_t s0 = sidx ? (uint64_t)sidx[r] : idx_base + r;
-    const bool ok = in && s0 < n_signers;
-    const uint64_t s = s0 < n_signers ? s0 : 0;  // a lane without a signer works on signer 0, stores zeros
-    const uint64_t o0 = off[r], mlen = off[r + 1] - o0;
-    const uint64_t maddr = reinterpret_cast<uint64_t>(msg + o0);
-    const DevMsg mw{reinterpret_cast<const uint32_t*>(maddr & ~3ull), (uint32_t)(maddr & 3)};
-    uint32_t rr[8], hdr[16];
-    {
-        uint32_t prefix[8];
-        pv_ld8(prefix, keys + 4 * s + 2);
-        pv_hash_hm<4>(rr, prefix, mlen, mw);
-    }
-    {
-        __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
-        const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        ge_p3 acc;
-        pv_sign_base_mult<W, Bc2<W>::POS>(acc, rr, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u});
-        pv_sign_encode(hdr, acc, ok, PvWaveInvert{});
-    }
-    pv_ld8(hdr + 8, sk + 4 * s + 2);
-    uint32_t k[8], a[8], S[8];
-    pv_hash_hm<8>(k, hdr, mlen, mw);
-    pv_ld8(a, keys + 4 * s);
-    pv_sign_s(S, k, a, rr);
-    if (in) {
-        pv_st8(sig_out + 4 * (uint64_t)r, hdr, ok);
-        pv_st8(sig_out + 4 * (uint64_t)r + 2, S, ok);
-    }
-}
-
 // ------------------------------------------------------------------------------------------ host
 
-namespace {
-
-struct Ctx {
-    int device = -1;
-    int cus = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t kstream = nullptr;           // per-key pipeline (chain + table fill), overlapped
-    hipEvent_t ev_keys_ready = nullptr;      // dedup done (main -> Straus side stream)
-    hipEvent_t ev_scan_done = nullptr;       // comb keys chosen (main -> kstream, before the scatter)
-    hipEvent_t ev_tables_ready = nullptr;    // comb tables done (fstream -> main)
-    hipStream_t fstream = nullptr;           // table fill of a chunk that may fill sparsely
-    hipEvent_t ev_chain = nullptr;           // chain done (kstream -> fstream)
-    hipEvent_t ev_prep_done = nullptr;        // comb_prep done: need masks ready (main -> fstream)
-    hipStream_t sstream = nullptr;           // Straus-path slots of a split chunk, overlapped
-    hipEvent_t ev_straus_done = nullptr;     // their q / flags written (sstream -> main)
-    // Workspace hand-over between callers' streams (workspace.h): every launch ends by recording it on
-    // its stream, and a launch on a DIFFERENT stream first makes its stream wait for it.
-    PvHandover hand;
-    uint32_t* d_btab = nullptr;
-    Work work{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-    KeyWork kw{};
-    bool last_keyed = false;  // the most recent chunk ran the dedup / split kernels
-    bool slots_dirty = true;  // the key hash table / need masks may hold entries (cleared before use)
-    // resident-table directory (KeyWork::dir_*): on/off, the slots it may list, and whether it has to be
-    // emptied before the next keyed chunk (first use, a control call, an enqueue failure in a keyed chunk)
-    bool dir_on = true;
-    uint32_t dir_cap = PV_DIR_DEFAULT_CAP;
-    bool dir_dirty = true;
-    bool aff_on = true;  // dense chunks convert the resident tables they hit to affine rows (pv_table_affine)
-    bool last_latency = false;  // the most recent launch took the latency path
-    bool verdict_zeroed = false;  // the caller's verdict words are already 0 (pv_verify_batch)
-    bool keyed_hint = false;      // pv_verify_batch saw few distinct keys: keyed path below PV_LATENCY_MAX
-    bool hint_set = false;        // pv_verify_batch decided keyed_hint on the host (no device-side choice)
-    bool last_dev_choice = false; // the last launch let its dedup pick latency vs keyed
-    uint32_t last_split[3] = {0, 0, 0};  // PV_SPLIT_* of it, read back by pv_last_path
-    uint4* d_bcomb = nullptr;  // fixed-base comb T_B (radix 65536; latency path)
-    uint4* d_bc2 = nullptr;    // wide fixed-base comb T_B2 (radix 2^W; comb path's [S]B)
-    int bc2_w = PV_BC2_W;      // its radix: PV_BC2_W, or 16 when d_bc2 aliases d_bcomb (fallback)
-    uint32_t prep_lds_pad = PV_PREP_LDS_PAD;  // dynamic LDS per comb_prep workgroup (occupancy cap)
-    int path = PV_PATH_AUTO;
-    // host-entry staging
-    PvPinnedBuf h_stage;
-    PvDevBuf d_stage;
-    PvPinnedBuf h_ver;  // verdict words of the pipelined host-buffer form
-    // pipelined host-buffer form: H2D of sub-batch j on cstream, its kernels on `stream` after ev_copy[j]
-    hipStream_t cstream = nullptr;
-    hipEvent_t ev_cstart = nullptr;  // the engine stream's work so far (cstream waits: staging reuse)
-    std::vector<hipEvent_t> ev_copy;
-    int inject_stage = 0;  // pv_test_inject(PV_INJECT_STAGE): host-buffer stagings left to fail
-    // the comb tables one pipelined host call's sub-batches share (pv_xtab_publish_kernel): room for
-    // PV_XT_KEYS keys, allocated on first use; xt_fill: the next chunk builds its tables here and
-    // publishes them; xt_use: the next chunks look keys up here (as in the node-side key cache)
-    struct {
-        uint32_t* htab = nullptr;
-        uint32_t* keys = nullptr;
-        uint32_t* flags = nullptr;
-        uint4* tab = nullptr;
-        bool failed = false;  // allocation failed once: the call's sub-batches build their own tables
-    } xt;
-    bool xt_fill = false, xt_use = false;
-    bool timing = false;
-    // PV_NSTAGES + 1 events per chunk launched since pv_set_timing(1) (stage boundaries, see
-    // pv_stage_times); unused stages record back-to-back events
-    std::vector<hipEvent_t> ev;
-    int ev_used = 0;
-    ncclComm_t comm = nullptr;
-    int nranks = 1, rank = 0;
-    // node-side key cache (keycache.h): device arrays + host index (LRU, most recent first)
-    struct {
-        uint32_t cap = 0;
-        uint32_t* d_htab = nullptr;
-        uint32_t* d_keys = nullptr;
-        uint32_t* d_flags = nullptr;
-        uint4* d_tab = nullptr;
-        uint4* d_ntab = nullptr;      // the tables with every entry divided by its Z (comb path), or null
-        uint4* d_wtab = nullptr;      // radix-65536 niels rows of slots < wcap (comb.h PV_KW_*), or null
-        uint32_t wcap = 0;
-        uint32_t* d_wscr = nullptr;   // Z products of one group of wide-row builds
-        uint8_t* d_put_pk = nullptr;  // keys of one put batch
-        uint32_t* d_put_slot = nullptr;
-        uint32_t hmask = 0, seed = 0;
-        bool enabled = true;  // consulted by the latency path
-        std::unordered_map<std::string, std::list<uint32_t>::iterator> index;  // key bytes -> LRU node
-        std::list<uint32_t> lru;                                                 // slots, most recent first
-        std::vector<std::string> slot_key;
-        std::vector<uint32_t> free_slots;
-        bool broken = false;  // a failed hash-table upload left the device table stale: not consulted
-        // automatic admission (pv_key_cache_auto): a key is put on its auto_min-th VERIFIED appearance
-        // in pv_verify_batch calls (every request of calls of <= PV_KC_AUTO_MAX_BATCH requests, a
-        // sample of larger ones). Appearances are counted in a SipHash-keyed table of full keys with
-        // bounded probing (kc_admit.h); an evicted key is forgotten there, so it can be re-admitted
-        uint32_t auto_min = 0;
-        pvhost::AdmitTable seen;
-        uint64_t auto_admitted = 0, auto_failed = 0;
-        // LRU refresh on use: every launch that consults the cache stamps the slots it reads with its
-        // epoch (d_stamp, pv_kc_lookup); before a put evicts, the slots stamped since the last fold
-        // move to the front of the host LRU (kc_fold_hits)
-        uint32_t* d_stamp = nullptr;
-        uint32_t epoch = 1, fold_epoch = 1;
-        // pinned staging of an asynchronous put (keys, slots, hash table), reused once ev_async is done
-        uint8_t* h_async = nullptr;
-        uint64_t h_async_cap = 0;
-        hipEvent_t ev_async = nullptr;
-        bool async_pending = false;
-    } kc;
-    // zero-copy verdict bytes (pinned, coherent: the host reads them while the kernel runs)
-    uint8_t* h_zc_verdict = nullptr;
-    bool last_zero_copy = false;  // the most recent pv_verify_batch took the zero-copy form
-    // pv_verify_batch_multi_gpu: this device's gathered verdict words (device) and their host copy
-    PvDevBuf d_mg;
-    PvPinnedBuf h_mg;
-    const uint32_t* last_nkeys = nullptr;  // split counters of the most recent keyed chunk
-    // Signing workspace (pv_sign_*), its own: the expanded keys (a mod L || prefix, 64 B per signer), the
-    // host entries' copies of the secret keys / seeds (pinned and device) and their chunk staging. Handed
-    // over between callers' streams like the verification workspace. The secret parts are overwritten
-    // before a call returns (device entry: behind its kernels, on its stream).
-    struct {
-        PvDevBuf d_keys;
-        PvDevBuf d_sk;
-        PvPinnedBuf h_sk;
-        PvDevBuf d_stage;
-        PvPinnedBuf h_stage;
-        PvHandover hand;
-    } sg;
-};
-
-// One context per device. The single-device ABI (pv_init, pv_verify_batch, ...) works on the device
-// pv_init bound (the primary); pv_init_devices adds contexts for more devices of the same process,
-// which pv_verify_batch_multi_gpu drives from one worker thread per device. g_ctx / g_mu name the
-// calling thread's context: a multi-GPU worker's device (t_dev), else the primary.
-constexpr int PV_MAX_DEV = 16;
+// The device contexts and the calling thread's error string (pv_ctx.h).
 Ctx g_ctxs[PV_MAX_DEV];
 std::mutex g_mus[PV_MAX_DEV];
 std::atomic<int> g_primary{-1};
 thread_local int t_dev = -1;
-inline int pv_cur_dev() {
-    if (t_dev >= 0) return t_dev;
-    const int p = g_primary.load(std::memory_order_acquire);
-    return p >= 0 ? p : 0;
-}
-#define g_ctx (g_ctxs[pv_cur_dev()])
-#define g_mu (g_mus[pv_cur_dev()])
-// Makes `dev` the calling thread's context for the scope (multi-GPU workers, per-device init).
-struct DevScope {
-    int prev;
-    explicit DevScope(int dev) : prev(t_dev) { t_dev = dev; }
-    ~DevScope() { t_dev = prev; }
-};
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-PvKeyCacheView kc_view() {
-    auto& k = g_ctx.kc;
-    PvKeyCacheView v{k.d_htab, k.d_keys, k.d_flags, k.d_tab, 0u, k.seed, k.d_wtab, k.wcap};
-    if (k.enabled && !k.broken && k.cap > 0 && !k.index.empty()) {
-        v.hmask = k.hmask;
-        v.stamp = k.d_stamp;
-        v.epoch = ++k.epoch;
-    }
-    return v;
-}
+namespace {
 
 void kc_free() {
     auto& k = g_ctx.kc;
@@ -2284,14 +1714,6 @@ int kc_upload_htab(hipStream_t s, uint32_t* hbuf = nullptr) {
     return PV_OK;
 }
 
-int kc_auto_after_batch(const uint8_t* pk, uint64_t n, hipStream_t s, const uint8_t* vb, const uint64_t* hver);
-
-int ensure_stage(uint64_t host_bytes, uint64_t dev_bytes) {
-    if (host_bytes)
-        if (int rc = g_ctx.h_stage.grow(std::max<uint64_t>(host_bytes, 1 << 20), hipHostMallocPortable)) return rc;
-    return dev_bytes ? g_ctx.d_stage.grow(std::max<uint64_t>(dev_bytes, 1 << 20)) : PV_OK;
-}
-
 int ensure_events(int count) {
     while ((int)g_ctx.ev.size() < count) {
         hipEvent_t e;
@@ -2299,66 +1721,6 @@ int ensure_events(int count) {
         g_ctx.ev.push_back(e);
     }
     return PV_OK;
-}
-
-int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
-                  hipStream_t stream);
-
-int lane_alloc_buffers(Work& w, KeyWork& kw);
-void lane_free_buffers(Work& w, KeyWork& kw);
-
-int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, const uint8_t* d_pk,
-                 uint64_t* d_verdict, hipStream_t stream, bool latency, bool dev_choice, int evb);
-
-// A kernel instantiated per wide-comb radix (Bc2<W>), launched for the radix pv_init chose.
-#define PV_LAUNCH_BC2(k, ...)                                                                      \
-    do {                                                                                           \
-        if (g_ctx.bc2_w == 16) hipLaunchKernelGGL(k<16>, __VA_ARGS__);                             \
-        else hipLaunchKernelGGL(k<PV_BC2_W>, __VA_ARGS__);                                          \
-    } while (0)
-
-// One batch on `stream` (caller holds g_mu). Chunks of at most work.stride requests (a multiple of
-// 64, so verdict words never straddle).
-int launch(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
-           hipStream_t stream) {
-    if (n == 0) return PV_OK;
-    int rc = g_ctx.hand.begin(stream);
-    if (rc) return rc;
-    rc = launch_chunks(d_sm, d_off, n, d_pk, d_verdict, stream);
-    // recorded even after a failed enqueue: whatever did get enqueued is covered
-    if (int rc2 = g_ctx.hand.end(stream)) return rc2;
-    return rc;
-}
-
-int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
-                  hipStream_t stream) {
-    const uint64_t cap = g_ctx.work.stride;
-    const int nchunks = (int)((n + cap - 1) / cap);
-    constexpr int NE = PV_NSTAGES + 1;
-    // small batches: one wave pair per request (pv_latency.hip); forced LATENCY takes it at any size.
-    // Between PV_KEYED_HINT_MIN and PV_LATENCY_MAX requests AUTO picks by key repeats: the host-buffer
-    // call counted the keys (keyed_hint, hint_set); a device-buffer call lets the dedup kernels count
-    // them and decide on the device (dev_choice: the keyed kernels exit at once and the latency kernel
-    // runs when the scan picks latency; no host round trip). A non-empty key cache keeps the latency
-    // path there (cached keys make it faster still).
-    const bool kc_nonempty = kc_view().hmask != 0;
-    const bool dev_choice = g_ctx.path == PV_PATH_AUTO && !g_ctx.hint_set && !kc_nonempty &&
-                            n >= PV_KEYED_HINT_MIN && n <= PV_LATENCY_MAX;
-    const bool latency = g_ctx.path == PV_PATH_LATENCY ||
-                         (g_ctx.path == PV_PATH_AUTO && n <= PV_LATENCY_MAX && !g_ctx.keyed_hint && !dev_choice);
-    g_ctx.last_latency = latency;
-    g_ctx.last_dev_choice = dev_choice;
-    int evb = 0;
-    if (g_ctx.timing) {
-        evb = g_ctx.ev_used;
-        int rc = ensure_events(evb + NE * nchunks);
-        if (rc) return rc;
-        g_ctx.ev_used = evb + NE * nchunks;
-    }
-    int rc = PV_OK;
-    for (int c = 0; c < nchunks && rc == PV_OK; c++)
-        rc = launch_chunk(c, n, d_sm, d_off, d_pk, d_verdict, stream, latency, dev_choice, evb);
-    return rc;
 }
 
 // Chunk c of the batch on `stream` (the workspace is the context's; key / fill / side streams join it).
@@ -2473,34 +1835,28 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
             if (PV_KEY_SEED > 0 && m > 16ull * PV_KEY_SEED) {  // small chunks: no contention worth a launch
                 const uint64_t ms = std::min<uint64_t>(m, PV_KEY_SEED);
-                hipLaunchKernelGGL(pv_key_seed_kernel, dim3((unsigned)((ms + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0,
-                                   stream, d_pk + 32 * c0, ms, kw);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                PV_LAUNCH(pv_key_seed_kernel, dim3((unsigned)((ms + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0,
+                          stream, d_pk + 32 * c0, ms, kw);
             }
-            hipLaunchKernelGGL(pv_key_insert_lds_kernel, dim3((unsigned)((m + PV_INS_REQS - 1) / PV_INS_REQS)),
-                               dim3(PV_INS_THREADS), 0, stream, d_pk + 32 * c0, m, kw);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-            hipLaunchKernelGGL(pv_key_assign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_key_insert_lds_kernel, dim3((unsigned)((m + PV_INS_REQS - 1) / PV_INS_REQS)),
+                      dim3(PV_INS_THREADS), 0, stream, d_pk + 32 * c0, m, kw);
+            PV_LAUNCH(pv_key_assign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
             if (kc_active || dir_use) {
                 PvKeyCacheView dirv{kw.dir_htab, kw.dir_keys, kw.dir_flags, kw.ctab, dir_use ? PV_DIR_HASH - 1 : 0u,
                                     kw.seed};
-                hipLaunchKernelGGL(pv_key_cache_probe_kernel, dim3((PV_NSEG * kw.seg_cap + PV_BLOCK - 1) / PV_BLOCK),
-                                   dim3(PV_BLOCK), 0, stream, d_pk + 32 * c0,
-                                   kw, kcv, xtv, dirv);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                PV_LAUNCH(pv_key_cache_probe_kernel, dim3((PV_NSEG * kw.seg_cap + PV_BLOCK - 1) / PV_BLOCK),
+                          dim3(PV_BLOCK), 0, stream, d_pk + 32 * c0,
+                          kw, kcv, xtv, dirv);
             }
             gate = Gate{kw.nkeys, kw.slot_req};
             // key-sorted slot order: comb keys' requests first, then the Straus requests
-            hipLaunchKernelGGL(pv_key_scan_kernel, dim3(1), dim3(PV_SCAN_THREADS), 0, stream, kw, kc_flags);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_key_scan_kernel, dim3(1), dim3(PV_SCAN_THREADS), 0, stream, kw, kc_flags);
             // the per-key chain (few, long-latency lanes) and the table fill run on kstream, overlapped
             // with the scatter and the per-request prep on the main stream: the chain needs only the
             // scan's comb-key list (comb_key, comb_cslot), so kstream forks before the scatter
             PV_HIP(hipEventRecord(g_ctx.ev_scan_done, stream), PV_ERR_LAUNCH);
             PV_HIP(hipStreamWaitEvent(g_ctx.kstream, g_ctx.ev_scan_done, 0), PV_ERR_LAUNCH);
-            hipLaunchKernelGGL(pv_key_scatter_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_key_scatter_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
             PV_HIP(hipEventRecord(g_ctx.ev_keys_ready, stream), PV_ERR_LAUNCH);
             // one chain launch over all positions, then the fill. direct_fill: back to back on kstream
             // and the tables-ready event right after the fill (no event hop to fstream, no gated
@@ -2509,15 +1865,13 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             const uint64_t items = (uint64_t)limit * PV_COMB_POS * PV_COMB_BLOCKS;
             const unsigned fgrid = (unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096);
             hipStream_t fs = direct_fill ? g_ctx.kstream : g_ctx.fstream;
-            hipLaunchKernelGGL(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64), 0,
-                               g_ctx.kstream, d_pk + 32 * c0, kw, gate, 0, PV_COMB_POS);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64), 0,
+                      g_ctx.kstream, d_pk + 32 * c0, kw, gate, 0, PV_COMB_POS);
             if (!direct_fill) {
                 PV_HIP(hipEventRecord(g_ctx.ev_chain, g_ctx.kstream), PV_ERR_LAUNCH);
                 PV_HIP(hipStreamWaitEvent(fs, g_ctx.ev_chain, 0), PV_ERR_LAUNCH);
             }
-            hipLaunchKernelGGL(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, fs, kw, gate, 0, PV_COMB_POS);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, fs, kw, gate, 0, PV_COMB_POS);
             if (direct_fill) PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.kstream), PV_ERR_LAUNCH);
         }
         if ((rc = mark(PV_STAGE_PREP))) return rc;
@@ -2536,38 +1890,30 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             PV_HIP(hipStreamWaitEvent(ss, g_ctx.ev_keys_ready, 0), PV_ERR_LAUNCH);
             PV_LAUNCH_BC2(pv_prep_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m,
                                d_pk + 32 * c0, g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             PV_LAUNCH_BC2(pv_split_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-            hipLaunchKernelGGL(pv_table_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, d_pk + 32 * c0,
-                               g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_table_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, d_pk + 32 * c0,
+                      g_ctx.work, gate);
             PV_LAUNCH_BC2(pv_msm_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.d_btab,
                           g_ctx.work, g_ctx.d_bc2, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             PV_HIP(hipEventRecord(g_ctx.ev_straus_done, ss), PV_ERR_LAUNCH);
             PV_LAUNCH_BC2(pv_comb_prep_req_kernel, dim3(grid), dim3(PV_BLOCK), g_ctx.prep_lds_pad, stream, d_sm,
                           d_off + c0, m, d_pk + 32 * c0, g_ctx.work, kw, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             if (!direct_fill) {
                 // a small chunk's sparse table fill (needs the chain's bases and the need masks comb_prep
                 // writes) runs on fstream after the full fill; for a large chunk it exits at once
                 PV_HIP(hipEventRecord(g_ctx.ev_prep_done, stream), PV_ERR_LAUNCH);
                 PV_HIP(hipStreamWaitEvent(g_ctx.fstream, g_ctx.ev_prep_done, 0), PV_ERR_LAUNCH);
-                hipLaunchKernelGGL(pv_key_fill_sparse_kernel, dim3(PV_ALLCOMB_KEYS * PV_COMB_POS / PV_BLOCK),
-                                   dim3(PV_BLOCK), 0, g_ctx.fstream, kw, gate);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                PV_LAUNCH(pv_key_fill_sparse_kernel, dim3(PV_ALLCOMB_KEYS * PV_COMB_POS / PV_BLOCK),
+                          dim3(PV_BLOCK), 0, g_ctx.fstream, kw, gate);
                 PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.fstream), PV_ERR_LAUNCH);
             }
             // the per-request results to slot-ordered rows, while the key stream finishes the tables
             PV_LAUNCH_BC2(pv_comb_digits_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, g_ctx.work, kw, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             if ((rc = mark(PV_STAGE_TABLE))) return rc;
             const bool fused = m > PV_FUSED_MIN_REQ;
             if (!fused) {  // [S]B while the key stream finishes the tables, then join
                 PV_LAUNCH_BC2(pv_comb_b_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
                               gate);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             }
             PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_tables_ready, 0), PV_ERR_LAUNCH);
             if ((rc = mark(PV_STAGE_MSM))) return rc;
@@ -2575,55 +1921,45 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                 PV_LAUNCH_BC2(pv_comb_ab_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
                               gate);
             else
-                hipLaunchKernelGGL(pv_comb_a_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                PV_LAUNCH(pv_comb_a_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, gate);
             PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_straus_done, 0), PV_ERR_LAUNCH);
         } else {
             PV_LAUNCH_BC2(pv_prep_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
                                d_pk + 32 * c0, g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             PV_LAUNCH_BC2(pv_split_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
             if ((rc = mark(PV_STAGE_TABLE))) return rc;
-            hipLaunchKernelGGL(pv_table_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, d_pk + 32 * c0,
-                               g_ctx.work, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_table_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, d_pk + 32 * c0,
+                      g_ctx.work, gate);
             if ((rc = mark(PV_STAGE_MSM))) return rc;
             PV_LAUNCH_BC2(pv_msm_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.d_btab,
                           g_ctx.work, g_ctx.d_bc2, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
         }
         if ((rc = mark(PV_STAGE_ENCODE))) return rc;
         if (m >= PV_ENC16_MIN) {
             const unsigned egrid = (unsigned)((m + PV_BLOCK * 16 - 1) / (PV_BLOCK * 16));
-            hipLaunchKernelGGL(pv_encode_kernel<16>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
-                           g_ctx.work, d_verdict + c0 / 64, kw, gate);
+            PV_LAUNCH(pv_encode_kernel<16>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
+                      g_ctx.work, d_verdict + c0 / 64, kw, gate);
         } else {
             const unsigned egrid = (unsigned)((m + PV_BLOCK * PV_ENC_SMALL_B - 1) / (PV_BLOCK * PV_ENC_SMALL_B));
-            hipLaunchKernelGGL(pv_encode_kernel<PV_ENC_SMALL_B>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
-                           g_ctx.work, d_verdict + c0 / 64, kw, gate);
+            PV_LAUNCH(pv_encode_kernel<PV_ENC_SMALL_B>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
+                      g_ctx.work, d_verdict + c0 / 64, kw, gate);
         }
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
         if (keyed) {
-            hipLaunchKernelGGL(pv_unpermute_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw,
-                               d_verdict + c0 / 64, gate);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_unpermute_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw,
+                      d_verdict + c0 / 64, gate);
             g_ctx.slots_dirty = false;
             if (g_ctx.xt_fill) {  // publish this chunk's tables for the call's later sub-batches
-                hipLaunchKernelGGL(pv_xtab_publish_kernel, dim3(PV_XT_KEYS / PV_BLOCK), dim3(PV_BLOCK), 0, stream,
-                                   d_pk + 32 * c0, kw, g_ctx.xt.htab, PV_XT_HASH - 1, g_ctx.kw.seed, g_ctx.xt.keys,
-                                   g_ctx.xt.flags);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                PV_LAUNCH(pv_xtab_publish_kernel, dim3(PV_XT_KEYS / PV_BLOCK), dim3(PV_BLOCK), 0, stream,
+                          d_pk + 32 * c0, kw, g_ctx.xt.htab, PV_XT_HASH - 1, g_ctx.kw.seed, g_ctx.xt.keys,
+                          g_ctx.xt.flags);
             }
             if (dir_use) {
                 if (kw.dir_pub) {  // list this chunk's tables for the chunks and calls that follow
-                    hipLaunchKernelGGL(pv_dir_publish_kernel, dim3((limit + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0,
-                                       stream, d_pk + 32 * c0, kw);
-                    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                    PV_LAUNCH(pv_dir_publish_kernel, dim3((limit + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0,
+                              stream, d_pk + 32 * c0, kw);
                 }
                 if (kw.aff_conv) {  // the listed tables this chunk hit: affine rows for the chunks that follow
-                    hipLaunchKernelGGL(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
-                    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+                    PV_LAUNCH(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
                 }
                 g_ctx.dir_dirty = false;
             }
@@ -2638,34 +1974,35 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
     return PV_OK;
 }
 
-}  // namespace
-
-hipStream_t pv_engine_stream() { return g_ctx.stream; }
-int pv_fail(int code, const std::string& msg) { return fail(code, msg); }
-
-extern "C" {
-
-int pv_abi_version(void) { return PV_ABI_VERSION; }
-uint32_t pv_build_flags(void) { return PV_BUILD_COMB_FUSED; }
-
-int pv_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-const char* pv_last_error(void) { return g_err.c_str(); }
-
-}  // extern "C"
-
-namespace {
-int check_device_index(int device, const char* who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(PV_ERR_NO_DEVICE, std::string(who) + ": no HIP device visible");
-    if (device < 0 || device >= ndev || device >= PV_MAX_DEV)
-        return fail(PV_ERR_ARG, std::string(who) + ": device index out of range");
-    return PV_OK;
+int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
+                  hipStream_t stream) {
+    const uint64_t cap = g_ctx.work.stride;
+    const int nchunks = (int)((n + cap - 1) / cap);
+    constexpr int NE = PV_NSTAGES + 1;
+    // small batches: one wave pair per request (pv_latency.hip); forced LATENCY takes it at any size.
+    // Between PV_KEYED_HINT_MIN and PV_LATENCY_MAX requests AUTO picks by key repeats: the host-buffer
+    // call counted the keys (keyed_hint, hint_set); a device-buffer call lets the dedup kernels count
+    // them and decide on the device (dev_choice: the keyed kernels exit at once and the latency kernel
+    // runs when the scan picks latency; no host round trip). A non-empty key cache keeps the latency
+    // path there (cached keys make it faster still).
+    const bool kc_nonempty = kc_view().hmask != 0;
+    const bool dev_choice = g_ctx.path == PV_PATH_AUTO && !g_ctx.hint_set && !kc_nonempty &&
+                            n >= PV_KEYED_HINT_MIN && n <= PV_LATENCY_MAX;
+    const bool latency = g_ctx.path == PV_PATH_LATENCY ||
+                         (g_ctx.path == PV_PATH_AUTO && n <= PV_LATENCY_MAX && !g_ctx.keyed_hint && !dev_choice);
+    g_ctx.last_latency = latency;
+    g_ctx.last_dev_choice = dev_choice;
+    int evb = 0;
+    if (g_ctx.timing) {
+        evb = g_ctx.ev_used;
+        int rc = ensure_events(evb + NE * nchunks);
+        if (rc) return rc;
+        g_ctx.ev_used = evb + NE * nchunks;
+    }
+    int rc = PV_OK;
+    for (int c = 0; c < nchunks && rc == PV_OK; c++)
+        rc = launch_chunk(c, n, d_sm, d_off, d_pk, d_verdict, stream, latency, dev_choice, evb);
+    return rc;
 }
 
 // The per-lane workspace: per-request rows (Work) and the keyed path's tables (KeyWork), ~15 GB.
@@ -2733,7 +2070,6 @@ void lane_free_buffers(Work& w, KeyWork& kw) {
     kw = KeyWork{};
 }
 
-void ctx_free();
 // Builds g_ctxs[device] (caller: g_mus[device] held, DevScope(device) active, context not built yet):
 // streams and events, the fixed-base tables, the workspace. Sets the calling thread's HIP device.
 bool env_flag_devscope() {
@@ -2860,20 +2196,6 @@ int ctx_init_parts(int device) {
     return PV_OK;
 }
 
-// ctx_init_parts, and on failure everything it had built is released (streams, events, the workspace,
-// the tables): a retry of pv_init / pv_init_devices starts from an empty context instead of allocating
-// ~25 GB on top of a half-built one.
-int ctx_init(int device) {
-    const int rc = ctx_init_parts(device);
-    if (rc != PV_OK) {
-        const std::string err = g_err;
-        g_ctx.device = device;  // ctx_free releases a context of a known device
-        ctx_free();
-        g_err = err;
-    }
-    return rc;
-}
-
 // Frees g_ctxs[t_dev or primary] (caller holds its mutex).
 void ctx_free() {
     if (g_ctx.device < 0) return;
@@ -2915,24 +2237,263 @@ void ctx_free() {
     g_ctx = Ctx();
 }
 
-// In-process multi-GPU state (pv_init_devices): the devices in mask order and one RCCL communicator
-// per device from ncclCommInitAll (a single-process clique).
-struct MultiGpu {
-    std::vector<int> devs;
-    std::vector<ncclComm_t> comms;
-};
-MultiGpu g_mg;
-std::mutex g_mg_mu;
-
-void mg_destroy_comms() {
-    for (ncclComm_t c : g_mg.comms)
-        if (c) ncclCommDestroy(c);
-    g_mg.comms.clear();
-    g_mg.devs.clear();
+// Builds the fresh keys' tables (slot PV_KC_EMPTY = evicted again within the same put) into their
+// cache slots, in batches of the workspace's comb capacity. async: one batch only (the caller caps
+// the keys), staged through the pinned h_async area and left running on the engine stream (the
+// next launch is stream-ordered after it). PV_TEST_FAIL_KC_PUT_BATCH=b (tests only) reports a
+// failure after batch b has been enqueued, to exercise the rollback.
+static int kc_build_tables(const std::vector<std::string>& fresh, const std::vector<uint32_t>& fresh_slot,
+                           bool async) {
+    auto& k = g_ctx.kc;
+    hipStream_t s = g_ctx.stream;
+    if (int rc = g_ctx.hand.begin(s)) return rc;
+    const char* fail_env = getenv("PV_TEST_FAIL_KC_PUT_BATCH");
+    const long fail_batch = fail_env ? atol(fail_env) : -1;
+    KeyWork kw = g_ctx.kw;
+    // the put builds comb index j's table in slot j of a scratch area: the part of ctab above the slots
+    // the resident-table directory may list when the batch fits there, else over the directory
+    constexpr uint64_t tab_q = (uint64_t)PV_COMB_POS * PV_COMB_ENT * 10;  // uint4 per table
+    uint4* const scratch_tab = g_ctx.kw.ctab + g_ctx.dir_cap * tab_q;
+    const uint32_t scratch_keys = kw.kcap - g_ctx.dir_cap;
+    std::vector<uint8_t> lpk;
+    std::vector<uint32_t> lslot;
+    long batch = 0;
+    for (size_t f0 = 0; f0 < fresh.size();) {
+        uint8_t* bpk;
+        uint32_t* bslot;
+        if (async) {  // pinned: keys [kcap][32], then slots [kcap]
+            bpk = k.h_async;
+            bslot = reinterpret_cast<uint32_t*>(k.h_async + (uint64_t)kw.kcap * 32);
+        } else {
+            lpk.resize((uint64_t)kw.kcap * 32);
+            lslot.resize(kw.kcap);
+            bpk = lpk.data();
+            bslot = lslot.data();
+        }
+        uint32_t m = 0;
+        size_t f = f0;
+        for (; f < fresh.size() && m < kw.kcap; f++) {
+            if (fresh_slot[f] == PV_KC_EMPTY) continue;
+            memcpy(bpk + 32ull * m, fresh[f].data(), 32);
+            bslot[m++] = fresh_slot[f];
+        }
+        f0 = f;
+        if (m == 0) continue;
+        if (async && f0 < fresh.size()) return fail(PV_ERR_ARG, "kc_build_tables: asynchronous put above one batch");
+        if (g_ctx.dir_on && m <= scratch_keys) {
+            kw.ctab = scratch_tab;
+        } else {
+            kw.ctab = g_ctx.kw.ctab;
+            g_ctx.dir_dirty = true;
+        }
+        PV_HIP(hipMemcpyAsync(k.d_put_pk, bpk, 32ull * m, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+        PV_HIP(hipMemcpyAsync(k.d_put_slot, bslot, (uint64_t)m * 4, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_kc_put_prep_kernel, dim3((m + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0, s, kw, m);
+        const Gate gate{kw.nkeys, kw.slot_req};
+        PV_LAUNCH(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(m, PV_LP_CHAIN_BLOCKS)), dim3(64), 0, s,
+                  k.d_put_pk, kw, gate, 0, PV_COMB_POS);
+        const uint64_t items = (uint64_t)m * PV_COMB_POS * PV_COMB_BLOCKS;
+        PV_LAUNCH(pv_key_fill_kernel, dim3((unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096)),
+                  dim3(PV_BLOCK), 0, s, kw, gate, 0, PV_COMB_POS);
+        PV_LAUNCH(pv_kc_scatter_kernel, dim3(64, m), dim3(PV_BLOCK), 0, s, kw.ctab, kw.key_flag, k.d_put_pk,
+                  k.d_put_slot, m, k.d_tab, k.d_flags, k.d_keys);
+        if (k.d_ntab) {
+            PV_LAUNCH(pv_kc_affine_kernel, dim3((m * PV_COMB_POS + 63) / 64), dim3(64), 0, s, k.d_tab,
+                      k.d_put_slot, m, k.d_ntab);
+        }
+        if (k.d_wtab) {
+            bool any = false;
+            for (uint32_t j = 0; j < m && !any; j++) any = bslot[j] < k.wcap;
+            for (uint32_t j0 = 0; any && j0 < m; j0 += PV_KW_GROUP) {
+                const uint32_t g = std::min<uint32_t>(PV_KW_GROUP, m - j0);
+                const uint64_t threads = (uint64_t)g * PV_KW_POS * PV_KW_RUNS;
+                PV_LAUNCH(pv_kc_wide_kernel, dim3((unsigned)((threads + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK),
+                          0, s, kw, k.d_put_slot, j0, g, k.wcap, k.d_wtab, k.d_wscr);
+            }
+        }
+        if (!async) PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);  // bpk / bslot are host locals
+        if (batch++ == fail_batch) return fail(PV_ERR_LAUNCH, "pv_key_cache_put: injected failure (PV_TEST_FAIL_KC_PUT_BATCH)");
+    }
+    return PV_OK;
 }
+
+// LRU refresh on use: the slots that launches read since the last fold (d_stamp newer than
+// fold_epoch) move to the front of the LRU, least recently read first, so eviction takes the least
+// recently USED keys rather than the least recently put. Launches still running on other streams are
+// folded at the next eviction.
+static int kc_fold_hits() {
+    auto& k = g_ctx.kc;
+    if (!k.d_stamp || k.cap == 0) return PV_OK;
+    std::vector<uint32_t> st(k.cap);
+    PV_HIP(hipMemcpyAsync(st.data(), k.d_stamp, (uint64_t)k.cap * 4, hipMemcpyDeviceToHost, g_ctx.stream), PV_ERR_LAUNCH);
+    PV_HIP(hipStreamSynchronize(g_ctx.stream), PV_ERR_LAUNCH);
+    std::vector<std::pair<uint32_t, uint32_t>> used;  // (age of the stamp past the fold, slot), LRU order
+    for (auto it = k.lru.rbegin(); it != k.lru.rend(); ++it) {
+        const uint32_t age = st[*it] - k.fold_epoch;
+        if ((int32_t)age > 0) used.emplace_back(age, *it);
+    }
+    std::stable_sort(used.begin(), used.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    for (const auto& u : used) {
+        auto it = k.index.find(k.slot_key[u.second]);
+        if (it != k.index.end() && *it->second == u.second) k.lru.splice(k.lru.begin(), k.lru, it->second);
+    }
+    k.fold_epoch = k.epoch;
+    return PV_OK;
+}
+
 }  // namespace
 
+// What the engine's other translation units call (declared in pv_ctx.h).
+
+int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+
+PvKeyCacheView kc_view() {
+    auto& k = g_ctx.kc;
+    PvKeyCacheView v{k.d_htab, k.d_keys, k.d_flags, k.d_tab, 0u, k.seed, k.d_wtab, k.wcap};
+    if (k.enabled && !k.broken && k.cap > 0 && !k.index.empty()) {
+        v.hmask = k.hmask;
+        v.stamp = k.d_stamp;
+        v.epoch = ++k.epoch;
+    }
+    return v;
+}
+
+// One batch on `stream` (caller holds g_mu). Chunks of at most work.stride requests (a multiple of
+// 64, so verdict words never straddle).
+int launch(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
+           hipStream_t stream) {
+    if (n == 0) return PV_OK;
+    int rc = g_ctx.hand.begin(stream);
+    if (rc) return rc;
+    rc = launch_chunks(d_sm, d_off, n, d_pk, d_verdict, stream);
+    // recorded even after a failed enqueue: whatever did get enqueued is covered
+    if (int rc2 = g_ctx.hand.end(stream)) return rc2;
+    return rc;
+}
+
+int check_device_index(int device, const char* who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(PV_ERR_NO_DEVICE, std::string(who) + ": no HIP device visible");
+    if (device < 0 || device >= ndev || device >= PV_MAX_DEV)
+        return fail(PV_ERR_ARG, std::string(who) + ": device index out of range");
+    return PV_OK;
+}
+
+// ctx_init_parts, and on failure everything it had built is released (streams, events, the workspace,
+// the tables): a retry of pv_init / pv_init_devices starts from an empty context instead of allocating
+// ~25 GB on top of a half-built one.
+int ctx_init(int device) {
+    const int rc = ctx_init_parts(device);
+    if (rc != PV_OK) {
+        const std::string err = g_err;
+        g_ctx.device = device;  // ctx_free releases a context of a known device
+        ctx_free();
+        g_err = err;
+    }
+    return rc;
+}
+
+// pv_key_cache_put under g_mu. async (automatic admission): at most kcap new keys, nothing waited
+// for (pinned staging; the hash-table upload and the hand-over event are stream-ordered after the build).
+int kc_put_locked(const uint8_t* pks, uint64_t n, bool async) {
+    auto& k = g_ctx.kc;
+    if (async) {
+        if (k.async_pending) PV_HIP(hipEventSynchronize(k.ev_async), PV_ERR_LAUNCH);  // h_async is free again
+        k.async_pending = false;
+    }
+    // slots for the new keys (at most cap of them: the last cap distinct keys of the call win).
+    // The device hash table still holds the state before this call until kc_upload_htab below.
+    std::vector<std::string> fresh;
+    std::vector<uint32_t> fresh_slot, touched;
+    if (k.free_slots.size() < n && !k.lru.empty()) {
+        const int rc = kc_fold_hits();  // evictions ahead: take the launches' reads into account
+        if (rc != PV_OK) return rc;
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        std::string key(reinterpret_cast<const char*>(pks + 32 * i), 32);
+        auto it = k.index.find(key);
+        if (it != k.index.end()) {  // refresh
+            k.lru.splice(k.lru.begin(), k.lru, it->second);
+            continue;
+        }
+        uint32_t slot;
+        if (!k.free_slots.empty()) {
+            slot = k.free_slots.back();
+            k.free_slots.pop_back();
+        } else {  // evict the least recently put key
+            slot = k.lru.back();
+            k.lru.pop_back();
+            k.index.erase(k.slot_key[slot]);
+            k.seen.forget(reinterpret_cast<const uint8_t*>(k.slot_key[slot].data()));  // re-admissible
+            for (size_t f = 0; f < fresh.size(); f++)
+                if (fresh_slot[f] == slot) fresh_slot[f] = PV_KC_EMPTY;  // evicted before it was built
+        }
+        k.lru.push_front(slot);
+        k.index[key] = k.lru.begin();
+        k.slot_key[slot] = key;
+        fresh.push_back(key);
+        fresh_slot.push_back(slot);
+        touched.push_back(slot);
+    }
+    int rc = kc_build_tables(fresh, fresh_slot, async);
+    if (rc != PV_OK) {
+        // roll back to a state in which every indexed key's table is built: every slot this call
+        // assigned (its new key's table may be unbuilt, and its evicted key's table may already be
+        // overwritten) leaves the index and returns to the free list; the keys this call did not
+        // touch keep their slots. Then the device hash table is re-uploaded; if even that fails,
+        // the cache is switched off (kc_view() reports it empty) until configure / clear.
+        const std::string err = g_err;
+        std::vector<char> seen(k.cap, 0);
+        for (uint32_t slot : touched) {
+            if (seen[slot]) continue;
+            seen[slot] = 1;
+            auto it = k.index.find(k.slot_key[slot]);
+            if (it != k.index.end() && *it->second == slot) {
+                k.lru.erase(it->second);
+                k.index.erase(it);
+            }
+            k.slot_key[slot].clear();
+            k.free_slots.push_back(slot);
+        }
+        (void)hipStreamSynchronize(g_ctx.stream);
+        if (kc_upload_htab(g_ctx.stream) != PV_OK) k.broken = true;
+        g_err = err;
+        return rc;
+    }
+    g_ctx.last_keyed = false;
+    if (async) {
+        rc = kc_upload_htab(g_ctx.stream, reinterpret_cast<uint32_t*>(k.h_async + (uint64_t)g_ctx.kw.kcap * 36));
+        if (rc == PV_OK) {
+            PV_HIP(hipEventRecord(k.ev_async, g_ctx.stream), PV_ERR_LAUNCH);
+            k.async_pending = true;
+        }
+    } else {
+        rc = kc_upload_htab(g_ctx.stream);
+    }
+    if (int rc2 = g_ctx.hand.end(g_ctx.stream)) return rc2;
+    k.broken = rc != PV_OK;  // a complete upload also repairs an earlier failed one
+    return rc;
+}
+
+hipStream_t pv_engine_stream() { return g_ctx.stream; }
+int pv_fail(int code, const std::string& msg) { return fail(code, msg); }
+
 extern "C" {
+
+int pv_abi_version(void) { return PV_ABI_VERSION; }
+uint32_t pv_build_flags(void) { return PV_BUILD_COMB_FUSED; }
+
+int pv_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+const char* pv_last_error(void) { return g_err.c_str(); }
 
 int pv_init(int device) {
     const int p = g_primary.load();
@@ -2953,11 +2514,6 @@ int pv_init(int device) {
     return PV_OK;
 }
 
-}  // extern "C"
-namespace {
-void pinned_cache_drain();
-}
-extern "C" {
 void pv_shutdown(void) {
     pinned_cache_drain();  // freed pv_host_alloc blocks back to the system (live ones stay the caller's)
     pv_ingress_shutdown();
@@ -3106,755 +2662,6 @@ int pv_verify_batch_device(const uint8_t* d_sm, const uint64_t* d_off, uint64_t 
     return launch(d_sm, d_off, n, d_pk, d_verdict_words, stream ? (hipStream_t)stream : g_ctx.stream);
 }
 
-// Host-side copy workers (copy_pool.h): one pool per device context, so the per-device workers of
-// pv_verify_batch_multi_gpu stage their shards at the same time; pinned host ranges the library owns
-// or registered (pv_host_alloc / pv_host_register), whose bytes the host-buffer entry DMAs directly.
-}  // extern "C"
-namespace {
-pvhost::PinnedRegistry g_pinned_alloc, g_pinned_reg;
-// freed pv_host_alloc blocks kept for reuse (copy_pool.h PinnedCache), up to PV_PINNED_CACHE_MB (4 GB)
-pvhost::PinnedCache& pinned_cache() {
-    static pvhost::PinnedCache* c = [] {
-        const char* e = getenv("PV_PINNED_CACHE_MB");
-        return new pvhost::PinnedCache((e && *e ? strtoull(e, nullptr, 10) : 4096ull) << 20);
-    }();
-    return *c;
-}
-void pinned_release(const std::vector<pvhost::PinnedCache::Block>& v) {
-    for (const auto& b : v) (void)hipHostFree(b.p);
-}
-void pinned_cache_drain() { pinned_release(pinned_cache().drain()); }
-bool pv_is_pinned(const void* p, uint64_t bytes) {
-    return g_pinned_alloc.contains(p, bytes) || g_pinned_reg.contains(p, bytes);
-}
-pvhost::CopyPool& cur_pool() {
-    static const unsigned ndev = (unsigned)std::max(1, pv_device_count());
-    return pvhost::copy_pool_for<PV_MAX_DEV>(pv_cur_dev(), ndev);
-}
-}  // namespace
-extern "C" {
-
-// Move the request blob host -> pinned staging -> HBM. One host thread copies ~10 GB/s, so the blob is
-// cut into pieces (256 KB - 4 MB) that the copy pool stages in parallel; with `dma`, each piece's DMA
-// (hipMemcpyAsync from pinned memory) is enqueued as soon as it is staged, so the PCIe transfer of
-// earlier pieces overlaps the staging of later ones (the pieces are disjoint: their order on the
-// stream does not matter, and the kernels launched on the same stream afterwards see every piece).
-static int pv_stage_to_device(uint8_t* d_dst, uint8_t* h_stage, const uint8_t* src, uint64_t bytes, hipStream_t s,
-                              bool dma) {
-    const uint64_t piece = std::min<uint64_t>(4ull << 20, std::max<uint64_t>(256ull << 10, bytes / 16));
-    const unsigned k = (unsigned)((bytes + piece - 1) / piece);
-    std::atomic<int> err{0};
-    cur_pool().run(k, [&](unsigned i) {
-        const uint64_t o = (uint64_t)i * piece, e = std::min(bytes, o + piece);
-        memcpy(h_stage + o, src + o, e - o);
-        if (dma && hipMemcpyAsync(d_dst + o, h_stage + o, e - o, hipMemcpyHostToDevice, s) != hipSuccess) err = 1;
-    });
-    return err.load() ? fail(PV_ERR_LAUNCH, "hipMemcpyAsync (request blob) failed") : PV_OK;
-}
-
-// AUTO between the latency path and the keyed path for a host batch of PV_KEYED_HINT_MIN..
-// PV_LATENCY_MAX requests: the device cannot count keys before the path is chosen, the host can
-// (~10 us for 4,096 keys). With >= 3 requests per key on average (and at most PV_ALLCOMB_KEYS keys:
-// every key a comb key, sparse fill) the keyed path is faster -- MI355X, 1,024 signers, PCIe
-// included (profiles/r02/latency_vs_keyed_crossover.txt): 3,072 requests 0.64 vs 0.71 ms, 4,096
-// 0.65 vs 0.92; at 2 requests per key (2,048) the latency path still wins (0.58 vs 0.61). Keys in
-// the node-side key cache make the latency path faster still: no hint while the cache holds keys.
-#ifndef PV_KC_AUTO_MAX_BATCH
-#define PV_KC_AUTO_MAX_BATCH 4096  // automatic admission counts every key of host batches up to this size (a sample above)
-#endif
-static int kc_put_locked(const uint8_t* pks, uint64_t n, bool async);
-// Automatic admission: count the VERIFIED appearances of this batch's keys (idx: the sampled requests,
-// or null for all n; pre: each one's entry located by kc_auto_locate while the kernels ran, or -1); the
-// keys reaching auto_min appearances in the window are returned, at most kcap of them. The verdicts are
-// vb[i] & 1 (zero-copy verdict bytes) or bit i of hver (verdict words).
-static void kc_auto_count(const uint8_t* pk, const uint64_t* idx, uint64_t n, const int32_t* pre, uint64_t gen,
-                          const uint8_t* vb, const uint64_t* hver, std::vector<uint8_t>& admit) {
-    auto& k = g_ctx.kc;
-    for (uint64_t j = 0; j < n; j++) {
-        const uint64_t i = idx ? idx[j] : j;
-        const bool ok = vb ? (vb[i] & 1u) != 0 : ((hver[i >> 6] >> (i & 63)) & 1u) != 0;
-        if (!ok) continue;  // a key is never counted on the strength of a failing signature
-        const auto o = pre && pre[j] >= 0 && k.seen.generation() == gen ? k.seen.bump_at(pre[j], k.auto_min)
-                                                                         : k.seen.count(pk + 32 * i, k.auto_min);
-        if (o == pvhost::AdmitTable::ADMIT) {
-            admit.insert(admit.end(), pk + 32 * i, pk + 32 * i + 32);
-            if (admit.size() >= 32ull * g_ctx.kw.kcap) break;
-        }
-    }
-}
-// The counting side's read-only lookups, run while the batch's kernels run (the verdicts decide later
-// which of them count).
-static void kc_auto_locate(const uint8_t* pk, const uint64_t* idx, uint64_t n, std::vector<int32_t>& pre) {
-    pre.resize(n);
-    for (uint64_t j = 0; j < n; j++) pre[j] = g_ctx.kc.seen.find(pk + 32 * (idx ? idx[j] : j));
-}
-static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk, uint64_t* d_out,
-                            uint64_t** dver_out, uint64_t** hver_out);
-
-// sm_off[0..n] non-decreasing (the host-buffer entries refuse anything else before touching the
-// device); large batches are checked in slices on the calling context's copy workers.
-static bool offsets_nondecreasing(const uint64_t* off, uint64_t n) {
-    if (n < (1u << 17)) return pv_offsets_monotone(off, n);
-    pvhost::CopyPool& pool = cur_pool();
-    const unsigned k = std::max(1u, pool.threads());
-    std::atomic<bool> good{true};
-    pool.run(k, [&](unsigned t) {
-        const uint64_t a = n * t / k, b = n * (t + 1) / k;
-        if (!pv_offsets_monotone(off + a, b - a)) good = false;
-    });
-    return good.load();
-}
-
-static bool pv_keyed_hint(const uint8_t* pk, uint64_t n) {
-    if (g_ctx.path != PV_PATH_AUTO || n < PV_KEYED_HINT_MIN || n > PV_LATENCY_MAX) return false;
-    if (g_ctx.kc.enabled && !g_ctx.kc.index.empty()) return false;
-    // distinct keys by open addressing on the keys' first 16 bytes (a heuristic: a rare collision
-    // only miscounts, the verdicts do not depend on the path)
-    constexpr uint32_t H = 16384;  // > 2 x PV_LATENCY_MAX
-    static_assert(H >= 2 * PV_LATENCY_MAX, "hint table too small");
-    static thread_local std::vector<uint64_t> tab;
-    tab.assign(2 * H, 0);
-    uint64_t distinct = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        uint64_t a, b;
-        memcpy(&a, pk + 32 * i, 8);
-        memcpy(&b, pk + 32 * i + 8, 8);
-        a |= 1;  // (0, 0) marks an empty entry
-        uint32_t h = (uint32_t)((a * 0x9E3779B97F4A7C15ull) >> 50) & (H - 1);
-        while (tab[2 * h] && !(tab[2 * h] == a && tab[2 * h + 1] == b)) h = (h + 1) & (H - 1);
-        if (!tab[2 * h]) {
-            tab[2 * h] = a;
-            tab[2 * h + 1] = b;
-            distinct++;
-        }
-    }
-    return distinct <= PV_ALLCOMB_KEYS && 3 * distinct <= n;
-}
-
-int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk,
-                    uint8_t* verdict_bits) {
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_verify_batch: call pv_init first");
-    if (n == 0) return PV_OK;
-    if (!sm || !sm_off || !pk || !verdict_bits) return fail(PV_ERR_ARG, "null pointer");
-    if (!offsets_nondecreasing(sm_off, n)) return fail(PV_ERR_ARG, "sm_off must be non-decreasing");
-    std::lock_guard<std::mutex> lk(g_mu);
-    {
-        // a small call that takes the latency path (the same choice launch_chunks makes for a host-buffer
-        // call) and whose records fit a 2 KB slot: the kernel reads the pinned staging slots over PCIe
-        // and stores one verdict byte per request back -- no copy kernels around it
-        uint64_t maxlen = 0;
-        for (uint64_t i = 0; i < n && n <= PV_ZC_MAX_REQ; i++) maxlen = std::max(maxlen, sm_off[i + 1] - sm_off[i]);
-        const uint64_t stride = (4ull * PV_ZC_REC_WORD + maxlen + PV_ZC_SLACK + 63) & ~63ull;
-        if (!g_ctx.timing && n <= PV_ZC_MAX_REQ && stride <= PV_ZC_MAX_STRIDE &&
-            (g_ctx.path == PV_PATH_LATENCY ||
-             (g_ctx.path == PV_PATH_AUTO && n <= PV_LATENCY_MAX && !pv_keyed_hint(pk, n)))) {
-            int rc = ensure_stage(n * stride, 0);
-            if (rc) return rc;
-            uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
-            uint8_t* slots = g_ctx.h_stage.p;
-            memset(vb, 0xFF, n);  // pending: the host spins on these bytes instead of a stream sync
-            auto fill_at = [&](uint8_t* base, uint64_t a, uint64_t b) {
-                for (uint64_t i = a; i < b; i++) {
-                    uint8_t* sl = base + i * stride;
-                    const uint64_t len = sm_off[i + 1] - sm_off[i];
-                    const uint32_t hdr[PV_ZC_PK_WORD] = {(uint32_t)len, 0u, 0u, 0u};
-                    memcpy(sl, hdr, sizeof(hdr));
-                    memcpy(sl + 4 * PV_ZC_PK_WORD, pk + 32 * i, 32);
-                    memcpy(sl + 4 * PV_ZC_REC_WORD, sm + sm_off[i], len);
-                    memset(sl + 4 * PV_ZC_REC_WORD + len, 0, stride - 4 * PV_ZC_REC_WORD - len);
-                }
-            };
-            const bool one = n == 1 && stride <= sizeof(PvZcOne);  // the slot goes in the kernel arguments
-            PvZcOne one_slot;
-            if (one) {
-                fill_at(reinterpret_cast<uint8_t*>(one_slot.w), 0, 1);
-            } else if (n * stride < (128u << 10)) {
-                fill_at(slots, 0, n);
-            } else {  // node-quota sizes: the slots are written by the copy pool's threads
-                const unsigned k = 8;
-                cur_pool().run(k, [&](unsigned t) { fill_at(slots, n * t / k, n * (t + 1) / k); });
-            }
-            hipStream_t s = g_ctx.stream;
-            if ((rc = g_ctx.hand.begin(s))) return rc;
-            g_ctx.last_latency = true;
-            g_ctx.last_keyed = false;
-            g_ctx.last_dev_choice = false;
-            g_ctx.last_zero_copy = true;
-            rc = one ? pv_latency_launch_zc_one(one_slot, (uint32_t)stride, g_ctx.d_bcomb, kc_view(), vb, s)
-                     : pv_latency_launch_zc(slots, (uint32_t)stride, n, g_ctx.d_bcomb, kc_view(), vb, s);
-            if (int rc2 = g_ctx.hand.end(s)) return rc2;
-            if (rc) {
-                (void)hipStreamSynchronize(s);
-                return rc;
-            }
-            rc = kc_auto_after_batch(pk, n, s, vb, nullptr);  // returns once the verdict bytes are written
-            if (rc) return rc;
-            memset(verdict_bits, 0, (n + 7) / 8);
-            for (uint64_t i = 0; i < n; i++) verdict_bits[i >> 3] |= (uint8_t)((vb[i] & 1u) << (i & 7));
-            return PV_OK;
-        }
-    }
-    uint64_t *dver = nullptr, *hver = nullptr;
-    int rc = stage_and_launch(sm, sm_off, n, pk, nullptr, &dver, &hver);
-    if (rc) return rc;
-    PV_HIP(hipMemcpyAsync(hver, dver, (n + 63) / 64 * 8, hipMemcpyDeviceToHost, g_ctx.stream), PV_ERR_LAUNCH);
-    rc = kc_auto_after_batch(pk, n, g_ctx.stream, nullptr, hver);
-    if (rc) return rc;
-    memcpy(verdict_bits, hver, (n + 7) / 8);  // little-endian words, LSB-first bits
-    return PV_OK;
-}
-
-// Requests per sub-batch of the pipelined host-buffer form (a multiple of 64; env PV_PIPE_SUB overrides
-// it for A/Bs). Sub-batch j's H2D runs on the copy stream while sub-batch j-1's kernels run, so a large
-// host batch costs about its PCIe time plus the last sub-batch's kernels instead of their sum.
-#ifndef PV_PIPE_SUB
-#define PV_PIPE_SUB 262144
-#endif
-#ifndef PV_PIPE_END_DEFAULT
-#define PV_PIPE_END_DEFAULT (PV_PIPE_SUB / 2)
-#endif
-static constexpr uint64_t PV_PIPE_MAX = 64;                // sub-batches per call (copy events)
-static constexpr uint64_t PV_PIPE_MIN_BLOB = 8ull << 20;   // smaller blobs: one piece
-static uint64_t pipe_sub() {
-    static const uint64_t v = [] {
-        const char* e = getenv("PV_PIPE_SUB");
-        const uint64_t x = e && *e ? strtoull(e, nullptr, 10) : (uint64_t)PV_PIPE_SUB;
-        return std::max<uint64_t>(8192, x / 64 * 64);
-    }();
-    return v;
-}
-
-// The shared-table store of the pipelined host path (on first use; a failed allocation is not retried:
-// the sub-batches then build their own tables, same verdicts).
-static int ensure_xtab() {
-    auto& x = g_ctx.xt;
-    if (x.tab) return PV_OK;
-    if (x.failed) return PV_ERR_ALLOC;
-    if (hipMalloc((void**)&x.htab, PV_XT_HASH * 4) != hipSuccess ||
-        hipMalloc((void**)&x.keys, PV_XT_KEYS * 32) != hipSuccess ||
-        hipMalloc((void**)&x.flags, PV_XT_KEYS * 4) != hipSuccess ||
-        hipMalloc((void**)&x.tab, (uint64_t)PV_XT_KEYS * PV_COMB_POS * PV_COMB_ENT * 160) != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* p : {(void*)x.htab, (void*)x.keys, (void*)x.flags, (void*)x.tab})
-            if (p) (void)hipFree(p);
-        x.htab = x.keys = x.flags = nullptr;
-        x.tab = nullptr;
-        x.failed = true;
-        return PV_ERR_ALLOC;
-    }
-    return PV_OK;
-}
-
-// The copy form of a host-buffer batch on the calling thread's context: moves the keys, offsets and
-// records to the device staging area and enqueues the verification on the context's stream. d_out:
-// where the verdict words go (nullptr = the staging area's own verdict section); *dver / *hver receive
-// the device verdict section and a pinned buffer for the caller's copy back.
-//   * small batches (blob < 8 MB, no input in pinned memory): one host copy into pinned staging in the
-//     device layout, one DMA, the kernels (the quota sizes: fewest packets on the path);
-//   * otherwise, in sub-batches of pipe_sub() requests: the copy workers stage sub-batch j's pageable
-//     inputs (inputs inside pv_host_alloc / pv_host_register memory are not copied: the DMA reads them
-//     where they are), its H2D goes on the copy stream, and its kernels on the engine stream after an
-//     event -- so PCIe, host staging and kernels of consecutive sub-batches overlap.
-// Staging layout (host and device, 256-B aligned sections): [pk n*32][off (n+1) u64][verdict][blob +
-// PV_BLOB_SLACK]. A failure after DMAs were enqueued returns only after both streams drained, so no copy
-// still reads the caller's or the staging buffers.
-static int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk, uint64_t* d_out,
-                            uint64_t** dver_out, uint64_t** hver_out) {
-    Ctx& c = g_ctx;
-    c.last_zero_copy = false;
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t pk_bytes = up(n * 32), off_bytes = up((n + 1) * 8), vwords = (n + 63) / 64;
-    const uint64_t v_bytes = up(vwords * 8);
-    const uint64_t base = sm_off[0], blob = sm_off[n] - base;
-    const uint64_t total = pk_bytes + off_bytes + v_bytes + blob + PV_BLOB_SLACK;
-    const bool pin_sm = pv_is_pinned(sm + base, blob), pin_pk = pv_is_pinned(pk, 32 * n);
-    const bool pin_off = base == 0 && pv_is_pinned(sm_off, 8 * (n + 1));
-    const bool any_pin = pin_sm || pin_pk || pin_off, all_pin = pin_sm && pin_pk && pin_off;
-    const uint64_t sub = pipe_sub();
-    // sub-batch bounds (64-aligned). The call ends one sub-batch's kernels after the last H2D, and
-    // the first sub-batch's kernels (which also build the shared tables) start only after the first
-    // H2D, so with >= 2 full sub-batches the first and the last are half-size
-    // (profiles/r05/host_path: 1M requests, 0.5 + 3 x 1 + 0.5 of 262,144)
-    std::vector<uint64_t> bnd{0};
-    static const bool halves = env_int("PV_PIPE_HALF_ENDS", 1) != 0;
-    // first / last piece size (env PV_PIPE_END, A/B): half a sub-batch by default. Smaller ends are slower
-    // (1M arena: 116.8-119.1 M/s at 131,072, 113.6-114.1 at 65,536, 110.4-112.7 at 32,768; profiles/r06/
-    // host_path/ab_pipe_end.txt): the copies are the critical path and a sub-batch's kernels beside a DMA
-    // take longer than a small last piece's copy, so the last FULL piece's kernels become the tail
-    static const uint64_t end_req = (uint64_t)std::max(8192, env_int("PV_PIPE_END", (int)(PV_PIPE_END_DEFAULT)));
-    if (blob >= PV_PIPE_MIN_BLOB && halves && n >= 3 * sub) {
-        const uint64_t h = std::min<uint64_t>(end_req, sub) / 64 * 64;
-        const uint64_t mid = n - 2 * h;
-        const uint64_t k = std::min<uint64_t>(PV_PIPE_MAX - 2, std::max<uint64_t>(1, (mid + sub / 2) / sub));
-        bnd.push_back(h);
-        for (uint64_t j = 1; j < k; j++) bnd.push_back(h + (mid * j / k) / 64 * 64);
-        bnd.push_back((n - h) & ~63ull);  // every bound a whole verdict word (n itself need not be)
-    } else if (blob >= PV_PIPE_MIN_BLOB) {
-        const uint64_t k = std::min<uint64_t>(PV_PIPE_MAX, std::max<uint64_t>(1, n / sub));
-        for (uint64_t j = 1; j < k; j++) bnd.push_back((n * j / k) & ~63ull);
-    }
-    bnd.push_back(n);
-    const uint64_t np = bnd.size() - 1;
-    hipStream_t s = c.stream;
-    int rc = ensure_stage(all_pin ? 0 : total, total);
-    if (rc) return rc;
-    uint8_t* h = c.h_stage.p;
-    uint8_t* d = c.d_stage.p;
-    uint64_t* dver = reinterpret_cast<uint64_t*>(d + pk_bytes + off_bytes);
-    uint8_t* dblob = d + pk_bytes + off_bytes + v_bytes;
-    auto finish_piece = [&](uint64_t lo, uint64_t hi) -> int {
-        c.verdict_zeroed = d_out == nullptr;
-        c.keyed_hint = pv_keyed_hint(pk + 32 * lo, hi - lo);
-        c.hint_set = true;
-        const int r = launch(dblob, reinterpret_cast<const uint64_t*>(d + pk_bytes) + lo, hi - lo, d + 32 * lo,
-                             (d_out ? d_out : dver) + lo / 64, s);
-        c.verdict_zeroed = false;
-        c.keyed_hint = false;
-        c.hint_set = false;
-        return r;
-    };
-    if (np == 1 && !any_pin) {
-        // the quota sizes: everything in the device layout in pinned staging, one DMA
-        uint64_t* hoff = reinterpret_cast<uint64_t*>(h + pk_bytes);
-        const unsigned k = n >= (1u << 16) ? 8u : 1u;
-        cur_pool().run(k, [&](unsigned t) {
-            const uint64_t a = n * t / k, b = n * (t + 1) / k;
-            memcpy(h + 32 * a, pk + 32 * a, 32 * (b - a));
-            for (uint64_t i = a; i < b; i++) hoff[i] = sm_off[i] - base;
-        });
-        hoff[n] = sm_off[n] - base;
-        uint8_t* hblob = h + pk_bytes + off_bytes + v_bytes;
-        memset(h + pk_bytes + off_bytes, 0, v_bytes);  // the verdict words travel zeroed
-        memset(hblob + blob, 0, PV_BLOB_SLACK);
-        if (c.inject_stage > 0) {
-            c.inject_stage--;
-            return fail(PV_ERR_ALLOC, "stage_and_launch: injected staging failure (pv_test_inject)");
-        }
-        if (blob < (256ull << 10)) {
-            memcpy(hblob, sm + base, blob);
-        } else {
-            rc = pv_stage_to_device(dblob, hblob, sm + base, blob, s, false);
-            if (rc) return rc;
-        }
-        PV_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        if ((rc = finish_piece(0, n))) return rc;
-        *dver_out = dver;
-        *hver_out = reinterpret_cast<uint64_t*>(h + pk_bytes + off_bytes);
-        return PV_OK;
-    }
-    if ((rc = c.h_ver.grow(std::max<uint64_t>(v_bytes, 64 << 10), hipHostMallocPortable))) return rc;
-    while (c.ev_copy.size() < np) {
-        hipEvent_t e;
-        PV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PV_ERR_LAUNCH);
-        c.ev_copy.push_back(e);
-    }
-    hipStream_t cs = c.cstream;
-    const uint8_t* spk = pin_pk ? pk : h;
-    const uint64_t* soff = pin_off ? sm_off : reinterpret_cast<const uint64_t*>(h + pk_bytes);
-    const uint8_t* sblob = pin_sm ? sm + base : h + pk_bytes + off_bytes + v_bytes;
-    uint64_t* hoff = reinterpret_cast<uint64_t*>(h + pk_bytes);
-    uint8_t* hblob = h + pk_bytes + off_bytes + v_bytes;
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d + pk_bytes);
-    // the copy stream starts after everything enqueued so far (the previous users of the staging area)
-    PV_HIP(hipEventRecord(c.ev_cstart, s), PV_ERR_LAUNCH);
-    PV_HIP(hipStreamWaitEvent(cs, c.ev_cstart, 0), PV_ERR_LAUNCH);
-    if ((rc = c.hand.wait(cs, s))) return rc;
-    // sub-batch j = requests [lo(j), lo(j + 1))
-    auto lo_of = [&](uint64_t j) -> uint64_t { return bnd[std::min<uint64_t>(j, np)]; };
-    pvhost::CopyPool& pool = cur_pool();
-    // sub-batch j's pageable inputs into pinned staging (copy workers), its H2D on the copy stream, then
-    // ev_copy[j]
-    auto stage_copy = [&](uint64_t j) -> int {
-        const uint64_t lo = lo_of(j), hi = lo_of(j + 1);
-        const uint64_t b0 = sm_off[lo] - base, b1 = sm_off[hi] - base;
-        if (!all_pin) {  // this sub-batch's pageable inputs into pinned staging, on the copy workers
-            const unsigned k = std::max(1u, std::min(pool.threads(), (unsigned)((b1 - b0) >> 22)));
-            pool.run(k, [&](unsigned t) {
-                const uint64_t a = lo + (hi - lo) * t / k, b = lo + (hi - lo) * (t + 1) / k;
-                if (!pin_pk) memcpy(h + 32 * a, pk + 32 * a, 32 * (b - a));
-                if (!pin_off)
-                    for (uint64_t i = a; i < b; i++) hoff[i] = sm_off[i] - base;
-                if (!pin_sm) memcpy(hblob + (sm_off[a] - base), sm + sm_off[a], sm_off[b] - sm_off[a]);
-            });
-            if (!pin_off) hoff[hi] = sm_off[hi] - base;
-        }
-        PV_HIP(hipMemcpyAsync(d + 32 * lo, spk + 32 * lo, 32 * (hi - lo), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(doff + lo, soff + lo, 8 * (hi - lo + 1), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        if (b1 > b0)
-            PV_HIP(hipMemcpyAsync(dblob + b0, sblob + b0, b1 - b0, hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        PV_HIP(hipEventRecord(c.ev_copy[j], cs), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    // PV_PIPE_TRACE=1 (development): timing events after each sub-batch's copies and kernels, printed to
-    // stderr relative to the call's first event -- the untraced pipeline timeline
-    static const bool ptrace = env_int("PV_PIPE_TRACE", 0) != 0;
-    static const int lookahead = env_int("PV_PIPE_LOOKAHEAD", 1);
-    std::vector<hipEvent_t> tev;
-    auto tmark = [&](hipStream_t st) {
-        if (!ptrace) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) == hipSuccess) {
-            (void)hipEventRecord(e, st);
-            tev.push_back(e);
-        }
-    };
-    // the sub-batches share one set of comb tables: sub-batch 0 builds the tables of its comb keys that
-    // the node-side key cache does not hold, the later ones read the cache's for cached keys and the
-    // shared store's for the rest (pv_key_cache_probe_kernel's two views)
-    static const bool share_env = env_int("PV_PIPE_SHARE", 1) != 0;
-    const bool share = share_env && np > 1 && (c.path == PV_PATH_AUTO || c.path == PV_PATH_COMB) &&
-                       ensure_xtab() == PV_OK;
-    auto run = [&]() -> int {
-        tmark(cs);
-        if (share) PV_HIP(hipMemsetAsync(c.xt.htab, 0xFF, PV_XT_HASH * 4, s), PV_ERR_LAUNCH);
-        if (!d_out) PV_HIP(hipMemsetAsync(dver, 0, vwords * 8, s), PV_ERR_LAUNCH);  // the latency path ORs bits
-        PV_HIP(hipMemsetAsync(dblob + blob, 0, PV_BLOB_SLACK, cs), PV_ERR_LAUNCH);
-        int r = stage_copy(0);
-        tmark(cs);
-        // sub-batch j + 1's copies are enqueued BEFORE sub-batch j's kernels: should the copy stream share a
-        // hardware queue with one of the engine's streams, no copy waits behind kernels enqueued before it
-        for (uint64_t j = 0; j < np && r == PV_OK; j++) {
-            if (lookahead && j + 1 < np) {
-                if ((r = stage_copy(j + 1)) != PV_OK) break;
-                tmark(cs);
-            }
-            if (c.inject_stage > 0 && j == std::min<uint64_t>(1, np - 1)) {  // sub-batch 0's kernels in flight
-                c.inject_stage--;
-                return fail(PV_ERR_ALLOC, "stage_and_launch: injected staging failure (pv_test_inject)");
-            }
-            PV_HIP(hipStreamWaitEvent(s, c.ev_copy[j], 0), PV_ERR_LAUNCH);
-            c.xt_fill = share && j == 0;
-            c.xt_use = share && j > 0;
-            r = finish_piece(lo_of(j), lo_of(j + 1));
-            c.xt_fill = c.xt_use = false;
-            tmark(s);
-            if (!lookahead && r == PV_OK && j + 1 < np) {
-                if ((r = stage_copy(j + 1)) != PV_OK) break;
-                tmark(cs);
-            }
-        }
-        return r;
-    };
-    if ((rc = run()) != PV_OK) {
-        (void)hipStreamSynchronize(cs);  // no DMA may still read the caller's or the staging buffers
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    if (ptrace && !tev.empty()) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize(cs);
-        std::string line = "pv_pipe: n " + std::to_string(n) + " pieces " + std::to_string(np) + " us:";
-        for (size_t i = 1; i < tev.size(); i++) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, tev[0], tev[i]);
-            line += " " + std::to_string((int)(ms * 1000));
-        }
-        fprintf(stderr, "%s\n", line.c_str());
-        for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-    }
-    *dver_out = dver;
-    *hver_out = c.h_ver.as<uint64_t>();
-    return PV_OK;
-}
-
-namespace {
-// Zero-copy verdict bytes start at 0xFF and each workgroup's last store sets its byte: the host spins
-// on them instead of the runtime's completion wait (a kernel fault surfaces at the next call's
-// synchronisation); bounded at 50 ms, then false and the caller waits on the stream.
-bool pv_spin_verdict_bytes(const uint8_t* vb, uint64_t n) {
-    const auto t0 = std::chrono::steady_clock::now();
-    volatile const uint8_t* vv = vb;
-    uint64_t i = 0;
-    while (i < n) {
-        if (vv[i] != 0xFFu) {
-            i++;
-            continue;
-        }
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) return false;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return true;
-}
-
-// Automatic key-cache admission after a host-buffer batch whose verdicts are the last thing enqueued on
-// `s`. Waits for the verdicts first (vb: zero-copy verdict bytes, spun on; else the verdict words hver
-// copied back on `s`), then counts the keys of the requests that VERIFIED -- a request with a failing
-// signature never counts towards its key's admission, so senders without a valid signature cannot make
-// the node build tables or evict its signers (plenum/server/client_authn.py:84-118: every signature is
-// untrusted input). The admitted keys' tables are built right behind the batch on the engine stream;
-// the call does not wait for the build (the next launch is stream-ordered after it).
-int kc_auto_after_batch(const uint8_t* pk, uint64_t n, hipStream_t s, const uint8_t* vb, const uint64_t* hver) {
-    auto& k = g_ctx.kc;
-    const bool on = k.auto_min > 0 && k.cap > 0 && k.enabled && !k.broken;
-    // the requests counted: all of a batch of <= 4,096, else a sample of one request from each block of
-    // ceil(n / 4,096), at a hashed position in the block (a fixed stride would alias with periodic
-    // signer orders); their table entries are located while the kernels still run
-    std::vector<uint64_t> sample;
-    std::vector<int32_t> pre;
-    uint64_t gen = 0;
-    if (on) {
-        if (n > PV_KC_AUTO_MAX_BATCH) {
-            const uint64_t stride = (n + PV_KC_AUTO_MAX_BATCH - 1) / PV_KC_AUTO_MAX_BATCH;
-            sample.reserve(n / stride + 1);
-            for (uint64_t b = 0, t = 0; b < n; b += stride, t++)
-                sample.push_back(b + ((t * 0x9E3779B97F4A7C15ull) >> 40) % std::min(stride, n - b));
-        }
-        gen = k.seen.generation();
-        kc_auto_locate(pk, sample.empty() ? nullptr : sample.data(), sample.empty() ? n : sample.size(), pre);
-    }
-    if (!(vb && pv_spin_verdict_bytes(vb, n))) PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-    if (!on) return PV_OK;
-    std::vector<uint8_t> admit;
-    kc_auto_count(pk, sample.empty() ? nullptr : sample.data(), sample.empty() ? n : sample.size(), pre.data(), gen,
-                  vb, hver, admit);
-    if (admit.empty()) return PV_OK;
-    const std::string err = g_err;
-    if (kc_put_locked(admit.data(), admit.size() / 32, true) == PV_OK) {
-        k.auto_admitted += admit.size() / 32;
-    } else {
-        k.auto_failed += admit.size() / 32;  // the verdicts stand; the keys stay uncached and re-admissible
-        for (size_t j = 0; j < admit.size(); j += 32) k.seen.forget(admit.data() + j);
-        g_err = err;
-    }
-    return PV_OK;
-}
-}  // namespace
-
-int pv_comm_unique_id(uint8_t out[128]) {
-    ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return fail(PV_ERR_COMM, "ncclGetUniqueId failed");
-    static_assert(sizeof(id.internal) == 128, "ncclUniqueId size");
-    memcpy(out, id.internal, 128);
-    return PV_OK;
-}
-
-int pv_comm_init(int nranks, int rank, const uint8_t id_bytes[128]) {
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_comm_init: call pv_init first");
-    if (nranks < 1 || rank < 0 || rank >= nranks) return fail(PV_ERR_ARG, "pv_comm_init: bad rank");
-    ncclUniqueId id;
-    memcpy(id.internal, id_bytes, 128);
-    ncclResult_t r = ncclCommInitRank(&g_ctx.comm, nranks, id, rank);
-    if (r != ncclSuccess) return fail(PV_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    g_ctx.nranks = nranks;
-    g_ctx.rank = rank;
-    return PV_OK;
-}
-
-int pv_allgather_verdicts(const uint64_t* d_local, uint64_t words_per_rank, uint64_t* d_all, void* stream) {
-    if (!g_ctx.comm) return fail(PV_ERR_NOT_INIT, "pv_allgather_verdicts: call pv_comm_init first");
-    ncclResult_t r = ncclAllGather(d_local, d_all, words_per_rank, ncclUint64, g_ctx.comm,
-                                   stream ? (hipStream_t)stream : g_ctx.stream);
-    if (r != ncclSuccess) return fail(PV_ERR_COMM, std::string("ncclAllGather: ") + ncclGetErrorString(r));
-    return PV_OK;
-}
-
-int pv_comm_count(int* nranks, int* rank) {
-    if (!g_ctx.comm) return fail(PV_ERR_NOT_INIT, "pv_comm_count: call pv_comm_init first");
-    int c = 0, r = -1;
-    ncclResult_t e = ncclCommCount(g_ctx.comm, &c);
-    if (e == ncclSuccess) e = ncclCommUserRank(g_ctx.comm, &r);
-    if (e != ncclSuccess) return fail(PV_ERR_COMM, std::string("ncclCommCount / ncclCommUserRank: ") + ncclGetErrorString(e));
-    if (nranks) *nranks = c;
-    if (rank) *rank = r;
-    return PV_OK;
-}
-
-void pv_comm_destroy(void) {
-    if (g_ctx.comm) ncclCommDestroy(g_ctx.comm);
-    g_ctx.comm = nullptr;
-}
-
-int pv_shard_plan(uint64_t n, int ndev, uint64_t* bounds, uint64_t* words_per_shard) {
-    if (ndev < 1 || ndev > PV_MAX_DEV || !bounds || !words_per_shard) return fail(PV_ERR_ARG, "pv_shard_plan: bad arguments");
-    // whole 64-request verdict words per shard (sharding.py shard_bounds): word ranges
-    // [words r / G, words (r + 1) / G), so every shard but the last is a multiple of 64 requests
-    const uint64_t words = (n + 63) / 64;
-    uint64_t wmax = 0;
-    for (int r = 0; r <= ndev; r++) bounds[r] = std::min<uint64_t>(n, 64 * (words * (uint64_t)r / (uint64_t)ndev));
-    for (int r = 0; r < ndev; r++)
-        wmax = std::max<uint64_t>(wmax, words * (uint64_t)(r + 1) / ndev - words * (uint64_t)r / ndev);
-    *words_per_shard = wmax;
-    return PV_OK;
-}
-
-int pv_init_devices(uint32_t device_mask) {
-    std::vector<int> devs;
-    for (int d = 0; d < PV_MAX_DEV; d++)
-        if ((device_mask >> d) & 1u) devs.push_back(d);
-    if (devs.empty() || (device_mask >> PV_MAX_DEV) != 0) return fail(PV_ERR_ARG, "pv_init_devices: bad device mask");
-    for (int d : devs) {
-        const int rc = check_device_index(d, "pv_init_devices");
-        if (rc) return rc;
-    }
-    std::lock_guard<std::mutex> mg(g_mg_mu);
-    // the missing contexts are built in parallel, one host thread per device (tables built on each GPU)
-    std::vector<int> rcs(devs.size(), PV_OK);
-    std::vector<std::string> errs(devs.size());
-    {
-        std::vector<std::thread> th;
-        for (size_t i = 0; i < devs.size(); i++)
-            th.emplace_back([&, i] {
-                const int d = devs[i];
-                std::lock_guard<std::mutex> lk(g_mus[d]);
-                DevScope ds(d);
-                if (g_ctx.device != d && (rcs[i] = ctx_init(d)) != PV_OK) errs[i] = g_err;
-            });
-        for (auto& t : th) t.join();
-    }
-    for (size_t i = 0; i < devs.size(); i++)
-        if (rcs[i]) return fail(rcs[i], "pv_init_devices: device " + std::to_string(devs[i]) + ": " + errs[i]);
-    if (g_mg.devs != devs) {
-        mg_destroy_comms();
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        std::vector<ncclComm_t> comms(devs.size(), nullptr);
-        const ncclResult_t r = ncclCommInitAll(comms.data(), (int)devs.size(), devs.data());
-        (void)hipSetDevice(cur);  // the caller's current device is unchanged
-        if (r != ncclSuccess) return fail(PV_ERR_COMM, std::string("ncclCommInitAll: ") + ncclGetErrorString(r));
-        g_mg.comms = comms;
-        g_mg.devs = devs;
-    }
-    return PV_OK;
-}
-
-int pv_multi_gpu_devices(int* devices, int max_devices) {
-    std::lock_guard<std::mutex> mg(g_mg_mu);
-    for (int i = 0; i < (int)g_mg.devs.size() && i < max_devices && devices; i++) devices[i] = g_mg.devs[i];
-    return (int)g_mg.devs.size();
-}
-
-int pv_multi_gpu_comm_ranks(int* nranks, int* ranks, int max_devices) {
-    std::lock_guard<std::mutex> mg(g_mg_mu);
-    if (g_mg.comms.empty()) return fail(PV_ERR_NOT_INIT, "pv_multi_gpu_comm_ranks: call pv_init_devices first");
-    int c = 0;
-    ncclResult_t e = ncclCommCount(g_mg.comms[0], &c);
-    for (int i = 0; e == ncclSuccess && i < (int)g_mg.comms.size() && i < max_devices && ranks; i++)
-        e = ncclCommUserRank(g_mg.comms[i], &ranks[i]);
-    if (e != ncclSuccess) return fail(PV_ERR_COMM, std::string("ncclCommCount / ncclCommUserRank: ") + ncclGetErrorString(e));
-    if (nranks) *nranks = c;
-    return PV_OK;
-}
-
-int pv_verify_batch_multi_gpu(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk,
-                              uint8_t* verdict_bits) {
-    if (n == 0) return PV_OK;
-    if (!sm || !sm_off || !pk || !verdict_bits) return fail(PV_ERR_ARG, "null pointer");
-    if (!offsets_nondecreasing(sm_off, n)) return fail(PV_ERR_ARG, "sm_off must be non-decreasing");
-    std::lock_guard<std::mutex> mg(g_mg_mu);
-    const int G = (int)g_mg.devs.size();
-    if (G == 0) return fail(PV_ERR_NOT_INIT, "pv_verify_batch_multi_gpu: call pv_init_devices first");
-    std::vector<uint64_t> b(G + 1);
-    uint64_t wpr = 0;
-    int rc = pv_shard_plan(n, G, b.data(), &wpr);
-    if (rc) return rc;
-    // every device's context for the whole call (ascending device order: no lock-order inversion)
-    std::vector<std::unique_lock<std::mutex>> locks;
-    for (int d : g_mg.devs) locks.emplace_back(g_mus[d]);
-    // one worker per device: stage its shard (host -> pinned -> HBM, its own stream) and enqueue the
-    // shard's verification with the verdict words landing in its slot of the gather buffer
-    std::vector<int> rcs(G, PV_OK);
-    std::vector<std::string> errs(G);
-    {
-        std::vector<std::thread> th;
-        for (int r = 0; r < G; r++)
-            th.emplace_back([&, r] {
-                const int d = g_mg.devs[r];
-                DevScope ds(d);
-                auto run = [&]() -> int {
-                    PV_HIP(hipSetDevice(d), PV_ERR_NO_DEVICE);
-                    Ctx& c = g_ctx;
-                    int rc;
-                    if ((rc = c.d_mg.grow((uint64_t)G * wpr * 8)) || (rc = c.hand.begin(c.stream))) return rc;
-                    uint64_t* slot = c.d_mg.as<uint64_t>() + (uint64_t)r * wpr;
-                    PV_HIP(hipMemsetAsync(slot, 0, wpr * 8, c.stream), PV_ERR_LAUNCH);
-                    const uint64_t lo = b[r], hi = b[r + 1];
-                    if (hi == lo) return PV_OK;
-                    uint64_t *dv = nullptr, *hv = nullptr;
-                    return stage_and_launch(sm, sm_off + lo, hi - lo, pk + 32 * lo, slot, &dv, &hv);
-                };
-                if ((rcs[r] = run()) != PV_OK) errs[r] = g_err;
-            });
-        for (auto& t : th) t.join();
-    }
-    for (int r = 0; r < G; r++)
-        if (rcs[r]) {
-            for (int d : g_mg.devs) (void)hipStreamSynchronize(g_ctxs[d].stream);  // no DMA still reads staging
-            return fail(rcs[r], "pv_verify_batch_multi_gpu: device " + std::to_string(g_mg.devs[r]) + ": " + errs[r]);
-        }
-    // ONE all-gather of the per-shard verdict words over the devices' RCCL clique (in place: shard r
-    // sits at r * wpr on every device), then the gathered words come back from the first device
-    ncclResult_t nr = ncclGroupStart();
-    for (int r = 0; r < G && nr == ncclSuccess; r++) {
-        Ctx& c = g_ctxs[g_mg.devs[r]];
-        nr = ncclAllGather(c.d_mg.as<uint64_t>() + (uint64_t)r * wpr, c.d_mg.p, wpr, ncclUint64, g_mg.comms[r], c.stream);
-    }
-    const ncclResult_t ne = ncclGroupEnd();
-    if (nr == ncclSuccess) nr = ne;
-    Ctx& c0 = g_ctxs[g_mg.devs[0]];
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    rc = PV_OK;
-    if (nr != ncclSuccess) rc = fail(PV_ERR_COMM, std::string("ncclAllGather: ") + ncclGetErrorString(nr));
-    const uint64_t gbytes = (uint64_t)G * wpr * 8;
-    if (rc == PV_OK && c0.h_mg.cap < gbytes &&
-        (hipSetDevice(c0.device) != hipSuccess || c0.h_mg.grow(gbytes, hipHostMallocPortable) != PV_OK))
-        rc = fail(PV_ERR_ALLOC, "pv_verify_batch_multi_gpu: pinned verdict buffer");
-    if (rc == PV_OK && hipMemcpyAsync(c0.h_mg.p, c0.d_mg.p, gbytes, hipMemcpyDeviceToHost, c0.stream) != hipSuccess)
-        rc = fail(PV_ERR_LAUNCH, "pv_verify_batch_multi_gpu: verdict copy");
-    for (int r = 0; r < G; r++) {
-        Ctx& c = g_ctxs[g_mg.devs[r]];
-        const hipError_t e = hipStreamSynchronize(c.stream);
-        if (e != hipSuccess && rc == PV_OK)
-            rc = fail(PV_ERR_LAUNCH, std::string("pv_verify_batch_multi_gpu: ") + hipGetErrorString(e));
-    }
-    (void)hipSetDevice(cur);
-    if (rc) return rc;
-    for (int r = 0; r < G; r++) {  // shard r's words start at bit b[r] (a multiple of 64)
-        const uint64_t lo = b[r], hi = b[r + 1];
-        if (hi > lo) memcpy(verdict_bits + lo / 8, c0.h_mg.p + (uint64_t)r * wpr * 8, (hi - lo + 7) / 8);
-    }
-    return PV_OK;
-}
-
-int pv_host_alloc(void** p, uint64_t bytes) {
-    if (!p) return fail(PV_ERR_ARG, "pv_host_alloc: null pointer");
-    *p = nullptr;
-    bytes = std::max<uint64_t>(bytes, 64);
-    pvhost::PinnedCache::Block b = pinned_cache().take(bytes);  // a block an earlier pv_host_free released
-    if (!b.p) {
-        b.bytes = bytes;
-        if (hipHostMalloc(&b.p, bytes, hipHostMallocPortable) != hipSuccess) {
-            (void)hipGetLastError();
-            pinned_release(pinned_cache().drain());  // the cached blocks back to the system, then once more
-            PV_HIP(hipHostMalloc(&b.p, bytes, hipHostMallocPortable), PV_ERR_ALLOC);
-        }
-    }
-    g_pinned_alloc.add(b.p, b.bytes);
-    *p = b.p;
-    return PV_OK;
-}
-int pv_host_free(void* p) {
-    if (!p) return PV_OK;
-    const uint64_t bytes = g_pinned_alloc.size_of(p);
-    if (!bytes || !g_pinned_alloc.remove(p)) return fail(PV_ERR_ARG, "pv_host_free: not a pv_host_alloc block");
-    pinned_release(pinned_cache().put(p, bytes));  // kept pinned for the next allocation of a similar size
-    return PV_OK;
-}
-int pv_host_register(void* p, uint64_t bytes) {
-    if (!p || bytes == 0) return fail(PV_ERR_ARG, "pv_host_register: empty range");
-    PV_HIP(hipHostRegister(p, bytes, hipHostRegisterPortable), PV_ERR_ALLOC);
-    g_pinned_reg.add(p, bytes);
-    return PV_OK;
-}
-int pv_host_unregister(void* p) {
-    if (!p || g_pinned_reg.size_of(p) == 0) return fail(PV_ERR_ARG, "pv_host_unregister: not a registered range");
-    // the runtime first: if it refuses, the registry still describes what is pinned
-    PV_HIP(hipHostUnregister(p), PV_ERR_ALLOC);
-    (void)g_pinned_reg.remove(p);
-    return PV_OK;
-}
-int pv_host_is_pinned(const void* p, uint64_t bytes) { return pv_is_pinned(p, bytes) ? 1 : 0; }
-
 int pv_test_clock_stamps(uint64_t* out, uint32_t max_blocks) {
 #if PV_CLOCK_PROBE
     const uint32_t k = std::min<uint32_t>(max_blocks, PV_CLOCK_SLOTS);
@@ -3869,54 +2676,6 @@ int pv_test_clock_stamps(uint64_t* out, uint32_t max_blocks) {
 #endif
 }
 
-int pv_test_inject(int what, int device, int count) {
-    const char* on = getenv("PV_ENABLE_TEST_HOOKS");
-    if (!on || strcmp(on, "1") != 0) return fail(PV_ERR_ARG, "pv_test_inject: test hooks are disabled (PV_ENABLE_TEST_HOOKS=1)");
-    if (what != PV_INJECT_STAGE) return fail(PV_ERR_ARG, "pv_test_inject: unknown fault");
-    if (device < 0 || device >= PV_MAX_DEV || count < 0) return fail(PV_ERR_ARG, "pv_test_inject: bad device / count");
-    std::lock_guard<std::mutex> lk(g_mus[device]);
-    g_ctxs[device].inject_stage = count;
-    return PV_OK;
-}
-
-int pv_dev_alloc(void** p, uint64_t bytes) {
-    PV_HIP(hipMalloc(p, std::max<uint64_t>(bytes, 16)), PV_ERR_ALLOC);
-    return PV_OK;
-}
-int pv_dev_free(void* p) {
-    PV_HIP(hipFree(p), PV_ERR_ALLOC);
-    return PV_OK;
-}
-}  // extern "C"
-
-namespace {
-// A copy ordered after every launch enqueued so far on the primary context, whatever stream the caller
-// gave it: the library stream first waits for the last launch's completion event, then copies; the
-// call returns once the copy is done. (A plain null-stream hipMemcpy is not ordered after the
-// library's non-blocking streams: a D2H could read verdict words before the launch wrote them, an H2D
-// could overwrite inputs a running launch still reads.)
-int ordered_copy(void* dst, const void* src, uint64_t bytes, hipMemcpyKind kind) {
-    if (bytes == 0) return PV_OK;
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) {
-        PV_HIP(hipMemcpy(dst, src, bytes, kind), PV_ERR_LAUNCH);
-        return PV_OK;
-    }
-    hipStream_t s = g_ctx.stream;
-    if (int rc = g_ctx.hand.begin(s)) return rc;
-    PV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s), PV_ERR_LAUNCH);
-    PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-    return PV_OK;
-}
-}  // namespace
-
-extern "C" {
-int pv_memcpy_h2d(void* dst, const void* src, uint64_t bytes) { return ordered_copy(dst, src, bytes, hipMemcpyHostToDevice); }
-int pv_memcpy_d2h(void* dst, const void* src, uint64_t bytes) { return ordered_copy(dst, src, bytes, hipMemcpyDeviceToHost); }
-int pv_last_zero_copy(void) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    return g_ctx.last_zero_copy ? 1 : 0;
-}
 int pv_sync(void) {
     PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
     return PV_OK;
@@ -3974,198 +2733,6 @@ int pv_key_cache_configure(uint32_t capacity) {
     k.slot_key.assign(capacity, std::string());
     for (uint32_t i = capacity; i-- > 0;) k.free_slots.push_back(i);
     return kc_upload_htab(g_ctx.stream);
-}
-
-// Builds the fresh keys' tables (slot PV_KC_EMPTY = evicted again within the same put) into their
-// cache slots, in batches of the workspace's comb capacity. async: one batch only (the caller caps
-// the keys), staged through the pinned h_async area and left running on the engine stream (the
-// next launch is stream-ordered after it). PV_TEST_FAIL_KC_PUT_BATCH=b (tests only) reports a
-// failure after batch b has been enqueued, to exercise the rollback.
-static int kc_build_tables(const std::vector<std::string>& fresh, const std::vector<uint32_t>& fresh_slot,
-                           bool async) {
-    auto& k = g_ctx.kc;
-    hipStream_t s = g_ctx.stream;
-    if (int rc = g_ctx.hand.begin(s)) return rc;
-    const char* fail_env = getenv("PV_TEST_FAIL_KC_PUT_BATCH");
-    const long fail_batch = fail_env ? atol(fail_env) : -1;
-    KeyWork kw = g_ctx.kw;
-    // the put builds comb index j's table in slot j of a scratch area: the part of ctab above the slots
-    // the resident-table directory may list when the batch fits there, else over the directory
-    constexpr uint64_t tab_q = (uint64_t)PV_COMB_POS * PV_COMB_ENT * 10;  // uint4 per table
-    uint4* const scratch_tab = g_ctx.kw.ctab + g_ctx.dir_cap * tab_q;
-    const uint32_t scratch_keys = kw.kcap - g_ctx.dir_cap;
-    std::vector<uint8_t> lpk;
-    std::vector<uint32_t> lslot;
-    long batch = 0;
-    for (size_t f0 = 0; f0 < fresh.size();) {
-        uint8_t* bpk;
-        uint32_t* bslot;
-        if (async) {  // pinned: keys [kcap][32], then slots [kcap]
-            bpk = k.h_async;
-            bslot = reinterpret_cast<uint32_t*>(k.h_async + (uint64_t)kw.kcap * 32);
-        } else {
-            lpk.resize((uint64_t)kw.kcap * 32);
-            lslot.resize(kw.kcap);
-            bpk = lpk.data();
-            bslot = lslot.data();
-        }
-        uint32_t m = 0;
-        size_t f = f0;
-        for (; f < fresh.size() && m < kw.kcap; f++) {
-            if (fresh_slot[f] == PV_KC_EMPTY) continue;
-            memcpy(bpk + 32ull * m, fresh[f].data(), 32);
-            bslot[m++] = fresh_slot[f];
-        }
-        f0 = f;
-        if (m == 0) continue;
-        if (async && f0 < fresh.size()) return fail(PV_ERR_ARG, "kc_build_tables: asynchronous put above one batch");
-        if (g_ctx.dir_on && m <= scratch_keys) {
-            kw.ctab = scratch_tab;
-        } else {
-            kw.ctab = g_ctx.kw.ctab;
-            g_ctx.dir_dirty = true;
-        }
-        PV_HIP(hipMemcpyAsync(k.d_put_pk, bpk, 32ull * m, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(k.d_put_slot, bslot, (uint64_t)m * 4, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        hipLaunchKernelGGL(pv_kc_put_prep_kernel, dim3((m + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0, s, kw, m);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        const Gate gate{kw.nkeys, kw.slot_req};
-        hipLaunchKernelGGL(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(m, PV_LP_CHAIN_BLOCKS)), dim3(64), 0, s,
-                           k.d_put_pk, kw, gate, 0, PV_COMB_POS);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        const uint64_t items = (uint64_t)m * PV_COMB_POS * PV_COMB_BLOCKS;
-        hipLaunchKernelGGL(pv_key_fill_kernel, dim3((unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096)),
-                           dim3(PV_BLOCK), 0, s, kw, gate, 0, PV_COMB_POS);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        hipLaunchKernelGGL(pv_kc_scatter_kernel, dim3(64, m), dim3(PV_BLOCK), 0, s, kw.ctab, kw.key_flag, k.d_put_pk,
-                           k.d_put_slot, m, k.d_tab, k.d_flags, k.d_keys);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        if (k.d_ntab) {
-            hipLaunchKernelGGL(pv_kc_affine_kernel, dim3((m * PV_COMB_POS + 63) / 64), dim3(64), 0, s, k.d_tab,
-                               k.d_put_slot, m, k.d_ntab);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        }
-        if (k.d_wtab) {
-            bool any = false;
-            for (uint32_t j = 0; j < m && !any; j++) any = bslot[j] < k.wcap;
-            for (uint32_t j0 = 0; any && j0 < m; j0 += PV_KW_GROUP) {
-                const uint32_t g = std::min<uint32_t>(PV_KW_GROUP, m - j0);
-                const uint64_t threads = (uint64_t)g * PV_KW_POS * PV_KW_RUNS;
-                hipLaunchKernelGGL(pv_kc_wide_kernel, dim3((unsigned)((threads + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK),
-                                   0, s, kw, k.d_put_slot, j0, g, k.wcap, k.d_wtab, k.d_wscr);
-                PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-            }
-        }
-        if (!async) PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);  // bpk / bslot are host locals
-        if (batch++ == fail_batch) return fail(PV_ERR_LAUNCH, "pv_key_cache_put: injected failure (PV_TEST_FAIL_KC_PUT_BATCH)");
-    }
-    return PV_OK;
-}
-
-// LRU refresh on use: the slots that launches read since the last fold (d_stamp newer than
-// fold_epoch) move to the front of the LRU, least recently read first, so eviction takes the least
-// recently USED keys rather than the least recently put. Launches still running on other streams are
-// folded at the next eviction.
-static int kc_fold_hits() {
-    auto& k = g_ctx.kc;
-    if (!k.d_stamp || k.cap == 0) return PV_OK;
-    std::vector<uint32_t> st(k.cap);
-    PV_HIP(hipMemcpyAsync(st.data(), k.d_stamp, (uint64_t)k.cap * 4, hipMemcpyDeviceToHost, g_ctx.stream), PV_ERR_LAUNCH);
-    PV_HIP(hipStreamSynchronize(g_ctx.stream), PV_ERR_LAUNCH);
-    std::vector<std::pair<uint32_t, uint32_t>> used;  // (age of the stamp past the fold, slot), LRU order
-    for (auto it = k.lru.rbegin(); it != k.lru.rend(); ++it) {
-        const uint32_t age = st[*it] - k.fold_epoch;
-        if ((int32_t)age > 0) used.emplace_back(age, *it);
-    }
-    std::stable_sort(used.begin(), used.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    for (const auto& u : used) {
-        auto it = k.index.find(k.slot_key[u.second]);
-        if (it != k.index.end() && *it->second == u.second) k.lru.splice(k.lru.begin(), k.lru, it->second);
-    }
-    k.fold_epoch = k.epoch;
-    return PV_OK;
-}
-
-// pv_key_cache_put under g_mu. async (automatic admission): at most kcap new keys, nothing waited
-// for (pinned staging; the hash-table upload and the hand-over event are stream-ordered after the build).
-static int kc_put_locked(const uint8_t* pks, uint64_t n, bool async) {
-    auto& k = g_ctx.kc;
-    if (async) {
-        if (k.async_pending) PV_HIP(hipEventSynchronize(k.ev_async), PV_ERR_LAUNCH);  // h_async is free again
-        k.async_pending = false;
-    }
-    // slots for the new keys (at most cap of them: the last cap distinct keys of the call win).
-    // The device hash table still holds the state before this call until kc_upload_htab below.
-    std::vector<std::string> fresh;
-    std::vector<uint32_t> fresh_slot, touched;
-    if (k.free_slots.size() < n && !k.lru.empty()) {
-        const int rc = kc_fold_hits();  // evictions ahead: take the launches' reads into account
-        if (rc != PV_OK) return rc;
-    }
-    for (uint64_t i = 0; i < n; i++) {
-        std::string key(reinterpret_cast<const char*>(pks + 32 * i), 32);
-        auto it = k.index.find(key);
-        if (it != k.index.end()) {  // refresh
-            k.lru.splice(k.lru.begin(), k.lru, it->second);
-            continue;
-        }
-        uint32_t slot;
-        if (!k.free_slots.empty()) {
-            slot = k.free_slots.back();
-            k.free_slots.pop_back();
-        } else {  // evict the least recently put key
-            slot = k.lru.back();
-            k.lru.pop_back();
-            k.index.erase(k.slot_key[slot]);
-            k.seen.forget(reinterpret_cast<const uint8_t*>(k.slot_key[slot].data()));  // re-admissible
-            for (size_t f = 0; f < fresh.size(); f++)
-                if (fresh_slot[f] == slot) fresh_slot[f] = PV_KC_EMPTY;  // evicted before it was built
-        }
-        k.lru.push_front(slot);
-        k.index[key] = k.lru.begin();
-        k.slot_key[slot] = key;
-        fresh.push_back(key);
-        fresh_slot.push_back(slot);
-        touched.push_back(slot);
-    }
-    int rc = kc_build_tables(fresh, fresh_slot, async);
-    if (rc != PV_OK) {
-        // roll back to a state in which every indexed key's table is built: every slot this call
-        // assigned (its new key's table may be unbuilt, and its evicted key's table may already be
-        // overwritten) leaves the index and returns to the free list; the keys this call did not
-        // touch keep their slots. Then the device hash table is re-uploaded; if even that fails,
-        // the cache is switched off (kc_view() reports it empty) until configure / clear.
-        const std::string err = g_err;
-        std::vector<char> seen(k.cap, 0);
-        for (uint32_t slot : touched) {
-            if (seen[slot]) continue;
-            seen[slot] = 1;
-            auto it = k.index.find(k.slot_key[slot]);
-            if (it != k.index.end() && *it->second == slot) {
-                k.lru.erase(it->second);
-                k.index.erase(it);
-            }
-            k.slot_key[slot].clear();
-            k.free_slots.push_back(slot);
-        }
-        (void)hipStreamSynchronize(g_ctx.stream);
-        if (kc_upload_htab(g_ctx.stream) != PV_OK) k.broken = true;
-        g_err = err;
-        return rc;
-    }
-    g_ctx.last_keyed = false;
-    if (async) {
-        rc = kc_upload_htab(g_ctx.stream, reinterpret_cast<uint32_t*>(k.h_async + (uint64_t)g_ctx.kw.kcap * 36));
-        if (rc == PV_OK) {
-            PV_HIP(hipEventRecord(k.ev_async, g_ctx.stream), PV_ERR_LAUNCH);
-            k.async_pending = true;
-        }
-    } else {
-        rc = kc_upload_htab(g_ctx.stream);
-    }
-    if (int rc2 = g_ctx.hand.end(g_ctx.stream)) return rc2;
-    k.broken = rc != PV_OK;  // a complete upload also repairs an earlier failed one
-    return rc;
 }
 
 int pv_key_cache_put(const uint8_t* pks, uint64_t n) {
@@ -4253,190 +2820,6 @@ int pv_stream_destroy(void* stream) {
 int pv_stream_sync(void* stream) {
     PV_HIP(hipStreamSynchronize(stream ? (hipStream_t)stream : g_ctx.stream), PV_ERR_LAUNCH);
     return PV_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- signing
-namespace {
-
-// Room for `signers` expanded keys, and the hand-over: `stream` waits for the workspace's last user.
-// Caller holds g_mu.
-int sg_begin(uint64_t signers, hipStream_t stream) {
-    auto& g = g_ctx.sg;
-    if (int rc = g.d_keys.grow(std::max<uint64_t>(signers, 4096) * 64)) return rc;
-    return g.hand.begin(stream);
-}
-// The expanded keys are overwritten behind the kernels that read them, and the workspace released.
-int sg_end(uint64_t signers, hipStream_t stream) {
-    auto& g = g_ctx.sg;
-    const hipError_t e = hipMemsetAsync(g.d_keys.p, 0, signers * 64, stream);
-    if (int rc = g.hand.end(stream)) return rc;
-    if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: key scrub: ") + hipGetErrorString(e));
-    return PV_OK;
-}
-// Key expansion of `signers` seeds (seed_q uint4 apart); d_pk: also the public keys (keypair entry).
-int sg_keys(const uint8_t* d_seeds, uint32_t seed_q, uint64_t signers, uint8_t* d_pk, hipStream_t stream) {
-    const unsigned grid = (unsigned)((signers + PV_BLOCK - 1) / PV_BLOCK);
-    PV_LAUNCH_BC2(pv_sign_keys_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, reinterpret_cast<const uint4*>(d_seeds),
-                  seed_q, signers, g_ctx.sg.d_keys.as<uint4>(), reinterpret_cast<uint4*>(d_pk), g_ctx.d_bc2);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-    return PV_OK;
-}
-// Messages [c0, c0 + m) of a batch whose offsets d_off (already moved to c0) index d_msg.
-int sg_chunk(const uint8_t* d_msg, const uint64_t* d_off, uint64_t m, const uint8_t* d_sk, uint64_t n_signers,
-             const uint32_t* d_idx, uint64_t idx_base, uint8_t* d_sig, hipStream_t stream) {
-    const unsigned grid = (unsigned)((m + PV_BLOCK - 1) / PV_BLOCK);
-    PV_LAUNCH_BC2(pv_sign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_msg, d_off, m,
-                  reinterpret_cast<const uint4*>(d_sk), g_ctx.sg.d_keys.as<uint4>(), n_signers, d_idx, idx_base,
-                  reinterpret_cast<uint4*>(d_sig), g_ctx.d_bc2);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-    return PV_OK;
-}
-constexpr uint64_t PV_SIGN_MAX = 0xffffffffull;  // items / signers per call (32-bit lane indices)
-
-// Device-buffer batch on `stream` (caller holds g_mu): expansion of every signer, then the chunks.
-int sg_enqueue(const uint8_t* d_msg, const uint64_t* d_off, uint64_t n, const uint8_t* d_sk, uint64_t n_signers,
-               const uint32_t* d_idx, uint8_t* d_sig, hipStream_t stream) {
-    int rc = sg_begin(n_signers, stream);
-    if (rc) return rc;
-    rc = sg_keys(d_sk, 4, n_signers, nullptr, stream);
-    for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK)
-        rc = sg_chunk(d_msg, d_off + c0, std::min<uint64_t>(PV_SIGN_CHUNK, n - c0), d_sk, n_signers,
-                      d_idx ? d_idx + c0 : nullptr, c0, d_sig + 64 * c0, stream);
-    const int rc2 = sg_end(n_signers, stream);
-    return rc ? rc : rc2;
-}
-
-// The host entries' copies of secret keys / seeds: overwritten on the device behind the work on `stream`
-// and, once that is done, in pinned memory.
-int sg_scrub_secrets(uint64_t bytes, hipStream_t stream) {
-    auto& g = g_ctx.sg;
-    hipError_t e = g.d_sk.p ? hipMemsetAsync(g.d_sk.p, 0, std::min(bytes, g.d_sk.cap), stream) : hipSuccess;
-    const hipError_t e2 = hipStreamSynchronize(stream);
-    if (g.h_sk.p) memset(g.h_sk.p, 0, std::min(bytes, g.h_sk.cap));
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: secret scrub: ") + hipGetErrorString(e));
-    return PV_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pv_sign_batch_device(const uint8_t* d_msg, const uint64_t* d_msg_off, uint64_t n, const uint8_t* d_sk,
-                         uint64_t n_signers, const uint32_t* d_signer_idx, uint8_t* d_sig_out, void* stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_batch_device: call pv_init first");
-    if (n == 0) return PV_OK;
-    if (!d_msg || !d_msg_off || !d_sk || !d_sig_out) return fail(PV_ERR_ARG, "pv_sign_batch_device: null pointer");
-    if (n_signers == 0 || n > PV_SIGN_MAX || n_signers > PV_SIGN_MAX)
-        return fail(PV_ERR_ARG, "pv_sign_batch_device: no signers, or more than 2^32 - 1 items");
-    if (!d_signer_idx && n_signers != n)
-        return fail(PV_ERR_ARG, "pv_sign_batch_device: without signer_idx, n_signers must equal n");
-    if ((reinterpret_cast<uintptr_t>(d_sk) | reinterpret_cast<uintptr_t>(d_sig_out)) & 15u)
-        return fail(PV_ERR_ARG, "pv_sign_batch_device: d_sk and d_sig_out must be 16-byte aligned");
-    return sg_enqueue(d_msg, d_msg_off, n, d_sk, n_signers, d_signer_idx, d_sig_out,
-                      stream ? (hipStream_t)stream : g_ctx.stream);
-}
-
-int pv_sign_batch(const uint8_t* msg, const uint64_t* msg_off, uint64_t n, const uint8_t* sk, uint64_t n_signers,
-                  const uint32_t* signer_idx, uint8_t* sig_out) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_batch: call pv_init first");
-    if (n == 0) return PV_OK;
-    if (!msg_off || !sk || !sig_out) return fail(PV_ERR_ARG, "pv_sign_batch: null pointer");
-    if (n_signers == 0 || n > PV_SIGN_MAX || n_signers > PV_SIGN_MAX)
-        return fail(PV_ERR_ARG, "pv_sign_batch: no signers, or more than 2^32 - 1 items");
-    if (!signer_idx && n_signers != n) return fail(PV_ERR_ARG, "pv_sign_batch: without signer_idx, n_signers must equal n");
-    // everything the kernels index with is validated, so a bad argument is an error and never a fault
-    // (of a bad offset and a bad signer index, the one at the earlier item is reported; the offset at a tie)
-    uint64_t bad_idx = n;
-    for (uint64_t i = 0; i < n && signer_idx && bad_idx == n; i++)
-        if (signer_idx[i] >= n_signers) bad_idx = i;
-    if (!pv_offsets_monotone(msg_off, std::min(bad_idx + 1, n)))
-        return fail(PV_ERR_ARG, "pv_sign_batch: offsets must be non-decreasing");
-    if (bad_idx < n) return fail(PV_ERR_ARG, "pv_sign_batch: signer index out of range");
-    if (!msg && msg_off[n] != msg_off[0]) return fail(PV_ERR_ARG, "pv_sign_batch: null message blob");
-    auto& g = g_ctx.sg;
-    const hipStream_t s = g_ctx.stream;
-    const uint64_t sk_bytes = n_signers * 64;
-    int rc;
-    if ((rc = g.h_sk.grow(sk_bytes, hipHostMallocDefault)) || (rc = g.d_sk.grow(sk_bytes)) ||
-        (rc = sg_begin(n_signers, s)))
-        return rc;
-    memcpy(g.h_sk.p, sk, sk_bytes);
-    auto run = [&]() -> int {
-        PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, sk_bytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        int rc = sg_keys(g.d_sk.p, 4, n_signers, nullptr, s);
-        for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK) {
-            // chunk staging: [offsets, rebased][signer indices][signatures][message bytes + slack]
-            const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
-            const uint64_t base = msg_off[c0], mbytes = msg_off[c0 + m] - base;
-            PvLayout l;
-            const uint64_t o_off = l.add((m + 1) * 8), o_idx = l.add(m * 4), o_sig = l.add(m * 64),
-                           o_msg = l.add(mbytes + PV_BLOB_SLACK), total = l.at;
-            if ((rc = g.h_stage.grow(total, hipHostMallocDefault)) || (rc = g.d_stage.grow(total))) break;
-            uint64_t* ho = reinterpret_cast<uint64_t*>(g.h_stage.p + o_off);
-            for (uint64_t i = 0; i <= m; i++) ho[i] = msg_off[c0 + i] - base;
-            if (signer_idx) memcpy(g.h_stage.p + o_idx, signer_idx + c0, m * 4);
-            if (mbytes) memcpy(g.h_stage.p + o_msg, msg + base, mbytes);
-            PV_HIP(hipMemcpyAsync(g.d_stage.p, g.h_stage.p, o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            if (mbytes)
-                PV_HIP(hipMemcpyAsync(g.d_stage.p + o_msg, g.h_stage.p + o_msg, mbytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            if ((rc = sg_chunk(g.d_stage.p + o_msg, reinterpret_cast<const uint64_t*>(g.d_stage.p + o_off), m, g.d_sk.p,
-                               n_signers, signer_idx ? reinterpret_cast<const uint32_t*>(g.d_stage.p + o_idx) : nullptr,
-                               c0, g.d_stage.p + o_sig, s)))
-                break;
-            PV_HIP(hipMemcpyAsync(g.h_stage.p + o_sig, g.d_stage.p + o_sig, m * 64, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-            memcpy(sig_out + 64 * c0, g.h_stage.p + o_sig, m * 64);
-        }
-        return rc;
-    };
-    rc = run();
-    const int rc2 = sg_end(n_signers, s);
-    const int rc3 = sg_scrub_secrets(sk_bytes, s);
-    return rc ? rc : (rc2 ? rc2 : rc3);
-}
-
-int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uint8_t* sk_out) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_seed_keypairs: call pv_init first");
-    if (n == 0) return PV_OK;
-    if (!seeds) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: null pointer");
-    if (n > PV_SIGN_MAX) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: more than 2^32 - 1 seeds");
-    auto& g = g_ctx.sg;
-    const hipStream_t s = g_ctx.stream;
-    const uint64_t cm = std::min<uint64_t>(PV_SIGN_CHUNK, n);
-    int rc;
-    if ((rc = g.h_sk.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_sk.grow(cm * 32)) ||
-        (rc = g.h_stage.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_stage.grow(cm * 32)) ||
-        (rc = sg_begin(cm, s)))
-        return rc;
-    auto run = [&]() -> int {
-        for (uint64_t c0 = 0; c0 < n; c0 += PV_SIGN_CHUNK) {
-            const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
-            memcpy(g.h_sk.p, seeds + 32 * c0, m * 32);
-            PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, m * 32, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            const int rc = sg_keys(g.d_sk.p, 2, m, g.d_stage.p, s);
-            if (rc) return rc;
-            PV_HIP(hipMemcpyAsync(g.h_stage.p, g.d_stage.p, m * 32, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-            for (uint64_t i = 0; i < m; i++) {
-                if (pk_out) memcpy(pk_out + 32 * (c0 + i), g.h_stage.p + 32 * i, 32);
-                if (sk_out) {
-                    memcpy(sk_out + 64 * (c0 + i), seeds + 32 * (c0 + i), 32);
-                    memcpy(sk_out + 64 * (c0 + i) + 32, g.h_stage.p + 32 * i, 32);
-                }
-            }
-        }
-        return PV_OK;
-    };
-    rc = run();
-    const int rc2 = sg_end(cm, s);
-    const int rc3 = sg_scrub_secrets(cm * 32, s);
-    return rc ? rc : (rc2 ? rc2 : rc3);
 }
 
 }  // extern "C"

@@ -10,9 +10,10 @@
 
 // The library's main stream (valid after pv_init).
 hipStream_t pv_engine_stream();
-// The workspaces outside pv_engine.hip (ingress, Merkle, state trie), each with the same pair of hooks:
-// pv_stream_destroy tells it that a caller stream is going (its hand-over forgets the stream), and
-// pv_shutdown releases it before the device contexts go.
+// The workspaces outside the device context (pv_ctx.h Ctx holds verification's and signing's): ingress,
+// Merkle and state trie, each with the same pair of hooks. pv_stream_destroy tells it that a caller
+// stream is going (its hand-over forgets the stream), and pv_shutdown releases it before the device
+// contexts go.
 void pv_ingress_forget_stream(void* stream);
 void pv_ingress_shutdown();
 void pv_merkle_forget_stream(void* stream);

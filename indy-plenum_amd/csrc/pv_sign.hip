@@ -1,0 +1,287 @@
+// libplenum_verify: batch Ed25519 signing on the engine's device context (kernels + C ABI entries).
+// The arithmetic is sign_core.h; the workspace is the `sg` member of Ctx (pv_ctx.h), used under the
+// context's mutex g_mu like the verification workspace; [r]B and [a]B read the engine's wide
+// fixed-base comb (Ctx::d_bc2), so the kernels are instantiated per radix like the engine's.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <algorithm>
+#include <mutex>
+#include <string>
+
+#include "sign_core.h"
+#include "verify_core.h"
+#include "pv_ctx.h"
+#include "../../include/plenum_verify.h"
+
+// ---------------------------------------------------------------------------------------- signing
+// Batch Ed25519 signing (sign_core.h: the arithmetic, and why it is NOT side-channel hardened). One
+// lane per item, wave64; every lane of a wave stays active to the end (the LDS staging of the comb
+// entries and the wave-wide inversion need whole waves), a lane past the batch or with a bad signer
+// index repeats the last item's work and stores nothing / zeros.
+static constexpr uint64_t PV_SIGN_CHUNK = 262144;  // messages (or seeds) per launch
+
+__device__ __forceinline__ void pv_ld8(uint32_t o[8], const uint4* p) {
+    const uint4 a = p[0], b = p[1];
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+}
+__device__ __forceinline__ void pv_st8(uint4* p, const uint32_t v[8], bool keep = true) {
+    p[0] = keep ? make_uint4(v[0], v[1], v[2], v[3]) : make_uint4(0, 0, 0, 0);
+    p[1] = keep ? make_uint4(v[4], v[5], v[6], v[7]) : make_uint4(0, 0, 0, 0);
+}
+
+// Per signer: key expansion of the seed at seeds[i * seed_q] (seed_q = 2: packed seeds; 4: the seed
+// half of 64-byte secret keys) to keys[4 i ..] = a mod L || prefix. With pk_out (the keypair entry,
+// kernel-uniform) also A = encode([a]B) to pk_out[2 i ..].
+template <int W>
+__global__ __launch_bounds__(PV_BLOCK, 2) void pv_sign_keys_kernel(const uint4* __restrict__ seeds, uint32_t seed_q,
+                                                                    uint64_t n, uint4* __restrict__ keys,
+                                                                    uint4* __restrict__ pk_out,
+                                                                    const uint4* __restrict__ bcomb) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * PV_BLOCK + threadIdx.x;
+    const bool in = i0 < n;
+    const uint64_t i = in ? i0 : n - 1;
+    uint32_t seed[8], a[8], prefix[8];
+    pv_ld8(seed, seeds + i * seed_q);
+    pv_sign_expand(a, prefix, seed);
+    if (in) {
+        pv_st8(keys + 4 * i, a);
+        pv_st8(keys + 4 * i + 2, prefix);
+    }
+    if (!pk_out) return;
+    __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    ge_p3 acc;
+    pv_sign_base_mult<W, Bc2<W>::POS>(acc, a, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u});
+    uint32_t enc[8];
+    pv_sign_encode(enc, acc, in, PvWaveInvert{});
+    if (in) pv_st8(pk_out + 2 * i, enc);
+}
+
+// Per message r of a chunk: signer s = sidx ? sidx[r] : idx_base + r; nonce hash, [r]B from the wide
+// comb, R by the wave's shared inversion, second hash over the key bytes as given (sk[s][32:64]), S, and
+// the 64-byte signature as four uint4 stores. s >= n_signers: 64 zero bytes.
+template <int W>
+__global__ __launch_bounds__(PV_BLOCK, 2) void pv_sign_kernel(const uint8_t* __restrict__ msg,
+                                                               const uint64_t* __restrict__ off, uint64_t n,
+                                                               const uint4* __restrict__ sk,
+                                                               const uint4* __restrict__ keys, uint64_t n_signers,
+                                                               const uint32_t* __restrict__ sidx, uint64_t idx_base,
+                                                               uint4* __restrict__ sig_out,
+                                                               const uint4* __restrict__ bcomb) {
+    const uint32_t r0 = blockIdx.x * PV_BLOCK + threadIdx.x;
+    const bool in = r0 < n;
+    const uint32_t r = in ? r0 : (uint32_t)n - 1;  // whole waves stay in step
+    const uint64_t s0 = sidx ? (uint64_t)sidx[r] : idx_base + r;
+    const bool ok = in && s0 < n_signers;
+    const uint64_t s = s0 < n_signers ? s0 : 0;  // a lane without a signer works on signer 0, stores zeros
+    const uint64_t o0 = off[r], mlen = off[r + 1] - o0;
+    const uint64_t maddr = reinterpret_cast<uint64_t>(msg + o0);
+    const DevMsg mw{reinterpret_cast<const uint32_t*>(maddr & ~3ull), (uint32_t)(maddr & 3)};
+    uint32_t rr[8], hdr[16];
+    {
+        uint32_t prefix[8];
+        pv_ld8(prefix, keys + 4 * s + 2);
+        pv_hash_hm<4>(rr, prefix, mlen, mw);
+    }
+    {
+        __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
+        const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        ge_p3 acc;
+        pv_sign_base_mult<W, Bc2<W>::POS>(acc, rr, DevB2Stage<Bc2<W>::ENT>{bcomb, &stg[wv][0][0], threadIdx.x & 63u});
+        pv_sign_encode(hdr, acc, ok, PvWaveInvert{});
+    }
+    pv_ld8(hdr + 8, sk + 4 * s + 2);
+    uint32_t k[8], a[8], S[8];
+    pv_hash_hm<8>(k, hdr, mlen, mw);
+    pv_ld8(a, keys + 4 * s);
+    pv_sign_s(S, k, a, rr);
+    if (in) {
+        pv_st8(sig_out + 4 * (uint64_t)r, hdr, ok);
+        pv_st8(sig_out + 4 * (uint64_t)r + 2, S, ok);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ host
+
+namespace {
+
+// Room for `signers` expanded keys, and the hand-over: `stream` waits for the workspace's last user.
+// Caller holds g_mu.
+int sg_begin(uint64_t signers, hipStream_t stream) {
+    auto& g = g_ctx.sg;
+    if (int rc = g.d_keys.grow(std::max<uint64_t>(signers, 4096) * 64)) return rc;
+    return g.hand.begin(stream);
+}
+// The expanded keys are overwritten behind the kernels that read them, and the workspace released.
+int sg_end(uint64_t signers, hipStream_t stream) {
+    auto& g = g_ctx.sg;
+    const hipError_t e = hipMemsetAsync(g.d_keys.p, 0, signers * 64, stream);
+    if (int rc = g.hand.end(stream)) return rc;
+    if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: key scrub: ") + hipGetErrorString(e));
+    return PV_OK;
+}
+// Key expansion of `signers` seeds (seed_q uint4 apart); d_pk: also the public keys (keypair entry).
+int sg_keys(const uint8_t* d_seeds, uint32_t seed_q, uint64_t signers, uint8_t* d_pk, hipStream_t stream) {
+    const unsigned grid = (unsigned)((signers + PV_BLOCK - 1) / PV_BLOCK);
+    PV_LAUNCH_BC2(pv_sign_keys_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, reinterpret_cast<const uint4*>(d_seeds),
+                  seed_q, signers, g_ctx.sg.d_keys.as<uint4>(), reinterpret_cast<uint4*>(d_pk), g_ctx.d_bc2);
+    return PV_OK;
+}
+// Messages [c0, c0 + m) of a batch whose offsets d_off (already moved to c0) index d_msg.
+int sg_chunk(const uint8_t* d_msg, const uint64_t* d_off, uint64_t m, const uint8_t* d_sk, uint64_t n_signers,
+             const uint32_t* d_idx, uint64_t idx_base, uint8_t* d_sig, hipStream_t stream) {
+    const unsigned grid = (unsigned)((m + PV_BLOCK - 1) / PV_BLOCK);
+    PV_LAUNCH_BC2(pv_sign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_msg, d_off, m,
+                  reinterpret_cast<const uint4*>(d_sk), g_ctx.sg.d_keys.as<uint4>(), n_signers, d_idx, idx_base,
+                  reinterpret_cast<uint4*>(d_sig), g_ctx.d_bc2);
+    return PV_OK;
+}
+constexpr uint64_t PV_SIGN_MAX = 0xffffffffull;  // items / signers per call (32-bit lane indices)
+
+// Device-buffer batch on `stream` (caller holds g_mu): expansion of every signer, then the chunks.
+int sg_enqueue(const uint8_t* d_msg, const uint64_t* d_off, uint64_t n, const uint8_t* d_sk, uint64_t n_signers,
+               const uint32_t* d_idx, uint8_t* d_sig, hipStream_t stream) {
+    int rc = sg_begin(n_signers, stream);
+    if (rc) return rc;
+    rc = sg_keys(d_sk, 4, n_signers, nullptr, stream);
+    for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK)
+        rc = sg_chunk(d_msg, d_off + c0, std::min<uint64_t>(PV_SIGN_CHUNK, n - c0), d_sk, n_signers,
+                      d_idx ? d_idx + c0 : nullptr, c0, d_sig + 64 * c0, stream);
+    const int rc2 = sg_end(n_signers, stream);
+    return rc ? rc : rc2;
+}
+
+// The host entries' copies of secret keys / seeds: overwritten on the device behind the work on `stream`
+// and, once that is done, in pinned memory.
+int sg_scrub_secrets(uint64_t bytes, hipStream_t stream) {
+    auto& g = g_ctx.sg;
+    hipError_t e = g.d_sk.p ? hipMemsetAsync(g.d_sk.p, 0, std::min(bytes, g.d_sk.cap), stream) : hipSuccess;
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (g.h_sk.p) memset(g.h_sk.p, 0, std::min(bytes, g.h_sk.cap));
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: secret scrub: ") + hipGetErrorString(e));
+    return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pv_sign_batch_device(const uint8_t* d_msg, const uint64_t* d_msg_off, uint64_t n, const uint8_t* d_sk,
+                         uint64_t n_signers, const uint32_t* d_signer_idx, uint8_t* d_sig_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_batch_device: call pv_init first");
+    if (n == 0) return PV_OK;
+    if (!d_msg || !d_msg_off || !d_sk || !d_sig_out) return fail(PV_ERR_ARG, "pv_sign_batch_device: null pointer");
+    if (n_signers == 0 || n > PV_SIGN_MAX || n_signers > PV_SIGN_MAX)
+        return fail(PV_ERR_ARG, "pv_sign_batch_device: no signers, or more than 2^32 - 1 items");
+    if (!d_signer_idx && n_signers != n)
+        return fail(PV_ERR_ARG, "pv_sign_batch_device: without signer_idx, n_signers must equal n");
+    if ((reinterpret_cast<uintptr_t>(d_sk) | reinterpret_cast<uintptr_t>(d_sig_out)) & 15u)
+        return fail(PV_ERR_ARG, "pv_sign_batch_device: d_sk and d_sig_out must be 16-byte aligned");
+    return sg_enqueue(d_msg, d_msg_off, n, d_sk, n_signers, d_signer_idx, d_sig_out,
+                      stream ? (hipStream_t)stream : g_ctx.stream);
+}
+
+int pv_sign_batch(const uint8_t* msg, const uint64_t* msg_off, uint64_t n, const uint8_t* sk, uint64_t n_signers,
+                  const uint32_t* signer_idx, uint8_t* sig_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_batch: call pv_init first");
+    if (n == 0) return PV_OK;
+    if (!msg_off || !sk || !sig_out) return fail(PV_ERR_ARG, "pv_sign_batch: null pointer");
+    if (n_signers == 0 || n > PV_SIGN_MAX || n_signers > PV_SIGN_MAX)
+        return fail(PV_ERR_ARG, "pv_sign_batch: no signers, or more than 2^32 - 1 items");
+    if (!signer_idx && n_signers != n) return fail(PV_ERR_ARG, "pv_sign_batch: without signer_idx, n_signers must equal n");
+    // everything the kernels index with is validated, so a bad argument is an error and never a fault
+    // (of a bad offset and a bad signer index, the one at the earlier item is reported; the offset at a tie)
+    uint64_t bad_idx = n;
+    for (uint64_t i = 0; i < n && signer_idx && bad_idx == n; i++)
+        if (signer_idx[i] >= n_signers) bad_idx = i;
+    if (!pv_offsets_monotone(msg_off, std::min(bad_idx + 1, n)))
+        return fail(PV_ERR_ARG, "pv_sign_batch: offsets must be non-decreasing");
+    if (bad_idx < n) return fail(PV_ERR_ARG, "pv_sign_batch: signer index out of range");
+    if (!msg && msg_off[n] != msg_off[0]) return fail(PV_ERR_ARG, "pv_sign_batch: null message blob");
+    auto& g = g_ctx.sg;
+    const hipStream_t s = g_ctx.stream;
+    const uint64_t sk_bytes = n_signers * 64;
+    int rc;
+    if ((rc = g.h_sk.grow(sk_bytes, hipHostMallocDefault)) || (rc = g.d_sk.grow(sk_bytes)) ||
+        (rc = sg_begin(n_signers, s)))
+        return rc;
+    memcpy(g.h_sk.p, sk, sk_bytes);
+    auto run = [&]() -> int {
+        PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, sk_bytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+        int rc = sg_keys(g.d_sk.p, 4, n_signers, nullptr, s);
+        for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK) {
+            // chunk staging: [offsets, rebased][signer indices][signatures][message bytes + slack]
+            const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
+            const uint64_t base = msg_off[c0], mbytes = msg_off[c0 + m] - base;
+            PvLayout l;
+            const uint64_t o_off = l.add((m + 1) * 8), o_idx = l.add(m * 4), o_sig = l.add(m * 64),
+                           o_msg = l.add(mbytes + PV_BLOB_SLACK), total = l.at;
+            if ((rc = g.h_stage.grow(total, hipHostMallocDefault)) || (rc = g.d_stage.grow(total))) break;
+            uint64_t* ho = reinterpret_cast<uint64_t*>(g.h_stage.p + o_off);
+            for (uint64_t i = 0; i <= m; i++) ho[i] = msg_off[c0 + i] - base;
+            if (signer_idx) memcpy(g.h_stage.p + o_idx, signer_idx + c0, m * 4);
+            if (mbytes) memcpy(g.h_stage.p + o_msg, msg + base, mbytes);
+            PV_HIP(hipMemcpyAsync(g.d_stage.p, g.h_stage.p, o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            if (mbytes)
+                PV_HIP(hipMemcpyAsync(g.d_stage.p + o_msg, g.h_stage.p + o_msg, mbytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            if ((rc = sg_chunk(g.d_stage.p + o_msg, reinterpret_cast<const uint64_t*>(g.d_stage.p + o_off), m, g.d_sk.p,
+                               n_signers, signer_idx ? reinterpret_cast<const uint32_t*>(g.d_stage.p + o_idx) : nullptr,
+                               c0, g.d_stage.p + o_sig, s)))
+                break;
+            PV_HIP(hipMemcpyAsync(g.h_stage.p + o_sig, g.d_stage.p + o_sig, m * 64, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
+            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
+            memcpy(sig_out + 64 * c0, g.h_stage.p + o_sig, m * 64);
+        }
+        return rc;
+    };
+    rc = run();
+    const int rc2 = sg_end(n_signers, s);
+    const int rc3 = sg_scrub_secrets(sk_bytes, s);
+    return rc ? rc : (rc2 ? rc2 : rc3);
+}
+
+int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uint8_t* sk_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_sign_seed_keypairs: call pv_init first");
+    if (n == 0) return PV_OK;
+    if (!seeds) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: null pointer");
+    if (n > PV_SIGN_MAX) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: more than 2^32 - 1 seeds");
+    auto& g = g_ctx.sg;
+    const hipStream_t s = g_ctx.stream;
+    const uint64_t cm = std::min<uint64_t>(PV_SIGN_CHUNK, n);
+    int rc;
+    if ((rc = g.h_sk.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_sk.grow(cm * 32)) ||
+        (rc = g.h_stage.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_stage.grow(cm * 32)) ||
+        (rc = sg_begin(cm, s)))
+        return rc;
+    auto run = [&]() -> int {
+        for (uint64_t c0 = 0; c0 < n; c0 += PV_SIGN_CHUNK) {
+            const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
+            memcpy(g.h_sk.p, seeds + 32 * c0, m * 32);
+            PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, m * 32, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+            const int rc = sg_keys(g.d_sk.p, 2, m, g.d_stage.p, s);
+            if (rc) return rc;
+            PV_HIP(hipMemcpyAsync(g.h_stage.p, g.d_stage.p, m * 32, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
+            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
+            for (uint64_t i = 0; i < m; i++) {
+                if (pk_out) memcpy(pk_out + 32 * (c0 + i), g.h_stage.p + 32 * i, 32);
+                if (sk_out) {
+                    memcpy(sk_out + 64 * (c0 + i), seeds + 32 * (c0 + i), 32);
+                    memcpy(sk_out + 64 * (c0 + i) + 32, g.h_stage.p + 32 * i, 32);
+                }
+            }
+        }
+        return PV_OK;
+    };
+    rc = run();
+    const int rc2 = sg_end(cm, s);
+    const int rc3 = sg_scrub_secrets(cm * 32, s);
+    return rc ? rc : (rc2 ? rc2 : rc3);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Ed25519 signing arithmetic (RFC 8032 / libsodium 1.0.18 crypto_sign_seed_keypair and
-// crypto_sign_detached), shared by the signing kernels (pv_engine.hip pv_sign_keys_kernel /
+// crypto_sign_detached), shared by the signing kernels (pv_sign.hip pv_sign_keys_kernel /
 // pv_sign_kernel) and the host check library (tests/native/signcheck.hip). Replaces, per signature,
 // stp_core/crypto/nacl_wrappers.py:141 (crypto_sign_seed_keypair) and :170 (crypto_sign) -> libnacl ->
 // libsodium.

@@ -33,7 +33,7 @@
 #include "../../include/plenum_verify.h"
 #include "sha256_host.h"
 
-int pv_fail(int code, const std::string& msg);  // pv_engine.hip
+int pv_fail(int code, const std::string& msg);  // workspace.h; defined in pv_engine.hip
 
 namespace {
 

@@ -486,7 +486,7 @@ PV_HD void pv_encode_prefix(const Src& src, bool* use, fe* c, int t0) {
     }
 }
 // The batch's one inversion: each lane inverts its own product (fe_invert), unless the caller passes a
-// wave-wide inverter (pv_engine.hip PvWaveInvert: every lane of the wave at once, limb-parallel).
+// wave-wide inverter (pv_engine_dev.h PvWaveInvert: every lane of the wave at once, limb-parallel).
 struct PvFeInvert {
     PV_HD void operator()(fe& x) const { fe_invert(x, x); }
 };

@@ -21,7 +21,7 @@ PV_ERR_NOT_INIT = -5
 PV_ERR_DECODE = -7
 PV_BLOB_SLACK = 256
 PV_ABI_VERSION = 1
-PV_SIGN_CHUNK = 262144  # messages per launch inside pv_sign_batch (csrc/pv_engine.hip PV_SIGN_CHUNK)
+PV_SIGN_CHUNK = 262144  # messages per launch inside pv_sign_batch (csrc/pv_sign.hip PV_SIGN_CHUNK)
 PV_BUILD_COMB_FUSED = 1  # pv_build_flags(): [S]B and [k](-A) of the comb path in one kernel
 
 PV_STAGES = ("keys", "prep", "table", "msm", "encode")  # PV_STAGE_* order
@@ -490,7 +490,7 @@ def last_split():
     return tuple(x.value for x in v)
 
 
-PV_TABLE_REUSE_CAP = 16384 - 2048  # default capacity of table reuse (csrc/pv_engine.hip PV_DIR_DEFAULT_CAP)
+PV_TABLE_REUSE_CAP = 16384 - 2048  # default capacity of table reuse (csrc/pv_engine_dev.h PV_DIR_DEFAULT_CAP)
 
 
 def table_reuse(on=True, capacity=0):

@@ -1,16 +1,12 @@
 #!/bin/bash
 # Build an A/B variant of libplenum_verify.so with extra defines into variants/<name>/ (selected at
 # run time with PLENUM_AMD_LIB=variants/<name>/libplenum_verify.so). Usage: build_variant.sh NAME -DX=1 ...
+# Every source of the library's Makefile is compiled with the flags (its SRC is the one list of them).
 set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/variants/$name
-mkdir -p "$out/build"
-cd "$root/indy-plenum_amd"
-for f in pv_engine.hip pv_latency.hip pv_ingress.hip host_prep.cpp signing_json.cpp; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -Wall "$@" -c -o "$out/build/$f.o" "csrc/$f" &
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$out/libplenum_verify.so" "$out"/build/*.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+make -s -j16 -C "$root/indy-plenum_amd" EXTRA="$*" BUILD="$out/build" OUT="$out/libplenum_verify.so" \
+  "$out/libplenum_verify.so"
 rm -rf "$out/build"
 echo "$out/libplenum_verify.so"
