@@ -33,6 +33,10 @@ inline int env_int(const char* name, int dflt) {
 struct Ctx {
     int device = -1;
     int cus = 0;
+    // Everything the context creates once and keeps until pv_shutdown (workspace.h): the streams and
+    // events below, the blocks of work / kw / xt, the fixed-base tables, h_zc_verdict, kc.ev_async. The
+    // fields are what the code reads; ctx_free releases through `own` alone.
+    PvOwner own;
     hipStream_t stream = nullptr;
     hipStream_t kstream = nullptr;           // per-key pipeline (chain + table fill), overlapped
     hipEvent_t ev_keys_ready = nullptr;      // dedup done (main -> Straus side stream)
@@ -97,6 +101,7 @@ struct Ctx {
     int nranks = 1, rank = 0;
     // node-side key cache (keycache.h): device arrays + host index (LRU, most recent first)
     struct {
+        PvOwner own;  // the device and pinned blocks below: they live from one configure call to the next
         uint32_t cap = 0;
         uint32_t* d_htab = nullptr;
         uint32_t* d_keys = nullptr;
@@ -130,7 +135,7 @@ struct Ctx {
         // pinned staging of an asynchronous put (keys, slots, hash table), reused once ev_async is done
         uint8_t* h_async = nullptr;
         uint64_t h_async_cap = 0;
-        hipEvent_t ev_async = nullptr;
+        hipEvent_t ev_async = nullptr;  // the context's (Ctx::own): it outlives a reconfigure
         bool async_pending = false;
     } kc;
     // zero-copy verdict bytes (pinned, coherent: the host reads them while the kernel runs)

@@ -1665,19 +1665,17 @@ thread_local std::string g_err;
 
 namespace {
 
+// Empties the key cache. enabled, auto_min, the admission counters, seed and ev_async survive: a
+// reconfigure keeps them.
 void kc_free() {
     auto& k = g_ctx.kc;
-    for (void* p : {(void*)k.d_htab, (void*)k.d_keys, (void*)k.d_flags, (void*)k.d_tab, (void*)k.d_ntab,
-                    (void*)k.d_wtab, (void*)k.d_wscr, (void*)k.d_put_pk, (void*)k.d_put_slot, (void*)k.d_stamp})
-        if (p) (void)hipFree(p);
+    if (k.async_pending && k.ev_async) (void)hipEventSynchronize(k.ev_async);  // the put reads h_async
+    k.async_pending = false;
+    k.own.release_all();
     k.d_htab = k.d_keys = k.d_flags = k.d_put_slot = k.d_wscr = k.d_stamp = nullptr;
     k.d_tab = k.d_ntab = k.d_wtab = nullptr;
+    k.d_put_pk = k.h_async = nullptr;
     k.wcap = 0;
-    k.d_put_pk = nullptr;
-    if (k.async_pending && k.ev_async) (void)hipEventSynchronize(k.ev_async);
-    k.async_pending = false;
-    if (k.h_async) (void)hipHostFree(k.h_async);
-    k.h_async = nullptr;
     k.h_async_cap = 0;
     k.cap = k.hmask = 0;
     k.broken = false;
@@ -1717,7 +1715,7 @@ int kc_upload_htab(hipStream_t s, uint32_t* hbuf = nullptr) {
 int ensure_events(int count) {
     while ((int)g_ctx.ev.size() < count) {
         hipEvent_t e;
-        PV_HIP(hipEventCreate(&e), PV_ERR_NO_DEVICE);
+        if (int rc = g_ctx.own.event(e, hipEventDefault)) return rc;
         g_ctx.ev.push_back(e);
     }
     return PV_OK;
@@ -2005,69 +2003,58 @@ int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const 
     return rc;
 }
 
-// The per-lane workspace: per-request rows (Work) and the keyed path's tables (KeyWork), ~15 GB.
+// The per-lane workspace: per-request rows (Work) and the keyed path's tables (KeyWork), ~15 GB, owned
+// by the context (Work::qb is never allocated: it only keeps the kernel-argument layout).
 int lane_alloc_buffers(Work& w, KeyWork& kw) {
+    PvOwner& own = g_ctx.own;
     const uint64_t S = PV_CHUNK;
     w.stride = S;
-    PV_HIP(hipMalloc((void**)&w.atab, S * PV_ATAB_ENT * 160), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&w.digits, S * PV_DIGIT_ROWS * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&w.flags, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&w.q, S * 40 * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&w.aos, S * PV_PREP_AOS_QMAX * 16), PV_ERR_ALLOC);
+    if (int rc = own.dev(w.atab, S * PV_ATAB_ENT * 160)) return rc;
+    if (int rc = own.dev(w.digits, S * PV_DIGIT_ROWS * 4)) return rc;
+    if (int rc = own.dev(w.flags, S * 4)) return rc;
+    if (int rc = own.dev(w.q, S * 40 * 4)) return rc;
+    if (int rc = own.dev(w.aos, S * PV_PREP_AOS_QMAX * 16)) return rc;
     const uint64_t H = 2 * S;
     kw.hmask = (uint32_t)(H - 1);
     kw.kcap = PV_KEY_CAP;
     kw.seed = (uint32_t)std::random_device{}() | 1u;
-    PV_HIP(hipMalloc((void**)&kw.slot, H * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.slot_id, H * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.slot_cnt, H * 4 * PV_RANK_SUB), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.req_key, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.req_rank, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.nkeys, PV_SPLIT_ALLOC_WORDS * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.key_owner, (S + 64 * PV_NSEG) * 4), PV_ERR_ALLOC);  // key ids: segment-major
-    PV_HIP(hipMalloc((void**)&kw.key_cid, (S + 64 * PV_NSEG) * 4), PV_ERR_ALLOC);  // key ids: segment-major
-    PV_HIP(hipMalloc((void**)&kw.comb_key, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.key_flag, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.bases, (uint64_t)kw.kcap * PV_COMB_POS * PV_COMB_PTS * 160), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.ctab, (uint64_t)kw.kcap * PV_COMB_POS * PV_COMB_ENT * 160), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.key_count, (S + 64 * PV_NSEG) * 4), PV_ERR_ALLOC);  // key ids: segment-major
-    PV_HIP(hipMalloc((void**)&kw.key_cursor, (S + 64 * PV_NSEG) * 4), PV_ERR_ALLOC);  // key ids: segment-major
-    PV_HIP(hipMalloc((void**)&kw.slot_req, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.req_pos, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.skey, S * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.sverdict, S / 64 * 8), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.key_cslot, (S + 64 * PV_NSEG) * 4), PV_ERR_ALLOC);  // key ids: segment-major
-    PV_HIP(hipMalloc((void**)&kw.comb_cslot, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.need, (uint64_t)PV_ALLCOMB_KEYS * PV_COMB_POS * 5 * 4), PV_ERR_ALLOC);
+    if (int rc = own.dev(kw.slot, H * 4)) return rc;
+    if (int rc = own.dev(kw.slot_id, H * 4)) return rc;
+    if (int rc = own.dev(kw.slot_cnt, H * 4 * PV_RANK_SUB)) return rc;
+    if (int rc = own.dev(kw.req_key, S * 4)) return rc;
+    if (int rc = own.dev(kw.req_rank, S * 4)) return rc;
+    if (int rc = own.dev(kw.nkeys, PV_SPLIT_ALLOC_WORDS * 4)) return rc;
+    if (int rc = own.dev(kw.key_owner, (S + 64 * PV_NSEG) * 4)) return rc;  // key ids: segment-major
+    if (int rc = own.dev(kw.key_cid, (S + 64 * PV_NSEG) * 4)) return rc;  // key ids: segment-major
+    if (int rc = own.dev(kw.comb_key, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.key_flag, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.bases, (uint64_t)kw.kcap * PV_COMB_POS * PV_COMB_PTS * 160)) return rc;
+    if (int rc = own.dev(kw.ctab, (uint64_t)kw.kcap * PV_COMB_POS * PV_COMB_ENT * 160)) return rc;
+    if (int rc = own.dev(kw.key_count, (S + 64 * PV_NSEG) * 4)) return rc;  // key ids: segment-major
+    if (int rc = own.dev(kw.key_cursor, (S + 64 * PV_NSEG) * 4)) return rc;  // key ids: segment-major
+    if (int rc = own.dev(kw.slot_req, S * 4)) return rc;
+    if (int rc = own.dev(kw.req_pos, S * 4)) return rc;
+    if (int rc = own.dev(kw.skey, S * 4)) return rc;
+    if (int rc = own.dev(kw.sverdict, S / 64 * 8)) return rc;
+    if (int rc = own.dev(kw.key_cslot, (S + 64 * PV_NSEG) * 4)) return rc;  // key ids: segment-major
+    if (int rc = own.dev(kw.comb_cslot, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.need, (uint64_t)PV_ALLCOMB_KEYS * PV_COMB_POS * 5 * 4)) return rc;
     PV_HIP(hipMemset(kw.comb_cslot, 0xFF, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.comb_tslot, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_htab, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_keys, (uint64_t)kw.kcap * 32), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_flags, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_cnt, 2 * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.dir_stat, 5 * 8), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.aff_list, (uint64_t)PV_AFF_CAP * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.aff_cnt, 4), PV_ERR_ALLOC);
-    PV_HIP(hipMalloc((void**)&kw.aff_scr, (uint64_t)PV_AFF_CAP * PV_AFF_SEG * 10 * PV_AFF_THREADS * 4), PV_ERR_ALLOC);
+    if (int rc = own.dev(kw.comb_tslot, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.dir_htab, (uint64_t)PV_DIR_HASH * 4)) return rc;
+    if (int rc = own.dev(kw.dir_keys, (uint64_t)kw.kcap * 32)) return rc;
+    if (int rc = own.dev(kw.dir_flags, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.dir_cnt, 2 * 4)) return rc;
+    if (int rc = own.dev(kw.dir_stat, 5 * 8)) return rc;
+    if (int rc = own.dev(kw.aff_list, (uint64_t)PV_AFF_CAP * 4)) return rc;
+    if (int rc = own.dev(kw.aff_cnt, 4)) return rc;
+    if (int rc = own.dev(kw.aff_scr, (uint64_t)PV_AFF_CAP * PV_AFF_SEG * 10 * PV_AFF_THREADS * 4)) return rc;
     PV_HIP(hipMemset(kw.aff_cnt, 0, 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.comb_tslot, 0, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_cnt, 0, 2 * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_stat, 0, 5 * 8), PV_ERR_ALLOC);
     return PV_OK;
-}
-
-void lane_free_buffers(Work& w, KeyWork& kw) {
-    for (void* p : {(void*)w.atab, (void*)w.digits, (void*)w.flags, (void*)w.q, (void*)w.qb, (void*)w.aos,
-                    (void*)kw.slot, (void*)kw.slot_id, (void*)kw.slot_cnt, (void*)kw.req_key, (void*)kw.req_rank,
-                    (void*)kw.nkeys, (void*)kw.key_owner, (void*)kw.key_cid, (void*)kw.comb_key, (void*)kw.key_flag,
-                    (void*)kw.bases, (void*)kw.ctab, (void*)kw.key_count, (void*)kw.key_cursor, (void*)kw.slot_req,
-                    (void*)kw.req_pos, (void*)kw.skey, (void*)kw.sverdict, (void*)kw.key_cslot, (void*)kw.comb_cslot,
-                    (void*)kw.need, (void*)kw.comb_tslot, (void*)kw.dir_htab, (void*)kw.dir_keys, (void*)kw.dir_flags,
-                    (void*)kw.dir_cnt, (void*)kw.dir_stat, (void*)kw.aff_list, (void*)kw.aff_cnt, (void*)kw.aff_scr})
-        if (p) (void)hipFree(p);
-    w = Work{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-    kw = KeyWork{};
 }
 
 // Builds g_ctxs[device] (caller: g_mus[device] held, DevScope(device) active, context not built yet):
@@ -2084,20 +2071,21 @@ int ctx_init_parts(int device) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PV_ERR_NO_DEVICE, std::string("pv_init: built for gfx950, device is ") + prop.gcnArchName);
     g_ctx.cus = prop.multiProcessorCount;
-    PV_HIP(hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-    PV_HIP(hipStreamCreateWithFlags(&g_ctx.kstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
+    PvOwner& own = g_ctx.own;
+    if (int rc = own.stream(g_ctx.stream, hipStreamNonBlocking)) return rc;
+    if (int rc = own.stream(g_ctx.kstream, hipStreamNonBlocking)) return rc;
     // stream-to-stream hand-overs inside the engine (one device, never read by the host) are recorded with
     // a device-scope release instead of the default system-scope fence: headline step 2.612-2.618 against
     // 2.620-2.624 ms interleaved (profiles/r05/ab_event_devscope.txt); PV_EVENT_DEVSCOPE=0 restores it
     const unsigned evf = hipEventDisableTiming | (env_flag_devscope() ? hipEventReleaseToDevice : 0u);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_keys_ready, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_scan_done, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_tables_ready, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipStreamCreateWithFlags(&g_ctx.fstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_chain, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_prep_done, evf), PV_ERR_NO_DEVICE);
-    PV_HIP(hipStreamCreateWithFlags(&g_ctx.sstream, hipStreamNonBlocking), PV_ERR_NO_DEVICE);
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_straus_done, evf), PV_ERR_NO_DEVICE);
+    if (int rc = own.event(g_ctx.ev_keys_ready, evf)) return rc;
+    if (int rc = own.event(g_ctx.ev_scan_done, evf)) return rc;
+    if (int rc = own.event(g_ctx.ev_tables_ready, evf)) return rc;
+    if (int rc = own.stream(g_ctx.fstream, hipStreamNonBlocking)) return rc;
+    if (int rc = own.event(g_ctx.ev_chain, evf)) return rc;
+    if (int rc = own.event(g_ctx.ev_prep_done, evf)) return rc;
+    if (int rc = own.stream(g_ctx.sstream, hipStreamNonBlocking)) return rc;
+    if (int rc = own.event(g_ctx.ev_straus_done, evf)) return rc;
     if (int rc = g_ctx.hand.ensure()) return rc;
     {
         // the host path's copy stream at the greatest priority: the runtime keeps such streams on hardware
@@ -2107,16 +2095,15 @@ int ctx_init_parts(int device) {
         PV_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest), PV_ERR_NO_DEVICE);
         const char* pe = getenv("PV_CSTREAM_PRIO");  // A/B knob: 0 = normal priority
         const bool hi = !(pe && *pe == '0');
-        PV_HIP(hipStreamCreateWithPriority(&g_ctx.cstream, hipStreamNonBlocking, hi ? greatest : least), PV_ERR_NO_DEVICE);
+        if (int rc = own.stream(g_ctx.cstream, hipStreamNonBlocking, hi ? greatest : least)) return rc;
     }
-    PV_HIP(hipEventCreateWithFlags(&g_ctx.ev_cstart, hipEventDisableTiming), PV_ERR_NO_DEVICE);
+    if (int rc = own.event(g_ctx.ev_cstart, hipEventDisableTiming)) return rc;
     std::vector<uint32_t> bt(PV_BTAB_ENTRIES * PV_BTAB_STRIDE);
     pv_build_b_table(bt.data());
-    PV_HIP(hipMalloc((void**)&g_ctx.d_btab, bt.size() * 4), PV_ERR_ALLOC);
+    if (int rc = own.dev(g_ctx.d_btab, bt.size() * 4)) return rc;
     PV_HIP(hipMemcpy(g_ctx.d_btab, bt.data(), bt.size() * 4, hipMemcpyHostToDevice), PV_ERR_ALLOC);
     {
-        int rc = lane_alloc_buffers(g_ctx.work, g_ctx.kw);
-        if (rc) return rc;
+        if (int rc = lane_alloc_buffers(g_ctx.work, g_ctx.kw)) return rc;
         std::vector<uint32_t> bc((size_t)PV_BCOMB_POS * PV_BCOMB_ENT * PV_BCOMB_STRIDE);
         {
             ge_p3 base[PV_BCOMB_POS];
@@ -2127,7 +2114,7 @@ int ctx_init_parts(int device) {
                                 std::cref(base[j]));
             for (auto& t : th) t.join();
         }
-        PV_HIP(hipMalloc((void**)&g_ctx.d_bcomb, bc.size() * 4), PV_ERR_ALLOC);
+        if (int rc = own.dev(g_ctx.d_bcomb, bc.size() * 4)) return rc;
         PV_HIP(hipMemcpy(g_ctx.d_bcomb, bc.data(), bc.size() * 4, hipMemcpyHostToDevice), PV_ERR_ALLOC);
         // the wide fixed-base comb, built on the device row by row (one scratch row of Z products)
         {
@@ -2137,9 +2124,9 @@ int ctx_init_parts(int device) {
             // 11, same verdicts; profiles/r02/ab_bcomb_radix.txt: ~2 % slower per step)
             const char* force16 = getenv("PV_FORCE_BCOMB16");
             if (PV_BC2_W == 16 || (force16 && *force16 && *force16 != '0') ||
-                hipMalloc((void**)&g_ctx.d_bc2, rows_ent * PV_BCOMB_STRIDE * 4) != hipSuccess) {
+                own.dev(g_ctx.d_bc2, rows_ent * PV_BCOMB_STRIDE * 4) != PV_OK) {
                 (void)hipGetLastError();  // clear a failed allocation's sticky error
-                g_ctx.d_bc2 = g_ctx.d_bcomb;
+                g_ctx.d_bc2 = g_ctx.d_bcomb;  // an alias: the owner holds the one block
                 g_ctx.bc2_w = 16;
             }
         }
@@ -2181,8 +2168,7 @@ int ctx_init_parts(int device) {
             if (rc != PV_OK) return rc;
         }
     }
-    PV_HIP(hipHostMalloc((void**)&g_ctx.h_zc_verdict, PV_ZC_MAX_REQ, hipHostMallocCoherent | hipHostMallocPortable),
-           PV_ERR_ALLOC);
+    if (int rc = own.pinned(g_ctx.h_zc_verdict, PV_ZC_MAX_REQ, hipHostMallocCoherent | hipHostMallocPortable)) return rc;
     if (const char* pad = getenv("PV_PREP_LDS_PAD")) g_ctx.prep_lds_pad = (uint32_t)atoi(pad);  // A/B knob
     {  // PV_TABLE_REUSE=0: start with table reuse off (pv_table_reuse), every keyed chunk builds its tables
         const char* tr = getenv("PV_TABLE_REUSE");
@@ -2201,39 +2187,12 @@ void ctx_free() {
     if (g_ctx.device < 0) return;
     (void)hipSetDevice(g_ctx.device);
     if (g_ctx.comm) ncclCommDestroy(g_ctx.comm);
-    if (g_ctx.h_zc_verdict) (void)hipHostFree(g_ctx.h_zc_verdict);
-    g_ctx.d_mg.release();
-    g_ctx.h_mg.release();
-    kc_free();
-    g_ctx.h_stage.release();
-    g_ctx.d_stage.release();
-    if (g_ctx.d_btab) (void)hipFree(g_ctx.d_btab);
-    lane_free_buffers(g_ctx.work, g_ctx.kw);
-    if (g_ctx.d_bcomb) (void)hipFree(g_ctx.d_bcomb);
-    if (g_ctx.d_bc2 && g_ctx.d_bc2 != g_ctx.d_bcomb) (void)hipFree(g_ctx.d_bc2);
-    for (hipEvent_t e : g_ctx.ev) (void)hipEventDestroy(e);
-    if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
-    if (g_ctx.kstream) (void)hipStreamDestroy(g_ctx.kstream);
-    if (g_ctx.ev_keys_ready) (void)hipEventDestroy(g_ctx.ev_keys_ready);
-    if (g_ctx.ev_scan_done) (void)hipEventDestroy(g_ctx.ev_scan_done);
-    if (g_ctx.ev_tables_ready) (void)hipEventDestroy(g_ctx.ev_tables_ready);
-    if (g_ctx.fstream) (void)hipStreamDestroy(g_ctx.fstream);
-    if (g_ctx.ev_chain) (void)hipEventDestroy(g_ctx.ev_chain);
-    if (g_ctx.ev_prep_done) (void)hipEventDestroy(g_ctx.ev_prep_done);
-    if (g_ctx.sstream) (void)hipStreamDestroy(g_ctx.sstream);
-    if (g_ctx.ev_straus_done) (void)hipEventDestroy(g_ctx.ev_straus_done);
+    kc_free();  // first: it waits for a pending asynchronous put
+    for (PvDevBuf* b : {&g_ctx.d_mg, &g_ctx.d_stage, &g_ctx.sg.d_keys, &g_ctx.sg.d_sk, &g_ctx.sg.d_stage}) b->release();
+    for (PvPinnedBuf* b : {&g_ctx.h_mg, &g_ctx.h_stage, &g_ctx.h_ver, &g_ctx.sg.h_sk, &g_ctx.sg.h_stage}) b->release();
     g_ctx.hand.destroy();
-    if (g_ctx.cstream) (void)hipStreamDestroy(g_ctx.cstream);
-    if (g_ctx.ev_cstart) (void)hipEventDestroy(g_ctx.ev_cstart);
-    for (hipEvent_t e : g_ctx.ev_copy) (void)hipEventDestroy(e);
-    g_ctx.h_ver.release();
-    for (void* p : {(void*)g_ctx.xt.htab, (void*)g_ctx.xt.keys, (void*)g_ctx.xt.flags, (void*)g_ctx.xt.tab})
-        if (p) (void)hipFree(p);
-    if (g_ctx.kc.ev_async) (void)hipEventDestroy(g_ctx.kc.ev_async);
-    for (PvDevBuf* b : {&g_ctx.sg.d_keys, &g_ctx.sg.d_sk, &g_ctx.sg.d_stage}) b->release();
-    g_ctx.sg.h_sk.release();
-    g_ctx.sg.h_stage.release();
     g_ctx.sg.hand.destroy();
+    g_ctx.own.release_all();
     g_ctx = Ctx();
 }
 
@@ -2691,38 +2650,40 @@ int pv_key_cache_configure(uint32_t capacity) {
     uint32_t H = 2;
     while (H < 2 * capacity) H <<= 1;
     const uint64_t per = (uint64_t)PV_COMB_POS * PV_COMB_ENT * 160;  // bytes per key table
-    hipError_t e;
-    if ((e = hipMalloc((void**)&k.d_tab, per * capacity)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_keys, (uint64_t)capacity * 32)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_flags, (uint64_t)capacity * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_htab, (uint64_t)H * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_stamp, (uint64_t)capacity * 4)) != hipSuccess ||
-        (e = hipMemset(k.d_stamp, 0, (uint64_t)capacity * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_put_pk, (uint64_t)g_ctx.kw.kcap * 32)) != hipSuccess ||
-        (e = hipMalloc((void**)&k.d_put_slot, (uint64_t)g_ctx.kw.kcap * 4)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&k.h_async, (uint64_t)g_ctx.kw.kcap * 36 + (uint64_t)H * 4,
-                           hipHostMallocDefault)) != hipSuccess ||
-        (!k.ev_async && (e = hipEventCreateWithFlags(&k.ev_async, hipEventDisableTiming)) != hipSuccess)) {
+    const uint64_t kcap = g_ctx.kw.kcap, async_bytes = kcap * 36 + (uint64_t)H * 4;
+    auto make = [&]() -> int {
+        if (int rc = k.own.dev(k.d_tab, per * capacity)) return rc;
+        if (int rc = k.own.dev(k.d_keys, (uint64_t)capacity * 32)) return rc;
+        if (int rc = k.own.dev(k.d_flags, (uint64_t)capacity * 4)) return rc;
+        if (int rc = k.own.dev(k.d_htab, (uint64_t)H * 4)) return rc;
+        if (int rc = k.own.dev(k.d_stamp, (uint64_t)capacity * 4)) return rc;
+        PV_HIP(hipMemset(k.d_stamp, 0, (uint64_t)capacity * 4), PV_ERR_ALLOC);
+        if (int rc = k.own.dev(k.d_put_pk, kcap * 32)) return rc;
+        if (int rc = k.own.dev(k.d_put_slot, kcap * 4)) return rc;
+        if (int rc = k.own.pinned(k.h_async, async_bytes, hipHostMallocDefault)) return rc;
+        // the context's, not the cache's: made on the first configure, kept across every later one
+        if (!k.ev_async) return g_ctx.own.event(k.ev_async, hipEventDisableTiming);
+        return PV_OK;
+    };
+    if (int rc = make()) {
         kc_free();
-        return fail(PV_ERR_ALLOC, std::string("pv_key_cache_configure: hipMalloc: ") + hipGetErrorString(e));
+        return rc;
     }
-    k.h_async_cap = (uint64_t)g_ctx.kw.kcap * 36 + (uint64_t)H * 4;
+    k.h_async_cap = async_bytes;
     // the affine rows (660 KB per key): optional -- without them cached keys use the cached-form rows
     static const bool affine = env_int("PV_KC_AFFINE", 1) != 0;
-    if (affine && hipMalloc((void**)&k.d_ntab, per * capacity) != hipSuccess) {
-        (void)hipGetLastError();
-        k.d_ntab = nullptr;
-    }
-    // the wide rows (67 MB per key) for the first min(capacity, PV_KC_WIDE_KEYS) slots: optional
+    if (affine && k.own.dev(k.d_ntab, per * capacity) != PV_OK) (void)hipGetLastError();
+    // the wide rows (67 MB per key) for the first min(capacity, PV_KC_WIDE_KEYS) slots: optional, and
+    // kept only together with their scratch
     {
         const uint32_t want = std::min<uint32_t>(capacity, (uint32_t)std::max(0, env_int("PV_KC_WIDE_KEYS", PV_KC_WIDE_KEYS)));
         const uint64_t per_w = (uint64_t)PV_KW_POS * PV_KW_ENT * 128;
-        if (want > 0 && hipMalloc((void**)&k.d_wtab, per_w * want) == hipSuccess &&
-            hipMalloc((void**)&k.d_wscr, (uint64_t)PV_KW_GROUP * PV_KW_POS * PV_KW_ENT * 40) == hipSuccess) {
+        if (want > 0 && k.own.dev(k.d_wtab, per_w * want) == PV_OK &&
+            k.own.dev(k.d_wscr, (uint64_t)PV_KW_GROUP * PV_KW_POS * PV_KW_ENT * 40) == PV_OK) {
             k.wcap = want;
         } else {
             (void)hipGetLastError();
-            if (k.d_wtab) (void)hipFree(k.d_wtab);
+            k.own.drop(k.d_wtab);
             k.d_wtab = nullptr;
             k.wcap = 0;
         }

@@ -178,15 +178,14 @@ static int ensure_xtab() {
     auto& x = g_ctx.xt;
     if (x.tab) return PV_OK;
     if (x.failed) return PV_ERR_ALLOC;
-    if (hipMalloc((void**)&x.htab, PV_XT_HASH * 4) != hipSuccess ||
-        hipMalloc((void**)&x.keys, PV_XT_KEYS * 32) != hipSuccess ||
-        hipMalloc((void**)&x.flags, PV_XT_KEYS * 4) != hipSuccess ||
-        hipMalloc((void**)&x.tab, (uint64_t)PV_XT_KEYS * PV_COMB_POS * PV_COMB_ENT * 160) != hipSuccess) {
+    PvOwner& own = g_ctx.own;
+    if (own.dev(x.htab, PV_XT_HASH * 4) || own.dev(x.keys, PV_XT_KEYS * 32) || own.dev(x.flags, PV_XT_KEYS * 4) ||
+        own.dev(x.tab, (uint64_t)PV_XT_KEYS * PV_COMB_POS * PV_COMB_ENT * 160)) {
         (void)hipGetLastError();
-        for (void* p : {(void*)x.htab, (void*)x.keys, (void*)x.flags, (void*)x.tab})
-            if (p) (void)hipFree(p);
+        own.drop(x.flags);  // whichever of them exist; x.tab, the last, failed
+        own.drop(x.keys);
+        own.drop(x.htab);
         x.htab = x.keys = x.flags = nullptr;
-        x.tab = nullptr;
         x.failed = true;
         return PV_ERR_ALLOC;
     }
@@ -375,7 +374,7 @@ int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, cons
     if ((rc = c.h_ver.grow(std::max<uint64_t>(v_bytes, 64 << 10), hipHostMallocPortable))) return rc;
     while (c.ev_copy.size() < np) {
         hipEvent_t e;
-        PV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PV_ERR_LAUNCH);
+        if ((rc = c.own.event(e, hipEventDisableTiming))) return rc;
         c.ev_copy.push_back(e);
     }
     hipStream_t cs = c.cstream;

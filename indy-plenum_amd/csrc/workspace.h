@@ -1,6 +1,7 @@
 // What every device workspace of libplenum_verify.so is made of (host code): the early-return macro,
-// grow-only device and pinned buffers, the event hand-over between caller streams, and the 256-byte
-// staging layout. Callers serialise use of a workspace on its own mutex.
+// grow-only device and pinned buffers, the owner of a set of resources created once, the event hand-over
+// between caller streams, and the 256-byte staging layout. Callers serialise use of a workspace on its
+// own mutex.
 #ifndef PV_WORKSPACE_H
 #define PV_WORKSPACE_H
 
@@ -8,6 +9,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/plenum_verify.h"
 
@@ -73,6 +75,70 @@ struct PvPinnedBuf {
     template <class T>
     T* as() const {
         return reinterpret_cast<T*>(p);
+    }
+};
+
+// The owner of a set of resources created once and released together (the engine context, its key
+// cache): each call creates one resource into the caller's plain field and remembers it, so release is
+// one call that cannot forget an entry. A failed creation leaves the field null and records nothing.
+// No destructor: an owner inside a global must not call a runtime that may be gone at process exit.
+struct PvOwner {
+    std::vector<void*> devs, pins;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+
+    template <class T>
+    int dev(T*& p, uint64_t bytes) {
+        void* q = nullptr;
+        p = nullptr;
+        PV_HIP(hipMalloc(&q, bytes), PV_ERR_ALLOC);
+        devs.push_back(q);
+        p = static_cast<T*>(q);
+        return PV_OK;
+    }
+    template <class T>
+    int pinned(T*& p, uint64_t bytes, unsigned flags) {
+        void* q = nullptr;
+        p = nullptr;
+        PV_HIP(hipHostMalloc(&q, bytes, flags), PV_ERR_ALLOC);
+        pins.push_back(q);
+        p = static_cast<T*>(q);
+        return PV_OK;
+    }
+    int stream(hipStream_t& s, unsigned flags) {
+        hipStream_t q = s = nullptr;
+        PV_HIP(hipStreamCreateWithFlags(&q, flags), PV_ERR_NO_DEVICE);
+        streams.push_back(s = q);
+        return PV_OK;
+    }
+    int stream(hipStream_t& s, unsigned flags, int priority) {
+        hipStream_t q = s = nullptr;
+        PV_HIP(hipStreamCreateWithPriority(&q, flags, priority), PV_ERR_NO_DEVICE);
+        streams.push_back(s = q);
+        return PV_OK;
+    }
+    int event(hipEvent_t& e, unsigned flags) {
+        hipEvent_t q = e = nullptr;
+        PV_HIP(hipEventCreateWithFlags(&q, flags), PV_ERR_NO_DEVICE);
+        events.push_back(e = q);
+        return PV_OK;
+    }
+    // Frees the recorded device block `p` now (the half of an optional pair whose other half failed).
+    void drop(void* p) {
+        for (size_t i = devs.size(); i-- > 0;)
+            if (devs[i] == p) {
+                (void)hipFree(p);
+                devs.erase(devs.begin() + i);
+                return;
+            }
+    }
+    // Each kind newest first. The device blocks go first: hipFree synchronises, so no stream or event
+    // is destroyed under work that is still running.
+    void release_all() {
+        while (!devs.empty()) (void)hipFree(devs.back()), devs.pop_back();
+        while (!pins.empty()) (void)hipHostFree(pins.back()), pins.pop_back();
+        while (!events.empty()) (void)hipEventDestroy(events.back()), events.pop_back();
+        while (!streams.empty()) (void)hipStreamDestroy(streams.back()), streams.pop_back();
     }
 };
 

@@ -1,7 +1,8 @@
 // csrc/workspace.h compiled with g++ against the stub runtime in stub_hip/ (no GPU): the grow-only buffers
 // leave themselves empty after a failed allocation, the hand-over issues exactly the waits it should, the
-// staging layout never overlaps. Prints one JSON object of named checks; tests/test_workspace_host.py
-// builds this with -fsanitize=address,undefined and asserts on it.
+// staging layout never overlaps, the owner releases exactly what it created however far creation got.
+// Prints one JSON object of named checks; tests/test_workspace_host.py builds this with
+// -fsanitize=address,undefined and asserts on it.
 #include <stdio.h>
 
 #include <string>
@@ -60,6 +61,156 @@ static void check_buffer(const char* group, const char* alloc_name, Grow grow) {
     put(group, "second_release_is_no_call", calls() == at && b.p == nullptr && b.cap == 0);
     put(group, "grow_after_release", grow(b, 64) == PV_OK && b.cap == 64);
     b.release();
+}
+
+// What an engine context creates through its owner, in miniature and interleaved as there: 3 streams (one
+// with a priority), 4 events, 6 device blocks, 2 pinned blocks. rc[i] is creation i's return code.
+struct OwnerSet {
+    static constexpr int N = 15;
+    static constexpr unsigned EVF = hipEventDisableTiming | hipEventReleaseToDevice;
+    hipStream_t s[3] = {};
+    hipEvent_t e[4] = {};
+    uint32_t* d[6] = {};
+    uint8_t* h[2] = {};
+    int rc[N] = {};
+
+    void create(PvOwner& o) {
+        int i = 0;
+        rc[i++] = o.stream(s[0], hipStreamNonBlocking);
+        rc[i++] = o.stream(s[1], hipStreamNonBlocking);
+        rc[i++] = o.event(e[0], EVF);
+        rc[i++] = o.event(e[1], EVF);
+        rc[i++] = o.stream(s[2], hipStreamNonBlocking, -1);
+        rc[i++] = o.event(e[2], hipEventDisableTiming);
+        for (int j = 0; j < 3; j++) rc[i++] = o.dev(d[j], 400 * (j + 1));
+        rc[i++] = o.pinned(h[0], 64, hipHostMallocPortable);
+        for (int j = 3; j < 6; j++) rc[i++] = o.dev(d[j], 400 * (j + 1));
+        rc[i++] = o.pinned(h[1], 128, hipHostMallocDefault);
+        rc[i++] = o.event(e[3], 0);
+    }
+    // creation i's out-parameter is null
+    bool null_at(int i) const {
+        const bool null[N] = {!s[0], !s[1], !e[0], !e[1], !s[2], !e[2], !d[0], !d[1], !d[2], !h[0],
+                              !d[3], !d[4], !d[5], !h[1], !e[3]};
+        return null[i];
+    }
+    static bool is_block(int i) { return i >= 6 && i <= 13; }
+};
+
+static bool stub_balanced() {
+    const StubState& t = stub();
+    return t.dev_allocs == t.dev_frees && t.host_allocs == t.host_frees && t.events == t.events_destroyed &&
+           t.streams == t.streams_destroyed;
+}
+static bool owner_empty(const PvOwner& o) {
+    return o.devs.empty() && o.pins.empty() && o.streams.empty() && o.events.empty();
+}
+
+static void check_owner() {
+    PvOwner o;
+    {
+        OwnerSet a;
+        size_t at = calls();
+        a.create(o);
+        bool ok = true;
+        for (int i = 0; i < OwnerSet::N; i++) ok = ok && a.rc[i] == PV_OK && !a.null_at(i);
+        put("owner", "creates_all_non_null", ok && o.devs.size() == 6 && o.pins.size() == 2 && o.streams.size() == 3 &&
+                                                 o.events.size() == 4 && calls() == at + OwnerSet::N);
+        for (int j = 0; j < 6; j++) a.d[j][0] = a.d[j][100 * (j + 1) - 1] = 7;  // really that large
+        a.h[0][63] = a.h[1][127] = 7;
+        std::vector<StubCall> m = since(at, "hipMalloc"), hm = since(at, "hipHostMalloc");
+        ok = m.size() == 6 && hm.size() == 2;
+        for (size_t j = 0; ok && j < 6; j++) ok = m[j].a == 400 * (j + 1);
+        put("owner", "sizes_and_pinned_flags_unchanged", ok && hm[0].a == 64 && hm[0].b == hipHostMallocPortable &&
+                                                             hm[1].a == 128 && hm[1].b == hipHostMallocDefault);
+        std::vector<StubCall> sf = since(at, "hipStreamCreateWithFlags"), sp = since(at, "hipStreamCreateWithPriority"),
+                              ev = since(at, "hipEventCreateWithFlags");
+        put("owner", "stream_flags_and_priority_unchanged",
+            sf.size() == 2 && sf[0].a == (uintptr_t)a.s[0] && sf[1].a == (uintptr_t)a.s[1] &&
+                sf[0].b == hipStreamNonBlocking && sf[1].b == hipStreamNonBlocking && sp.size() == 1 &&
+                sp[0].a == (uintptr_t)a.s[2] && sp[0].b == hipStreamNonBlocking && sp[0].c == -1);
+        put("owner", "event_flags_unchanged", ev.size() == 4 && ev[0].b == OwnerSet::EVF && ev[1].b == OwnerSet::EVF &&
+                                                  ev[2].b == hipEventDisableTiming && ev[3].b == 0);
+        at = calls();
+        o.release_all();
+        put("owner", "release_all_balances_every_kind", stub_balanced() && owner_empty(o) && calls() == at + OwnerSet::N);
+        std::vector<StubCall> f = since(at, "hipFree"), hf = since(at, "hipHostFree"), sd = since(at, "hipStreamDestroy"),
+                              ed = since(at, "hipEventDestroy");
+        ok = f.size() == 6 && hf.size() == 2 && sd.size() == 3 && ed.size() == 4;
+        for (size_t j = 0; ok && j < 6; j++) ok = f[j].a == (uintptr_t)a.d[5 - j];
+        for (size_t j = 0; ok && j < 2; j++) ok = hf[j].a == (uintptr_t)a.h[1 - j];
+        for (size_t j = 0; ok && j < 3; j++) ok = sd[j].a == (uintptr_t)a.s[2 - j];
+        for (size_t j = 0; ok && j < 4; j++) ok = ed[j].a == (uintptr_t)a.e[3 - j];
+        put("owner", "releases_newest_first", ok);
+        at = calls();
+        o.release_all();
+        put("owner", "second_release_all_is_no_call", calls() == at && owner_empty(o));
+    }
+    {  // the emptied owner is used again
+        OwnerSet a;
+        a.create(o);
+        bool ok = true;
+        for (int i = 0; i < OwnerSet::N; i++) ok = ok && a.rc[i] == PV_OK && !a.null_at(i);
+        o.release_all();
+        put("owner", "used_again_after_release_all", ok && stub_balanced() && owner_empty(o));
+    }
+    {
+        OwnerSet a;
+        a.create(o);
+        size_t at = calls();
+        o.drop(a.d[2]);
+        std::vector<StubCall> f = since(at, "hipFree");
+        put("owner", "drop_frees_that_block_once",
+            calls() == at + 1 && f.size() == 1 && f[0].a == (uintptr_t)a.d[2] && o.devs.size() == 5);
+        at = calls();
+        int local = 0;
+        o.drop(&local);
+        o.drop(nullptr);
+        o.drop(a.d[2]);  // forgotten: not freed a second time (AddressSanitizer watches)
+        put("owner", "drop_of_unknown_pointer_is_no_call", calls() == at && o.devs.size() == 5);
+        at = calls();
+        o.release_all();
+        bool again = false;
+        for (const StubCall& c : since(at, "hipFree")) again = again || c.a == (uintptr_t)a.d[2];
+        put("owner", "release_all_skips_dropped_block", !again && since(at, "hipFree").size() == 5 && stub_balanced());
+    }
+    {  // a half-built context: creation k fails, the rest is made, one release_all leaves nothing behind
+        bool code = true, null = true, rest = true, named = true, balanced = true, recorded = true;
+        for (int k = 0; k < OwnerSet::N; k++) {
+            OwnerSet a;
+            stub().fail_in = k + 1;
+            g_last_error.clear();
+            a.create(o);
+            code = code && a.rc[k] == (OwnerSet::is_block(k) ? PV_ERR_ALLOC : PV_ERR_NO_DEVICE);
+            null = null && a.null_at(k);
+            for (int i = 0; i < OwnerSet::N; i++) rest = rest && (i == k || (a.rc[i] == PV_OK && !a.null_at(i)));
+            named = named && g_last_error.find("hip") == 0 && g_last_error.find("out of memory (stub)") != std::string::npos;
+            recorded = recorded && o.devs.size() + o.pins.size() + o.streams.size() + o.events.size() == OwnerSet::N - 1;
+            o.release_all();
+            balanced = balanced && stub_balanced() && owner_empty(o) && stub().fail_in == 0;
+        }
+        put("owner", "failed_creation_returns_its_error_code", code);
+        put("owner", "failed_creation_leaves_null", null);
+        put("owner", "failed_creation_names_call_and_error", named);
+        put("owner", "creations_around_a_failure_succeed", rest);
+        put("owner", "failed_creation_is_not_recorded", recorded);
+        put("owner", "release_all_after_any_failure_balances", balanced);
+    }
+    {  // an optional pair (the key cache's wide rows and their scratch): kept only if both exist
+        OwnerSet a;
+        a.create(o);
+        const size_t before = o.devs.size();
+        const uint64_t allocs = stub().dev_allocs, frees = stub().dev_frees;
+        uint32_t *first = nullptr, *second = (uint32_t*)&a;
+        bool ok = o.dev(first, 4096) == PV_OK && first != nullptr;
+        stub().fail_in = 1;
+        ok = ok && o.dev(second, 4096) == PV_ERR_ALLOC && second == nullptr;
+        o.drop(first);
+        put("owner", "optional_pair_leaves_count_as_before",
+            ok && o.devs.size() == before && stub().dev_allocs == allocs + 1 && stub().dev_frees == frees + 1);
+        o.release_all();
+        put("owner", "all_released_at_the_end", stub_balanced() && owner_empty(o));
+    }
 }
 
 int main() {
@@ -165,6 +316,7 @@ int main() {
         put("monotone", "decrease_at_last_pair", !pv_offsets_monotone(last, 4));
         put("monotone", "prefix_before_the_decrease", pv_offsets_monotone(last, 3));
     }
+    check_owner();
     printf("{%s}\n", g_json.c_str());
     return 0;
 }

@@ -394,3 +394,92 @@ def test_lru_refresh_and_readmission(nat, sodium, oracle):
     finally:
         kc.auto(0)
         kc.configure(0)
+
+
+# The cache's device blocks live from one configure call to the next, the context's from pv_init to
+# pv_shutdown: both release paths, run in a child process so this session's library state stays as it is.
+_RECONFIGURE_CHILD = r"""
+import json
+import numpy as np
+from plenum_amd import _native as N
+from oracle.libsodium_ref import LibSodium
+from vectors import pack
+
+sod, rng = LibSodium(), np.random.default_rng(83)
+signers = [sod.seed_keypair(rng.bytes(32)) for _ in range(4)]
+cases = []
+for i in range(8):
+    pk, sk = signers[i % 4]
+    m = rng.bytes(int(rng.integers(1, 200)))
+    cases.append((sod.sign_detached(m, sk) + m, pk))
+sm = bytearray(cases[2][0])
+sm[9] ^= 0x10  # one flipped signature bit
+cases[2] = (bytes(sm), cases[2][1])
+blob, off, pks = pack(cases)
+keys = [pk for pk, _ in signers]
+kc, out = N.KeyCache, {"want": [sod.sign_open_ok(s, pk) for s, pk in cases], "verdicts": [], "stats": []}
+
+
+def verify():
+    out["verdicts"].append(N.verify_sm_batch(blob, off, pks).tolist())
+
+
+def configure_put(capacity):
+    kc.configure(capacity)
+    kc.put(keys)
+    out["stats"].append(kc.stats())
+    verify()
+
+
+N.ensure_device()
+configure_put(8)
+# automatic admission on, the cache off: both survive the reconfigure, so the batch below admits nothing
+kc.auto(2)
+kc.enable(False)
+kc.configure(4)  # releases the first cache's blocks on a live context
+out["verdicts_disabled"] = N.verify_sm_batch(blob, off, pks).tolist()
+out["disabled"] = [kc.stats(), kc.auto_stats()]
+kc.auto(0)
+kc.enable(True)
+configure_put(4)
+kc.configure(0)
+out["stats"].append(kc.stats())
+verify()
+N.shutdown()
+N.ensure_device()
+configure_put(8)
+# the same batch with the cache on (a fresh context's default) does admit: the three signers with two
+# valid requests. The shutdown then meets an asynchronous put that nothing has waited for
+kc.configure(8)
+kc.auto(2)
+out["verdicts_enabled"] = N.verify_sm_batch(blob, off, pks).tolist()
+out["enabled"] = [kc.stats(), kc.auto_stats()]
+N.shutdown()
+print(json.dumps(out))
+"""
+
+
+def test_reconfigure_and_reinit_release_paths(sodium):
+    """pv_init; the cache configured for 8, 4 and 0 keys, then pv_shutdown, pv_init and 8 keys again; 8
+    requests of 4 cached signers (request 2 tampered) verified after each: libsodium's verdicts every time,
+    size 4 after each put, capacities 8, 4, 0, 8. pv_key_cache_enable(0) outlives a reconfigure: automatic
+    admission, which a disabled cache never performs, admits nothing after it, and admits on a fresh
+    context whose cache is on."""
+    import json
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([root, os.path.join(root, "indy-plenum_amd"), here, env.get("PYTHONPATH", "")])
+    r = subprocess.run([sys.executable, "-c", _RECONFIGURE_CHILD], cwd=root, env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    want = [True, True, False, True, True, True, True, True]
+    assert out["want"] == want
+    assert out["verdicts"] == [want] * 4
+    assert out["stats"] == [[4, 8], [4, 4], [0, 0], [4, 8]]
+    assert out["verdicts_disabled"] == want and out["disabled"] == [[0, 4], [0, 0]]
+    assert out["verdicts_enabled"] == want and out["enabled"] == [[3, 8], [3, 0]]

@@ -1,7 +1,7 @@
 """The shared pieces of the device workspaces (indy-plenum_amd/csrc/workspace.h: grow-only device and
-pinned buffers, the event hand-over between caller streams, the 256-byte staging layout, the offsets
-check), compiled with g++ against a stub HIP runtime (tests/native/stub_hip) that logs every call and can
-fail an allocation. Built with AddressSanitizer and UBSan and run as a stand-alone program. CPU only."""
+pinned buffers, the owner of a context's resources, the event hand-over between caller streams, the
+256-byte staging layout, the offsets check), compiled with g++ against a stub HIP runtime
+(tests/native/stub_hip) that logs every call and can fail a creation. Built with AddressSanitizer and UBSan and run as a stand-alone program. CPU only."""
 import json
 import os
 import subprocess
@@ -48,6 +48,16 @@ def test_hand_over_waits_only_for_another_stream(report):
     last, exactly one wait (on the waiting stream, for the recorded event) otherwise; a forgotten stream is
     never waited for; destroy, then begin, recreates the event."""
     _group(report, "hand", 15)
+
+
+def test_owner_releases_what_it_created_however_far_creation_got(report):
+    """PvOwner over 3 streams, 4 events, 6 device and 2 pinned blocks created interleaved as an engine context
+    creates them: sizes, flags and the priority reach the runtime unchanged; release_all balances every kind,
+    newest first, and a second one makes no call; drop frees one block once; with creation k failing, for
+    every k, that call returns its error code with a null out-parameter and one release_all leaves nothing
+    behind (the half-built context no GPU test can reach); an optional pair whose second half fails leaves
+    the owner as it was."""
+    _group(report, "owner", 19)
 
 
 def test_layout_sections_are_aligned_and_disjoint(report):
