@@ -146,15 +146,15 @@ struct Ctx {
     PvPinnedBuf h_mg;
     const uint32_t* last_nkeys = nullptr;  // split counters of the most recent keyed chunk
     // Signing workspace (pv_sign_*), its own: the expanded keys (a mod L || prefix, 64 B per signer), the
-    // host entries' copies of the secret keys / seeds (pinned and device) and their chunk staging. Handed
-    // over between callers' streams like the verification workspace. The secret parts are overwritten
-    // before a call returns (device entry: behind its kernels, on its stream).
+    // host entries' copy of the secret keys (pinned and device) and their pinned chunk stage, which also
+    // carries pv_sign_seed_keypairs' seeds. Handed over between callers' streams like the verification
+    // workspace. The secret parts are overwritten before a call returns (device entry: behind its
+    // kernels, on its stream).
     struct {
         PvDevBuf d_keys;
         PvDevBuf d_sk;
         PvPinnedBuf h_sk;
-        PvDevBuf d_stage;
-        PvPinnedBuf h_stage;
+        PvStage stage;
         PvHandover hand;
     } sg;
 };
@@ -185,13 +185,8 @@ extern thread_local std::string g_err;
 
 int fail(int code, const std::string& msg);
 
-// A kernel launch and its check: a launch the runtime refuses returns PV_ERR_LAUNCH from the caller.
-#define PV_LAUNCH(k, ...)                                                                          \
-    do {                                                                                           \
-        hipLaunchKernelGGL(k, __VA_ARGS__);                                                        \
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);                                                  \
-    } while (0)
-// The same for a kernel instantiated per wide-comb radix (Bc2<W>), launched for the radix pv_init chose.
+// PV_LAUNCH (workspace.h) for a kernel instantiated per wide-comb radix (Bc2<W>), launched for the radix
+// pv_init chose.
 #define PV_LAUNCH_BC2(k, ...)                                                                      \
     do {                                                                                           \
         if (g_ctx.bc2_w == 16) hipLaunchKernelGGL(k<16>, __VA_ARGS__);                             \

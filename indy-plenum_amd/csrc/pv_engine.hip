@@ -2188,8 +2188,9 @@ void ctx_free() {
     (void)hipSetDevice(g_ctx.device);
     if (g_ctx.comm) ncclCommDestroy(g_ctx.comm);
     kc_free();  // first: it waits for a pending asynchronous put
-    for (PvDevBuf* b : {&g_ctx.d_mg, &g_ctx.d_stage, &g_ctx.sg.d_keys, &g_ctx.sg.d_sk, &g_ctx.sg.d_stage}) b->release();
-    for (PvPinnedBuf* b : {&g_ctx.h_mg, &g_ctx.h_stage, &g_ctx.h_ver, &g_ctx.sg.h_sk, &g_ctx.sg.h_stage}) b->release();
+    for (PvDevBuf* b : {&g_ctx.d_mg, &g_ctx.d_stage, &g_ctx.sg.d_keys, &g_ctx.sg.d_sk}) b->release();
+    for (PvPinnedBuf* b : {&g_ctx.h_mg, &g_ctx.h_stage, &g_ctx.h_ver, &g_ctx.sg.h_sk}) b->release();
+    g_ctx.sg.stage.release();
     g_ctx.hand.destroy();
     g_ctx.sg.hand.destroy();
     g_ctx.own.release_all();

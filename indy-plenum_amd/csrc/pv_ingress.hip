@@ -463,9 +463,7 @@ struct IngWork {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     PvHandover hand;
-    // host-entry staging (pv_ingress_verify)
-    PvPinnedBuf h_stage;
-    PvDevBuf d_stage;
+    PvStage stage;  // host-entry staging (pv_ingress_verify), pinned
 };
 
 IngWork g_ing;
@@ -504,11 +502,10 @@ int ingress_device(const uint8_t* sig_chars, const uint64_t* sig_off, const uint
     const uint64_t cap = 96 * n + msg_bytes_total;
     int rc = ensure_work(n, nsig, cap);
     if (rc) return rc;
-    if ((rc = g_ing.hand.begin(s))) return rc;
-    rc = ingress_enqueue(sig_chars, sig_off, msg_idx, signer_idx, n, msg, msg_off, nmsg, cap, idr_chars, idr_off,
-                         vk_chars, vk_off, vk_present, nsig, status, verdict, s);
-    const int rc2 = g_ing.hand.end(s);  // also after a failed enqueue: whatever did get enqueued is covered
-    return rc ? rc : rc2;
+    return g_ing.hand.run(s, [&]() -> int {
+        return ingress_enqueue(sig_chars, sig_off, msg_idx, signer_idx, n, msg, msg_off, nmsg, cap, idr_chars, idr_off,
+                               vk_chars, vk_off, vk_present, nsig, status, verdict, s);
+    });
 }
 
 int ingress_enqueue(const uint8_t* sig_chars, const uint64_t* sig_off, const uint32_t* msg_idx,
@@ -523,25 +520,20 @@ int ingress_enqueue(const uint8_t* sig_chars, const uint64_t* sig_off, const uin
     uint8_t *const kstatus = g_ing.kstatus.p, *const blob = g_ing.blob.p;
     PV_HIP(hipEventRecord(g_ing.ev0, s), PV_ERR_LAUNCH);
     if (nsig > 0) {
-        hipLaunchKernelGGL(pv_ing_signer_kernel, dim3((unsigned)((nsig + ING_BLOCK - 1) / ING_BLOCK)), dim3(ING_BLOCK),
-                           0, s, idr_chars, idr_off, vk_chars, vk_off, vk_present, nsig, kpk, kstatus);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_ing_signer_kernel, dim3((unsigned)((nsig + ING_BLOCK - 1) / ING_BLOCK)), dim3(ING_BLOCK),
+                  0, s, idr_chars, idr_off, vk_chars, vk_off, vk_present, nsig, kpk, kstatus);
     }
     const unsigned grid = (unsigned)((n + ING_BLOCK - 1) / ING_BLOCK);
-    hipLaunchKernelGGL(pv_ing_sig_kernel, dim3(grid), dim3(ING_BLOCK), 0, s, sig_chars, sig_off, msg_idx, signer_idx,
-                       n, msg_off, nmsg, kpk, kstatus, nsig, sigfix, pk, siginfo, rec_len, status);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_ing_sig_kernel, dim3(grid), dim3(ING_BLOCK), 0, s, sig_chars, sig_off, msg_idx, signer_idx,
+              n, msg_off, nmsg, kpk, kstatus, nsig, sigfix, pk, siginfo, rec_len, status);
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(pv_ing_scan_tiles_kernel, dim3((unsigned)tiles), dim3(ING_BLOCK), 0, s, rec_len, n, local,
-                       tile_sum);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-    hipLaunchKernelGGL(pv_ing_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, s, tile_sum, tiles, n, off, cap, overrun);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_ing_scan_tiles_kernel, dim3((unsigned)tiles), dim3(ING_BLOCK), 0, s, rec_len, n, local,
+              tile_sum);
+    PV_LAUNCH(pv_ing_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, s, tile_sum, tiles, n, off, cap, overrun);
     const uint64_t athreads = n * ASM_LANES;
-    hipLaunchKernelGGL(pv_ing_assemble_kernel, dim3((unsigned)((athreads + ING_BLOCK - 1) / ING_BLOCK)),
-                       dim3(ING_BLOCK), 0, s, n, local, tile_sum, rec_len, siginfo, g_ing.sigfix.p, msg_idx, msg, msg_off,
-                       overrun, blob, off, status);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_ing_assemble_kernel, dim3((unsigned)((athreads + ING_BLOCK - 1) / ING_BLOCK)),
+              dim3(ING_BLOCK), 0, s, n, local, tile_sum, rec_len, siginfo, g_ing.sigfix.p, msg_idx, msg, msg_off,
+              overrun, blob, off, status);
     PV_HIP(hipEventRecord(g_ing.ev1, s), PV_ERR_LAUNCH);
     g_ing.timed = true;
     return pv_verify_batch_device(blob, off, n, g_ing.pk.p, verdict, s);
@@ -557,9 +549,9 @@ void pv_ingress_forget_stream(void* stream) {
 void pv_ingress_shutdown() {
     std::lock_guard<std::mutex> lk(g_ing_mu);
     for (PvDevBuf* b : {&g_ing.sigfix, &g_ing.pk, &g_ing.siginfo, &g_ing.rec_len, &g_ing.local, &g_ing.off, &g_ing.tile_sum,
-                        &g_ing.overrun, &g_ing.kpk, &g_ing.kstatus, &g_ing.blob, &g_ing.d_stage})
+                        &g_ing.overrun, &g_ing.kpk, &g_ing.kstatus, &g_ing.blob})
         b->release();
-    g_ing.h_stage.release();
+    g_ing.stage.release();
     if (g_ing.ev0) (void)hipEventDestroy(g_ing.ev0);
     if (g_ing.ev1) (void)hipEventDestroy(g_ing.ev1);
     g_ing.hand.destroy();
@@ -618,53 +610,28 @@ int pv_ingress_verify(const char* sig_chars, const uint64_t* sig_off, const uint
         mtotal += msg_off[msg_idx[i] + 1] - msg_off[msg_idx[i]];
     }
     std::lock_guard<std::mutex> lk(g_ing_mu);
-    // staging: [sig_off][msg_off][idr_off][vk_off] u64, [msg_idx][signer_idx] u32, [vk_present][status],
-    // [verdict words], then the byte blobs; every section 256-B aligned
-    const uint64_t sig_base = sig_off[0], msg_base = n_msgs ? msg_off[0] : 0;
-    const uint64_t idr_base = n_signers ? idr_off[0] : 0, vk_base = n_signers ? vk_off[0] : 0;
-    PvLayout l;
-    const uint64_t o_sigoff = l.add((n + 1) * 8), o_msgoff = l.add((n_msgs + 1) * 8), o_idroff = l.add((n_signers + 1) * 8),
-                   o_vkoff = l.add((n_signers + 1) * 8), o_midx = l.add(n * 4), o_sidx = l.add(n * 4),
-                   o_vkp = l.add(n_signers + 1), o_status = l.add(n), o_ver = l.add((n + 63) / 64 * 8),
-                   o_sig = l.add(sig_off[n] - sig_base + 8), o_msg = l.add((n_msgs ? msg_off[n_msgs] - msg_base : 0) + 8),
-                   o_idr = l.add((n_signers ? idr_off[n_signers] - idr_base : 0) + 8),
-                   o_vk = l.add((n_signers ? vk_off[n_signers] - vk_base : 0) + 8), total = l.at;
-    int rc;
-    if ((rc = g_ing.h_stage.grow(total, hipHostMallocDefault)) || (rc = g_ing.d_stage.grow(total))) return rc;
-    uint8_t* h = g_ing.h_stage.p;
-    auto rebase = [&](uint64_t o, const uint64_t* src, uint64_t k, uint64_t base) {
-        uint64_t* d = reinterpret_cast<uint64_t*>(h + o);
-        for (uint64_t i = 0; i <= k; i++) d[i] = src[i] - base;
-    };
-    rebase(o_sigoff, sig_off, n, sig_base);
-    if (n_msgs) rebase(o_msgoff, msg_off, n_msgs, msg_base);
-    if (n_signers) {
-        rebase(o_idroff, idr_off, n_signers, idr_base);
-        rebase(o_vkoff, vk_off, n_signers, vk_base);
-        memcpy(h + o_vkp, vk_present, n_signers);
-        memcpy(h + o_idr, idr_chars + idr_base, idr_off[n_signers] - idr_base);
-        memcpy(h + o_vk, vk_chars + vk_base, vk_off[n_signers] - vk_base);
-    }
-    memcpy(h + o_midx, msg_idx, n * 4);
-    memcpy(h + o_sidx, signer_idx, n * 4);
-    memcpy(h + o_sig, sig_chars + sig_base, sig_off[n] - sig_base);
-    if (n_msgs) memcpy(h + o_msg, msg + msg_base, msg_off[n_msgs] - msg_base);
-    uint8_t* d = g_ing.d_stage.p;
+    // n > 0 and the indices in range: there is a message and a signer
     const hipStream_t s = pv_engine_stream();
-    PV_HIP(hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-    PV_HIP(hipMemcpyAsync(d + o_sig, h + o_sig, total - o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-    rc = ingress_device(d + o_sig, reinterpret_cast<const uint64_t*>(d + o_sigoff),
-                        reinterpret_cast<const uint32_t*>(d + o_midx), reinterpret_cast<const uint32_t*>(d + o_sidx), n,
-                        d + o_msg, reinterpret_cast<const uint64_t*>(d + o_msgoff), n_msgs, mtotal, d + o_idr,
-                        reinterpret_cast<const uint64_t*>(d + o_idroff), d + o_vk,
-                        reinterpret_cast<const uint64_t*>(d + o_vkoff), d + o_vkp, n_signers, d + o_status,
-                        reinterpret_cast<uint64_t*>(d + o_ver), s);
+    PvStage& g = g_ing.stage;
+    int rc = g.reset(s, true);
     if (rc) return rc;
-    PV_HIP(hipMemcpyAsync(h + o_status, d + o_status, o_sig - o_status, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-    PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-    memcpy(status, h + o_status, n);
-    memcpy(verdict_bits, h + o_ver, (n + 7) / 8);
-    return PV_OK;
+    const uint64_t vbytes = (n + 7) / 8;
+    const int i_sigoff = g.in_offsets(sig_off, n), i_msgoff = g.in_offsets(msg_off, n_msgs),
+              i_idroff = g.in_offsets(idr_off, n_signers), i_vkoff = g.in_offsets(vk_off, n_signers),
+              i_midx = g.in(msg_idx, n * 4), i_sidx = g.in(signer_idx, n * 4), i_vkp = g.in(vk_present, n_signers, 1),
+              i_sig = g.in(sig_chars + sig_off[0], sig_off[n] - sig_off[0], 8),
+              i_msg = g.in(msg + msg_off[0], msg_off[n_msgs] - msg_off[0], 8),
+              i_idr = g.in(idr_chars + idr_off[0], idr_off[n_signers] - idr_off[0], 8),
+              i_vk = g.in(vk_chars + vk_off[0], vk_off[n_signers] - vk_off[0], 8), o_status = g.out(status, n),
+              o_ver = g.out(verdict_bits, vbytes, (n + 63) / 64 * 8 - vbytes);  // whole words written
+    if ((rc = g.upload()) ||
+        (rc = ingress_device(g.dev<const uint8_t>(i_sig), g.dev<const uint64_t>(i_sigoff), g.dev<const uint32_t>(i_midx),
+                             g.dev<const uint32_t>(i_sidx), n, g.dev<const uint8_t>(i_msg), g.dev<const uint64_t>(i_msgoff),
+                             n_msgs, mtotal, g.dev<const uint8_t>(i_idr), g.dev<const uint64_t>(i_idroff),
+                             g.dev<const uint8_t>(i_vk), g.dev<const uint64_t>(i_vkoff), g.dev<const uint8_t>(i_vkp), n_signers,
+                             g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_ver), s)))
+        return rc;
+    return g.download();
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 
 #include <string>
 
-#include "workspace.h"  // pv_fail, PV_HIP and what the workspaces below are made of
+#include "stage.h"  // with workspace.h: pv_fail, PV_HIP and what the workspaces below are made of
 
 // The library's main stream (valid after pv_init).
 hipStream_t pv_engine_stream();

@@ -25,7 +25,6 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
-#include <vector>
 
 #include "../../include/plenum_verify.h"
 #include "merkle_core.h"
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
 struct MkWork {
     PvDevBuf leaf, node;   // a chunk's leaf hashes / new nodes when the caller does not take them
     PvDevBuf front;        // three frontiers of 64 hashes: two for chunk chaining, one for a host entry's input
-    PvDevBuf d_in, d_out;  // host entries: staged inputs and outputs of one chunk
+    PvStage stage;         // host entries: staged inputs and outputs of one chunk
     PvHandover hand;
 };
 MkWork g_mk;
@@ -252,10 +251,12 @@ int g_mk_path = PV_MERKLE_AUTO;
 constexpr uint64_t MK_CHUNK_BYTES = 1ull << 30;  // a host-entry chunk also ends at this many data bytes
 constexpr uint64_t MK_FRONT_BYTES = 64 * 32;
 
-// The hand-over: `stream` waits for the workspace's last user. Caller holds g_mk_mu.
-int mk_begin(hipStream_t stream) {
+// One use of the workspace on `stream`: the frontiers exist, and the hand-over around `body`. Caller
+// holds g_mk_mu.
+template <class F>
+int mk_run(hipStream_t stream, F&& body) {
     if (int rc = g_mk.front.grow(3 * MK_FRONT_BYTES)) return rc;
-    return g_mk.hand.begin(stream);
+    return g_mk.hand.run(stream, body);
 }
 uint32_t* mk_front(int which) { return g_mk.front.as<uint32_t>() + which * (MK_FRONT_BYTES / 4); }
 
@@ -270,7 +271,7 @@ struct MkChunkOut {  // device pointers, null = not wanted
 };
 
 // One chunk: m > 0 leaves (d_off[0..m] into d_data) appended at size s with input frontier d_fin; the
-// frontier after it goes to d_fout. Caller holds g_mk_mu and ran mk_begin.
+// frontier after it goes to d_fout. Caller holds g_mk_mu and is inside mk_run.
 int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uint64_t* d_off, uint64_t m,
              const MkChunkOut& o, uint32_t* d_fout, hipStream_t stream) {
     uint64_t n_nodes, n_front, n_path;
@@ -288,25 +289,20 @@ int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uin
     }
     const MkView v{s, m, d_fin, leaf, node};
     const unsigned grid = (unsigned)((m + MK_BLOCK - 1) / MK_BLOCK);
-    hipLaunchKernelGGL(pv_merkle_leaf_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, d_data, d_off, m, leaf);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_merkle_leaf_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, d_data, d_off, m, leaf);
     if (n_nodes) {
         uint64_t first, count;
         pv_merkle_tiles(s, m, 0, &first, &count);
-        hipLaunchKernelGGL(pv_merkle_tile_kernel, dim3((unsigned)count), dim3(MK_BLOCK), 0, stream, v, first, node);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_merkle_tile_kernel, dim3((unsigned)count), dim3(MK_BLOCK), 0, stream, v, first, node);
         if (pv_merkle_any_above(s, m, PV_MERKLE_TILE_LOG)) {
-            hipLaunchKernelGGL(pv_merkle_upper_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, v, node);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_merkle_upper_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, v, node);
         }
     }
     if (o.path || o.roots) {
-        hipLaunchKernelGGL(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
-                           o.poff_base, o.roots);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
+                  o.poff_base, o.roots);
     }
-    hipLaunchKernelGGL(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
     return PV_OK;
 }
 
@@ -321,115 +317,86 @@ bool mk_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u
 // Device buffers, n > 0, on `stream`. Caller holds g_mk_mu.
 int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, const uint64_t* d_off, uint64_t n,
                const PvMerkleOut& out, hipStream_t stream) {
-    int rc = mk_begin(stream);
-    if (rc) return rc;
-    const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
-    int cur = 0;
-    const uint32_t* fin = reinterpret_cast<const uint32_t*>(d_frontier);
-    if (n == 0) {  // the input tree's frontier and root
-        const MkView v{s0, 0, fin, nullptr, nullptr};
-        hipLaunchKernelGGL(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, mk_front(0),
-                           reinterpret_cast<uint32_t*>(out.root));
-        if (hipGetLastError() != hipSuccess) rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: launch failed");
-        if (out.path_off && hipMemsetAsync(out.path_off, 0, 8, stream) != hipSuccess)  // path_off[0] = 0, as the host path
-            rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: path_off[0] store failed");
-        fin = mk_front(0);
-    }
-    for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += g_mk_chunk) {
-        const uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0), s = s0 + c0;
-        const bool is_last = c0 + m == n;
-        const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
-        const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(out.leaf_hash + 32 * c0) : nullptr,
-                           out.node_hash ? reinterpret_cast<uint32_t*>(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0))
-                                         : nullptr,
-                           out.roots ? reinterpret_cast<uint32_t*>(out.roots + 32 * c0) : nullptr,
-                           out.path ? reinterpret_cast<uint32_t*>(out.path + 32 * pbase) : nullptr,
-                           out.path ? out.path_off + c0 : nullptr,
-                           pbase,
-                           is_last ? reinterpret_cast<uint32_t*>(out.root) : nullptr};
-        rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream);
-        fin = mk_front(cur);
-        cur ^= 1;
-    }
-    if (rc == PV_OK && out.frontier)
-        if (hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-            rc = pv_fail(PV_ERR_LAUNCH, "pv_merkle_append_batch_device: frontier copy failed");
-    const int rc2 = g_mk.hand.end(stream);
-    return rc ? rc : rc2;
+    return mk_run(stream, [&]() -> int {
+        const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
+        int cur = 0;
+        const uint32_t* fin = reinterpret_cast<const uint32_t*>(d_frontier);
+        if (n == 0) {  // the input tree's frontier and root
+            const MkView v{s0, 0, fin, nullptr, nullptr};
+            PV_LAUNCH(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, mk_front(0),
+                      reinterpret_cast<uint32_t*>(out.root));
+            // path_off[0] = 0, as the host path
+            if (out.path_off) PV_HIP(hipMemsetAsync(out.path_off, 0, 8, stream), PV_ERR_LAUNCH);
+            fin = mk_front(0);
+        }
+        for (uint64_t c0 = 0; c0 < n; c0 += g_mk_chunk) {
+            const uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0), s = s0 + c0;
+            const bool is_last = c0 + m == n;
+            const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
+            const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(out.leaf_hash + 32 * c0) : nullptr,
+                               out.node_hash ? reinterpret_cast<uint32_t*>(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0))
+                                             : nullptr,
+                               out.roots ? reinterpret_cast<uint32_t*>(out.roots + 32 * c0) : nullptr,
+                               out.path ? reinterpret_cast<uint32_t*>(out.path + 32 * pbase) : nullptr,
+                               out.path ? out.path_off + c0 : nullptr,
+                               pbase,
+                               is_last ? reinterpret_cast<uint32_t*>(out.root) : nullptr};
+            if (int rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream)) return rc;
+            fin = mk_front(cur);
+            cur ^= 1;
+        }
+        if (out.frontier)
+            PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToDevice, stream), PV_ERR_LAUNCH);
+        return PV_OK;
+    });
 }
 
-// The device path of the host entry: chunk by chunk through the staging blocks. Arguments validated, n > 0.
+// The device path of the host entry: chunk by chunk through the stage. Arguments validated, n > 0.
 int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
                          const PvMerkleOut& out) {
     const hipStream_t st = pv_engine_stream();
-    int rc = mk_begin(st);
-    if (rc) return rc;
-    auto run = [&]() -> int {
+    return mk_run(st, [&]() -> int {
         const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
         if (s0) PV_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
         const uint32_t* fin = mk_front(2);
         int cur = 0;
-        std::vector<uint64_t> rebased;
+        PvStage& g = g_mk.stage;
         for (uint64_t c0 = 0; c0 < n;) {
             uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0);
             if (off[c0 + m] - off[c0] > MK_CHUNK_BYTES) {  // the byte bound: the longest prefix within it, at least one leaf
                 const uint64_t* e = std::upper_bound(off + c0 + 1, off + c0 + m + 1, off[c0] + MK_CHUNK_BYTES);
                 m = std::max<uint64_t>(1, (uint64_t)(e - (off + c0)) - 1);
             }
-            const uint64_t s = s0 + c0, base = off[c0], bytes = off[c0 + m] - base;
+            const uint64_t s = s0 + c0, pbase = pv_merkle_popc_sum(s) - paths0;
             const bool is_last = c0 + m == n;
             uint64_t n_nodes, n_front, n_path;
             pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
-            // inputs: [offsets, rebased][data + slack]; outputs: [leaf][node][roots][path_off][path][root]
-            PvLayout li, lo;  // the sections of an output the caller does not take stay empty
-            const uint64_t i_off = li.add((m + 1) * 8), i_data = li.add(bytes + PV_BLOB_SLACK);
-            const uint64_t o_leaf = out.leaf_hash ? lo.add(32 * m) : 0, o_node = out.node_hash ? lo.add(32 * n_nodes) : 0,
-                           o_roots = out.roots ? lo.add(32 * m) : 0, o_poff = out.path ? lo.add(8 * (m + 1)) : 0,
-                           o_path = out.path ? lo.add(32 * n_path) : 0, o_root = lo.add(32);
-            int rc;
-            if ((rc = g_mk.d_in.grow(li.at)) || (rc = g_mk.d_out.grow(lo.at))) return rc;
-            rebased.resize(m + 1);
-            for (uint64_t i = 0; i <= m; i++) rebased[i] = off[c0 + i] - base;
-            PV_HIP(hipMemcpyAsync(g_mk.d_in.p + i_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-            if (bytes) PV_HIP(hipMemcpyAsync(g_mk.d_in.p + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-            uint8_t* d = g_mk.d_out.p;
-            const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
-            const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(d + o_leaf) : nullptr,
-                               out.node_hash ? reinterpret_cast<uint32_t*>(d + o_node) : nullptr,
-                               out.roots ? reinterpret_cast<uint32_t*>(d + o_roots) : nullptr,
-                               out.path ? reinterpret_cast<uint32_t*>(d + o_path) : nullptr,
-                               out.path ? reinterpret_cast<uint64_t*>(d + o_poff) : nullptr,
-                               pbase,
-                               is_last && out.root ? reinterpret_cast<uint32_t*>(d + o_root) : nullptr};
-            if ((rc = mk_chunk(s, fin, g_mk.d_in.p + i_data, reinterpret_cast<const uint64_t*>(g_mk.d_in.p + i_off), m, o,
-                               mk_front(cur), st)))
+            int rc = g.reset(st, false);
+            if (rc) return rc;
+            // an output the caller does not take has no section
+            uint8_t* const nodes = out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0);
+            const int i_off = g.in_offsets(off + c0, m),
+                      i_data = g.in(data + off[c0], off[c0 + m] - off[c0], PV_BLOB_SLACK),
+                      o_leaf = out.leaf_hash ? g.out(out.leaf_hash + 32 * c0, 32 * m) : -1,
+                      o_node = out.node_hash ? g.out(nodes, 32 * n_nodes) : -1,
+                      o_roots = out.roots ? g.out(out.roots + 32 * c0, 32 * m) : -1,
+                      o_poff = out.path ? g.out(out.path_off + c0, 8 * (m + 1)) : -1,
+                      o_path = out.path ? g.out(out.path + 32 * pbase, 32 * n_path) : -1,
+                      o_root = is_last && out.root ? g.out(out.root, 32) : -1;
+            if ((rc = g.upload())) return rc;
+            const MkChunkOut o{g.dev<uint32_t>(o_leaf), g.dev<uint32_t>(o_node), g.dev<uint32_t>(o_roots),
+                               g.dev<uint32_t>(o_path), g.dev<uint64_t>(o_poff), pbase, g.dev<uint32_t>(o_root)};
+            if ((rc = mk_chunk(s, fin, g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), m, o, mk_front(cur), st)))
                 return rc;
             fin = mk_front(cur);
             cur ^= 1;
-            if (out.leaf_hash)
-                PV_HIP(hipMemcpyAsync(out.leaf_hash + 32 * c0, d + o_leaf, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            if (out.node_hash && n_nodes)
-                PV_HIP(hipMemcpyAsync(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0), d + o_node, 32 * n_nodes,
-                                      hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            if (out.roots)
-                PV_HIP(hipMemcpyAsync(out.roots + 32 * c0, d + o_roots, 32 * m, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            if (out.path) {
-                PV_HIP(hipMemcpyAsync(out.path_off + c0, d + o_poff, 8 * (m + 1), hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-                if (n_path)
-                    PV_HIP(hipMemcpyAsync(out.path + 32 * pbase, d + o_path, 32 * n_path, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            }
-            if (is_last) {
-                if (out.root) PV_HIP(hipMemcpyAsync(out.root, d + o_root, 32, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-                if (out.frontier) PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            }
-            PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);  // the staging blocks are free for the next chunk
+            if (is_last && out.frontier)
+                PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+            if ((rc = g.download())) return rc;  // synchronised: the stage is free for the next chunk
             c0 += m;
         }
         return PV_OK;
-    };
-    rc = run();
-    const int rc2 = g_mk.hand.end(st);
-    return rc ? rc : rc2;
+    });
 }
 
 int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash, const uint64_t* d_index,
@@ -438,12 +405,11 @@ int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_
     const uint64_t chunk = (g_mk_chunk + 63) & ~63ull;  // whole verdict words per chunk
     for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
         const uint64_t m = std::min<uint64_t>(chunk, n - c0);
-        hipLaunchKernelGGL(pv_merkle_verify_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
-                           stream, d_data, d_off ? d_off + c0 : nullptr,
-                           d_leaf_hash ? reinterpret_cast<const uint32_t*>(d_leaf_hash + 32 * c0) : nullptr, d_index + c0,
-                           d_size + c0, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off + c0,
-                           reinterpret_cast<const uint32_t*>(d_root + 32 * c0), m, d_status + c0, d_verdict + c0 / 64);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_merkle_verify_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
+                  stream, d_data, d_off ? d_off + c0 : nullptr,
+                  d_leaf_hash ? reinterpret_cast<const uint32_t*>(d_leaf_hash + 32 * c0) : nullptr, d_index + c0,
+                  d_size + c0, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off + c0,
+                  reinterpret_cast<const uint32_t*>(d_root + 32 * c0), m, d_status + c0, d_verdict + c0 / 64);
     }
     return PV_OK;
 }
@@ -457,7 +423,8 @@ void pv_merkle_forget_stream(void* stream) {
 
 void pv_merkle_shutdown() {
     std::lock_guard<std::mutex> lk(g_mk_mu);
-    for (PvDevBuf* b : {&g_mk.leaf, &g_mk.node, &g_mk.front, &g_mk.d_in, &g_mk.d_out}) b->release();
+    for (PvDevBuf* b : {&g_mk.leaf, &g_mk.node, &g_mk.front}) b->release();
+    g_mk.stage.release();
     g_mk.hand.destroy();
 }
 
@@ -502,12 +469,12 @@ int pv_merkle_append_batch(uint64_t tree_size, const uint8_t* frontier, const ui
         if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null data");
     }
     std::unique_lock<std::mutex> lk(g_mk_mu);
-    const bool have_dev = pv_engine_stream() != nullptr;
-    if (g_mk_path == PV_MERKLE_DEVICE && !have_dev)
-        return pv_fail(PV_ERR_NO_DEVICE, "pv_merkle_append_batch: the device path is forced and no device is initialised");
-    const uint64_t auto_min = out->roots || out->path ? PV_MERKLE_AUTO_MIN_PROOFS : PV_MERKLE_AUTO_MIN;
-    const bool device = n > 0 && have_dev && (g_mk_path == PV_MERKLE_DEVICE || (g_mk_path == PV_MERKLE_AUTO && n >= auto_min));
-    if (!device) {
+    bool device;
+    if ((rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n,
+                             out->roots || out->path ? PV_MERKLE_AUTO_MIN_PROOFS : PV_MERKLE_AUTO_MIN,
+                             "pv_merkle_append_batch", &device)))
+        return rc;
+    if (!device || n == 0) {
         lk.unlock();  // the host path shares no workspace: CPU-only callers run side by side
         pv_merkle_host_append(tree_size, frontier, data, off, n, out);
         return PV_OK;
@@ -548,61 +515,37 @@ int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, c
         return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: proof offsets must be non-decreasing over a proof array");
     if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: more than 2^32 - 1 proofs");
     std::unique_lock<std::mutex> lk(g_mk_mu);
-    const bool have_dev = pv_engine_stream() != nullptr;
-    if (g_mk_path == PV_MERKLE_DEVICE && !have_dev)
-        return pv_fail(PV_ERR_NO_DEVICE, "pv_merkle_verify_inclusion_batch: the device path is forced and no device is initialised");
-    if (!(have_dev && (g_mk_path == PV_MERKLE_DEVICE || (g_mk_path == PV_MERKLE_AUTO && n >= PV_MERKLE_AUTO_MIN_VERIFY)))) {
+    bool device;
+    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_VERIFY,
+                            "pv_merkle_verify_inclusion_batch", &device);
+    if (rc) return rc;
+    if (!device) {
         lk.unlock();
         pv_merkle_host_verify(data, off, leaf_hash, leaf_index, tree_size, proof, proof_off, root, n, status, verdict_bits);
         return PV_OK;
     }
     const hipStream_t st = pv_engine_stream();
-    int rc = mk_begin(st);
-    if (rc) return rc;
-    auto run = [&]() -> int {
-        // staged whole: [leaf off | leaf hashes][index][size][proof off, rebased][root][data + slack | -][proof]; out: [status][words]
-        const uint64_t dbase = off ? off[0] : 0, dbytes = off ? off[n] - dbase : 0;
-        const uint64_t pbase = proof_off[0], phashes = proof_off[n] - pbase;
-        PvLayout li, lo;
-        const uint64_t i_leaf = li.add(off ? (n + 1) * 8 : 32 * n), i_index = li.add(8 * n), i_size = li.add(8 * n),
-                       i_poff = li.add(8 * (n + 1)), i_root = li.add(32 * n),
-                       i_data = off ? li.add(dbytes + PV_BLOB_SLACK) : 0, i_proof = li.add(32 * phashes + 32);
-        const uint64_t o_status = lo.add(n), o_words = lo.add((n + 63) / 64 * 8);
-        int rc;
-        if ((rc = g_mk.d_in.grow(li.at)) || (rc = g_mk.d_out.grow(lo.at))) return rc;
-        uint8_t* d = g_mk.d_in.p;
-        // every copy on st; the temporaries live until the synchronisation below
-        std::vector<uint64_t> loff(off ? n + 1 : 0), poff(n + 1);
-        auto h2d = [&](uint64_t at, const void* src, uint64_t bytes) {
-            return bytes ? hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-        };
-        if (off) {
-            for (uint64_t i = 0; i <= n; i++) loff[i] = off[i] - dbase;
-            PV_HIP(h2d(i_leaf, loff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
-            PV_HIP(h2d(i_data, data + dbase, dbytes), PV_ERR_LAUNCH);
-        } else {
-            PV_HIP(h2d(i_leaf, leaf_hash, 32 * n), PV_ERR_LAUNCH);
-        }
-        for (uint64_t i = 0; i <= n; i++) poff[i] = proof_off[i] - pbase;
-        PV_HIP(h2d(i_poff, poff.data(), (n + 1) * 8), PV_ERR_LAUNCH);
-        PV_HIP(h2d(i_index, leaf_index, 8 * n), PV_ERR_LAUNCH);
-        PV_HIP(h2d(i_size, tree_size, 8 * n), PV_ERR_LAUNCH);
-        PV_HIP(h2d(i_root, root, 32 * n), PV_ERR_LAUNCH);
-        PV_HIP(h2d(i_proof, proof + 32 * pbase, 32 * phashes), PV_ERR_LAUNCH);
-        if ((rc = mk_verify_enqueue(off ? d + i_data : nullptr, off ? reinterpret_cast<const uint64_t*>(d + i_leaf) : nullptr,
-                                    off ? nullptr : d + i_leaf, reinterpret_cast<const uint64_t*>(d + i_index),
-                                    reinterpret_cast<const uint64_t*>(d + i_size), d + i_proof,
-                                    reinterpret_cast<const uint64_t*>(d + i_poff), d + i_root, n, g_mk.d_out.p + o_status,
-                                    reinterpret_cast<uint64_t*>(g_mk.d_out.p + o_words), st)))
+    return mk_run(st, [&]() -> int {
+        PvStage& g = g_mk.stage;
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        // staged whole: the leaves as data and offsets or as hashes, and the proofs with room for one hash more
+        const int i_off = off ? g.in_offsets(off, n) : -1,
+                  i_data = off ? g.in(data + off[0], off[n] - off[0], PV_BLOB_SLACK) : -1,
+                  i_leaf = off ? -1 : g.in(leaf_hash, 32 * n), i_index = g.in(leaf_index, 8 * n),
+                  i_size = g.in(tree_size, 8 * n),
+                  i_poff = g.in_offsets(proof_off, n), i_root = g.in(root, 32 * n),
+                  i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
+                  o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
+        if ((rc = g.upload()) ||
+            (rc = mk_verify_enqueue(g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off),
+                                    g.dev<const uint8_t>(i_leaf), g.dev<const uint64_t>(i_index),
+                                    g.dev<const uint64_t>(i_size), g.dev<const uint8_t>(i_proof),
+                                    g.dev<const uint64_t>(i_poff), g.dev<const uint8_t>(i_root), n,
+                                    g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
             return rc;
-        PV_HIP(hipMemcpyAsync(status, g_mk.d_out.p + o_status, n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(verdict_bits, g_mk.d_out.p + o_words, (n + 7) / 8, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    rc = run();
-    const int rc2 = g_mk.hand.end(st);
-    return rc ? rc : rc2;
+        return g.download();
+    });
 }
 
 int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash,

@@ -107,20 +107,20 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_sign_kernel(const uint8_t* __r
 
 namespace {
 
-// Room for `signers` expanded keys, and the hand-over: `stream` waits for the workspace's last user.
-// Caller holds g_mu.
-int sg_begin(uint64_t signers, hipStream_t stream) {
+// One use of the workspace on `stream` (caller holds g_mu): room for `signers` expanded keys, the
+// hand-over around `body`, and the expanded keys overwritten behind the kernels that read them, also
+// after a failure.
+template <class F>
+int sg_run(uint64_t signers, hipStream_t stream, F&& body) {
     auto& g = g_ctx.sg;
     if (int rc = g.d_keys.grow(std::max<uint64_t>(signers, 4096) * 64)) return rc;
-    return g.hand.begin(stream);
-}
-// The expanded keys are overwritten behind the kernels that read them, and the workspace released.
-int sg_end(uint64_t signers, hipStream_t stream) {
-    auto& g = g_ctx.sg;
-    const hipError_t e = hipMemsetAsync(g.d_keys.p, 0, signers * 64, stream);
-    if (int rc = g.hand.end(stream)) return rc;
-    if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: key scrub: ") + hipGetErrorString(e));
-    return PV_OK;
+    return g.hand.run(stream, [&]() -> int {
+        const int rc = body();
+        const hipError_t e = hipMemsetAsync(g.d_keys.p, 0, signers * 64, stream);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: key scrub: ") + hipGetErrorString(e));
+        return PV_OK;
+    });
 }
 // Key expansion of `signers` seeds (seed_q uint4 apart); d_pk: also the public keys (keypair entry).
 int sg_keys(const uint8_t* d_seeds, uint32_t seed_q, uint64_t signers, uint8_t* d_pk, hipStream_t stream) {
@@ -143,23 +143,21 @@ constexpr uint64_t PV_SIGN_MAX = 0xffffffffull;  // items / signers per call (32
 // Device-buffer batch on `stream` (caller holds g_mu): expansion of every signer, then the chunks.
 int sg_enqueue(const uint8_t* d_msg, const uint64_t* d_off, uint64_t n, const uint8_t* d_sk, uint64_t n_signers,
                const uint32_t* d_idx, uint8_t* d_sig, hipStream_t stream) {
-    int rc = sg_begin(n_signers, stream);
-    if (rc) return rc;
-    rc = sg_keys(d_sk, 4, n_signers, nullptr, stream);
-    for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK)
-        rc = sg_chunk(d_msg, d_off + c0, std::min<uint64_t>(PV_SIGN_CHUNK, n - c0), d_sk, n_signers,
-                      d_idx ? d_idx + c0 : nullptr, c0, d_sig + 64 * c0, stream);
-    const int rc2 = sg_end(n_signers, stream);
-    return rc ? rc : rc2;
+    return sg_run(n_signers, stream, [&]() -> int {
+        int rc = sg_keys(d_sk, 4, n_signers, nullptr, stream);
+        for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK)
+            rc = sg_chunk(d_msg, d_off + c0, std::min<uint64_t>(PV_SIGN_CHUNK, n - c0), d_sk, n_signers,
+                          d_idx ? d_idx + c0 : nullptr, c0, d_sig + 64 * c0, stream);
+        return rc;
+    });
 }
 
-// The host entries' copies of secret keys / seeds: overwritten on the device behind the work on `stream`
-// and, once that is done, in pinned memory.
-int sg_scrub_secrets(uint64_t bytes, hipStream_t stream) {
-    auto& g = g_ctx.sg;
-    hipError_t e = g.d_sk.p ? hipMemsetAsync(g.d_sk.p, 0, std::min(bytes, g.d_sk.cap), stream) : hipSuccess;
+// The host entries' copies of secret keys / seeds, the first `bytes` of d and h: overwritten on the device
+// behind the work on `stream` and, once that is done, in pinned memory.
+int sg_scrub_secrets(const PvDevBuf& d, const PvPinnedBuf& h, uint64_t bytes, hipStream_t stream) {
+    hipError_t e = d.p ? hipMemsetAsync(d.p, 0, std::min(bytes, d.cap), stream) : hipSuccess;
     const hipError_t e2 = hipStreamSynchronize(stream);
-    if (g.h_sk.p) memset(g.h_sk.p, 0, std::min(bytes, g.h_sk.cap));
+    if (h.p) memset(h.p, 0, std::min(bytes, h.cap));
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(PV_ERR_LAUNCH, std::string("pv_sign: secret scrub: ") + hipGetErrorString(e));
     return PV_OK;
@@ -207,42 +205,29 @@ int pv_sign_batch(const uint8_t* msg, const uint64_t* msg_off, uint64_t n, const
     const hipStream_t s = g_ctx.stream;
     const uint64_t sk_bytes = n_signers * 64;
     int rc;
-    if ((rc = g.h_sk.grow(sk_bytes, hipHostMallocDefault)) || (rc = g.d_sk.grow(sk_bytes)) ||
-        (rc = sg_begin(n_signers, s)))
-        return rc;
+    if ((rc = g.h_sk.grow(sk_bytes, hipHostMallocDefault)) || (rc = g.d_sk.grow(sk_bytes))) return rc;
     memcpy(g.h_sk.p, sk, sk_bytes);
-    auto run = [&]() -> int {
+    rc = sg_run(n_signers, s, [&]() -> int {
         PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, sk_bytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
         int rc = sg_keys(g.d_sk.p, 4, n_signers, nullptr, s);
+        PvStage& st = g.stage;
         for (uint64_t c0 = 0; c0 < n && rc == PV_OK; c0 += PV_SIGN_CHUNK) {
-            // chunk staging: [offsets, rebased][signer indices][signatures][message bytes + slack]
             const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
-            const uint64_t base = msg_off[c0], mbytes = msg_off[c0 + m] - base;
-            PvLayout l;
-            const uint64_t o_off = l.add((m + 1) * 8), o_idx = l.add(m * 4), o_sig = l.add(m * 64),
-                           o_msg = l.add(mbytes + PV_BLOB_SLACK), total = l.at;
-            if ((rc = g.h_stage.grow(total, hipHostMallocDefault)) || (rc = g.d_stage.grow(total))) break;
-            uint64_t* ho = reinterpret_cast<uint64_t*>(g.h_stage.p + o_off);
-            for (uint64_t i = 0; i <= m; i++) ho[i] = msg_off[c0 + i] - base;
-            if (signer_idx) memcpy(g.h_stage.p + o_idx, signer_idx + c0, m * 4);
-            if (mbytes) memcpy(g.h_stage.p + o_msg, msg + base, mbytes);
-            PV_HIP(hipMemcpyAsync(g.d_stage.p, g.h_stage.p, o_sig, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            if (mbytes)
-                PV_HIP(hipMemcpyAsync(g.d_stage.p + o_msg, g.h_stage.p + o_msg, mbytes, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            if ((rc = sg_chunk(g.d_stage.p + o_msg, reinterpret_cast<const uint64_t*>(g.d_stage.p + o_off), m, g.d_sk.p,
-                               n_signers, signer_idx ? reinterpret_cast<const uint32_t*>(g.d_stage.p + o_idx) : nullptr,
-                               c0, g.d_stage.p + o_sig, s)))
+            if ((rc = st.reset(s, true))) break;
+            // chunk staging: offsets moved to the chunk's first byte, signer indices, message bytes + slack
+            const int off = st.in_offsets(msg_off + c0, m), idx = signer_idx ? st.in(signer_idx + c0, m * 4) : -1,
+                      mb = st.in(msg + msg_off[c0], msg_off[c0 + m] - msg_off[c0], PV_BLOB_SLACK),
+                      sig = st.out(sig_out + 64 * c0, m * 64);
+            if ((rc = st.upload()) ||
+                (rc = sg_chunk(st.dev<const uint8_t>(mb), st.dev<const uint64_t>(off), m, g.d_sk.p, n_signers,
+                               st.dev<const uint32_t>(idx), c0, st.dev<uint8_t>(sig), s)))
                 break;
-            PV_HIP(hipMemcpyAsync(g.h_stage.p + o_sig, g.d_stage.p + o_sig, m * 64, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-            memcpy(sig_out + 64 * c0, g.h_stage.p + o_sig, m * 64);
+            rc = st.download();
         }
         return rc;
-    };
-    rc = run();
-    const int rc2 = sg_end(n_signers, s);
-    const int rc3 = sg_scrub_secrets(sk_bytes, s);
-    return rc ? rc : (rc2 ? rc2 : rc3);
+    });
+    const int rc2 = sg_scrub_secrets(g.d_sk, g.h_sk, sk_bytes, s);
+    return rc ? rc : rc2;
 }
 
 int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uint8_t* sk_out) {
@@ -251,37 +236,27 @@ int pv_sign_seed_keypairs(const uint8_t* seeds, uint64_t n, uint8_t* pk_out, uin
     if (n == 0) return PV_OK;
     if (!seeds) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: null pointer");
     if (n > PV_SIGN_MAX) return fail(PV_ERR_ARG, "pv_sign_seed_keypairs: more than 2^32 - 1 seeds");
-    auto& g = g_ctx.sg;
     const hipStream_t s = g_ctx.stream;
     const uint64_t cm = std::min<uint64_t>(PV_SIGN_CHUNK, n);
-    int rc;
-    if ((rc = g.h_sk.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_sk.grow(cm * 32)) ||
-        (rc = g.h_stage.grow(cm * 32, hipHostMallocDefault)) || (rc = g.d_stage.grow(cm * 32)) ||
-        (rc = sg_begin(cm, s)))
-        return rc;
-    auto run = [&]() -> int {
+    PvStage& st = g_ctx.sg.stage;  // the seeds travel in its input blocks, scrubbed below
+    const int rc = sg_run(cm, s, [&]() -> int {
         for (uint64_t c0 = 0; c0 < n; c0 += PV_SIGN_CHUNK) {
             const uint64_t m = std::min<uint64_t>(PV_SIGN_CHUNK, n - c0);
-            memcpy(g.h_sk.p, seeds + 32 * c0, m * 32);
-            PV_HIP(hipMemcpyAsync(g.d_sk.p, g.h_sk.p, m * 32, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-            const int rc = sg_keys(g.d_sk.p, 2, m, g.d_stage.p, s);
+            int rc = st.reset(s, true);
             if (rc) return rc;
-            PV_HIP(hipMemcpyAsync(g.h_stage.p, g.d_stage.p, m * 32, hipMemcpyDeviceToHost, s), PV_ERR_LAUNCH);
-            PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);
-            for (uint64_t i = 0; i < m; i++) {
-                if (pk_out) memcpy(pk_out + 32 * (c0 + i), g.h_stage.p + 32 * i, 32);
-                if (sk_out) {
-                    memcpy(sk_out + 64 * (c0 + i), seeds + 32 * (c0 + i), 32);
-                    memcpy(sk_out + 64 * (c0 + i) + 32, g.h_stage.p + 32 * i, 32);
-                }
+            const int seed = st.in(seeds + 32 * c0, m * 32), pk = st.out(pk_out ? pk_out + 32 * c0 : nullptr, m * 32);
+            if ((rc = st.upload()) || (rc = sg_keys(st.dev<const uint8_t>(seed), 2, m, st.dev<uint8_t>(pk), s)) ||
+                (rc = st.download()))
+                return rc;
+            for (uint64_t i = 0; i < m && sk_out; i++) {
+                memcpy(sk_out + 64 * (c0 + i), seeds + 32 * (c0 + i), 32);
+                memcpy(sk_out + 64 * (c0 + i) + 32, st.host(pk) + 32 * i, 32);
             }
         }
         return PV_OK;
-    };
-    rc = run();
-    const int rc2 = sg_end(cm, s);
-    const int rc3 = sg_scrub_secrets(cm * 32, s);
-    return rc ? rc : (rc2 ? rc2 : rc3);
+    });
+    const int rc2 = sg_scrub_secrets(st.d_in, st.h, pv_up256(cm * 32), s);
+    return rc ? rc : rc2;
 }
 
 }  // extern "C"

@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
-#include <vector>
 
 #include "../../include/plenum_verify.h"
 #include "keccak.h"
@@ -132,8 +131,7 @@ __global__ __launch_bounds__(TR_BLOCK) void pv_proof_walk_kernel(const PvProofIn
 // nothing), freed by pv_shutdown, handed over between caller streams by an event (workspace.h).
 // Launches are serialised on g_tr_mu.
 struct TrWork {
-    PvDevBuf d_in;   // the arena and its records, or a blob and its offsets
-    PvDevBuf d_out;  // digests
+    PvStage stage;  // in: the arena and its records, a blob and its offsets, or proofs; out: digests, flags, statuses
     PvHandover hand;
 };
 TrWork g_tr;
@@ -145,17 +143,15 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
                hipStream_t st, uint64_t* launches, uint64_t* tail_records) {
     for (uint64_t i0 = 0; i0 < nr;) {
         if (nr - i0 <= TR_TAIL_MAX) {
-            hipLaunchKernelGGL(pv_sha3_tail_kernel, dim3(1), dim3(TR_BLOCK), 0, st, d_arena, d_recs, (uint32_t)i0,
-                               (uint32_t)nr, d_hashes);
-            PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+            PV_LAUNCH(pv_sha3_tail_kernel, dim3(1), dim3(TR_BLOCK), 0, st, d_arena, d_recs, (uint32_t)i0,
+                      (uint32_t)nr, d_hashes);
             ++*launches;
             *tail_records = nr - i0;
             break;
         }
         const uint64_t i1 = recs[i0].next, count = i1 - i0;
-        hipLaunchKernelGGL(pv_sha3_batch_kernel, dim3((unsigned)((count + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
-                           d_arena, d_recs, (uint32_t)i0, (uint32_t)count, d_hashes);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_sha3_batch_kernel, dim3((unsigned)((count + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
+                  d_arena, d_recs, (uint32_t)i0, (uint32_t)count, d_hashes);
         ++*launches;
         i0 = i1;
     }
@@ -165,49 +161,33 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
 // arena and records staged whole, hashed, copied back: arena -> blob, digests -> hashes
 int tr_device_hash(PvTriePlan& plan, uint8_t* blob, uint8_t* hashes, uint64_t* launches, uint64_t* tail_records) {
     const hipStream_t st = pv_engine_stream();
-    int rc = g_tr.hand.begin(st);
-    if (rc) return rc;
-    auto run = [&]() -> int {
-        const uint64_t nr = plan.recs.size(), i_recs = pv_up256(plan.arena_bytes);
-        int rc;
-        if ((rc = g_tr.d_in.grow(i_recs + pv_up256(nr * sizeof(PvTrieRec)))) ||
-            (rc = g_tr.d_out.grow(pv_up256(32 * nr))))
+    return g_tr.hand.run(st, [&]() -> int {
+        PvStage& g = g_tr.stage;
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        const uint64_t nr = plan.recs.size();
+        const int arena = g.inout(plan.arena.data(), blob, plan.arena_bytes),
+                  recs = g.in(plan.recs.data(), nr * sizeof(PvTrieRec)), digest = g.out(hashes, 32 * nr);
+        if ((rc = g.upload()) || (rc = tr_enqueue(g.dev<uint8_t>(arena), g.dev<const PvTrieRec>(recs), plan.recs.data(), nr,
+                                                  g.dev<uint64_t>(digest), st, launches, tail_records)))
             return rc;
-        PV_HIP(hipMemcpyAsync(g_tr.d_in.p, plan.arena.data(), plan.arena_bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(g_tr.d_in.p + i_recs, plan.recs.data(), nr * sizeof(PvTrieRec), hipMemcpyHostToDevice, st),
-               PV_ERR_LAUNCH);
-        if ((rc = tr_enqueue(g_tr.d_in.p, reinterpret_cast<const PvTrieRec*>(g_tr.d_in.p + i_recs), plan.recs.data(), nr,
-                             reinterpret_cast<uint64_t*>(g_tr.d_out.p), st, launches, tail_records)))
-            return rc;
-        PV_HIP(hipMemcpyAsync(blob, g_tr.d_in.p, plan.arena_bytes, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(hashes, g_tr.d_out.p, 32 * nr, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    rc = run();
-    const int rc2 = g_tr.hand.end(st);
-    return rc ? rc : rc2;
+        return g.download();
+    });
 }
 
-// PV_OK with *device set, or PV_ERR_NO_DEVICE for a forced device path without a device. Caller holds g_tr_mu.
-int tr_choose(uint64_t work, const char* who, bool* device) {
-    const bool have_dev = pv_engine_stream() != nullptr;
-    if (g_tr_path == PV_TRIE_DEVICE && !have_dev)
-        return pv_fail(PV_ERR_NO_DEVICE, std::string(who) + ": the device path is forced and no device is initialised");
-    *device = work > 0 && have_dev && (g_tr_path == PV_TRIE_DEVICE || (g_tr_path == PV_TRIE_AUTO && work >= PV_TRIE_AUTO_MIN));
-    return PV_OK;
+// The path of entry `who` with `work` records under pv_trie_path's mode. Caller holds g_tr_mu.
+int tr_choose(uint64_t work, uint64_t auto_min, const char* who, bool* device) {
+    return pv_choose_path(g_tr_path, pv_engine_stream() != nullptr, work, auto_min, who, device);
 }
 
 // Both proof launches for device buffers. Caller holds g_tr_mu.
 int tr_proof_enqueue(const PvProofIn& d, uint64_t* d_digest, uint8_t* d_flag, uint8_t* d_status, hipStream_t st) {
     if (d.n_nodes) {
-        hipLaunchKernelGGL(pv_proof_node_kernel, dim3((unsigned)((d.n_nodes + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
-                           st, d.node_blob, d.node_off, d.node_len, d.n_nodes, d_digest, d_flag);
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_proof_node_kernel, dim3((unsigned)((d.n_nodes + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
+                  st, d.node_blob, d.node_off, d.node_len, d.n_nodes, d_digest, d_flag);
     }
-    hipLaunchKernelGGL(pv_proof_walk_kernel, dim3((unsigned)((d.n_queries + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
-                       d, (const uint64_t*)d_digest, (const uint8_t*)d_flag, d_status);
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_proof_walk_kernel, dim3((unsigned)((d.n_queries + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
+              d, (const uint64_t*)d_digest, (const uint8_t*)d_flag, d_status);
     return PV_OK;
 }
 
@@ -215,9 +195,7 @@ int tr_proof_enqueue(const PvProofIn& d, uint64_t* d_digest, uint8_t* d_flag, ui
 // bytes that are copied, statuses copied back. Caller holds g_tr_mu and has validated `in`.
 int tr_proof_device(const PvProofIn& in, uint8_t* status) {
     const hipStream_t st = pv_engine_stream();
-    int rc = g_tr.hand.begin(st);
-    if (rc) return rc;
-    auto run = [&]() -> int {
+    return g_tr.hand.run(st, [&]() -> int {
         const uint64_t nn = in.n_nodes, np = in.n_proofs, nq = in.n_queries;
         uint64_t lo = ~0ull, hi = 0;  // the span of the node blob the records lie in
         for (uint64_t i = 0; i < nn; i++) {
@@ -226,60 +204,29 @@ int tr_proof_device(const PvProofIn& in, uint8_t* status) {
             hi = std::max(hi, in.node_off[i] + len);
         }
         if (nn == 0) lo = hi = 0;
-        const uint64_t kbase = in.key_off[0], kbytes = in.key_off[nq] - kbase, vbase = in.val_off[0],
-                       vbytes = in.val_off[nq] - vbase;
-        std::vector<uint64_t> noff(nn + 1), koff(nq + 1), voff(nq + 1);
+        PvStage& g = g_tr.stage;
+        int rc = g.reset(st, false), i_noff;
+        if (rc) return rc;
+        uint64_t* noff = g.in_u64(nn + 1, &i_noff);  // records need not lie in order: moved to the span's start
         for (uint64_t i = 0; i < nn; i++) noff[i] = in.node_off[i] - lo;
         noff[nn] = in.node_len ? hi - lo : in.node_off[nn] - lo;
-        for (uint64_t i = 0; i <= nq; i++) {
-            koff[i] = in.key_off[i] - kbase;
-            voff[i] = in.val_off[i] - vbase;
-        }
-        PvLayout li;
-        const uint64_t i_noff = li.add(8 * (nn + 1)), i_nlen = li.add(in.node_len ? 8 * nn : 0),
-                       i_pf = li.add(8 * (np + 1)), i_koff = li.add(8 * (nq + 1)), i_voff = li.add(8 * (nq + 1)),
-                       i_qp = li.add(4 * nq), i_root = li.add(32 * nq), i_key = li.add(kbytes), i_val = li.add(vbytes),
-                       i_blob = li.add(hi - lo + 8);
-        const uint64_t o_flag = pv_up256(32 * nn + 1), o_status = o_flag + pv_up256(nn + 1);
-        int rc;
-        if ((rc = g_tr.d_in.grow(li.at)) || (rc = g_tr.d_out.grow(o_status + pv_up256(nq)))) return rc;
-        uint8_t *const din = g_tr.d_in.p, *const dout = g_tr.d_out.p;
-        auto put = [&](uint64_t where, const void* src, uint64_t bytes) -> hipError_t {
-            return bytes ? hipMemcpyAsync(din + where, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-        };
-        PV_HIP(put(i_noff, noff.data(), 8 * (nn + 1)), PV_ERR_LAUNCH);
-        if (in.node_len) PV_HIP(put(i_nlen, in.node_len, 8 * nn), PV_ERR_LAUNCH);
-        PV_HIP(put(i_pf, in.proof_first, 8 * (np + 1)), PV_ERR_LAUNCH);
-        PV_HIP(put(i_koff, koff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
-        PV_HIP(put(i_voff, voff.data(), 8 * (nq + 1)), PV_ERR_LAUNCH);
-        PV_HIP(put(i_qp, in.query_proof, 4 * nq), PV_ERR_LAUNCH);
-        PV_HIP(put(i_root, in.root, 32 * nq), PV_ERR_LAUNCH);
-        PV_HIP(put(i_key, kbytes ? in.key_blob + kbase : nullptr, kbytes), PV_ERR_LAUNCH);
-        PV_HIP(put(i_val, vbytes ? in.val_blob + vbase : nullptr, vbytes), PV_ERR_LAUNCH);
-        PV_HIP(put(i_blob, hi > lo ? in.node_blob + lo : nullptr, hi - lo), PV_ERR_LAUNCH);
-        auto u64p = [&](uint64_t where) { return reinterpret_cast<const uint64_t*>(din + where); };
-        PvProofIn d;
-        d.node_blob = din + i_blob;
-        d.node_off = u64p(i_noff);
-        d.n_nodes = nn;
-        d.proof_first = u64p(i_pf);
-        d.n_proofs = np;
-        d.query_proof = reinterpret_cast<const uint32_t*>(din + i_qp);
-        d.root = din + i_root;
-        d.key_blob = din + i_key;
-        d.key_off = u64p(i_koff);
-        d.val_blob = din + i_val;
-        d.val_off = u64p(i_voff);
-        d.n_queries = nq;
-        d.node_len = in.node_len ? u64p(i_nlen) : nullptr;
-        if ((rc = tr_proof_enqueue(d, reinterpret_cast<uint64_t*>(dout), dout + o_flag, dout + o_status, st))) return rc;
-        PV_HIP(hipMemcpyAsync(status, dout + o_status, nq, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    rc = run();
-    const int rc2 = g_tr.hand.end(st);
-    return rc ? rc : rc2;
+        const int i_nlen = in.node_len ? g.in(in.node_len, 8 * nn) : -1, i_pf = g.in(in.proof_first, 8 * (np + 1)),
+                  i_koff = g.in_offsets(in.key_off, nq), i_voff = g.in_offsets(in.val_off, nq),
+                  i_qp = g.in(in.query_proof, 4 * nq), i_root = g.in(in.root, 32 * nq),
+                  i_key = g.in(in.key_blob + in.key_off[0], in.key_off[nq] - in.key_off[0]),
+                  i_val = g.in(in.val_blob + in.val_off[0], in.val_off[nq] - in.val_off[0]),
+                  i_blob = g.in(in.node_blob + lo, hi - lo, 8),  // the hash reads to a whole word
+                  o_digest = g.out(nullptr, 32 * nn + 1), o_flag = g.out(nullptr, nn + 1), o_status = g.out(status, nq);
+        if ((rc = g.upload())) return rc;
+        const PvProofIn d{g.dev<const uint8_t>(i_blob), g.dev<const uint64_t>(i_noff), nn,
+                          g.dev<const uint64_t>(i_pf),  np,                             g.dev<const uint32_t>(i_qp),
+                          g.dev<const uint8_t>(i_root), g.dev<const uint8_t>(i_key),    g.dev<const uint64_t>(i_koff),
+                          g.dev<const uint8_t>(i_val),  g.dev<const uint64_t>(i_voff),  nq,
+                          g.dev<const uint64_t>(i_nlen)};
+        if ((rc = tr_proof_enqueue(d, g.dev<uint64_t>(o_digest), g.dev<uint8_t>(o_flag), g.dev<uint8_t>(o_status), st)))
+            return rc;
+        return g.download();
+    });
 }
 
 }  // namespace
@@ -291,8 +238,7 @@ void pv_trie_forget_stream(void* stream) {
 
 void pv_trie_shutdown() {
     std::lock_guard<std::mutex> lk(g_tr_mu);
-    g_tr.d_in.release();
-    g_tr.d_out.release();
+    g_tr.stage.release();
     g_tr.hand.destroy();
 }
 
@@ -314,7 +260,7 @@ int pv_sha3_256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint
     if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch: more than 2^31 - 1 records");
     std::unique_lock<std::mutex> lk(g_tr_mu);
     bool device;
-    int rc = tr_choose(n, "pv_sha3_256_batch", &device);
+    int rc = tr_choose(n, PV_TRIE_AUTO_MIN, "pv_sha3_256_batch", &device);
     if (rc) return rc;
     if (!device) {
         lk.unlock();  // the host path shares no workspace
@@ -322,29 +268,17 @@ int pv_sha3_256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint
         return PV_OK;
     }
     const hipStream_t st = pv_engine_stream();
-    if ((rc = g_tr.hand.begin(st))) return rc;
-    auto run = [&]() -> int {
-        // staged whole: [offsets, rebased][data, to a whole word]
-        const uint64_t base = off[0], bytes = off[n] - base, i_data = pv_up256(8 * (n + 1));
-        int rc;
-        if ((rc = g_tr.d_in.grow(i_data + pv_up256(bytes + 8))) ||
-            (rc = g_tr.d_out.grow(pv_up256(32 * n))))
-            return rc;
-        std::vector<uint64_t> rebased(n + 1);
-        for (uint64_t i = 0; i <= n; i++) rebased[i] = off[i] - base;
-        PV_HIP(hipMemcpyAsync(g_tr.d_in.p, rebased.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        if (bytes) PV_HIP(hipMemcpyAsync(g_tr.d_in.p + i_data, data + base, bytes, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        hipLaunchKernelGGL(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
-                           g_tr.d_in.p + i_data, reinterpret_cast<const uint64_t*>(g_tr.d_in.p), n,
-                           reinterpret_cast<uint64_t*>(g_tr.d_out.p));
-        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(out, g_tr.d_out.p, 32 * n, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-        PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    rc = run();
-    const int rc2 = g_tr.hand.end(st);
-    return rc ? rc : rc2;
+    return g_tr.hand.run(st, [&]() -> int {
+        PvStage& g = g_tr.stage;
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        // staged whole; the hash reads to a whole word
+        const int i_off = g.in_offsets(off, n), i_data = g.in(data + off[0], off[n] - off[0], 8), o_digest = g.out(out, 32 * n);
+        if ((rc = g.upload())) return rc;
+        PV_LAUNCH(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
+                  g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), n, g.dev<uint64_t>(o_digest));
+        return g.download();
+    });
 }
 
 int pv_sha3_256_batch_device(const uint8_t* d_data, const uint64_t* d_off, uint64_t n, uint8_t* d_out, void* stream) {
@@ -353,9 +287,8 @@ int pv_sha3_256_batch_device(const uint8_t* d_data, const uint64_t* d_off, uint6
     if (!d_data || !d_off || !d_out) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch_device: null pointer");
     if (reinterpret_cast<uintptr_t>(d_out) & 7u) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch_device: d_out must be 8-byte aligned");
     if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_sha3_256_batch_device: more than 2^31 - 1 records");
-    hipLaunchKernelGGL(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
-                       stream ? (hipStream_t)stream : pv_engine_stream(), d_data, d_off, n, reinterpret_cast<uint64_t*>(d_out));
-    PV_HIP(hipGetLastError(), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_sha3_blob_kernel, dim3((unsigned)((n + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0,
+              stream ? (hipStream_t)stream : pv_engine_stream(), d_data, d_off, n, reinterpret_cast<uint64_t*>(d_out));
     return PV_OK;
 }
 
@@ -377,10 +310,10 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
     if ((out->node_cap && (!out->node_hash || !out->node_off || !out->node_len)) || (out->blob_cap && !out->node_blob) ||
         (out->missing_cap && !out->missing))
         return pv_fail(PV_ERR_ARG, "pv_trie_update_batch: a capacity without its array");
-    {
+    bool device;
+    {  // a forced device path without a device fails before the build
         std::lock_guard<std::mutex> lk(g_tr_mu);
-        if (g_tr_path == PV_TRIE_DEVICE && !pv_engine_stream())
-            return pv_fail(PV_ERR_NO_DEVICE, "pv_trie_update_batch: the device path is forced and no device is initialised");
+        if (int rc = tr_choose(0, 0, "pv_trie_update_batch", &device)) return rc;
     }
     const PvTrieIn in{root, known_hash, known_blob, known_off, n_known, key_blob, key_off, val_blob, val_off, n};
     PvTriePlan plan;
@@ -401,8 +334,7 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
     }
     if (nr > out->node_cap || plan.arena_bytes > out->blob_cap) return PV_TRIE_NEED_SPACE;
     std::unique_lock<std::mutex> lk(g_tr_mu);
-    bool device;
-    if ((rc = tr_choose(nr, "pv_trie_update_batch", &device))) return rc;
+    if ((rc = tr_choose(nr, PV_TRIE_AUTO_MIN, "pv_trie_update_batch", &device))) return rc;
     if (device) {
         if ((rc = tr_device_hash(plan, out->node_blob, out->node_hash, &out->launches, &out->tail_records))) return rc;
     } else {
@@ -425,11 +357,9 @@ int pv_trie_verify_proofs(const PvProofIn* in, uint8_t* status) {
     const char* why = nullptr;
     if (pv_proof_check_args(*in, &why)) return pv_fail(PV_ERR_ARG, std::string("pv_trie_verify_proofs: ") + why);
     std::unique_lock<std::mutex> lk(g_tr_mu);
-    const bool have_dev = pv_engine_stream() != nullptr;
-    if (g_tr_path == PV_TRIE_DEVICE && !have_dev)
-        return pv_fail(PV_ERR_NO_DEVICE, "pv_trie_verify_proofs: the device path is forced and no device is initialised");
-    if (have_dev && (g_tr_path == PV_TRIE_DEVICE || (g_tr_path == PV_TRIE_AUTO && in->n_nodes >= PV_TRIE_PROOF_AUTO_MIN)))
-        return tr_proof_device(*in, status);
+    bool device;
+    if (int rc = tr_choose(in->n_nodes, PV_TRIE_PROOF_AUTO_MIN, "pv_trie_verify_proofs", &device)) return rc;
+    if (device) return tr_proof_device(*in, status);
     lk.unlock();  // the host path shares no workspace
     pv_proof_host(*in, status);
     return PV_OK;
@@ -448,12 +378,11 @@ int pv_trie_verify_proofs_device(const PvProofIn* d_in, uint8_t* d_status, uint8
         return pv_fail(PV_ERR_ARG, "pv_trie_verify_proofs_device: more than 2^31 - 1 records, proofs or queries");
     const hipStream_t st = stream ? (hipStream_t)stream : pv_engine_stream();
     std::lock_guard<std::mutex> lk(g_tr_mu);
-    int rc = g_tr.hand.begin(st);  // the flags live in the workspace: handed over from the stream that used it last
-    if (rc) return rc;
-    if (!(rc = g_tr.d_out.grow(pv_up256(d_in->n_nodes + 1))))
-        rc = tr_proof_enqueue(*d_in, reinterpret_cast<uint64_t*>(d_node_hash), g_tr.d_out.p, d_status, st);
-    const int rc2 = g_tr.hand.end(st);
-    return rc ? rc : rc2;
+    return g_tr.hand.run(st, [&]() -> int {  // the flags live in the workspace: handed over from the stream that used it last
+        PvDevBuf& flag = g_tr.stage.d_out;
+        if (int rc = flag.grow(pv_up256(d_in->n_nodes + 1))) return rc;
+        return tr_proof_enqueue(*d_in, reinterpret_cast<uint64_t*>(d_node_hash), flag.p, d_status, st);
+    });
 }
 
 int pv_trie_proof_split(const uint8_t* ser, const uint64_t* ser_off, uint64_t n_proofs, uint64_t* proof_first,

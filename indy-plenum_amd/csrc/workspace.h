@@ -1,7 +1,8 @@
 // What every device workspace of libplenum_verify.so is made of (host code): the early-return macro,
 // grow-only device and pinned buffers, the owner of a set of resources created once, the event hand-over
-// between caller streams, and the 256-byte staging layout. Callers serialise use of a workspace on its
-// own mutex.
+// between caller streams, the 256-byte staging layout, and the AUTO / HOST / DEVICE path choice. The
+// staged call of a host-buffer entry built on them, PvStage, is in stage.h. Callers serialise use of a
+// workspace on its own mutex.
 #ifndef PV_WORKSPACE_H
 #define PV_WORKSPACE_H
 
@@ -20,6 +21,13 @@ int pv_fail(int code, const std::string& msg);
     do {                                                                                               \
         hipError_t e_ = (call);                                                                        \
         if (e_ != hipSuccess) return pv_fail(code, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// A kernel launch and its check: a launch the runtime refuses returns PV_ERR_LAUNCH from the caller.
+#define PV_LAUNCH(k, ...)                         \
+    do {                                          \
+        hipLaunchKernelGGL(k, __VA_ARGS__);       \
+        PV_HIP(hipGetLastError(), PV_ERR_LAUNCH); \
     } while (0)
 
 inline uint64_t pv_up256(uint64_t x) { return (x + 255) & ~255ull; }
@@ -166,6 +174,15 @@ struct PvHandover {
         last = s;
         return PV_OK;
     }
+    // One use on `s`: the hand-over begun, `body` run, and the hand-over ended also after a failure
+    // (whatever did get enqueued is covered). The first error is returned.
+    template <class F>
+    int run(hipStream_t s, F&& body) {
+        if (int rc = begin(s)) return rc;
+        const int rc = body();
+        const int rc2 = end(s);
+        return rc ? rc : rc2;
+    }
     // `s` is being destroyed.
     void forget(hipStream_t s) {
         if (last == s) last = nullptr;
@@ -187,5 +204,16 @@ struct PvLayout {
         return o;
     }
 };
+
+// The path of a host-buffer entry `who` under a PV_MERKLE_* / PV_TRIE_* mode (both AUTO 0, HOST 1,
+// DEVICE 2): PV_ERR_NO_DEVICE for a forced device path without a device, else PV_OK with *device set
+// (forced, or AUTO with `work` at or above `auto_min`).
+inline int pv_choose_path(int mode, bool have_dev, uint64_t work, uint64_t auto_min, const char* who, bool* device) {
+    static_assert(PV_MERKLE_AUTO == PV_TRIE_AUTO && PV_MERKLE_DEVICE == PV_TRIE_DEVICE, "one set of mode values");
+    if (mode == PV_TRIE_DEVICE && !have_dev)
+        return pv_fail(PV_ERR_NO_DEVICE, std::string(who) + ": the device path is forced and no device is initialised");
+    *device = have_dev && (mode == PV_TRIE_DEVICE || (mode == PV_TRIE_AUTO && work >= auto_min));
+    return PV_OK;
+}
 
 #endif  // PV_WORKSPACE_H

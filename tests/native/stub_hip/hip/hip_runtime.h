@@ -1,17 +1,22 @@
 // A stand-in for <hip/hip_runtime.h> that lets workspace_check.cpp compile csrc/workspace.h with g++ and
-// no GPU: allocations over malloc, events and streams as small integers, a log of every runtime call and
-// a switch that makes the k-th creation from now on (a block, a stream or an event) fail.
+// no GPU: allocations over malloc, events and streams as small integers, copies as memcpy between those
+// blocks, a log of every runtime call, a switch that makes the k-th creation from now on (a block, a stream
+// or an event) fail and one of its own for the k-th copy or synchronisation.
 #ifndef STUB_HIP_RUNTIME_H
 #define STUB_HIP_RUNTIME_H
 
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
 
-enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
-inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "out of memory (stub)"; }
+enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorLaunchFailure = 719 };
+inline const char* hipGetErrorString(hipError_t e) {
+    return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory (stub)" : "launch failure (stub)";
+}
+enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 
 typedef struct StubEvent* hipEvent_t;    // never dereferenced: (hipEvent_t)id
 typedef struct StubStream* hipStream_t;  // the same
@@ -20,12 +25,14 @@ constexpr unsigned hipStreamNonBlocking = 1, hipEventReleaseToDevice = 0x4000000
 
 struct StubCall {
     std::string name;  // "hipMalloc", "hipStreamWaitEvent", ...
-    uintptr_t a, b;    // bytes and flags / stream and event / the pointer freed / the handle made and its flags
-    int c = 0;         // the priority of a stream made with one
+    uintptr_t a, b;    // bytes and flags / stream and event / the pointer freed / the handle made and its flags /
+                       // a copy's destination and bytes / the stream synchronised
+    int c = 0;         // the priority of a stream made with one / a copy's kind
 };
 struct StubState {
     std::vector<StubCall> log;
-    int fail_in = 0;  // > 0: the fail_in-th creation from now fails
+    int fail_in = 0;       // > 0: the fail_in-th creation from now fails
+    int fail_call_in = 0;  // > 0: the fail_call_in-th copy or synchronisation from now fails (and copies nothing)
     uint64_t dev_allocs = 0, dev_frees = 0, host_allocs = 0, host_frees = 0, events = 0, events_destroyed = 0;
     uint64_t streams = 0, streams_destroyed = 0;
 };
@@ -98,6 +105,17 @@ inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
 inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     stub().log.push_back({"hipStreamWaitEvent", (uintptr_t)s, (uintptr_t)e});
     return hipSuccess;
+}
+inline bool stub_call_fails() { return stub().fail_call_in > 0 && --stub().fail_call_in == 0; }
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t) {
+    stub().log.push_back({"hipMemcpyAsync", (uintptr_t)dst, bytes, (int)kind});
+    if (stub_call_fails()) return hipErrorLaunchFailure;
+    memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+inline hipError_t hipStreamSynchronize(hipStream_t s) {
+    stub().log.push_back({"hipStreamSynchronize", (uintptr_t)s, 0});
+    return stub_call_fails() ? hipErrorLaunchFailure : hipSuccess;
 }
 
 #endif  // STUB_HIP_RUNTIME_H

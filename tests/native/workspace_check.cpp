@@ -1,13 +1,17 @@
-// csrc/workspace.h compiled with g++ against the stub runtime in stub_hip/ (no GPU): the grow-only buffers
+// csrc/workspace.h and csrc/stage.h compiled with g++ against the stub runtime in stub_hip/ (no GPU): the grow-only buffers
 // leave themselves empty after a failed allocation, the hand-over issues exactly the waits it should, the
-// staging layout never overlaps, the owner releases exactly what it created however far creation got.
+// staging layout never overlaps, the owner releases exactly what it created however far creation got, a
+// staged call (PvStage) lays out, rebases, copies and recovers from every failing step in both its modes,
+// and the path choice answers its whole table.
 // Prints one JSON object of named checks; tests/test_workspace_host.py builds this with
 // -fsanitize=address,undefined and asserts on it.
 #include <stdio.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
 
+#include "../../indy-plenum_amd/csrc/stage.h"
 #include "../../indy-plenum_amd/csrc/workspace.h"
 
 static std::string g_last_error;
@@ -213,6 +217,188 @@ static void check_owner() {
     }
 }
 
+// One use of a stage as a host-buffer entry makes it, sizes scaled by k: a blob with 37 bytes in front
+// and offsets that start there, a lent array, an empty section, an arena that goes up and comes back, three
+// outputs (one without a dst, one whose tail is only reserved), a stand-in for the kernels in between.
+static const hipStream_t STAGE_STREAM = (hipStream_t)0x50;
+struct StageUse {
+    bool layout = false, rebased = false, caller_array_untouched = false, slack = false, empty = false, inputs = false,
+         outs = false, inout = false, lent = false;
+    size_t up = 0, down = 0, syncs = 0, want_up = 0, want_down = 0;
+    bool good() const {
+        return layout && rebased && caller_array_untouched && slack && empty && inputs && outs && inout && lent &&
+               up == want_up && down == want_down && syncs == 1;
+    }
+};
+static int stage_use(PvStage& st, bool pinned, uint64_t k, StageUse* r) {
+    *r = StageUse();
+    const uint64_t nb = 53 * k;
+    std::vector<uint8_t> blob(37 + nb);  // exactly: a copy that takes the slack along reads past its end
+    for (size_t i = 0; i < blob.size(); i++) blob[i] = (uint8_t)(7 * i + 1);
+    const std::vector<uint64_t> off = {37, 40, 40, 37 + nb}, off_before = off;
+    std::vector<uint8_t> arena(300 * k), arena_out(300 * k, 0), dst1(70 * k, 0), dst3(16, 0xAA);
+    for (size_t i = 0; i < arena.size(); i++) arena[i] = (uint8_t)(3 * i);
+    const std::vector<uint8_t> arena_before = arena;
+    if (int rc = st.reset(STAGE_STREAM, pinned)) return rc;
+    int i_lent;
+    uint64_t* lent = st.in_u64(5, &i_lent);
+    for (uint64_t j = 0; j < 5; j++) lent[j] = 1000 + j;
+    const int i_off = st.in_offsets(off.data(), 3);
+    for (int j = 0; j < 20; j++) (void)st.in_offsets(off.data(), 3);  // the stage's own arrays grow in number
+    const int i_empty = st.in(nullptr, 0), i_blob = st.in(blob.data() + 37, nb, 200),
+              i_arena = st.inout(arena.data(), arena_out.data(), arena.size()), o1 = st.out(dst1.data(), dst1.size()),
+              o2 = st.out(nullptr, 33), o3 = st.out(dst3.data(), 9, 7), o_empty = st.out(nullptr, 0);
+    r->lent = true;
+    for (uint64_t j = 0; j < 5; j++) r->lent = r->lent && lent[j] == 1000 + j;  // still there (AddressSanitizer watches)
+    r->want_up = pinned ? 1 : 24;  // lent, 21 offset arrays, blob, arena; nothing for the empty section
+    r->want_down = pinned ? 1 : 3;  // arena, dst1, dst3
+    const size_t at = calls();
+    if (int rc = st.upload()) return rc;
+
+    struct Span {
+        uint8_t* p;
+        uint64_t bytes;  // reserved
+        bool out;
+    };
+    const Span spans[] = {{st.dev<uint8_t>(i_lent), 40, false},     {st.dev<uint8_t>(i_off), 32, false},
+                          {st.dev<uint8_t>(i_empty), 1, false},     {st.dev<uint8_t>(i_blob), nb + 200, false},
+                          {st.dev<uint8_t>(i_arena), 300 * k, false}, {st.dev<uint8_t>(o1), 70 * k, true},
+                          {st.dev<uint8_t>(o2), 33, true},          {st.dev<uint8_t>(o3), 16, true},
+                          {st.dev<uint8_t>(o_empty), 1, true}};
+    r->layout = st.dev<uint8_t>(-1) == nullptr;
+    for (const Span& a : spans) {
+        const PvDevBuf& blk = a.out && !pinned ? st.d_out : st.d_in;
+        r->layout = r->layout && a.p != nullptr && (uintptr_t)(a.p - blk.p) % 256 == 0 && a.p >= blk.p &&
+                    a.p + a.bytes <= blk.p + blk.cap;
+        for (const Span& b : spans) r->layout = r->layout && (&a == &b || a.p + a.bytes <= b.p || b.p + b.bytes <= a.p);
+    }
+    r->empty = st.dev<uint8_t>(i_empty) != nullptr && st.dev<uint8_t>(o_empty) != nullptr;
+    const uint64_t* d_off = st.dev<const uint64_t>(i_off);
+    r->rebased = d_off[0] == 0 && d_off[1] == 3 && d_off[2] == 3 && d_off[3] == nb;
+    r->caller_array_untouched = off == off_before;
+    r->inputs = memcmp(st.dev<uint8_t>(i_blob), blob.data() + 37, nb) == 0 && memcmp(st.dev<uint8_t>(i_lent), lent, 40) == 0;
+    r->slack = true;  // reserved: the span check above; not copied: the copy into the blob's section has its bytes alone
+    for (const StubCall& c : since(at, "hipMemcpyAsync"))
+        if (!pinned && c.a == (uintptr_t)st.dev<uint8_t>(i_blob)) r->slack = c.b == nb;
+    // the kernels
+    for (uint64_t i = 0; i < 70 * k; i++) st.dev<uint8_t>(o1)[i] = (uint8_t)(5 * i + 2);
+    memset(st.dev<uint8_t>(o2), 0x33, 33);
+    memset(st.dev<uint8_t>(o3), 0x44, 16);  // whole words, of which dst3 takes 9 bytes
+    for (uint64_t i = 0; i < 300 * k; i++) st.dev<uint8_t>(i_arena)[i] += 1;
+    if (int rc = st.download()) return rc;
+
+    r->outs = true;
+    for (uint64_t i = 0; i < 70 * k; i++) r->outs = r->outs && dst1[i] == (uint8_t)(5 * i + 2);
+    for (int i = 0; i < 16; i++) r->outs = r->outs && dst3[i] == (i < 9 ? 0x44 : 0xAA);
+    r->inout = arena == arena_before;
+    for (uint64_t i = 0; i < 300 * k; i++) r->inout = r->inout && arena_out[i] == (uint8_t)(arena[i] + 1);
+    for (const StubCall& c : since(at, "hipMemcpyAsync")) (c.c == hipMemcpyHostToDevice ? r->up : r->down)++;
+    r->syncs = since(at, "hipStreamSynchronize").size();
+    return PV_OK;
+}
+
+// the first synchronisation logged from `from` on comes before the first copy
+static bool sync_comes_first(size_t from) {
+    for (size_t i = from; i < stub().log.size(); i++) {
+        if (stub().log[i].name == "hipStreamSynchronize") return stub().log[i].a == (uintptr_t)STAGE_STREAM;
+        if (stub().log[i].name == "hipMemcpyAsync") return false;
+    }
+    return false;
+}
+
+static void check_stage(bool pinned) {
+    const std::string m = pinned ? "pinned_" : "caller_";
+    auto say = [&](const char* name, bool ok) { put("stage", (m + name).c_str(), ok); };
+    StageUse r;
+    size_t allocs = 0, steps = 0;  // what one use of a fresh stage creates, and its copies and synchronisation
+    {
+        PvStage st;
+        const size_t at = calls();
+        const int rc = stage_use(st, pinned, 2, &r);
+        allocs = since(at, "hipMalloc").size() + since(at, "hipHostMalloc").size();
+        steps = since(at, "hipMemcpyAsync").size() + since(at, "hipStreamSynchronize").size();
+        say("use_succeeds", rc == PV_OK && allocs == 2 && since(at, "hipHostMalloc").size() == (pinned ? 1u : 0u));
+        say("sections_aligned_disjoint_in_their_blocks", r.layout);
+        say("empty_section_has_a_pointer_and_no_copy", r.empty && r.up == r.want_up);
+        say("offsets_arrive_rebased", r.rebased && r.inputs);
+        say("callers_offsets_untouched", r.caller_array_untouched);
+        say("slack_reserved_not_copied", r.slack);
+        say("outputs_arrive_and_null_dst_is_skipped", r.outs);
+        say("inout_round_trips", r.inout);
+        say("lent_array_survives_later_sections", r.lent);
+        say("copy_count", r.up == r.want_up && r.down == r.want_down);
+        say("one_synchronise", r.syncs == 1);
+        // chunk after chunk: a larger one grows the blocks, then a smaller and an equal one allocate nothing
+        size_t at2 = calls();
+        bool ok = stage_use(st, pinned, 5, &r) == PV_OK && r.good();
+        ok = ok && since(at2, "hipMalloc").size() + since(at2, "hipHostMalloc").size() == 2;
+        at2 = calls();
+        ok = ok && stage_use(st, pinned, 1, &r) == PV_OK && r.good() && stage_use(st, pinned, 5, &r) == PV_OK && r.good();
+        say("reset_reuses_blocks_that_fit", ok && since(at2, "hipMalloc").empty() && since(at2, "hipHostMalloc").empty() &&
+                                                since(at2, "hipFree").empty() && since(at2, "hipHostFree").empty());
+        // the other mode on the same stage
+        say("mode_can_change_between_uses", stage_use(st, !pinned, 3, &r) == PV_OK && r.good());
+        st.release();
+        say("release_frees_every_block", stub().dev_allocs == stub().dev_frees && stub().host_allocs == stub().host_frees);
+    }
+    bool code = true, next = true, synced = true;
+    for (size_t k = 1; k <= allocs; k++) {  // each grow
+        PvStage st;
+        stub().fail_in = (int)k;
+        g_last_error.clear();
+        code = code && stage_use(st, pinned, 2, &r) == PV_ERR_ALLOC && !g_last_error.empty() && stub().fail_in == 0;
+        const size_t at = calls();
+        next = next && stage_use(st, pinned, 2, &r) == PV_OK && r.good();
+        synced = synced && sync_comes_first(at);
+        st.release();
+    }
+    say("failed_grow_returns_alloc_error", code);
+    say("use_after_failed_grow_succeeds", next);
+    say("use_after_failed_grow_synchronises_first", synced);
+    code = next = synced = true;
+    for (size_t k = 1; k <= steps; k++) {  // each copy, the synchronisation
+        PvStage st;
+        stub().fail_call_in = (int)k;
+        g_last_error.clear();
+        code = code && stage_use(st, pinned, 2, &r) == PV_ERR_LAUNCH && !g_last_error.empty() && stub().fail_call_in == 0;
+        const size_t at = calls();
+        next = next && stage_use(st, pinned, 2, &r) == PV_OK && r.good();
+        synced = synced && sync_comes_first(at);
+        st.release();
+    }
+    say("failed_copy_or_synchronise_returns_launch_error", code && steps == (pinned ? 3u : 28u));
+    say("use_after_failed_copy_succeeds", next);
+    say("use_after_failed_copy_synchronises_first", synced);
+    say("all_released_at_the_end", stub().dev_allocs == stub().dev_frees && stub().host_allocs == stub().host_frees);
+}
+
+// mode x have-device x work {0, below, at the threshold}
+static void check_path_choice() {
+    bool code = true, choice = true, text = true, untouched = true;
+    const uint64_t works[] = {0, 351, 352};
+    for (int mode = 0; mode < 3; mode++)
+        for (int have = 0; have < 2; have++)
+            for (uint64_t work : works) {
+                bool device = true;
+                g_last_error.clear();
+                const int rc = pv_choose_path(mode, have != 0, work, 352, "pv_some_entry", &device);
+                const bool forced_without = mode == PV_TRIE_DEVICE && !have;
+                code = code && rc == (forced_without ? PV_ERR_NO_DEVICE : PV_OK);
+                if (forced_without) {
+                    text = text && g_last_error == "pv_some_entry: the device path is forced and no device is initialised";
+                    untouched = untouched && device;
+                } else {
+                    const bool want = have && (mode == PV_TRIE_DEVICE || (mode == PV_TRIE_AUTO && work >= 352));
+                    choice = choice && device == want && g_last_error.empty();
+                }
+            }
+    put("stage", "path_forced_device_without_device_is_an_error", code);
+    put("stage", "path_error_text", text && untouched);
+    put("stage", "path_choice_table", choice);
+    put("stage", "path_modes_are_0_1_2", PV_MERKLE_AUTO == 0 && PV_MERKLE_HOST == 1 && PV_MERKLE_DEVICE == 2 &&
+                                             PV_TRIE_AUTO == 0 && PV_TRIE_HOST == 1 && PV_TRIE_DEVICE == 2);
+}
+
 int main() {
     check_buffer<PvDevBuf>("dev", "hipMalloc", [](PvDevBuf& b, uint64_t want) { return b.grow(want); });
     check_buffer<PvPinnedBuf>("pinned", "hipHostMalloc",
@@ -283,6 +469,12 @@ int main() {
         ok = h.end(A) == PV_OK;
         put("hand", "end_first_creates_event", ok && since(at, "hipEventCreateWithFlags").size() == 1 && h.last == A);
         h.destroy();
+        // run: the body's error comes back and the hand-over is ended all the same
+        at = calls();
+        ok = h.run(B, [] { return (int)PV_ERR_ARG; }) == PV_ERR_ARG;
+        put("hand", "run_ends_after_a_failed_body", ok && since(at, "hipEventRecord").size() == 1 && h.last == B);
+        put("hand", "run_returns_ok", h.run(B, [] { return (int)PV_OK; }) == PV_OK);
+        h.destroy();
         put("hand", "events_all_destroyed", stub().events == stub().events_destroyed);
     }
     {
@@ -317,6 +509,9 @@ int main() {
         put("monotone", "prefix_before_the_decrease", pv_offsets_monotone(last, 3));
     }
     check_owner();
+    check_stage(false);
+    check_stage(true);
+    check_path_choice();
     printf("{%s}\n", g_json.c_str());
     return 0;
 }

@@ -1,7 +1,7 @@
-"""The shared pieces of the device workspaces (indy-plenum_amd/csrc/workspace.h: grow-only device and
+"""The shared pieces of the device workspaces (indy-plenum_amd/csrc/workspace.h and stage.h: grow-only device and
 pinned buffers, the owner of a context's resources, the event hand-over between caller streams, the
-256-byte staging layout, the offsets check), compiled with g++ against a stub HIP runtime
-(tests/native/stub_hip) that logs every call and can fail a creation. Built with AddressSanitizer and UBSan and run as a stand-alone program. CPU only."""
+256-byte staging layout, the offsets check, the staged call of a host-buffer entry, the path choice), compiled with g++ against a stub HIP runtime
+(tests/native/stub_hip) that logs every call and can fail a creation, a copy or a synchronisation. Built with AddressSanitizer and UBSan and run as a stand-alone program. CPU only."""
 import json
 import os
 import subprocess
@@ -12,12 +12,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "workspace_check.cpp")
 STUB = os.path.join(HERE, "native", "stub_hip")
 HDR = os.path.join(HERE, "..", "indy-plenum_amd", "csrc", "workspace.h")
+STAGE_HDR = os.path.join(HERE, "..", "indy-plenum_amd", "csrc", "stage.h")
 BIN = os.path.join(HERE, "native", "workspace_check")
 
 
 @pytest.fixture(scope="module")
 def report():
-    deps = [SRC, HDR, os.path.join(STUB, "hip", "hip_runtime.h")]
+    deps = [SRC, HDR, STAGE_HDR, os.path.join(STUB, "hip", "hip_runtime.h")]
     if not os.path.exists(BIN) or os.path.getmtime(BIN) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
                                "-fno-sanitize-recover=undefined", "-Wall", "-Werror", "-I", STUB, "-o", BIN, SRC])
@@ -58,6 +59,20 @@ def test_owner_releases_what_it_created_however_far_creation_got(report):
     behind (the half-built context no GPU test can reach); an optional pair whose second half fails leaves
     the owner as it was."""
     _group(report, "owner", 19)
+
+
+def test_stage_lays_out_rebases_copies_and_recovers_in_both_modes(report):
+    """PvStage in caller-memory and in pinned mode over the stub's malloc-backed blocks: sections are 256-byte
+    aligned, disjoint, inside their block and non-null when empty; offsets that start at 37 arrive starting at
+    0 and the caller's array is untouched; slack is reserved and never read from the caller; outputs arrive
+    byte for byte, a null dst is skipped, an arena goes up and comes back; the log holds one copy per
+    non-empty section (caller memory) or one up and one down (pinned) and one synchronise; a larger chunk
+    grows the blocks and smaller ones allocate nothing; with each grow, each copy and the synchronise failing
+    in turn the use returns PV_ERR_ALLOC / PV_ERR_LAUNCH, and the next use synchronises before its first copy
+    and succeeds; a lent array survives later sections; the AUTO / HOST / DEVICE choice over its whole table,
+    error text included."""
+    _group(report, "stage", 2 * 21 + 4)
+    assert sum(k.startswith("stage.caller_") for k in report) == sum(k.startswith("stage.pinned_") for k in report)
 
 
 def test_layout_sections_are_aligned_and_disjoint(report):
