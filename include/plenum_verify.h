@@ -317,6 +317,25 @@ int pv_table_reuse_stats(uint64_t* hits, uint64_t* built, uint64_t* resets);
 int pv_table_affine(int on);
 int pv_table_affine_stats(uint64_t* converted, uint64_t* affine_reads);
 
+/* Wide rows for resident tables (on by default; it needs table reuse and affine rows). A chunk of more
+ * than 65,536 requests that reads a listed table in affine form (the table's third hit by such a chunk)
+ * builds, after its own kernels, radix-2^11 affine niels rows of that key in a pool of its own: 23 rows of
+ * 1,025 entries, 3.0 MB per key, beside the radix-256 table, which stays. Every later keyed chunk that
+ * hits the table, of any size, computes [k](-A) as 23 additions from those rows instead of 32. Verdicts
+ * do not change. At most 1,024 tables are widened behind one chunk and only while the pool has room; the
+ * rest stay in affine form. The pool is allocated by the first chunk that can widen a table; when that
+ * allocation fails the feature turns itself off and pv_last_error() says so. The pool empties whenever the
+ * directory does.
+ *   pv_table_wide(capacity)          tables the pool holds; 0 = off (default 2,048 = 6.2 GB). A change
+ *                                    empties the directory. Applies to every device of the process.
+ *   pv_table_wide_stats(w, r)        tables widened / tables read from wide rows, since pv_init; the
+ *                                    latter are counted in pv_table_affine_stats's affine reads as well
+ *                                    (they are affine rows of the same table). Synchronises the device:
+ *                                    for tests and tools.
+ * PV_TABLE_WIDE=0 in the environment at pv_init starts with it off. */
+int pv_table_wide(uint32_t capacity);
+int pv_table_wide_stats(uint64_t* widened, uint64_t* wide_reads);
+
 /* Batched base58 decode (Bitcoin alphabet, PyPI base58 2.x b58decode semantics: trailing ASCII
  * whitespace stripped, each leading '1' -> 0x00). Input: strings concatenated in `chars` with
  * n+1 offsets. Output: out[i * out_stride ...], out_len[i] bytes, status[i] = 0 ok, 1 invalid

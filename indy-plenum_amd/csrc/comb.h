@@ -449,7 +449,7 @@ static_assert(PV_BC2_TOP_ENT <= PV_BC2_ENT, "top row larger than a full row");
 //
 // total > P (per lane): positions total - 1 .. 0 with the stage / digit objects mapping the extra
 // positions to other niels rows -- a cached key's radix-65536 rows (pv_kc_wide: [k](-A) as 16 more
-// niels additions in the same loop).
+// niels additions in the same loop) or a resident table's radix-2^11 rows (PV_KR_*: 23 more).
 // Niels additions of positions jtop .. 0 into acc; f = the digit of position jtop, whose entry is
 // already staging (st.stage(jtop, |f|)).
 template <class BStage, class Digit>
@@ -529,6 +529,53 @@ PV_HD int pv_kw_digit(uint32_t ek_word, int q) {  // ek_word = radix-256 digit w
     return pv_byte(ek_word, 2 * q) + 256 * pv_byte(ek_word, 2 * q + 1);
 }
 
+// ---------------------------------------------------------------- wide per-key rows (resident tables)
+// A resident table that dense chunks keep hitting gets radix-2^11 rows beside its radix-256 ones:
+// T_W[q][d] = [d 2^(11 q)](-A), q = 0..22, d = 0..1024, the same entry format as above (3.0 MB per key).
+// 253 = 11 x 23: [k](-A) is 23 niels additions, and every row has the same length. The digits are
+// sc_recode_w_packed<11, 23>(k): |d_q| <= 1024, top digit >= 0.
+// A 1,025-entry TOP row is enough only because k is reduced below L = 2^252 + c, c < 2^125: the top raw
+// digit k >> 242 is then <= 1024, and when it is 1024 the bits below it down to bit 125 are 0, so the
+// digit below is 0 and nothing carries in (the recoding clamps all the same, for the lookup's bounds).
+static constexpr int PV_KR_W = 11;
+static constexpr int PV_KR_POS = 23;
+static constexpr uint32_t PV_KR_ENT = (1u << (PV_KR_W - 1)) + 1u;
+static constexpr int PV_KR_WORDS = (PV_KR_POS + 1) / 2;  // digit words per request, two digits each
+static constexpr uint32_t PV_KR_RUN = 64;                 // entries per build run (pv_kr_build_run)
+static constexpr uint32_t PV_KR_RUNS = (PV_KR_ENT - 1) / PV_KR_RUN;  // runs per row: entries 1..1024
+static_assert(PV_KR_W * PV_KR_POS == 253 && PV_KR_RUNS * PV_KR_RUN + 1 == PV_KR_ENT, "23 full rows, 16 full runs");
+PV_HD int pv_kr_digit(uint32_t word, int q) { return pv_half(word, q); }  // word = digit word q >> 1
+
+// The base of position q, [2^(11 q)](-A), is entry (i, d) = (11 q / 8, 2^(11 q mod 8)) of the key's
+// radix-256 table. From that entry's 40 words, cached form (Y+X, Y-X, 2Z, 2dT) or affine rows (y+x, y-x,
+// 0, 2dxy; Z = 1): the point with every coordinate doubled, X = (Y+X) - (Y-X), Y = (Y+X) + (Y-X),
+// Z = 2Z, T = 2dT / d, as pv_comb_fill_sparse takes T[16 q] back.
+PV_HD int pv_kr_base_row(int q) { return (PV_KR_W * q) >> 3; }
+PV_HD int pv_kr_base_ent(int q) { return 1 << ((PV_KR_W * q) & 7); }
+PV_HD void pv_kr_base(ge_p3& P, const uint32_t w[40], bool affine) {
+    fe ypx, ymx, z2, t2d, invd;
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+        ypx.v[i] = w[i];
+        ymx.v[i] = w[10 + i];
+        z2.v[i] = affine ? (i == 0 ? 2u : 0u) : w[20 + i];
+        t2d.v[i] = w[30 + i];
+    }
+    fe_sub4p(P.X, ypx, ymx);
+    fe_carry(P.X, P.X);
+    fe_add(P.Y, ypx, ymx);
+    fe_carry(P.Y, P.Y);
+    fe_copy(P.Z, z2);
+    fe_const(invd, PV_INVD);
+    fe_mul(P.T, t2d, invd);
+}
+
+// Run r (0..PV_KR_RUNS-1) of the row of base point P: entries 64 r + 1 .. 64 r + 64 by pv_bc2_build_run
+// (below: one inversion per run); run 0 also writes the identity at d = 0. scr.store / scr.load take the
+// entry index, as there.
+template <class Row, class Scr>
+PV_HD void pv_kr_build_run(const Row& row, const Scr& scr, const ge_p3& P, uint32_t r);
+
 // Wide fixed-base comb build, one run of cnt consecutive entries d0 .. d0 + cnt - 1 of the row of
 // base point P (pv_bc2_build_kernel: one run per thread): the start [d0] P by double-and-add, then
 // P-steps, each projective point parked in its own entry (row.e(d): 32 words) with the running
@@ -543,7 +590,7 @@ PV_HD void pv_bc2_build_run(const Row& row, const Scr& scr, const ge_p3& P, uint
     ge_p3_identity(cur);
     ge_p1p1 t;
     for (int b = 31; b >= 0; b--) {
-        if (d0 >> (b + 1)) {
+        if ((uint64_t)d0 >> (b + 1)) {  // 64-bit: b + 1 reaches 32
             ge_p2_dbl(t, cur.X, cur.Y, cur.Z);
             ge_p1p1_to_p3(cur, t);
         }
@@ -605,6 +652,16 @@ PV_HD void pv_bc2_build_run(const Row& row, const Scr& scr, const ge_p3& P, uint
         e[30] = 0;
         e[31] = 0;
     }
+}
+
+template <class Row, class Scr>
+PV_HD void pv_kr_build_run(const Row& row, const Scr& scr, const ge_p3& P, uint32_t r) {
+    if (r == 0) {  // the identity: (y + x, y - x, 2dxy) = (1, 1, 0)
+        uint32_t* e = row.e(0);
+#pragma unroll
+        for (int q = 0; q < PV_BCOMB_STRIDE; q++) e[q] = (q == 0 || q == 10) ? 1u : 0u;
+    }
+    pv_bc2_build_run(row, scr, P, r * PV_KR_RUN + 1u, PV_KR_RUN);
 }
 
 // ---------------------------------------------------------------- fixed-base comb (host, init)

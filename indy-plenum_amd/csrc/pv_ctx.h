@@ -61,6 +61,12 @@ struct Ctx {
     uint32_t dir_cap = PV_DIR_DEFAULT_CAP;
     bool dir_dirty = true;
     bool aff_on = true;  // dense chunks convert the resident tables they hit to affine rows (pv_table_affine)
+    // radix-2^11 rows of resident tables (pv_table_wide): the pool's capacity in tables (0: off), the pool
+    // and its builder's scratch (allocated by the first chunk that can widen), dense chunks seen until then
+    uint32_t wide_cap = PV_WIDE_DEFAULT;
+    bool wide_failed = false;  // the pool's allocation failed: off until pv_table_wide names a capacity again
+    uint32_t wide_dense = 0;
+    PvDevBuf d_wide, d_wide_scr;
     bool last_latency = false;  // the most recent launch took the latency path
     bool verdict_zeroed = false;  // the caller's verdict words are already 0 (pv_verify_batch)
     bool keyed_hint = false;      // pv_verify_batch saw few distinct keys: keyed path below PV_LATENCY_MAX

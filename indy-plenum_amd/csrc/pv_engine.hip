@@ -172,13 +172,17 @@ struct DevATab {
 // Straus path: rows PV_K2_ROW.. hold k2's radix-16 digits, row PV_NW_ROW the lane's window count
 static constexpr int PV_K2_ROW = 8 + (Bc2<16>::POS > PV_BC2_POS ? Bc2<16>::POS : PV_BC2_POS);
 static constexpr int PV_NW_ROW = PV_K2_ROW + 8;
-static constexpr int PV_DIGIT_ROWS = PV_NW_ROW + 1;
+// comb path, a key read from its radix-2^11 rows (comb.h PV_KR_*): the 23 digits of k, two per word, in
+// rows 0..7 (in place of the radix-256 digits) and PV_KR_ROW .. PV_KR_ROW + 3
+static constexpr int PV_KR_ROW = PV_NW_ROW + 1;
+static constexpr int PV_DIGIT_ROWS = PV_KR_ROW + (PV_KR_WORDS - 8);
 struct DevDigits {
     Soa d;
     uint32_t slot;
     __device__ __forceinline__ DevDigits(uint32_t* base, uint32_t stride, uint32_t slot_)
         : d(base, PV_DIGIT_ROWS, stride), slot(slot_) {}
     __device__ __forceinline__ uint32_t ek(int q) const { return d.ld(q, slot); }
+    __device__ __forceinline__ uint32_t kr(int q) const { return d.ld(q < 8 ? q : PV_KR_ROW - 8 + q, slot); }
     __device__ __forceinline__ uint32_t ek2(int q) const { return d.ld(PV_K2_ROW + q, slot); }
     __device__ __forceinline__ uint32_t nw() const { return d.ld(PV_NW_ROW, slot); }
     __device__ __forceinline__ int fb(int j) const { return (int)d.ld(8 + j, slot); }
@@ -763,8 +767,10 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
     // every comb key without a cached table is a miss and they take slots 0, 1, ...
     uint32_t tnext = 0;  // this thread's next slot
     bool dir_reset = false;
+    uint32_t wbase = 0;  // wide pool: the first free slot; this chunk's q-th queued table takes slot wbase + q
     if (kw.dir_on) {
-        if (t == 0) kw.aff_cnt[0] = 0;  // the queue below fills after the scans' barriers
+        wbase = kw.wide_cnt[1];  // pool slots in use: read by every thread before the scans' barriers, written after
+        if (t == 0) kw.aff_cnt[0] = kw.wide_cnt[0] = 0;  // the queues below fill after the scans' barriers
         const uint32_t have = kw.dir_cnt[0];  // read by every thread before the scans' barriers, written after
         uint32_t M, D;
         const uint32_t mb = pv_block_scan(nm, part, &M);
@@ -777,6 +783,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
             const uint32_t built = dir_reset ? M + D : M;
             const uint32_t base = dir_reset ? 0u : have;
             kw.dir_cnt[0] = base;
+            if (dir_reset) kw.wide_cnt[1] = 0;  // the wide pool empties with the directory (a reset chunk hits nothing)
             kw.dir_cnt[1] = kw.dir_pub && !lat ? min(base + built, kw.dir_cap) : base;
             if (!lat) {
                 kw.dir_stat[0] += dir_reset ? 0u : D;
@@ -785,7 +792,9 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
             kw.dir_stat[2] += dir_reset ? 1u : 0u;
         }
     }
-    uint32_t na = 0;  // this thread's directory hits whose rows are affine
+    // tables this chunk may queue for widening: the queue's length and what the pool has left
+    const uint32_t wroom = dir_reset || kw.wide_cap <= wbase ? 0u : min(PV_WIDE_CAP, kw.wide_cap - wbase);
+    uint32_t na = 0, nw = 0;  // this thread's directory hits whose rows are affine / that are read wide
     for (uint32_t v = lo, j = jbase; v < hi; v++) {
         const uint32_t id = vid(v);
         const uint32_t c = count(v, id);
@@ -803,6 +812,7 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
             kw.comb_key[j] = id;
             kw.comb_cslot[j] = cslot;
             kw.comb_tslot[j] = tslot;
+            uint32_t wslot = PV_EMPTY;  // the pool slot of a resident table read from its wide rows
             // a cached or resident key's libsodium checks ran when its table was built (the chain skips it)
             if (cslot != PV_EMPTY) {
                 const uint32_t f = (cslot & PV_CSLOT_DIR)  ? kw.dir_flags[tslot]
@@ -823,7 +833,23 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
                         }
                     }
                 }
+                if ((cslot & PV_CSLOT_DIR) && kw.wide_cap) {
+                    if (f & PV_KF_WIDE) {
+                        wslot = kw.dir_wslot[tslot];
+                        if (!lat) nw++;
+                    } else if (kw.wide_conv && !lat && (f & (PV_KF_OK | PV_KF_AFF)) == (PV_KF_OK | PV_KF_AFF)) {
+                        // a dense chunk's hit on affine rows -- the table's third dense hit: queued while the
+                        // queue and the pool have room (thread 0 settles both counts below); the chunk itself
+                        // reads the affine rows, pv_dir_widen_kernel builds the wide ones behind it
+                        const uint32_t q = atomicAdd(&kw.wide_cnt[0], 1u);
+                        if (q < wroom) {
+                            kw.wide_list[2 * q] = tslot;
+                            kw.wide_list[2 * q + 1] = wbase + q;
+                        }
+                    }
+                }
             }
+            kw.comb_wslot[j] = wslot;
             kw.key_cursor[id] = cc;
             cc += c;
         } else {
@@ -834,6 +860,15 @@ __global__ __launch_bounds__(1024) void pv_key_scan_kernel(KeyWork kw, const uin
         if (cand_id) j++;
     }
     if (na) atomicAdd(&kw.dir_stat[4], (unsigned long long)na);
+    if (nw) atomicAdd(&kw.dir_stat[6], (unsigned long long)nw);
+    if (kw.wide_conv) {  // uniform: the queue is complete once every thread is here
+        __syncthreads();
+        if (t == 0 && !dir_reset) {
+            const uint32_t queued = min(atomicAdd(&kw.wide_cnt[0], 0u), wroom);
+            kw.wide_cnt[0] = queued;  // what pv_dir_widen_kernel builds: entries [0, queued) are all filled
+            kw.wide_cnt[1] = wbase + queued;
+        }
+    }
     if (t == 0) {
         kw.nkeys[PV_SPLIT_KEYS] = nk;  // distinct keys (pv_last_path)
         // AUTO's device-side choice for a 2,049..4,096-request batch of pv_verify_batch_device: the
@@ -1210,11 +1245,12 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_put_prep_kernel(KeyWork kw, ui
 // The key's own checks (key_flag) are written by the chain kernel on the key stream, which runs
 // concurrently with this kernel: the comb kernels fold them into flags[slot].
 template <int W>
-struct PrepAos {  // uint4 per request: ek[8], fb[POS], flag, padding
-    static constexpr int WORDS = 8 + Bc2<W>::POS + 1;
+struct PrepAos {  // uint4 per request: ek[8], fb[POS], flag, the digit words 8..11 of a key read wide, padding
+    static constexpr int KR = 8 + Bc2<W>::POS + 1;  // first of those words
+    static constexpr int WORDS = KR + (PV_KR_WORDS - 8);
     static constexpr int Q = (WORDS + 3) / 4;
 };
-static constexpr int PV_PREP_AOS_QMAX = 7;  // the largest PrepAos<W>::Q (W = 16: 25 words)
+static constexpr int PV_PREP_AOS_QMAX = 8;  // the largest PrepAos<W>::Q (W = 16: 29 words)
 static_assert(PrepAos<16>::Q <= PV_PREP_AOS_QMAX && PrepAos<PV_BC2_W>::Q <= PV_PREP_AOS_QMAX, "AoS record size");
 template <int W>
 __global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_prep_req_kernel(const uint8_t* __restrict__ sm,
@@ -1242,18 +1278,31 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_prep_req_kernel(const uin
     pv_hash_k(k, in, smlen, mw);
     constexpr int P = Bc2<W>::POS;
     uint32_t w[4 * PrepAos<W>::Q];
-    sc_recode256(w, k);
+    const bool wide = kw.comb_wslot[kw.skey[i]] != PV_EMPTY;  // the scan's word, not key_flag (pv_engine_dev.h)
+    if (wide) {
+        uint32_t d[PV_KR_WORDS];
+        sc_recode_w_packed<PV_KR_W, PV_KR_POS>(d, k);
+#pragma unroll
+        for (int q = 0; q < 8; q++) w[q] = d[q];
+#pragma unroll
+        for (int q = 8; q < PV_KR_WORDS; q++) w[PrepAos<W>::KR - 8 + q] = d[q];
+    } else {
+        sc_recode256(w, k);
+#pragma unroll
+        for (int q = 8; q < PV_KR_WORDS; q++) w[PrepAos<W>::KR - 8 + q] = 0u;
+    }
     int32_t fb[P];
     sc_recode_w<W, P>(fb, in.S);
 #pragma unroll
     for (int j = 0; j < P; j++) w[8 + j] = (uint32_t)fb[j];
     w[8 + P] = ok ? 1u : 0u;
 #pragma unroll
-    for (int j = 9 + P; j < 4 * PrepAos<W>::Q; j++) w[j] = 0u;
+    for (int j = PrepAos<W>::WORDS; j < 4 * PrepAos<W>::Q; j++) w[j] = 0u;
     uint4* o = wk.aos + (uint64_t)r * PrepAos<W>::Q;
 #pragma unroll
-    for (int q = 0; q < PrepAos<W>::Q; q++) o[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-    if (kw.nkeys[PV_SPLIT_SPARSE]) {  // small chunk: record which entries of each row this request uses
+    for (int q = 0; q < PrepAos<W>::Q; q++)  // a piece that holds nothing but the wide digit words: wide keys only
+        if (4 * q < PrepAos<W>::KR || wide) o[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    if (kw.nkeys[PV_SPLIT_SPARSE] && !wide) {  // small chunk: record which entries of each row this request uses
         uint32_t* nd = kw.need + (uint64_t)kw.skey[i] * PV_COMB_POS * 5;
 #pragma unroll
         for (int pos = 0; pos < PV_COMB_POS; pos++) {
@@ -1273,9 +1322,10 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_comb_digits_kernel(Work wk, KeyWo
     if (i >= gate.ncomb()) return;
     const uint4* a = wk.aos + (uint64_t)kw.slot_req[i] * PrepAos<W>::Q;
     uint32_t w[4 * PrepAos<W>::Q];
+    const bool wide = kw.comb_wslot[kw.skey[i]] != PV_EMPTY;  // as the prep kernel decided
 #pragma unroll
     for (int q = 0; q < PrepAos<W>::Q; q++) {
-        const uint4 v = a[q];
+        const uint4 v = 4 * q < PrepAos<W>::KR || wide ? a[q] : make_uint4(0u, 0u, 0u, 0u);
         w[4 * q] = v.x;
         w[4 * q + 1] = v.y;
         w[4 * q + 2] = v.z;
@@ -1284,22 +1334,31 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_comb_digits_kernel(Work wk, KeyWo
     const Soa ds(wk.digits, PV_DIGIT_ROWS, wk.stride);
 #pragma unroll
     for (int q = 0; q < 8 + Bc2<W>::POS; q++) ds.st(q, i, w[q]);
+#pragma unroll
+    for (int q = 8; q < PV_KR_WORDS; q++)
+        if (wide) ds.st(PV_KR_ROW - 8 + q, i, w[PrepAos<W>::KR - 8 + q]);
     wk.flags[i] = w[8 + Bc2<W>::POS];
 }
 
-// The niels loop of a comb slot over the wide fixed-base rows and, when the slot's key has wide cached
-// rows (wkey != null), over those too: positions 16.. are the fixed base's (row j - 16), 0..15 the
-// key's radix-65536 rows (comb.h PV_KW_*). Same entry format, same LDS staging as DevB2Stage.
+// The niels loop of a comb slot over the wide fixed-base rows and, when the slot's key has wide rows
+// (kpos != 0), over those too: positions kpos.. are the fixed base's (row j - kpos), 0..kpos-1 the key's --
+// a cached key's 16 radix-65536 rows (comb.h PV_KW_*) or a resident table's 23 radix-2^11 rows (PV_KR_*),
+// per lane. Same entry format, same LDS staging as DevB2Stage.
+struct DevKeyWide {
+    const uint4* rows;  // [kpos][entries][8], or null
+    int kpos;           // PV_KW_POS, PV_KR_POS, or 0: the key has no wide rows
+    __device__ __forceinline__ uint32_t ent() const { return kpos == PV_KR_POS ? PV_KR_ENT : PV_KW_ENT; }
+};
 template <uint32_t ENT>
 struct DevBWStage {
     const uint4* base;  // T_B2
-    const uint4* wkey;  // the key's wide rows [16][PV_KW_ENT][8], or null
+    DevKeyWide key;
     uint4* lds;
     uint32_t lane;
     __device__ __forceinline__ void stage(int j, int d) const {
-        const uint4* e = wkey && j < PV_KW_POS
-                             ? wkey + ((uint64_t)j * PV_KW_ENT + (uint32_t)d) * (PV_BCOMB_STRIDE / 4)
-                             : base + ((uint64_t)(wkey ? j - PV_KW_POS : j) * ENT + (uint32_t)d) * (PV_BCOMB_STRIDE / 4);
+        const uint4* e = j < key.kpos
+                             ? key.rows + ((uint64_t)j * key.ent() + (uint32_t)d) * (PV_BCOMB_STRIDE / 4)
+                             : base + ((uint64_t)(j - key.kpos) * ENT + (uint32_t)d) * (PV_BCOMB_STRIDE / 4);
         pv_lds_reads_done();
         pv_glds16_row<PV_BCOMB_STRIDE / 4>(e, lds);
     }
@@ -1315,25 +1374,36 @@ struct DevBWStage {
         }
     }
 };
-// The wide rows of slot i's key (null unless the key is cached with wide rows).
-__device__ __forceinline__ const uint4* pv_kw_rows(const KeyWork& kw, uint32_t i) {
-    if (!kw.kc_wtab) return nullptr;
-    const uint32_t cslot = kw.comb_cslot[kw.skey[i]];
-    return cslot < kw.kc_wcap ? kw.kc_wtab + (uint64_t)cslot * PV_KW_POS * PV_KW_ENT * (PV_BCOMB_STRIDE / 4)
-                              : nullptr;
+// The wide rows of slot i's key: a resident table's (comb_wslot, written by the scan for every comb index),
+// else a cached key's; kpos = 0 when it has neither.
+__device__ __forceinline__ DevKeyWide pv_key_wide(const KeyWork& kw, uint32_t i) {
+    const uint32_t j = kw.skey[i];
+    const uint32_t ws = kw.comb_wslot[j];
+    if (ws != PV_EMPTY)
+        return DevKeyWide{kw.wide_tab + (uint64_t)ws * PV_KR_POS * PV_KR_ENT * (PV_BCOMB_STRIDE / 4), PV_KR_POS};
+    if (kw.kc_wtab) {
+        const uint32_t cslot = kw.comb_cslot[j];
+        if (cslot < kw.kc_wcap)
+            return DevKeyWide{kw.kc_wtab + (uint64_t)cslot * PV_KW_POS * PV_KW_ENT * (PV_BCOMB_STRIDE / 4), PV_KW_POS};
+    }
+    return DevKeyWide{nullptr, 0};
 }
-// [S]B, plus [k](-A) when wkey: the niels loop over 11 (+ 16) positions (comb.h pv_comb_b_acc_w).
+// [S]B, plus [k](-A) when the key has wide rows: the niels loop over 11 (+ 16 or 23) positions (comb.h
+// pv_comb_b_acc_w). Digit word j >> 1 holds digit j of either wide form.
 template <int W>
-__device__ __forceinline__ void pv_comb_bw_acc(ge_p3& acc, const uint4* bcomb, const uint4* wkey, const DevDigits& dig,
-                                               uint4* stg_wave) {
+__device__ __forceinline__ void pv_comb_bw_acc(ge_p3& acc, const uint4* bcomb, const DevKeyWide& key,
+                                               const DevDigits& dig, uint4* stg_wave) {
     constexpr int P = Bc2<W>::POS;
     pv_comb_b_acc_w<P>(
-        acc, DevBWStage<Bc2<W>::ENT>{bcomb, wkey, stg_wave, threadIdx.x & 63u},
+        acc, DevBWStage<Bc2<W>::ENT>{bcomb, key, stg_wave, threadIdx.x & 63u},
         [&](int j) {
-            if (wkey && j < PV_KW_POS) return pv_kw_digit(dig.ek(j >> 1), j);
-            return dig.fb(wkey ? j - PV_KW_POS : j);
+            if (j < key.kpos) {
+                const uint32_t w = dig.kr(j >> 1);
+                return key.kpos == PV_KR_POS ? pv_kr_digit(w, j) : pv_kw_digit(w, j);
+            }
+            return dig.fb(j - key.kpos);
         },
-        wkey ? P + PV_KW_POS : P);
+        P + key.kpos);
 }
 // A slot whose [k](-A) was added in the niels loop: projective Q to q rows 0..29 and the key's flag.
 __device__ __forceinline__ void pv_comb_store_q(const Work& wk, const KeyWork& kw, uint32_t i, const ge_p3& acc) {
@@ -1363,7 +1433,7 @@ __global__ __launch_bounds__(PV_BLOCK, 2) void pv_comb_b_kernel(uint64_t n, Work
     ge_p3 acc;
     __shared__ uint4 stg[PV_BLOCK / 64][PV_BCOMB_STRIDE / 4][64];
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    pv_comb_bw_acc<W>(acc, bcomb, pv_kw_rows(kw, i), dig, &stg[wv][0][0]);
+    pv_comb_bw_acc<W>(acc, bcomb, pv_key_wide(kw, i), dig, &stg[wv][0][0]);
     const Soa qs(wk.q, 40, wk.stride);
 #pragma unroll
     for (int q = 0; q < 10; q++) {
@@ -1439,6 +1509,63 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_kc_wide_kernel(KeyWork kw, const 
                      min(PV_BC2_RUN, PV_KW_ENT - d0));
 }
 
+// Resident tables to radix-2^11 rows (comb.h PV_KR_*): the tables this chunk's scan queued (wide_list,
+// wide_cnt[0]: device-side, so the launch is fixed -- PV_WIDE_GRID workgroups that stride over the queue
+// and leave at once when it is empty). One workgroup per table at a time, one thread per (position, run of
+// 64 entries): the position's base from the table's affine radix-256 row (pv_kr_base), then
+// pv_kr_build_run straight into the pool slot; the runs' Z products go to the workgroup's own scratch
+// [64][10][PV_WIDE_THREADS], one word per thread and step, coalesced, so the scratch is sized by the grid
+// and not by the queue. Runs on the main stream behind pv_dir_affine_kernel: after every kernel of the
+// chunk that reads the pool or ctab, before any of the next chunk. dir_wslot and PV_KF_WIDE are stored once
+// the whole table is written (fence, barrier, flag), as pv_dir_affine_kernel does.
+struct DevWideScr {
+    uint32_t* z;  // this thread's column of [PV_KR_RUN][10][PV_WIDE_THREADS]
+    __device__ __forceinline__ void store(uint32_t d, const fe& f) const {
+        const uint32_t k = (d - 1u) % PV_KR_RUN;
+#pragma unroll
+        for (int q = 0; q < 10; q++) z[(k * 10 + q) * PV_WIDE_THREADS] = f.v[q];
+    }
+    __device__ __forceinline__ void load(uint32_t d, fe& f) const {
+        const uint32_t k = (d - 1u) % PV_KR_RUN;
+#pragma unroll
+        for (int q = 0; q < 10; q++) f.v[q] = z[(k * 10 + q) * PV_WIDE_THREADS];
+    }
+};
+__global__ __launch_bounds__(PV_WIDE_THREADS) void pv_dir_widen_kernel(KeyWork kw) {
+    // a chunk that took the latency choice or reset the directory queued nothing
+    const uint32_t cnt = min(kw.wide_cnt[0], PV_WIDE_CAP);  // settled by the scan: every entry below it is filled
+    const uint32_t pos = threadIdx.x / PV_KR_RUNS, run = threadIdx.x % PV_KR_RUNS;
+    for (uint32_t u = blockIdx.x; u < cnt; u += gridDim.x) {
+        const uint64_t slot = kw.wide_list[2 * u];  // < dir_cnt <= kcap: a listed slot the scan read from the hash
+        const uint64_t ws = kw.wide_list[2 * u + 1];
+        if (slot >= kw.kcap || ws >= kw.wide_cap) continue;  // never: the scan's bounds (uniform over the workgroup)
+        if (pos < (uint32_t)PV_KR_POS) {
+            const uint4* e = kw.ctab + ((slot * PV_COMB_POS + pv_kr_base_row(pos)) * PV_COMB_ENT + pv_kr_base_ent(pos)) * 10;
+            uint32_t w[40];
+#pragma unroll
+            for (int q = 0; q < 10; q++) {
+                const uint4 v = e[q];
+                w[4 * q] = v.x;
+                w[4 * q + 1] = v.y;
+                w[4 * q + 2] = v.z;
+                w[4 * q + 3] = v.w;
+            }
+            ge_p3 P;
+            pv_kr_base(P, w, true);  // the scan queues tables with PV_KF_AFF only
+            pv_kr_build_run(
+                DevBc2Row{reinterpret_cast<uint32_t*>(kw.wide_tab + (ws * PV_KR_POS + pos) * PV_KR_ENT * (PV_BCOMB_STRIDE / 4))},
+                DevWideScr{kw.wide_scr + (uint64_t)blockIdx.x * PV_KR_RUN * 10 * PV_WIDE_THREADS + threadIdx.x}, P, run);
+        }
+        __threadfence();  // the rows before the bit that says they exist
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            kw.dir_wslot[slot] = (uint32_t)ws;
+            kw.dir_flags[slot] |= PV_KF_WIDE;
+            atomicAdd(&kw.dir_stat[5], 1ull);
+        }
+    }
+}
+
 // XCD-aware block order. Workgroups are dealt round-robin over the 8 XCDs (block b runs on the XCD
 // of b % 8; MI355X_MICROARCH.md, workgroup dispatch), each XCD with its own 4 MB L2. Slot order is
 // key-sorted, so mapping the blocks of XCD x to ONE contiguous range of slots keeps a key's table
@@ -1498,7 +1625,7 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_a_kerne
     if (!gate.keyed() || gate.off()) return;
     const uint32_t i = pv_xcd_block() * PV_BLOCK + threadIdx.x;  // slot
     if (i >= gate.ncomb()) return;
-    if (pv_kw_rows(kw, i)) {  // pv_comb_b_kernel added [k](-A) from the key's wide rows: Q is in q rows 0..29
+    if (pv_key_wide(kw, i).kpos) {  // pv_comb_b_kernel added [k](-A) from the key's wide rows: Q is in q rows 0..29
         if ((kw.key_flag[kw.skey[i]] & PV_KF_OK) == 0) wk.flags[i] = 0;
         return;
     }
@@ -1554,9 +1681,9 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_ab_kern
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const DevDigits dig{wk.digits, (uint32_t)wk.stride, i};
     ge_p3 acc;
-    const uint4* wkey = pv_kw_rows(kw, i);
+    const DevKeyWide wkey = pv_key_wide(kw, i);
     pv_comb_bw_acc<W>(acc, bcomb, wkey, dig, &stg[wv][0][0]);
-    if (wkey)  // [k](-A) came from the key's wide rows in the same loop
+    if (wkey.kpos)  // [k](-A) came from the key's wide rows in the same loop
         pv_comb_store_q(wk, kw, i, acc);
     else
         pv_comb_a_from(wk, kw, i, acc, &stg[wv][0][0]);
@@ -1793,6 +1920,26 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
         kw.dir_cap = g_ctx.dir_cap;
         kw.dir_pub = dir_use && m > PV_SPARSE_CHUNK ? 1u : 0u;  // direct_fill below: the tables are whole
         kw.aff_conv = kw.dir_pub && g_ctx.aff_on ? 1u : 0u;
+        // Wide rows: the pool is allocated by the first dense chunk that can widen a table -- the fourth since
+        // pv_init at the earliest (build, first hit, affine rows, then this) -- and not at pv_init. When the
+        // allocation fails the feature turns itself off and says so once through the error string.
+        // A pool that has to grow (pv_table_wide) is replaced: that call marked the directory dirty already.
+        const uint64_t wide_want = (uint64_t)g_ctx.wide_cap * PV_KR_POS * PV_KR_ENT * PV_BCOMB_STRIDE * 4;
+        if (keyed && kw.dir_pub && !g_ctx.wide_failed && g_ctx.d_wide.cap < wide_want && ++g_ctx.wide_dense >= 4) {
+            if (g_ctx.d_wide.grow(wide_want) != PV_OK ||
+                g_ctx.d_wide_scr.grow((uint64_t)PV_WIDE_GRID * PV_KR_RUN * 10 * PV_WIDE_THREADS * 4) != PV_OK) {
+                (void)hipGetLastError();  // clear the failed allocation's sticky error
+                g_ctx.d_wide.release();
+                g_ctx.d_wide_scr.release();
+                g_ctx.wide_failed = true;
+                (void)fail(PV_ERR_ALLOC, "wide rows of resident tables: no memory for the pool, the feature is off");
+            }
+        }
+        kw.wide_tab = g_ctx.d_wide.as<uint4>();
+        kw.wide_scr = g_ctx.d_wide_scr.as<uint32_t>();
+        const uint64_t wide_have = g_ctx.d_wide.cap / ((uint64_t)PV_KR_POS * PV_KR_ENT * PV_BCOMB_STRIDE * 4);
+        kw.wide_cap = dir_use ? (uint32_t)std::min<uint64_t>(g_ctx.wide_cap, wide_have) : 0u;
+        kw.wide_conv = kw.dir_pub && kw.wide_cap ? 1u : 0u;
         kw.chunk_n = (uint32_t)m;
         // a key-id segment holds the owners among its waves (every PV_NSEG-th wave of the chunk)
         kw.seg_cap = (uint32_t)((((m + 63) / 64) + PV_NSEG - 1) / PV_NSEG * 64);
@@ -1828,6 +1975,7 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
             if (dir_use && g_ctx.dir_dirty) {
                 PV_HIP(hipMemsetAsync(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4, stream), PV_ERR_LAUNCH);
                 PV_HIP(hipMemsetAsync(kw.dir_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);
+                PV_HIP(hipMemsetAsync(kw.wide_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);  // the pool empties with it
             }
             if (!g_ctx.xt_fill) g_ctx.dir_dirty = true;
             // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
@@ -1959,6 +2107,9 @@ int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, 
                 if (kw.aff_conv) {  // the listed tables this chunk hit: affine rows for the chunks that follow
                     PV_LAUNCH(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
                 }
+                if (kw.wide_conv) {  // the affine tables this chunk hit: radix-2^11 rows for the chunks that follow
+                    PV_LAUNCH(pv_dir_widen_kernel, dim3(PV_WIDE_GRID), dim3(PV_WIDE_THREADS), 0, stream, kw);
+                }
                 g_ctx.dir_dirty = false;
             }
             if (dev_choice) {  // runs only when the scan picked latency (the words were zeroed above)
@@ -2045,15 +2196,21 @@ int lane_alloc_buffers(Work& w, KeyWork& kw) {
     if (int rc = own.dev(kw.dir_keys, (uint64_t)kw.kcap * 32)) return rc;
     if (int rc = own.dev(kw.dir_flags, (uint64_t)kw.kcap * 4)) return rc;
     if (int rc = own.dev(kw.dir_cnt, 2 * 4)) return rc;
-    if (int rc = own.dev(kw.dir_stat, 5 * 8)) return rc;
+    if (int rc = own.dev(kw.dir_stat, PV_DIR_STATS * 8)) return rc;
     if (int rc = own.dev(kw.aff_list, (uint64_t)PV_AFF_CAP * 4)) return rc;
     if (int rc = own.dev(kw.aff_cnt, 4)) return rc;
+    if (int rc = own.dev(kw.wide_list, (uint64_t)PV_WIDE_CAP * 2 * 4)) return rc;
+    if (int rc = own.dev(kw.wide_cnt, 2 * 4)) return rc;
+    if (int rc = own.dev(kw.dir_wslot, (uint64_t)kw.kcap * 4)) return rc;
+    if (int rc = own.dev(kw.comb_wslot, (uint64_t)kw.kcap * 4)) return rc;
+    PV_HIP(hipMemset(kw.wide_cnt, 0, 2 * 4), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.comb_wslot, 0xFF, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     if (int rc = own.dev(kw.aff_scr, (uint64_t)PV_AFF_CAP * PV_AFF_SEG * 10 * PV_AFF_THREADS * 4)) return rc;
     PV_HIP(hipMemset(kw.aff_cnt, 0, 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.comb_tslot, 0, (uint64_t)kw.kcap * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4), PV_ERR_ALLOC);
     PV_HIP(hipMemset(kw.dir_cnt, 0, 2 * 4), PV_ERR_ALLOC);
-    PV_HIP(hipMemset(kw.dir_stat, 0, 5 * 8), PV_ERR_ALLOC);
+    PV_HIP(hipMemset(kw.dir_stat, 0, PV_DIR_STATS * 8), PV_ERR_ALLOC);
     return PV_OK;
 }
 
@@ -2177,6 +2334,8 @@ int ctx_init_parts(int device) {
         g_ctx.dir_dirty = true;
         const char* ta = getenv("PV_TABLE_AFFINE");  // PV_TABLE_AFFINE=0: resident tables stay in cached form
         g_ctx.aff_on = !(ta && *ta == '0');
+        const char* tw = getenv("PV_TABLE_WIDE");  // PV_TABLE_WIDE=0: resident tables get no radix-2^11 rows
+        g_ctx.wide_cap = tw && *tw == '0' ? 0u : PV_WIDE_DEFAULT;
     }
     g_ctx.device = device;
     return PV_OK;
@@ -2188,7 +2347,8 @@ void ctx_free() {
     (void)hipSetDevice(g_ctx.device);
     if (g_ctx.comm) ncclCommDestroy(g_ctx.comm);
     kc_free();  // first: it waits for a pending asynchronous put
-    for (PvDevBuf* b : {&g_ctx.d_mg, &g_ctx.d_stage, &g_ctx.sg.d_keys, &g_ctx.sg.d_sk}) b->release();
+    for (PvDevBuf* b : {&g_ctx.d_mg, &g_ctx.d_stage, &g_ctx.sg.d_keys, &g_ctx.sg.d_sk, &g_ctx.d_wide, &g_ctx.d_wide_scr})
+        b->release();
     for (PvPinnedBuf* b : {&g_ctx.h_mg, &g_ctx.h_stage, &g_ctx.h_ver, &g_ctx.sg.h_sk}) b->release();
     g_ctx.sg.stage.release();
     g_ctx.hand.destroy();
@@ -2574,6 +2734,28 @@ int pv_table_affine_stats(uint64_t* converted, uint64_t* affine_reads) {
     PV_HIP(hipMemcpy(u, g_ctx.kw.dir_stat, sizeof(u), hipMemcpyDeviceToHost), PV_ERR_LAUNCH);
     if (converted) *converted = u[3];
     if (affine_reads) *affine_reads = u[4];
+    return PV_OK;
+}
+
+int pv_table_wide(uint32_t capacity) {
+    for (int d = 0; d < PV_MAX_DEV; d++) {  // every device context of the process
+        std::lock_guard<std::mutex> lk(g_mus[d]);
+        Ctx& c = g_ctxs[d];
+        if (capacity != c.wide_cap) c.dir_dirty = true;  // emptied before its next use, and the pool with it
+        c.wide_cap = capacity;
+        if (capacity) c.wide_failed = false;  // a new capacity may fit where the last one did not
+    }
+    return PV_OK;
+}
+
+int pv_table_wide_stats(uint64_t* widened, uint64_t* wide_reads) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_table_wide_stats: call pv_init first");
+    unsigned long long u[PV_DIR_STATS] = {};
+    PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpy(u, g_ctx.kw.dir_stat, sizeof(u), hipMemcpyDeviceToHost), PV_ERR_LAUNCH);
+    if (widened) *widened = u[5];
+    if (wide_reads) *wide_reads = u[6];
     return PV_OK;
 }
 

@@ -150,10 +150,12 @@ struct Gate {
 //   dir_htab [PV_DIR_HASH] open-addressing hash of listed slots (pv_kc_lookup with kw.seed: a hit
 //            compares the full 32-byte key), dir_keys [kcap][8], dir_flags [kcap]: bit 0 (PV_KF_OK) the
 //            libsodium key checks passed, bit 1 (PV_KF_AFF) the slot's rows are affine, bit 2 (PV_KF_HIT)
-//            a dense chunk has read the slot once already (both below)
+//            a dense chunk has read the slot once already (both below), bit 3 (PV_KF_WIDE) the slot has
+//            radix-2^11 rows in the wide pool (further below)
 //   dir_cnt  [2]  count: slots [0, count) are listed, nothing above them is; and the count the
 //            chunk's publish kernel stores once its tables are built and listed
-//   dir_stat [5]  u64 hits, built, resets, tables converted to affine rows, tables read in affine form
+//   dir_stat [PV_DIR_STATS]  u64 hits, built, resets, tables converted to affine rows, tables read in affine
+//            form (wide reads included: they are affine rows of the same table), tables widened, tables read wide
 // Affine rows: a dense chunk (dir_pub) that hits a listed table whose key passed the checks marks the
 // slot PV_KF_HIT; the next dense chunk that hits it -- the table's second hit: converting 1,024 tables
 // costs as much as ten warm 1M-request chunks save, so a table that comes back once is left alone --
@@ -166,6 +168,16 @@ struct Gate {
 // failure, a key-cache put that ran over the directory), and for the tables built above the count.
 //   aff_list [PV_AFF_CAP] slots queued by this chunk's scan;  aff_cnt [1] how many it queued (may exceed
 //            the cap: the rest wait for their next hit);  aff_scr  the conversion's parked Z2 products
+// Wide rows: a dense chunk that hits a listed table with PV_KF_OK and PV_KF_AFF but not PV_KF_WIDE -- the
+// table's third dense hit -- queues it in wide_list with a slot of the wide pool (wide_cnt[1], a bump
+// counter reset wherever dir_cnt is), at most PV_WIDE_CAP tables per chunk and while the pool has room;
+// pv_dir_widen_kernel builds the table's radix-2^11 rows (comb.h PV_KR_*) into that slot behind the chunk's
+// kernels, stores dir_wslot and sets PV_KF_WIDE. Every later keyed chunk that hits the table reads [k](-A)
+// from the wide rows; the radix-256 table stays where it is (the bases' source, the latency path's table).
+// PV_KF_WIDE follows PV_KF_AFF's discipline: cleared by pv_dir_publish_kernel for every rebuilt slot.
+//   comb_wslot [kcap] written by the scan for every comb index: the pool slot, or PV_EMPTY. The prep, digits
+//            and comb kernels decide a request's form from it and never from key_flag, whose upper bits
+//            are not settled before ev_tables_ready for a key the chunk builds.
 // A key takes the comb path when it carries >= min_req requests of the chunk (the per-key table
 // costs about as much as ~50 requests save; 1 when the comb path is forced) and fewer than kcap
 // keys came before it; the rest -- singletons such as the adversarial keys of config 3 -- take the
@@ -228,11 +240,27 @@ struct KeyWork {
     uint32_t dir_cap;     // slots the directory may list (<= kcap)
     uint32_t dir_pub;     // a dense chunk: its tables are whole and pv_dir_publish_kernel lists them
     uint32_t aff_conv;    // a dense chunk with pv_table_affine on: its scan queues hit tables for conversion
+    // wide rows of resident tables (above); every pointer is null until the pool exists
+    uint4* wide_tab;       // [wide_cap][PV_KR_POS][PV_KR_ENT][8]
+    uint32_t* wide_scr;    // [PV_WIDE_GRID][PV_KR_RUN][10][PV_WIDE_THREADS] Z products of the runs in flight
+    uint32_t* wide_list;   // [PV_WIDE_CAP][2] (ctab slot, pool slot) queued by this chunk's scan
+    uint32_t* wide_cnt;    // [2] entries queued by this chunk; pool slots handed out (the bump counter)
+    uint32_t* dir_wslot;   // [kcap] pool slot of a directory slot whose dir_flags has PV_KF_WIDE
+    uint32_t* comb_wslot;  // [kcap] pool slot of comb index j, PV_EMPTY unless its table is read wide
+    uint32_t wide_cap;     // pool slots (0: the feature is off for this chunk)
+    uint32_t wide_conv;    // a dense chunk with the pool in place: its scan queues affine tables for widening
 };
 static constexpr uint32_t PV_KF_OK = 1u;   // key_flag / dir_flags: libsodium's key checks passed
 static constexpr uint32_t PV_KF_AFF = 2u;  // the table's rows are affine (a directory hit only)
 static constexpr uint32_t PV_KF_HIT = 4u;  // a dense chunk has hit the table before: its next dense hit converts it
+static constexpr uint32_t PV_DIR_STATS = 7;
+static constexpr uint32_t PV_KF_WIDE = 8u; // the table has radix-2^11 rows in the wide pool (dir_wslot)
 static constexpr uint32_t PV_AFF_CAP = 1024;  // tables one chunk converts (aff_scr: 165 KB each, 173 MB)
+static constexpr uint32_t PV_WIDE_CAP = 1024;       // tables one chunk widens
+static constexpr uint32_t PV_WIDE_DEFAULT = 2048;   // slots of the wide pool (3.0 MB each, 6.2 GB)
+static constexpr uint32_t PV_WIDE_THREADS = 384;    // pv_dir_widen_kernel: one run per thread, 23 x 16 = 368 used
+static constexpr uint32_t PV_WIDE_GRID = 512;       // its workgroups, each with 0.98 MB of scratch (503 MB)
+static_assert(PV_KR_POS * PV_KR_RUNS <= PV_WIDE_THREADS, "one thread per run of a table");
 static constexpr uint32_t PV_EMPTY = 0xFFFFFFFFu;
 static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call's shared store (KeyWork::xt_*)
 static constexpr uint32_t PV_CSLOT_DIR = 0x20000000u;  // slot of kw.ctab listed in the resident-table directory

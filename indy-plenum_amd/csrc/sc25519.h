@@ -527,3 +527,28 @@ PV_HD void sc_recode_w(int32_t out[P], const uint32_t a[8]) {
     if (top > (1u << TOP)) top = 1u << TOP;
     out[P - 1] = (int32_t)top;
 }
+
+// The same digits for a comb whose top row is no longer than the others (2^(W-1) + 1 entries in every
+// row: comb.h PV_KR_*), packed two signed 16-bit digits per word (digit j = half j & 1 of word j >> 1,
+// pv_half; W <= 16). The top digit is clamped to 2^(W-1); it never reaches the clamp when the scalar's
+// top raw digit is at most 2^(W-1) and, where it equals 2^(W-1), the digit below it is 0 (no carry in).
+template <int W, int P>
+PV_HD void sc_recode_w_packed(uint32_t out[(P + 1) / 2], const uint32_t a[8]) {
+    static_assert(W <= 16 && W * (P - 1) < 256, "digits fit 16 bits, the top digit starts inside the scalar");
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < (P + 1) / 2; j++) out[j] = 0;
+#pragma unroll
+    for (int j = 0; j < P; j++) {
+        uint32_t d;
+        if (j < P - 1) {
+            const uint32_t v = sc_bits(a, W * j, W) + carry;
+            carry = (v + (1u << (W - 1))) >> W;
+            d = v - (carry << W);
+        } else {
+            d = sc_bits(a, W * (P - 1), 256 - W * (P - 1)) + carry;
+            if (d > (1u << (W - 1))) d = 1u << (W - 1);
+        }
+        out[j >> 1] |= (d & 0xFFFFu) << (16 * (j & 1));
+    }
+}

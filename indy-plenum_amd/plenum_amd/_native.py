@@ -88,6 +88,8 @@ SIGNATURES = {
     "pv_table_reuse_stats": (ctypes.c_int, [_c_u64p, _c_u64p, _c_u64p]),
     "pv_table_affine": (ctypes.c_int, [ctypes.c_int]),
     "pv_table_affine_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
+    "pv_table_wide": (ctypes.c_int, [ctypes.c_uint32]),
+    "pv_table_wide_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
     "pv_last_zero_copy": (ctypes.c_int, []),
     "pv_init_devices": (ctypes.c_int, [ctypes.c_uint32]),
     "pv_verify_batch_multi_gpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -518,6 +520,23 @@ def table_affine_stats():
     read in that form. Synchronises the device."""
     v = [ctypes.c_uint64() for _ in range(2)]
     check(lib().pv_table_affine_stats(*[ctypes.byref(x) for x in v]), "pv_table_affine_stats")
+    return tuple(x.value for x in v)
+
+
+PV_TABLE_WIDE_CAP = 2048  # default capacity of the wide-row pool (csrc/pv_engine_dev.h PV_WIDE_DEFAULT)
+
+
+def table_wide(capacity=PV_TABLE_WIDE_CAP):
+    """Build radix-2^11 rows for the kept tables large keyed chunks keep reading, in a pool of `capacity`
+    tables (pv_table_wide; 2,048 by default, 0 = off). A change empties the kept tables."""
+    check(lib().pv_table_wide(int(capacity)), "pv_table_wide")
+
+
+def table_wide_stats():
+    """(widened, wide_reads) since pv_init: kept tables given wide rows, and kept tables read from them
+    (counted among table_affine_stats' affine reads too). Synchronises the device."""
+    v = [ctypes.c_uint64() for _ in range(2)]
+    check(lib().pv_table_wide_stats(*[ctypes.byref(x) for x in v]), "pv_table_wide_stats")
     return tuple(x.value for x in v)
 
 

@@ -15,9 +15,14 @@ around a sync, median of --calls calls after --warmup:
              1,024 tables that are never read again -- the promotion's worst case. Reported apart: the
              calls that build (first of a pair) and the calls that hit (second); the conversion's own
              time is the second's median less the same figure with PV_TABLE_AFFINE=0
+  four       capacity 1,024, three sets in the order A A A A B B B B C C C C: every table is built, hit,
+             converted, and -- with wide rows on (pv_table_wide) -- widened behind the fourth call and never
+             read wide: the widening's worst case. Reported per position in the group of four; the
+             widening's own time is the fourth's median less the same figure with PV_TABLE_WIDE=0
 
-Prints one JSON line. A library without pv_table_reuse or pv_table_affine (an older build) runs the
-same loops."""
+Prints one JSON line; every leg reports the counters the library has (hits_built_resets,
+converted_affine_reads, widened_wide_reads). A library without pv_table_reuse, pv_table_affine or
+pv_table_wide (an older build) runs the same loops."""
 import argparse
 import ctypes
 import json
@@ -109,12 +114,44 @@ def loop_pairs(devs, rounds, warmup_rounds):
             "second_min_ms": round(min(second), 4), "second_max_ms": round(max(second), 4)}
 
 
+def loop_groups(devs, group, rounds, warmup_rounds):
+    """devs in groups of `group` equal entries: the median per position in the group."""
+    ts = [[] for _ in range(group)]
+    for r in range(warmup_rounds + rounds):
+        for i, d in enumerate(devs):
+            t = d.call()
+            if r >= warmup_rounds:
+                ts[i % group].append(t)
+    return {"position_ms": [round(float(np.median(v)), 4) for v in ts],
+            "last_min_ms": round(min(ts[-1]), 4), "last_max_ms": round(max(ts[-1]), 4)}
+
+
+class Counters:
+    """The counters the loaded library has, as deltas per leg."""
+
+    GETTERS = (("hits_built_resets", "table_reuse_stats"), ("converted_affine_reads", "table_affine_stats"),
+               ("widened_wide_reads", "table_wide_stats"))
+
+    def __init__(self):
+        self.v = self._read()
+
+    def _read(self):
+        return {k: getattr(_native, f)() for k, f in self.GETTERS if hasattr(_native, f)}
+
+    def into(self, leg):
+        v = self._read()
+        for k in v:
+            leg[k] = [int(x - y) for x, y in zip(v[k], self.v[k])]
+        self.v = v
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--no-multi", action="store_true")
     ap.add_argument("--no-twice", action="store_true")
+    ap.add_argument("--no-four", action="store_true")
     a = ap.parse_args()
     ls = LibSodium()
     _native.ensure_device()
@@ -122,37 +159,43 @@ def main():
     has = hasattr(_native, "table_reuse")
     A, B = Dev(L, *make_batch(ls, 1)), Dev(L, *make_batch(ls, 2))
     out = {"lib": os.path.basename(_native.LIB_PATH), "table_reuse": has and os.environ.get("PV_TABLE_REUSE") != "0"}
-    has_aff = hasattr(_native, "table_affine")
-    out["table_affine"] = has_aff and os.environ.get("PV_TABLE_AFFINE") != "0"
-    a0 = _native.table_affine_stats() if has_aff else None
+    out["table_affine"] = hasattr(_native, "table_affine") and os.environ.get("PV_TABLE_AFFINE") != "0"
+    out["table_wide"] = hasattr(_native, "table_wide") and os.environ.get("PV_TABLE_WIDE") != "0"
     if has:
         _native.table_reuse(out["table_reuse"], SIGNERS)
-        s0 = _native.table_reuse_stats()
+    c = Counters()
     out["alternate"] = loop([A, B], a.calls, a.warmup)
+    c.into(out["alternate"])
     if has:
-        out["alternate"]["hits_built_resets"] = [int(x - y) for x, y in zip(_native.table_reuse_stats(), s0)]
         _native.table_reuse(out["table_reuse"], _native.PV_TABLE_REUSE_CAP)
-        s0 = _native.table_reuse_stats()
     out["recur"] = loop([A], a.calls, a.warmup)
-    if has:
-        out["recur"]["hits_built_resets"] = [int(x - y) for x, y in zip(_native.table_reuse_stats(), s0)]
+    c.into(out["recur"])
     assert A.valid() == A.n and B.valid() == B.n
-    if has_aff:
-        out["recur"]["converted_affine_reads"] = [int(x - y) for x, y in zip(_native.table_affine_stats(), a0)]
-    if not a.no_twice:
+    if not (a.no_twice and a.no_four):
         C = Dev(L, *make_batch(ls, 3))
+    if not a.no_twice:
         if has:
             _native.table_reuse(out["table_reuse"], SIGNERS)
-        a0 = _native.table_affine_stats() if has_aff else None
+        c = Counters()
         out["twice"] = loop_pairs([A, A, B, B, C, C], max(3, a.calls // 4), 1)
-        if has_aff:
-            out["twice"]["converted_affine_reads"] = [int(x - y) for x, y in zip(_native.table_affine_stats(), a0)]
+        c.into(out["twice"])
+        if has:
+            _native.table_reuse(out["table_reuse"], _native.PV_TABLE_REUSE_CAP)
+        assert A.valid() == A.n and B.valid() == B.n and C.valid() == C.n
+    if not a.no_four:
+        if has:
+            _native.table_reuse(out["table_reuse"], SIGNERS)
+        c = Counters()
+        out["four"] = loop_groups([A] * 4 + [B] * 4 + [C] * 4, 4, max(3, a.calls // 4), 1)
+        c.into(out["four"])
         if has:
             _native.table_reuse(out["table_reuse"], _native.PV_TABLE_REUSE_CAP)
         assert A.valid() == A.n and B.valid() == B.n and C.valid() == C.n
     if not a.no_multi:
         M = Dev(L, *make_batch(ls, 1, reps=4))
+        c = Counters()
         out["multi_4m"] = loop([M], max(5, a.calls // 2), 2)
+        c.into(out["multi_4m"])
         assert M.valid() == M.n
     print(json.dumps(out), flush=True)
 
