@@ -593,6 +593,43 @@ int pv_stream_sync(void* stream);
  *   pv_merkle_verify_inclusion_batch_device
  *                           the same on device buffers (16-byte aligned hash arrays); verdicts as
  *                           ceil(n / 64) 64-bit words like pv_verify_batch_device.
+ *   pv_merkle_verify_consistency_batch
+ *                           MerkleVerifier.verify_tree_consistency (ledger/merkle_verifier.py:23-153) for n
+ *                           proofs: proof i is proof[32 proof_off[i] : 32 proof_off[i+1]], for the trees of
+ *                           old_size[i] and new_size[i] leaves with roots old_root[32 i] and new_root[32 i].
+ *                           Host buffers, synchronous, GPU or C++ host path (pv_merkle_path; AUTO from
+ *                           PV_MERKLE_AUTO_MIN_CONSISTENCY proofs); works without a device. Verdict bit i
+ *                           (LSB-first) = 1 iff the reference returns True. status[i]:
+ *                             0 consistent; equal sizes with equal roots and old_size 0 ignore the proof
+ *                             1 old_size > new_size (the reference's ValueError)
+ *                             2 proof too short: a hash the walk needs is missing (ProofError); hashes
+ *                               left over are accepted
+ *                             3 the second (new) root differs (ProofError); also a wrong old root when
+ *                               old_size is a power of two, as the new chain starts from it
+ *                             4 the new root matches, the first (old) one differs (ConsistencyError)
+ *                             5 equal sizes, different roots (ConsistencyError)
+ *   pv_merkle_verify_consistency_batch_device
+ *                           the same on device buffers (16-byte aligned hash arrays), enqueued on `stream`
+ *                           without synchronising, no workspace; verdicts as ceil(n / 64) 64-bit words.
+ *   pv_merkle_catchup_batch what plenum/server/catchup/catchup_rep_service.py:375-426
+ *                           (_has_valid_catchup_replies) does per CatchupRep, for a whole chain of replies:
+ *                           pv_merkle_append_batch's arguments (the ledger's tree and the n leaves of all
+ *                           replies) and outputs (every PvMerkleOut pointer, or `out` itself, may be NULL;
+ *                           what is asked for is filled exactly as pv_merkle_append_batch fills it, so one
+ *                           pass over the leaves also yields what a commit needs), plus the replies: reply r
+ *                           is leaves [reply_end[r-1], reply_end[r]) in absolute sizes, reply_end[-1] =
+ *                           tree_size, and proof[32 proof_off[r] : 32 proof_off[r+1]] is its consistency
+ *                           proof between the tree of reply_end[r] leaves (the temporary tree of plenum/
+ *                           common/ledger.py:129-143 treeWithAppliedTxns, whose root the call computes) and
+ *                           the tree of final_size leaves with root final_root[32]. status[r] as above,
+ *                           verdict bit r = 1 iff status[r] = 0. reply_end must increase strictly within
+ *                           (tree_size, tree_size + n]. GPU or host path by n as an append with per-leaf
+ *                           outputs (PV_MERKLE_AUTO_MIN_PROOFS).
+ *   pv_merkle_catchup_batch_device
+ *                           the same with everything in device memory, enqueued on `stream` without a host
+ *                           round trip (alignment and readability as pv_merkle_append_batch_device;
+ *                           d_final_root and d_proof 16-byte aligned). A reply whose end is not in
+ *                           (tree_size, tree_size + n] gets status 6 and verdict 0.
  *   pv_merkle_chunk         leaves (or proofs) per device pass; larger batches are chained chunk by
  *                           chunk through the frontier. 0 restores the default, 1,048,576; at most
  *                           PV_MERKLE_CHUNK_MAX (the upper levels of a chunk run in one workgroup).
@@ -601,15 +638,18 @@ int pv_stream_sync(void* stream);
  *                           (PV_MERKLE_AUTO_MIN_PROOFS when per-leaf roots or paths are asked for,
  *                           PV_MERKLE_AUTO_MIN_VERIFY proofs for the check): the smallest measured sizes
  *                           at which the device path won by more than the run-to-run spread on one
- *                           MI355X.
- * Bad arguments (decreasing offsets, tree_size + n >= 2^48, no frontier for tree_size > 0, path without
- * path_off) return PV_ERR_ARG before anything is launched. */
+ *                           MI355X; PV_MERKLE_AUTO_MIN_CONSISTENCY proofs for the consistency
+ *                           check, measured the same way.
+ * Bad arguments (decreasing offsets, tree_size + n >= 2^48, a tree size >= 2^48, no frontier for tree_size
+ * > 0, path without path_off, 2^32 or more proofs or replies, reply ends out of order or range) return
+ * PV_ERR_ARG before anything is launched. */
 #define PV_MERKLE_AUTO 0
 #define PV_MERKLE_HOST 1
 #define PV_MERKLE_DEVICE 2
 #define PV_MERKLE_AUTO_MIN 2048        /* appends: frontier / root / leaf and node hashes only */
 #define PV_MERKLE_AUTO_MIN_PROOFS 1024 /* appends with per-leaf roots or audit paths */
 #define PV_MERKLE_AUTO_MIN_VERIFY 512  /* the proof check */
+#define PV_MERKLE_AUTO_MIN_CONSISTENCY 256 /* the consistency check */
 #define PV_MERKLE_CHUNK 1048576
 #define PV_MERKLE_CHUNK_MAX 16777216 /* 2^24: the largest chunk pv_merkle_chunk accepts */
 typedef struct {
@@ -634,6 +674,22 @@ int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_
                                             const uint64_t* d_leaf_index, const uint64_t* d_tree_size,
                                             const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
                                             uint64_t n, uint8_t* d_status, uint64_t* d_verdict_words, void* stream);
+int pv_merkle_verify_consistency_batch(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_root,
+                                       const uint8_t* new_root, const uint8_t* proof, const uint64_t* proof_off,
+                                       uint64_t n, uint8_t* status, uint8_t* verdict_bits);
+int pv_merkle_verify_consistency_batch_device(const uint64_t* d_old_size, const uint64_t* d_new_size,
+                                              const uint8_t* d_old_root, const uint8_t* d_new_root, const uint8_t* d_proof,
+                                              const uint64_t* d_proof_off, uint64_t n, uint8_t* d_status,
+                                              uint64_t* d_verdict_words, void* stream);
+int pv_merkle_catchup_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                            const uint64_t* reply_end, uint64_t n_replies, uint64_t final_size, const uint8_t* final_root,
+                            const uint8_t* proof, const uint64_t* proof_off, const PvMerkleOut* out, uint8_t* status,
+                            uint8_t* verdict_bits);
+int pv_merkle_catchup_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
+                                   const uint64_t* d_off, uint64_t n, const uint64_t* d_reply_end, uint64_t n_replies,
+                                   uint64_t final_size, const uint8_t* d_final_root, const uint8_t* d_proof,
+                                   const uint64_t* d_proof_off, const PvMerkleOut* d_out, uint8_t* d_status,
+                                   uint64_t* d_verdict_words, void* stream);
 int pv_merkle_chunk(uint64_t leaves);
 int pv_merkle_path(int mode);
 

@@ -1,7 +1,8 @@
 // Index arithmetic of the batched ledger Merkle append (ledger/compact_merkle_tree.py:95-160 append /
-// _push_subtree, :81-88 root_hash) and of the audit-path check (ledger/merkle_verifier.py:155-181).
-// One source for the kernels (pv_merkle.hip), the host path (merkle_host.cpp) and the host-compiled
-// check library (tests/native/merklecheck.hip); no hashing here, hashes pass through template hooks.
+// _push_subtree, :81-88 root_hash), of the audit-path check (ledger/merkle_verifier.py:155-181) and of the
+// consistency check (:23-153). One source for the kernels (pv_merkle.hip), the host path (merkle_host.cpp)
+// and the host-compiled check libraries (tests/native/merklecheck.hip, conscheck.hip); no hashing here,
+// hashes pass through template hooks.
 //
 // A tree is its size s and its frontier: one hash per set bit of s, largest subtree first. A batch
 // appends n leaves with absolute indices s .. s + n - 1. The node of height h >= 1 "completed at size
@@ -118,6 +119,70 @@ PV_HD uint32_t pv_merkle_path_check(T& acc, uint64_t index, uint64_t size, uint6
         }
     }
     return used < plen ? PV_MK_TOO_LONG : PV_MK_COMPARED;
+}
+
+// MerkleVerifier.verify_tree_consistency (ledger/merkle_verifier.py:23-153). A consistency proof is the
+// audit path of node old_size - 1 in the new tree, already hashed together up to the first node that
+// only the new tree has: trailing one-bits of old_size - 1 are stripped (right children, in both trees),
+// both chains start from proof[0], or from old_root when nothing is left of the node (old_size a power
+// of two), a right child extends both chains with its left sibling, a left child below `last` extends
+// the new chain only, and the new chain then climbs while `last` is non-zero. proof(k, out) loads hash k
+// of a proof of plen hashes; a hash is asked for only where the walk needs one (unlike the inclusion
+// walk above), so "too short" is a needed hash that is missing, and hashes left over are accepted.
+// eq(a, b) compares two hashes. Verdict 1 iff the status is PV_MK_CONSISTENT.
+enum : uint32_t {
+    PV_MK_CONSISTENT = 0,
+    PV_MK_OLD_LARGER = 1,      // old_size > new_size (the reference's ValueError)
+    PV_MK_CONS_TOO_SHORT = 2,  // ProofError "Merkle proof is too short"
+    PV_MK_NEW_DIFFERS = 3,     // the second (new) root differs: ProofError
+    PV_MK_OLD_DIFFERS = 4,     // the new root matches, the first (old) one does not: ConsistencyError
+    PV_MK_SAME_SIZE = 5,       // equal sizes, different roots: ConsistencyError
+    PV_MK_REPLY_RANGE = 6      // catch-up only: the reply's end is not in (tree_size, tree_size + n]
+};
+template <class T, class Proof, class Hash, class Eq>
+PV_HD uint32_t pv_merkle_consistency_check(uint64_t old_size, uint64_t new_size, const T& old_root, const T& new_root,
+                                           uint64_t plen, const Proof& proof, const Hash& hash, const Eq& eq) {
+    if (old_size > new_size) return PV_MK_OLD_LARGER;
+    if (old_size == new_size) return eq(old_root, new_root) ? PV_MK_CONSISTENT : PV_MK_SAME_SIZE;  // the proof is ignored
+    if (old_size == 0) return PV_MK_CONSISTENT;  // anything is consistent with the empty tree
+    uint64_t node = old_size - 1, last = new_size - 1, used = 0;
+    while (node & 1) {
+        node >>= 1;
+        last >>= 1;
+    }
+    T old_acc = old_root, new_acc = old_root;
+    if (node) {
+        if (used == plen) return PV_MK_CONS_TOO_SHORT;
+        proof(used++, new_acc);
+        old_acc = new_acc;
+    }
+    for (; node; node >>= 1, last >>= 1) {
+        if (node & 1) {
+            if (used == plen) return PV_MK_CONS_TOO_SHORT;
+            T sib, next;
+            proof(used++, sib);
+            hash(next, sib, old_acc);
+            old_acc = next;
+            hash(next, sib, new_acc);
+            new_acc = next;
+        } else if (node < last) {
+            if (used == plen) return PV_MK_CONS_TOO_SHORT;
+            T sib, next;
+            proof(used++, sib);
+            hash(next, new_acc, sib);
+            new_acc = next;
+        }
+    }
+    for (; last; last >>= 1) {
+        if (used == plen) return PV_MK_CONS_TOO_SHORT;
+        T sib, next;
+        proof(used++, sib);
+        hash(next, new_acc, sib);
+        new_acc = next;
+    }
+    if (!eq(new_acc, new_root)) return PV_MK_NEW_DIFFERS;
+    if (!eq(old_acc, old_root)) return PV_MK_OLD_DIFFERS;
+    return PV_MK_CONSISTENT;
 }
 
 // ---- the level kernel's tiling (absolute indices, so node alignment is the tree's) ----------------

@@ -1,4 +1,5 @@
-// Host path of the batched Merkle append and audit-proof check: the same contract as the kernels of
+// Host path of the batched Merkle append, the audit-proof and consistency-proof checks and the catch-up
+// entry: the same contract as the kernels of
 // pv_merkle.hip, in C++ over merkle_core.h (one source for the index arithmetic) and the host SHA-256
 // of signing_json.cpp. pv_merkle_append_batch takes it for small batches (a 3PC batch of ten
 // transactions must not pay kernel launches) and when no device is initialised.
@@ -145,4 +146,84 @@ void pv_merkle_host_verify(const uint8_t* data, const uint64_t* off, const uint8
     memset(verdict_bits, 0, (n + 7) / 8);
     for (uint64_t i = 0; i < n; i++)
         if (ok[i]) verdict_bits[i >> 3] |= (uint8_t)(1u << (i & 7));
+}
+
+namespace {
+
+uint32_t consistency_walk(uint64_t old_size, uint64_t new_size, const H32& old_root, const H32& new_root, const H32* p,
+                          uint64_t plen) {
+    return pv_merkle_consistency_check(
+        old_size, new_size, old_root, new_root, plen, [&](uint64_t k, H32& o) { o = p[k]; },
+        [](H32& o, const H32& l, const H32& r) { hash_children(o, l, r); },
+        [](const H32& a, const H32& b) { return memcmp(a.b, b.b, 32) == 0; });
+}
+
+void pack_verdicts(const std::vector<uint8_t>& ok, uint8_t* verdict_bits) {
+    const uint64_t n = ok.size();
+    memset(verdict_bits, 0, (n + 7) / 8);
+    for (uint64_t i = 0; i < n; i++)
+        if (ok[i]) verdict_bits[i >> 3] |= (uint8_t)(1u << (i & 7));
+}
+
+}  // namespace
+
+void pv_merkle_host_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_root,
+                                const uint8_t* new_root, const uint8_t* proof, const uint64_t* proof_off, uint64_t n,
+                                uint8_t* status, uint8_t* verdict_bits) {
+    std::vector<uint8_t> ok(n);
+    const H32* oldr = reinterpret_cast<const H32*>(old_root);
+    const H32* newr = reinterpret_cast<const H32*>(new_root);
+    parallel_for(n, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            const uint32_t st = consistency_walk(old_size[i], new_size[i], oldr[i], newr[i],
+                                                 reinterpret_cast<const H32*>(proof) + proof_off[i],
+                                                 proof_off[i + 1] - proof_off[i]);
+            status[i] = (uint8_t)st;
+            ok[i] = st == PV_MK_CONSISTENT;
+        }
+    });
+    pack_verdicts(ok, verdict_bits);
+}
+
+void pv_merkle_host_catchup(uint64_t s, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                            const uint64_t* reply_end, uint64_t n_replies, uint64_t final_size, const uint8_t* final_root,
+                            const uint8_t* proof, const uint64_t* proof_off, const PvMerkleOut* out, uint8_t* status,
+                            uint8_t* verdict_bits) {
+    // the append keeps its leaf hashes and nodes here when the caller does not take them: the replies' roots fold from them
+    uint64_t n_nodes, n_front, n_path;
+    pv_merkle_plan_core(s, n, &n_nodes, &n_front, &n_path);
+    std::vector<H32> leaf_own, node_own;
+    PvMerkleOut o = *out;
+    if (!o.leaf_hash && n_replies) {
+        leaf_own.resize(n + 1);
+        o.leaf_hash = leaf_own[0].b;
+    }
+    if (!o.node_hash && n_replies) {
+        node_own.resize(n_nodes + 1);
+        o.node_hash = node_own[0].b;
+    }
+    pv_merkle_host_append(s, frontier, data, off, n, &o);
+    if (!n_replies) return;
+    const H32* oldf = reinterpret_cast<const H32*>(frontier);
+    const H32* leaf = reinterpret_cast<const H32*>(o.leaf_hash);
+    const H32* node = reinterpret_cast<const H32*>(o.node_hash);
+    auto get = [&](const PvMerkleRef& r, H32& h) {
+        h = r.kind == PV_MK_OLD ? oldf[r.idx] : r.kind == PV_MK_LEAF ? leaf[r.idx] : node[r.idx];
+    };
+    auto hash = [](H32& h, const H32& l, const H32& r) { hash_children(h, l, r); };
+    H32 new_root;
+    memcpy(new_root.b, final_root, 32);
+    std::vector<uint8_t> ok(n_replies);
+    parallel_for(n_replies, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t r = lo; r < hi; r++) {
+            H32 old_root;
+            pv_merkle_fold_root(old_root, s, reply_end[r], get, hash);
+            const uint32_t st = consistency_walk(reply_end[r], final_size, old_root, new_root,
+                                                 reinterpret_cast<const H32*>(proof) + proof_off[r],
+                                                 proof_off[r + 1] - proof_off[r]);
+            status[r] = (uint8_t)st;
+            ok[r] = st == PV_MK_CONSISTENT;
+        }
+    });
+    pack_verdicts(ok, verdict_bits);
 }

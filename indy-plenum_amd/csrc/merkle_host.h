@@ -1,5 +1,5 @@
-// The host path of the Merkle entries (merkle_host.cpp): the contract of pv_merkle_append_batch and
-// pv_merkle_verify_inclusion_batch in C++ over merkle_core.h and the host SHA-256, arguments already
+// The host path of the Merkle entries (merkle_host.cpp): the contract of pv_merkle_append_batch,
+// pv_merkle_verify_inclusion_batch, pv_merkle_verify_consistency_batch and pv_merkle_catchup_batch in C++ over merkle_core.h and the host SHA-256, arguments already
 // validated. Internal, not ABI.
 #ifndef PV_MERKLE_HOST_H
 #define PV_MERKLE_HOST_H
@@ -14,5 +14,12 @@ void pv_merkle_host_verify(const uint8_t* data, const uint64_t* off, const uint8
                            const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* proof,
                            const uint64_t* proof_off, const uint8_t* root, uint64_t n, uint8_t* status,
                            uint8_t* verdict_bits);
+void pv_merkle_host_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_root,
+                                const uint8_t* new_root, const uint8_t* proof, const uint64_t* proof_off, uint64_t n,
+                                uint8_t* status, uint8_t* verdict_bits);
+void pv_merkle_host_catchup(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                            const uint64_t* reply_end, uint64_t n_replies, uint64_t final_size, const uint8_t* final_root,
+                            const uint8_t* proof, const uint64_t* proof_off, const PvMerkleOut* out, uint8_t* status,
+                            uint8_t* verdict_bits);
 
 #endif  // PV_MERKLE_HOST_H

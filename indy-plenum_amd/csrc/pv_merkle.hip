@@ -16,8 +16,12 @@
 //   3. pv_merkle_proof_kernel   (optional) one lane per leaf: its audit path gathered from the input
 //                               frontier, the new nodes and the leaf hashes, and the root after it.
 //   4. pv_merkle_finish_kernel  one wave: the frontier after the chunk (the next chunk's input) and its root.
-// and pv_merkle_verify_kernel, one lane per proof. Launches per chunk: at most five, whatever n is; no
-// host round trip between them.
+//   5. pv_merkle_catchup_kernel (catch-up only) one lane per reply whose end lies in the chunk: the root at
+//                               that size folded from the chunk's view, then the consistency walk against
+//                               the call's final size and root.
+// and pv_merkle_verify_kernel / pv_merkle_consistency_kernel (MerkleVerifier.verify_tree_consistency,
+// ledger/merkle_verifier.py:23-153), one lane per proof. Launches per chunk: at most six, whatever n is;
+// no host round trip between them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -233,6 +237,77 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
     if ((threadIdx.x & 63) == 0 && i < n) verdict[i >> 6] = word;
 }
 
+__device__ __forceinline__ bool mk_equal(const MkHash& a, const MkHash& b) {
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) diff |= a.w[k] ^ b.w[k];
+    return diff == 0;
+}
+// the consistency walk of merkle_core.h over proof hashes [p0, p0 + plen) of `proof`
+__device__ __forceinline__ uint32_t mk_consistency(uint64_t old_size, uint64_t new_size, const MkHash& old_root,
+                                                   const MkHash& new_root, const uint32_t* __restrict__ proof,
+                                                   uint64_t p0, uint64_t plen) {
+    return pv_merkle_consistency_check(
+        old_size, new_size, old_root, new_root, plen, [&](uint64_t k, MkHash& o) { o = mk_load(proof + 8 * (p0 + k)); },
+        [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); },
+        [](const MkHash& a, const MkHash& b) { return mk_equal(a, b); });
+}
+
+// One lane per consistency proof; verdict words as pv_merkle_verify_kernel.
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_consistency_kernel(
+    const uint64_t* __restrict__ old_size, const uint64_t* __restrict__ new_size, const uint32_t* __restrict__ old_root,
+    const uint32_t* __restrict__ new_root, const uint32_t* __restrict__ proof, const uint64_t* __restrict__ proof_off,
+    uint64_t n, uint8_t* __restrict__ status, uint64_t* __restrict__ verdict) {
+    const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    bool ok = false;
+    if (i < n) {
+        const uint64_t p0 = proof_off[i];
+        const uint32_t st = mk_consistency(old_size[i], new_size[i], mk_load(old_root + 8 * i), mk_load(new_root + 8 * i),
+                                           proof, p0, proof_off[i + 1] - p0);
+        status[i] = (uint8_t)st;
+        ok = st == PV_MK_CONSISTENT;
+    }
+    const uint64_t word = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && i < n) verdict[i >> 6] = word;
+}
+
+// The replies of a catch-up: reply r ends at absolute size end[r] and carries proof hashes
+// [proof_off[r], proof_off[r + 1]) for (end[r], final_size). status is preset to PV_MK_REPLY_RANGE and the
+// verdict words to zero before the first chunk; a chunk's launch covers replies [r0, r1), r0 a multiple of 64.
+struct MkReplies {
+    const uint64_t* end;
+    const uint32_t* proof;
+    const uint64_t* proof_off;
+    const uint32_t* final_root;
+    uint64_t final_size, r0, r1;
+    uint8_t* status;
+    uint64_t* verdict;
+};
+
+// One lane per reply; the lanes whose reply ends inside the chunk (s < end <= s + n) fold the root at that
+// size from the chunk's view (old frontier entries, leaf hashes, new nodes) and walk the proof. A wave's
+// 64 replies may end in different chunks, so the ballot is OR-ed into the verdict word.
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_catchup_kernel(MkView v, MkReplies q) {
+    const uint64_t r = q.r0 + (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    bool ok = false;
+    if (r < q.r1) {
+        const uint64_t e = q.end[r];
+        if (e > v.s && e <= v.s + v.n) {
+            MkHash old_root;
+            pv_merkle_fold_root(
+                old_root, v.s, e, [&](const PvMerkleRef& ref, MkHash& o) { o = mk_load(v.at(ref)); },
+                [](MkHash& o, const MkHash& l, const MkHash& rr) { o = mk_children(l, rr); });
+            const uint64_t p0 = q.proof_off[r];
+            const uint32_t st = mk_consistency(e, q.final_size, old_root, mk_load(q.final_root), q.proof, p0,
+                                               q.proof_off[r + 1] - p0);
+            q.status[r] = (uint8_t)st;
+            ok = st == PV_MK_CONSISTENT;
+        }
+    }
+    const uint64_t word = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && word) atomicOr(reinterpret_cast<unsigned long long*>(q.verdict + (r >> 6)), word);
+}
+
 // --------------------------------------------------------------------------------------------- host
 
 // The Merkle code's own workspace: allocated on first use (an engine that never hashes a leaf holds
@@ -242,6 +317,7 @@ struct MkWork {
     PvDevBuf leaf, node;   // a chunk's leaf hashes / new nodes when the caller does not take them
     PvDevBuf front;        // three frontiers of 64 hashes: two for chunk chaining, one for a host entry's input
     PvStage stage;         // host entries: staged inputs and outputs of one chunk
+    PvStage replies;       // the catch-up host entry: replies, proofs, status and verdicts, staged once per call
     PvHandover hand;
 };
 MkWork g_mk;
@@ -271,9 +347,10 @@ struct MkChunkOut {  // device pointers, null = not wanted
 };
 
 // One chunk: m > 0 leaves (d_off[0..m] into d_data) appended at size s with input frontier d_fin; the
-// frontier after it goes to d_fout. Caller holds g_mk_mu and is inside mk_run.
+// frontier after it goes to d_fout. rep (may be null): the replies to check against this chunk. Caller
+// holds g_mk_mu and is inside mk_run.
 int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uint64_t* d_off, uint64_t m,
-             const MkChunkOut& o, uint32_t* d_fout, hipStream_t stream) {
+             const MkChunkOut& o, uint32_t* d_fout, hipStream_t stream, const MkReplies* rep = nullptr) {
     uint64_t n_nodes, n_front, n_path;
     pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
     uint32_t* leaf = o.leaf;
@@ -302,7 +379,18 @@ int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uin
         PV_LAUNCH(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
                   o.poff_base, o.roots);
     }
+    if (rep && rep->r1 > rep->r0) {
+        PV_LAUNCH(pv_merkle_catchup_kernel, dim3((unsigned)((rep->r1 - rep->r0 + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK),
+                  0, stream, v, *rep);
+    }
     PV_LAUNCH(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
+    return PV_OK;
+}
+
+// Before the first chunk of a catch-up: no reply claimed yet.
+int mk_replies_preset(const MkReplies& q, uint64_t n_replies, hipStream_t stream) {
+    PV_HIP(hipMemsetAsync(q.status, PV_MK_REPLY_RANGE, n_replies, stream), PV_ERR_LAUNCH);
+    PV_HIP(hipMemsetAsync(q.verdict, 0, 8 * ((n_replies + 63) / 64), stream), PV_ERR_LAUNCH);
     return PV_OK;
 }
 
@@ -315,11 +403,14 @@ int mk_check_out(const PvMerkleOut* out, const char* who) {
 bool mk_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 // Device buffers, n > 0, on `stream`. Caller holds g_mk_mu.
+// rep (may be null): a catch-up's replies, every chunk looks at all of them (their ends are device data).
 int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, const uint64_t* d_off, uint64_t n,
-               const PvMerkleOut& out, hipStream_t stream) {
+               const PvMerkleOut& out, hipStream_t stream, const MkReplies* rep = nullptr) {
     return mk_run(stream, [&]() -> int {
         const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
         int cur = 0;
+        if (rep)
+            if (int rc = mk_replies_preset(*rep, rep->r1, stream)) return rc;
         const uint32_t* fin = reinterpret_cast<const uint32_t*>(d_frontier);
         if (n == 0) {  // the input tree's frontier and root
             const MkView v{s0, 0, fin, nullptr, nullptr};
@@ -341,7 +432,7 @@ int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, co
                                out.path ? out.path_off + c0 : nullptr,
                                pbase,
                                is_last ? reinterpret_cast<uint32_t*>(out.root) : nullptr};
-            if (int rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream)) return rc;
+            if (int rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream, rep)) return rc;
             fin = mk_front(cur);
             cur ^= 1;
         }
@@ -352,11 +443,38 @@ int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, co
 }
 
 // The device path of the host entry: chunk by chunk through the stage. Arguments validated, n > 0.
+// A catch-up's replies as the host entry has them (validated: ends strictly increasing in (s0, s0 + n]).
+struct MkHostReplies {
+    const uint64_t* end;
+    uint64_t count, final_size;
+    const uint8_t* final_root;
+    const uint8_t* proof;
+    const uint64_t* proof_off;
+    uint8_t* status;
+    uint8_t* verdict_bits;
+};
+
 int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
-                         const PvMerkleOut& out) {
+                         const PvMerkleOut& out, const MkHostReplies* hr = nullptr) {
     const hipStream_t st = pv_engine_stream();
     return mk_run(st, [&]() -> int {
         const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
+        MkReplies rep{};
+        if (hr) {  // staged once for all chunks, in a stage of their own
+            PvStage& q = g_mk.replies;
+            const uint64_t R = hr->count;
+            int rc = q.reset(st, false);
+            if (rc) return rc;
+            const int i_end = q.in(hr->end, 8 * R), i_poff = q.in_offsets(hr->proof_off, R),
+                      i_root = q.in(hr->final_root, 32),
+                      i_proof = q.in(hr->proof + 32 * hr->proof_off[0], 32 * (hr->proof_off[R] - hr->proof_off[0]), 32),
+                      o_status = q.out(hr->status, R), o_words = q.out(hr->verdict_bits, (R + 7) / 8, 8);
+            if ((rc = q.upload())) return rc;
+            rep = MkReplies{q.dev<const uint64_t>(i_end), q.dev<const uint32_t>(i_proof), q.dev<const uint64_t>(i_poff),
+                            q.dev<const uint32_t>(i_root), hr->final_size, 0, R, q.dev<uint8_t>(o_status),
+                            q.dev<uint64_t>(o_words)};
+            if ((rc = mk_replies_preset(rep, R, st))) return rc;
+        }
         if (s0) PV_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
         const uint32_t* fin = mk_front(2);
         int cur = 0;
@@ -386,7 +504,13 @@ int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* da
             if ((rc = g.upload())) return rc;
             const MkChunkOut o{g.dev<uint32_t>(o_leaf), g.dev<uint32_t>(o_node), g.dev<uint32_t>(o_roots),
                                g.dev<uint32_t>(o_path), g.dev<uint64_t>(o_poff), pbase, g.dev<uint32_t>(o_root)};
-            if ((rc = mk_chunk(s, fin, g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), m, o, mk_front(cur), st)))
+            if (hr) {  // the replies that end in this chunk, from the start of the first one's verdict word
+                const uint64_t* e = hr->end;
+                rep.r0 = (uint64_t)(std::upper_bound(e, e + hr->count, s) - e) & ~63ull;
+                rep.r1 = (uint64_t)(std::upper_bound(e, e + hr->count, s + m) - e);
+            }
+            if ((rc = mk_chunk(s, fin, g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), m, o, mk_front(cur), st,
+                               hr ? &rep : nullptr)))
                 return rc;
             fin = mk_front(cur);
             cur ^= 1;
@@ -395,7 +519,7 @@ int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* da
             if ((rc = g.download())) return rc;  // synchronised: the stage is free for the next chunk
             c0 += m;
         }
-        return PV_OK;
+        return hr ? g_mk.replies.download() : PV_OK;
     });
 }
 
@@ -414,6 +538,34 @@ int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_
     return PV_OK;
 }
 
+int mk_consistency_enqueue(const uint64_t* d_old_size, const uint64_t* d_new_size, const uint8_t* d_old_root,
+                           const uint8_t* d_new_root, const uint8_t* d_proof, const uint64_t* d_proof_off, uint64_t n,
+                           uint8_t* d_status, uint64_t* d_verdict, hipStream_t stream) {
+    const uint64_t chunk = (g_mk_chunk + 63) & ~63ull;  // whole verdict words per chunk
+    for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint64_t m = std::min<uint64_t>(chunk, n - c0);
+        PV_LAUNCH(pv_merkle_consistency_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
+                  stream, d_old_size + c0, d_new_size + c0, reinterpret_cast<const uint32_t*>(d_old_root + 32 * c0),
+                  reinterpret_cast<const uint32_t*>(d_new_root + 32 * c0), reinterpret_cast<const uint32_t*>(d_proof),
+                  d_proof_off + c0, m, d_status + c0, d_verdict + c0 / 64);
+    }
+    return PV_OK;
+}
+
+// the append arguments every append-like entry checks
+int mk_check_append_args(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                         const std::string& who) {
+    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
+        return pv_fail(PV_ERR_ARG, who + ": tree_size + n must stay below 2^48");
+    if (tree_size > 0 && !frontier) return pv_fail(PV_ERR_ARG, who + ": a tree of size > 0 needs its frontier");
+    if (n > 0) {
+        if (!off) return pv_fail(PV_ERR_ARG, who + ": null offsets");
+        if (!pv_offsets_monotone(off, n)) return pv_fail(PV_ERR_ARG, who + ": offsets must be non-decreasing");
+        if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, who + ": null data");
+    }
+    return PV_OK;
+}
+
 }  // namespace
 
 void pv_merkle_forget_stream(void* stream) {
@@ -425,6 +577,7 @@ void pv_merkle_shutdown() {
     std::lock_guard<std::mutex> lk(g_mk_mu);
     for (PvDevBuf* b : {&g_mk.leaf, &g_mk.node, &g_mk.front}) b->release();
     g_mk.stage.release();
+    g_mk.replies.release();
     g_mk.hand.destroy();
 }
 
@@ -564,6 +717,127 @@ int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_
     std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
     return mk_verify_enqueue(d_data, d_off, d_leaf_hash, d_leaf_index, d_tree_size, d_proof, d_proof_off, d_root, n, d_status,
                              d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+}
+
+int pv_merkle_verify_consistency_batch(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_root,
+                                       const uint8_t* new_root, const uint8_t* proof, const uint64_t* proof_off,
+                                       uint64_t n, uint8_t* status, uint8_t* verdict_bits) {
+    const char* who = "pv_merkle_verify_consistency_batch";
+    if (n == 0) return PV_OK;
+    if (!old_size || !new_size || !old_root || !new_root || !proof_off || !status || !verdict_bits)
+        return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
+    if (n >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 proofs");
+    if (!pv_offsets_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
+        return pv_fail(PV_ERR_ARG, std::string(who) + ": proof offsets must be non-decreasing over a proof array");
+    uint64_t all = 0;
+    for (uint64_t i = 0; i < n; i++) all |= old_size[i] | new_size[i];
+    if (all >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, std::string(who) + ": tree sizes must stay below 2^48");
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    bool device;
+    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_CONSISTENCY, who, &device);
+    if (rc) return rc;
+    if (!device) {
+        lk.unlock();
+        pv_merkle_host_consistency(old_size, new_size, old_root, new_root, proof, proof_off, n, status, verdict_bits);
+        return PV_OK;
+    }
+    const hipStream_t st = pv_engine_stream();
+    return mk_run(st, [&]() -> int {
+        PvStage& g = g_mk.stage;
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        const int i_old = g.in(old_size, 8 * n), i_new = g.in(new_size, 8 * n), i_oroot = g.in(old_root, 32 * n),
+                  i_nroot = g.in(new_root, 32 * n), i_poff = g.in_offsets(proof_off, n),
+                  i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
+                  o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
+        if ((rc = g.upload()) ||
+            (rc = mk_consistency_enqueue(g.dev<const uint64_t>(i_old), g.dev<const uint64_t>(i_new),
+                                         g.dev<const uint8_t>(i_oroot), g.dev<const uint8_t>(i_nroot),
+                                         g.dev<const uint8_t>(i_proof), g.dev<const uint64_t>(i_poff), n,
+                                         g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
+            return rc;
+        return g.download();
+    });
+}
+
+int pv_merkle_verify_consistency_batch_device(const uint64_t* d_old_size, const uint64_t* d_new_size,
+                                              const uint8_t* d_old_root, const uint8_t* d_new_root, const uint8_t* d_proof,
+                                              const uint64_t* d_proof_off, uint64_t n, uint8_t* d_status,
+                                              uint64_t* d_verdict_words, void* stream) {
+    const char* who = "pv_merkle_verify_consistency_batch_device";
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, std::string(who) + ": call pv_init first");
+    if (n == 0) return PV_OK;
+    if (!d_old_size || !d_new_size || !d_old_root || !d_new_root || !d_proof || !d_proof_off || !d_status || !d_verdict_words)
+        return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
+    if (mk_misaligned(d_old_root) || mk_misaligned(d_new_root) || mk_misaligned(d_proof))
+        return pv_fail(PV_ERR_ARG, std::string(who) + ": hash arrays must be 16-byte aligned");
+    if (n >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 proofs");
+    std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
+    return mk_consistency_enqueue(d_old_size, d_new_size, d_old_root, d_new_root, d_proof, d_proof_off, n, d_status,
+                                  d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+}
+
+int pv_merkle_catchup_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
+                            const uint64_t* reply_end, uint64_t n_replies, uint64_t final_size, const uint8_t* final_root,
+                            const uint8_t* proof, const uint64_t* proof_off, const PvMerkleOut* out, uint8_t* status,
+                            uint8_t* verdict_bits) {
+    const std::string who = "pv_merkle_catchup_batch";
+    const PvMerkleOut none{};
+    if (!out) out = &none;
+    int rc = mk_check_out(out, who.c_str());
+    if (rc || (rc = mk_check_append_args(tree_size, frontier, data, off, n, who))) return rc;
+    if (final_size >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": final_size must stay below 2^48");
+    if (n_replies >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 replies");
+    if (n_replies) {
+        if (!reply_end || !final_root || !proof_off || !status || !verdict_bits) return pv_fail(PV_ERR_ARG, who + ": null pointer");
+        if (!pv_offsets_monotone(proof_off, n_replies) || (!proof && proof_off[n_replies] != proof_off[0]))
+            return pv_fail(PV_ERR_ARG, who + ": proof offsets must be non-decreasing over a proof array");
+        uint64_t bad = reply_end[0] <= tree_size || reply_end[n_replies - 1] > tree_size + n;
+        for (uint64_t r = 1; r < n_replies; r++) bad |= reply_end[r] <= reply_end[r - 1];
+        if (bad) return pv_fail(PV_ERR_ARG, who + ": reply ends must increase strictly within (tree_size, tree_size + n]");
+    }
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    bool device;
+    if ((rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_PROOFS, who.c_str(), &device)))
+        return rc;
+    if (!device || n == 0) {
+        lk.unlock();
+        pv_merkle_host_catchup(tree_size, frontier, data, off, n, reply_end, n_replies, final_size, final_root, proof, proof_off,
+                               out, status, verdict_bits);
+        return PV_OK;
+    }
+    const MkHostReplies hr{reply_end, n_replies, final_size, final_root, proof, proof_off, status, verdict_bits};
+    return mk_host_entry_device(tree_size, frontier, data, off, n, *out, n_replies ? &hr : nullptr);
+}
+
+int pv_merkle_catchup_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
+                                   const uint64_t* d_off, uint64_t n, const uint64_t* d_reply_end, uint64_t n_replies,
+                                   uint64_t final_size, const uint8_t* d_final_root, const uint8_t* d_proof,
+                                   const uint64_t* d_proof_off, const PvMerkleOut* d_out, uint8_t* d_status,
+                                   uint64_t* d_verdict_words, void* stream) {
+    const std::string who = "pv_merkle_catchup_batch_device";
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, who + ": call pv_init first");
+    const PvMerkleOut none{};
+    if (!d_out) d_out = &none;
+    int rc = mk_check_out(d_out, who.c_str());
+    if (rc) return rc;
+    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS ||
+        final_size >> PV_MERKLE_MAX_BITS)
+        return pv_fail(PV_ERR_ARG, who + ": tree_size + n and final_size must stay below 2^48");
+    if (n_replies >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 replies");
+    if (tree_size > 0 && !d_frontier) return pv_fail(PV_ERR_ARG, who + ": a tree of size > 0 needs its frontier");
+    if (n > 0 && (!d_data || !d_off)) return pv_fail(PV_ERR_ARG, who + ": null pointer");
+    if (n_replies && (!d_reply_end || !d_final_root || !d_proof || !d_proof_off || !d_status || !d_verdict_words))
+        return pv_fail(PV_ERR_ARG, who + ": null pointer");
+    for (const void* p : {(const void*)d_frontier, (const void*)d_out->leaf_hash, (const void*)d_out->node_hash,
+                          (const void*)d_out->frontier, (const void*)d_out->root, (const void*)d_out->roots,
+                          (const void*)d_out->path, (const void*)d_final_root, (const void*)d_proof})
+        if (mk_misaligned(p)) return pv_fail(PV_ERR_ARG, who + ": hash arrays must be 16-byte aligned");
+    const MkReplies rep{d_reply_end, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off,
+                        reinterpret_cast<const uint32_t*>(d_final_root), final_size, 0, n_replies, d_status, d_verdict_words};
+    std::lock_guard<std::mutex> lk(g_mk_mu);
+    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, stream ? (hipStream_t)stream : pv_engine_stream(),
+                      n_replies ? &rep : nullptr);
 }
 
 }  // extern "C"

@@ -122,6 +122,15 @@ SIGNATURES = {
                                                                                 ctypes.c_void_p]),
     "pv_merkle_verify_inclusion_batch_device": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p,
                                                                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "pv_merkle_verify_consistency_batch": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p,
+                                                                                  ctypes.c_void_p]),
+    "pv_merkle_verify_consistency_batch_device": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint64] +
+                                                  [ctypes.c_void_p] * 3),
+    "pv_merkle_catchup_batch": (ctypes.c_int, [ctypes.c_uint64] + [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.c_uint64] + [ctypes.c_void_p] * 6),
+    "pv_merkle_catchup_batch_device": (ctypes.c_int, [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+                                       [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64] +
+                                       [ctypes.c_void_p] * 7),
     "pv_merkle_chunk": (ctypes.c_int, [ctypes.c_uint64]),
     "pv_merkle_path": (ctypes.c_int, [ctypes.c_int]),
     "pv_sha3_256_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
@@ -645,6 +654,10 @@ PV_MERKLE_AUTO, PV_MERKLE_HOST, PV_MERKLE_DEVICE = 0, 1, 2
 PV_MERKLE_AUTO_MIN = 2048   # include/plenum_verify.h: AUTO takes the device path from this many leaves
 PV_MERKLE_AUTO_MIN_PROOFS = 1024  # the same when per-leaf roots or audit paths are asked for
 PV_MERKLE_AUTO_MIN_VERIFY = 512  # proofs from which AUTO checks on the device
+PV_MERKLE_AUTO_MIN_CONSISTENCY = 256  # the same for consistency proofs
+# status of a consistency check (csrc/merkle_core.h pv_merkle_consistency_check)
+(PV_MK_CONSISTENT, PV_MK_OLD_LARGER, PV_MK_CONS_TOO_SHORT, PV_MK_NEW_DIFFERS, PV_MK_OLD_DIFFERS, PV_MK_SAME_SIZE,
+ PV_MK_REPLY_RANGE) = range(7)
 PV_MERKLE_CHUNK = 1048576
 MERKLE_OUTPUTS = ("leaf_hash", "node_hash", "frontier", "root", "roots", "path")
 
@@ -689,13 +702,14 @@ def _merkle_device_ready(n, auto_min):
         _merkle_no_device = True
 
 
-def merkle_append(tree_size, frontier, blob, off, want=MERKLE_OUTPUTS):
+def merkle_append(tree_size, frontier, blob, off, want=MERKLE_OUTPUTS, _catchup=None):
     """n sequential CompactMerkleTree.append calls as one pv_merkle_append_batch: leaf i = blob[off[i]:off[i+1]]
     appended to the tree (tree_size, frontier = tree.hashes joined). Returns a dict of the outputs named in
     `want` (uint8 arrays; "path" also brings "path_off", uint64 in hash units)."""
     off = np.ascontiguousarray(off, dtype=np.uint64)
     n = off.shape[0] - 1
-    _merkle_device_ready(n, PV_MERKLE_AUTO_MIN_PROOFS if "roots" in want or "path" in want else PV_MERKLE_AUTO_MIN)
+    _merkle_device_ready(n, PV_MERKLE_AUTO_MIN_PROOFS if "roots" in want or "path" in want or _catchup
+                         else PV_MERKLE_AUTO_MIN)
     if n < 0:
         raise ValueError("merkle_append: offsets must hold n + 1 entries")
     blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
@@ -718,8 +732,14 @@ def merkle_append(tree_size, frontier, blob, off, want=MERKLE_OUTPUTS):
     if "path" in want:
         res["path_off"] = np.zeros(n + 1, np.uint64)
         out.path_off = res["path_off"].ctypes.data
-    check(lib().pv_merkle_append_batch(tree_size, _ptr(front) if tree_size else None, _ptr(blob), _ptr(off), n,
-                                       ctypes.byref(out)), "pv_merkle_append_batch")
+    if _catchup:  # merkle_catchup: the same outputs, and the replies checked in the same call
+        ends, final_size, final_root, pbuf, poff, status, bits = _catchup
+        check(lib().pv_merkle_catchup_batch(tree_size, _ptr(front) if tree_size else None, _ptr(blob), _ptr(off), n,
+                                            _ptr(ends), ends.shape[0], final_size, _ptr(final_root), _ptr(pbuf), _ptr(poff),
+                                            ctypes.byref(out), _ptr(status), _ptr(bits)), "pv_merkle_catchup_batch")
+    else:
+        check(lib().pv_merkle_append_batch(tree_size, _ptr(front) if tree_size else None, _ptr(blob), _ptr(off), n,
+                                           ctypes.byref(out)), "pv_merkle_append_batch")
     if "frontier" in res:
         res["frontier"] = res["frontier"][:bin(tree_size + n).count("1")]
     return res
@@ -759,6 +779,58 @@ def merkle_verify_inclusion(leaf_index, tree_size, proofs, roots, leaves=None, l
         _ptr(lh) if lh is not None else None, _ptr(idx), _ptr(size), _ptr(pbuf), _ptr(poff), _ptr(rbuf), n, _ptr(status),
         _ptr(bits)), "pv_merkle_verify_inclusion_batch")
     return np.unpackbits(bits, count=n, bitorder="little").view(bool), status
+
+
+def _proof_arrays(proofs, who):
+    n = len(proofs)
+    poff = np.zeros(n + 1, np.uint64)
+    if n:
+        np.cumsum([len(p) for p in proofs], out=poff[1:])
+    pbuf = np.frombuffer(b"".join(b"".join(p) for p in proofs) or bytes(32), dtype=np.uint8)
+    if pbuf.size != 32 * int(poff[n]) and int(poff[n]):
+        raise ValueError(who + ": proof hashes must be 32 bytes each")
+    return pbuf, poff
+
+
+def merkle_verify_consistency(old_sizes, new_sizes, old_roots, new_roots, proofs):
+    """MerkleVerifier.verify_tree_consistency for n proofs as one pv_merkle_verify_consistency_batch: proofs[i] a
+    list of 32-byte hashes, the roots 32 bytes each. Returns (verdicts bool[n], status uint8[n]); status codes
+    PV_MK_* above."""
+    n = len(proofs)
+    _merkle_device_ready(n, PV_MERKLE_AUTO_MIN_CONSISTENCY)
+    if n == 0:
+        return np.zeros(0, bool), np.zeros(0, np.uint8)
+    pbuf, poff = _proof_arrays(proofs, "merkle_verify_consistency")
+    obuf, nbuf = np.frombuffer(b"".join(old_roots), dtype=np.uint8), np.frombuffer(b"".join(new_roots), dtype=np.uint8)
+    if obuf.size != 32 * n or nbuf.size != 32 * n:
+        raise ValueError("merkle_verify_consistency: roots must be 32 bytes each")
+    old = np.ascontiguousarray(old_sizes, dtype=np.uint64)
+    new = np.ascontiguousarray(new_sizes, dtype=np.uint64)
+    if old.shape != (n,) or new.shape != (n,):
+        raise ValueError("merkle_verify_consistency: one old and one new size per proof")
+    status, bits = np.zeros(n, np.uint8), np.zeros((n + 7) // 8, np.uint8)
+    check(lib().pv_merkle_verify_consistency_batch(_ptr(old), _ptr(new), _ptr(obuf), _ptr(nbuf), _ptr(pbuf), _ptr(poff), n,
+                                                   _ptr(status), _ptr(bits)), "pv_merkle_verify_consistency_batch")
+    return np.unpackbits(bits, count=n, bitorder="little").view(bool), status
+
+
+def merkle_catchup(tree_size, frontier, blob, off, reply_end, final_size, final_root, proofs, want=()):
+    """pv_merkle_catchup_batch: the n leaves of a chain of catch-up replies appended to the tree (tree_size,
+    frontier) as merkle_append does, and reply r (ending at absolute size reply_end[r], with consistency
+    proof proofs[r] towards the tree of final_size leaves and root final_root) checked in the same call.
+    Returns (verdicts bool[R], status uint8[R], merkle_append's dict for `want`)."""
+    ends = np.ascontiguousarray(reply_end, dtype=np.uint64)
+    R = ends.shape[0]
+    if len(proofs) != R:
+        raise ValueError("merkle_catchup: one proof per reply")
+    if len(final_root) != 32:
+        raise ValueError("merkle_catchup: the final root must be 32 bytes")
+    pbuf, poff = _proof_arrays(proofs, "merkle_catchup")
+    status, bits = np.zeros(max(R, 1), np.uint8), np.zeros((R + 7) // 8 + 1, np.uint8)
+    root = np.frombuffer(bytes(final_root), dtype=np.uint8)
+    res = merkle_append(tree_size, frontier, blob, off, want=want,
+                        _catchup=(ends if R else np.zeros(1, np.uint64)[:0], int(final_size), root, pbuf, poff, status, bits))
+    return np.unpackbits(bits, count=R, bitorder="little").view(bool), status[:R], res
 
 
 # -------------------------------------------------------------------------------------- state trie

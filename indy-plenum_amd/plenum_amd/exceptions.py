@@ -178,5 +178,9 @@ class ProofError(VerifyError):
     """A cryptographic proof is not valid."""
 
 
+class ConsistencyError(VerifyError):
+    """Two trees that should be consistent are not: a proof of inconsistency (ledger/error.py:62-65)."""
+
+
 class ConsistencyVerificationFailed(Exception):
     pass

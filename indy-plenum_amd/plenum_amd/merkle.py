@@ -1,8 +1,8 @@
 """The ledger's compact Merkle tree with batched appends and audit-proof checks.
 
 The interface (member names, arguments, exception classes and texts) of the reference's
-ledger/tree_hasher.py, ledger/compact_merkle_tree.py, ledger/hash_stores (the in-memory store) and the
-inclusion half of ledger/merkle_verifier.py, implemented independently: a tree is its size and its
+ledger/tree_hasher.py, ledger/compact_merkle_tree.py, ledger/hash_stores (the in-memory store) and
+ledger/merkle_verifier.py, implemented independently: a tree is its size and its
 frontier (one hash per set bit of the size, largest subtree first), an append is a binary-counter carry
 over that frontier, node positions are closed forms, and the store-backed hashes and proofs follow the
 RFC 6962 definitions of MTH, PATH and PROOF. Added: one library call for a whole batch.
@@ -11,17 +11,21 @@ RFC 6962 definitions of MTH, PATH and PROOF. Added: one library call for a whole
     CompactMerkleTree.extended_batch(leaves)  a new tree, no store (ledger.py:129-143 treeWithAppliedTxns)
     TreeHasher.hash_leaves(leaves)            the leaf hashes of a batch (catch-up)
     MerkleVerifier.verify_leaf_inclusion_batch(items)
+    MerkleVerifier.verify_tree_consistency_batch(items)
+    CompactMerkleTree.verify_catchup_replies(replies, final_size, final_root)
+                                              a chain of CatchupReps checked as plenum/server/catchup/
+                                              catchup_rep_service.py:375-426 checks them one by one
 
-The batch calls go through libplenum_verify (pv_merkle_append_batch, pv_merkle_verify_inclusion_batch),
-which runs them on the GPU or, for small batches and on a machine without one, in C++ on the host;
-the results are byte-identical to the sequential methods below. Not here: verify_tree_consistency,
-the persistent hash stores and the Ledger class."""
+The batch calls go through libplenum_verify (pv_merkle_append_batch, pv_merkle_verify_inclusion_batch,
+pv_merkle_verify_consistency_batch, pv_merkle_catchup_batch), which runs them on the GPU or, for small
+batches and on a machine without one, in C++ on the host; the results are byte-identical to the
+sequential methods below. Not here: the persistent hash stores and the Ledger class."""
 import hashlib
 from binascii import hexlify
 from collections import namedtuple
 
 from . import _native
-from .exceptions import ConsistencyVerificationFailed, ProofError
+from .exceptions import ConsistencyError, ConsistencyVerificationFailed, ProofError
 
 STH = namedtuple("STH", ["tree_size", "sha256_root_hash"])
 
@@ -388,9 +392,52 @@ class CompactMerkleTree:
         self._store.reset()
         self._update(0, ())
 
+    def verify_catchup_replies(self, replies, final_size, final_root):
+        """replies: (leaves, proof) per CatchupRep, chained: reply r's old tree is this tree plus the leaves
+        of replies 0..r. Returns, per reply, True or the exception that
+        MerkleVerifier.verify_tree_consistency(temp.tree_size, final_size, temp.root_hash, final_root, proof)
+        raises for temp = self.extended(all leaves up to and including the reply): what
+        catchup_rep_service.py:375-426 computes per reply. Replies are chained whether or not earlier ones
+        verified; the tree and its store are untouched. One library call (pv_merkle_catchup_batch); a reply
+        that does not verify is re-run sequentially for the reference's exception and text, and a reply
+        without leaves or a hasher other than SHA-256 sends the whole call through the sequential path."""
+        replies = [(list(leaves), list(proof)) for leaves, proof in replies]
+        out = [None] * len(replies)
+        try:
+            total = self._size + sum(len(lv) for lv, _ in replies)
+            fast = (bool(replies) and self._hasher.hashfunc is hashlib.sha256 and all(lv for lv, _ in replies)
+                    and 0 <= int(final_size) < 2 ** 48 and total < 2 ** 48 and len(final_root) == 32
+                    and all(len(h) == 32 for _, proof in replies for h in proof))
+        except (TypeError, ValueError):
+            fast = False
+        if fast:
+            blob, off = _native._blob([bytes(x) for lv, _ in replies for x in lv])
+            ends, at = [], self._size
+            for lv, _ in replies:
+                at += len(lv)
+                ends.append(at)
+            verdicts, _status, _ = _native.merkle_catchup(self._size, b"".join(self._hashes), blob, off, ends,
+                                                          int(final_size), bytes(final_root), [p for _, p in replies])
+            for r, v in enumerate(verdicts):
+                if v:
+                    out[r] = True
+        if None in out:
+            verifier = MerkleVerifier(self._hasher)
+            temp = self.__copy__()
+            last = max(r for r, x in enumerate(out) if x is None)
+            for r, (leaves, proof) in enumerate(replies[:last + 1]):
+                temp.extend(leaves)
+                if out[r] is None:
+                    try:
+                        out[r] = verifier.verify_tree_consistency(temp.tree_size, final_size, temp.root_hash, final_root,
+                                                                  proof)
+                    except Exception as ex:  # the reference's ValueError / ProofError / ConsistencyError, per reply
+                        out[r] = ex
+        return out
+
 
 class MerkleVerifier(object):
-    """Merkle audit-path checks (the inclusion half of the reference's MerkleVerifier)."""
+    """Merkle audit-path and consistency-proof checks (the reference's MerkleVerifier)."""
 
     def __init__(self, hasher=None):
         self.hasher = hasher or TreeHasher()
@@ -400,6 +447,83 @@ class MerkleVerifier(object):
 
     def __str__(self):
         return "%s(hasher: %s)" % (self.__class__.__name__, self.hasher)
+
+    def verify_tree_consistency(self, old_tree_size, new_tree_size, old_root, new_root, proof):
+        """True, or raises ValueError / ProofError / ConsistencyError with the reference's texts. The walk is
+        csrc/merkle_core.h's pv_merkle_consistency_check: the proof is the audit path of node old_size - 1
+        in the new tree, hashed together up to the first node only the new tree has. A proof hash is taken
+        only where one is needed; hashes left over are accepted."""
+        old_size, new_size = old_tree_size, new_tree_size
+        if old_size < 0 or new_size < 0:
+            raise ValueError("Negative tree size")
+        if old_size > new_size:
+            raise ValueError("Older tree has bigger size (%d vs %d), did you supply inputs in the wrong order?" %
+                             (old_size, new_size))
+        if old_size == new_size:
+            if old_root == new_root:
+                return True
+            raise ConsistencyError("Inconsistency: different root hashes for the same tree size")
+        if old_size == 0:
+            return True
+        node, last = old_size - 1, new_size - 1
+        while node & 1:
+            node, last = node >> 1, last >> 1
+        hashes = iter(proof)
+        try:
+            new_hash = old_hash = next(hashes) if node else old_root
+            while node:
+                if node & 1:
+                    sibling = next(hashes)
+                    old_hash = self.hasher.hash_children(sibling, old_hash)
+                    new_hash = self.hasher.hash_children(sibling, new_hash)
+                elif node < last:
+                    new_hash = self.hasher.hash_children(new_hash, next(hashes))
+                node, last = node >> 1, last >> 1
+            while last:
+                new_hash = self.hasher.hash_children(new_hash, next(hashes))
+                last >>= 1
+        except StopIteration:
+            raise ProofError("Merkle proof is too short")
+        if new_hash != new_root:
+            raise ProofError("Bad Merkle proof: second root hash does not match. Expected hash: %s , computed hash: %s" %
+                             (hexlify(new_root).strip(), hexlify(new_hash).strip()))
+        if old_hash != old_root:
+            raise ConsistencyError("Inconsistency: first root hash does not match. Expected hash: %s, computed hash: %s" %
+                                   (hexlify(old_root).strip(), hexlify(old_hash).strip()))
+        return True
+
+    def verify_tree_consistency_batch(self, items):
+        """items: (old_tree_size, new_tree_size, old_root, new_root, proof) tuples. Returns a list with True or
+        the exception the reference's verify_tree_consistency raises, per item. One library call for the
+        batch; an item that does not verify, or that the library cannot represent (negative or huge sizes,
+        odd-sized hashes, a hasher other than SHA-256), is re-run through the sequential method so the
+        exception and its text are the reference's."""
+        items = list(items)
+        out = [None] * len(items)
+        fast = []
+        for i, (old, new, old_root, new_root, proof) in enumerate(items):
+            try:
+                ok = (self.hasher.hashfunc is hashlib.sha256 and 0 <= int(old) < 2 ** 48 and 0 <= int(new) < 2 ** 48
+                      and int(old) == old and int(new) == new and len(old_root) == 32 and len(new_root) == 32
+                      and all(len(p) == 32 for p in proof))
+            except (TypeError, ValueError):
+                ok = False
+            if ok:
+                fast.append(i)
+        if fast:
+            verdicts, _status = _native.merkle_verify_consistency(
+                [int(items[i][0]) for i in fast], [int(items[i][1]) for i in fast], [bytes(items[i][2]) for i in fast],
+                [bytes(items[i][3]) for i in fast], [list(items[i][4]) for i in fast])
+            for i, v in zip(fast, verdicts):
+                if v:
+                    out[i] = True
+        for i, item in enumerate(items):
+            if out[i] is None:
+                try:
+                    out[i] = self.verify_tree_consistency(*item)
+                except Exception as ex:  # the reference's ValueError / ProofError / ConsistencyError, per item
+                    out[i] = ex
+        return out
 
     @classmethod
     def audit_path_length(cls, index, tree_size):
