@@ -418,6 +418,48 @@ int hc_sc_nwin16(const uint8_t* a) {
     return sc_nwin16(e);
 }
 
+// The units tests/native/devcheck.hip wraps that had no entry of their own here (tests/devarith_cases.py
+// drives both libraries with the same vectors)
+void hc_fe_mul_pre(uint32_t* h, const uint32_t* f, const uint32_t* g) {
+    fe a, b, c; memcpy(a.v, f, 40); memcpy(b.v, g, 40);
+    uint32_t g19[10];
+    fe_mul19(g19, b);
+    fe_mul_pre(c, a, b, g19);
+    memcpy(h, c.v, 40);
+}
+void hc_sc_mul5(uint8_t* r, const uint8_t* a, const uint8_t* b) {  // a < 2^160
+    uint32_t aw[8], bw[8], rw[8];
+    load_words(aw, a);
+    load_words(bw, b);
+    sc_mul<5>(rw, aw, bw);
+    memcpy(r, rw, 32);
+}
+// ge_frombytes_negate: returns ok; out = X, Y, Z, T (10 limbs each)
+int hc_ge_frombytes_negate(uint32_t* out, const uint8_t* s) {
+    uint32_t w[8];
+    load_words(w, s);
+    ge_p3 p;
+    const bool ok = ge_frombytes_negate(p, w);
+    memcpy(out, p.X.v, 40); memcpy(out + 10, p.Y.v, 40); memcpy(out + 20, p.Z.v, 40); memcpy(out + 30, p.T.v, 40);
+    return ok;
+}
+void hc_ge_p2_tobytes(uint8_t* s, const uint32_t* xyz) {
+    fe X, Y, Z;
+    memcpy(X.v, xyz, 40); memcpy(Y.v, xyz + 10, 40); memcpy(Z.v, xyz + 20, 40);
+    uint32_t w[8];
+    ge_p2_tobytes(w, X, Y, Z);
+    memcpy(s, w, 32);
+}
+// k = SHA-512(R || A || M) mod L by pv_hash_k alone (sm = R || S || M, smlen >= 64)
+void hc_hash_k(uint8_t* kout, const uint8_t* sm, uint64_t smlen, const uint8_t* pk) {
+    std::vector<uint8_t> buf(smlen + 256, 0);  // PV_BLOB_SLACK
+    memcpy(buf.data(), sm, smlen);
+    pv_sig_words in; memcpy(in.R, buf.data(), 32); memcpy(in.S, buf.data() + 32, 32); memcpy(in.A, pk, 32);
+    uint32_t k[8];
+    pv_hash_k(k, in, smlen, HostMsg{buf.data()});
+    memcpy(kout, k, 32);
+}
+
 // lp_halfsize (the latency path's limb-parallel split) on a 32-byte scalar, same outputs as
 // hc_sc_halfsize
 int hc_lp_halfsize(const uint8_t* k, uint8_t* k1, uint8_t* k2, int* neg) {
@@ -684,6 +726,24 @@ void hc_lp_sub(uint32_t* out, const uint32_t* p, const uint32_t* q) {
     const LpLane c = LpLane::make();
     const LpConsts K = LpConsts::make(c);
     hc_rows_out(out, lp_add_cached(c, hc_rows_in(p), lp_neg_cached(c, lp_to_cached(c, hc_rows_in(q), K.d2))));
+}
+
+// lp_decompress_ar on the key's encoding (row 0, and row 2) and R's (rows 1, 3): flags = ok_a, ok_r,
+// x_r_zero; xy = the four rows of X, then of Y
+void hc_lp_decompress_ar(int* flags, uint32_t* xy, const uint8_t* a_enc, const uint8_t* r_enc) {
+    uint32_t wa[8], wr[8];
+    load_words(wa, a_enc);
+    load_words(wr, r_enc);
+    const LpLane c = LpLane::make();
+    const LpConsts K = LpConsts::make(c);
+    lu sw[8];
+    for (int q = 0; q < 8; q++) sw[q] = lp_sel(lp_eq(c.row & 1u, 1u), wr[q], wa[q]);
+    const LpDecomp d = lp_decompress_ar(c, K, sw);
+    flags[0] = d.ok_a;
+    flags[1] = d.ok_r;
+    flags[2] = d.x_r_zero;
+    hc_rows_out(xy, d.X);
+    hc_rows_out(xy + 40, d.Y);
 }
 
 // crypto_sign_open through the latency path: the kernel's two waves, one after the other (wave 1

@@ -149,6 +149,29 @@ def test_small_calls_zero_copy_records(native, sodium, oracle):
         assert native.last_zero_copy() == (native.last_path()[0] == native.PV_PATH_LATENCY), lead
 
 
+def test_sha512_block_edges_every_length(native, sodium, oracle):
+    """k = SHA-512(R || A || M) at every block edge: one valid record for EVERY message length 0..300
+    (R || A || M is 64..364 bytes: every residue mod 128, the padding edges 111/112 and 127/128 among them,
+    and one-, two- and three-block inputs) and the same record with its last byte flipped (for the empty
+    message that is a byte of S), at leading offsets 0..3, against libsodium."""
+    g = VectorGen(sodium, oracle, seed=33)
+    cases = []
+    for ln in range(301):
+        sm, pk = g.valid(bytes(g.rng.getrandbits(8) for _ in range(ln)))
+        bad = bytearray(sm)
+        bad[-1] ^= 0x10
+        cases += [(sm, pk), (bytes(bad), pk)]
+    assert len(cases) == 602 and sorted({len(sm) for sm, _ in cases}) == list(range(64, 365))
+    blob, off, pks = pack(cases)
+    want = reference_verdicts(sodium, cases)
+    assert want[0::2].all() and not want[1::2].any()
+    for lead in (0, 1, 2, 3):
+        blob2 = np.concatenate([np.full(lead, 0x55, np.uint8), blob])
+        got = native.verify_sm_batch(blob2, off + lead, pks)
+        bad = np.nonzero(got != want)[0]
+        assert len(bad) == 0, (lead, [(int(i), len(cases[i][0]) - 64) for i in bad[:8]])
+
+
 def test_one_request_calls(native, sodium, oracle):
     """One-request host-buffer calls (verifySignature singletons): a slot of <= 1,024 bytes (records
     up to 816 bytes) travels in the kernel arguments (pv_lat4_one_kernel), longer ones in a pinned

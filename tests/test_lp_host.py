@@ -2,7 +2,12 @@
 64 lanes of a wave simulated exactly (DPP row broadcast / rotate / shift and the gfx950 permlane
 swaps as specified), every lp_mul column recomputed in 128 bits and bound-checked (PV_BOUNDS_CHECK),
 against Python big integers, the C oracle, the golden libsodium verdicts and libsodium itself.
-tests/test_gpu_parity.py runs the same code on the GPU (PV_PATH_LATENCY)."""
+A pass here proves the limb-parallel algorithms and their bounds on a MODEL of the lane instructions
+(row_newbcast / row_ror / row_shr / row_shl with bound_ctrl, permlane16_swap, permlane32_swap,
+readlane, ballot); whether the model matches the hardware is checked by tests/test_gpu_devarith.py,
+which runs the device forms on the GPU with the same operands and compares them with this simulation
+limb for limb (shared vectors: tests/devarith_cases.py). tests/test_gpu_parity.py runs the whole
+latency path on the GPU (PV_PATH_LATENCY)."""
 import ctypes
 import json
 import os
@@ -10,6 +15,7 @@ import random
 
 import pytest
 
+from devarith_cases import LP_MUL_COMBOS, LP_MUL_DUAL_COMBOS, rand_limbs
 from test_native_host import HERE, L, P, W, from_limbs, hc, to_limbs  # noqa: F401
 
 A40 = ctypes.c_uint32 * 40
@@ -28,18 +34,12 @@ def rows_out(a):
     return [a[10 * r:10 * r + 10] for r in range(4)]
 
 
-def rand_limbs(rng, bound_bits):
-    """Limbs below 2^bound_bits (even) / 2^(bound_bits - 1) (odd): odd limbs are 25 bits wide, so
-    every value the formulas form (sums, differences with 2p or 4p) keeps them half as large."""
-    return [rng.randrange(int(2 ** (bound_bits - (i & 1)))) for i in range(10)]
-
-
 def test_lp_mul_random_and_bounds(hc):
     rng = random.Random(3)
     h = A40()
     # operand widths the group formulas produce: LR products, sums of two (2^27.13), differences
     # with 2p (2^27.6) on either side, and the doubling's uncarried E (2^28.4) against H or F
-    combos = [(26.01, 26.01), (27.13, 27.13), (27.6, 27.6), (28.4, 27.13), (28.4, 26.01)]
+    combos = LP_MUL_COMBOS
     for it in range(600):
         fb, gb = combos[it % len(combos)]
         f = [rand_limbs(rng, fb) for _ in range(4)]
@@ -113,7 +113,7 @@ def test_lp_mul_dual_matches_lp_mul(hc):
     rng = random.Random(5)
     h, h2 = A40(), A40()
     for it in range(400):
-        fb, gb = [(26.01, 26.01), (27.13, 27.13), (27.6, 26.6)][it % 3]
+        fb, gb = LP_MUL_DUAL_COMBOS[it % 3]
         f = [rand_limbs(rng, fb) for _ in range(2)]
         g = [rand_limbs(rng, gb) for _ in range(2)]
         if it < 3:

@@ -1,7 +1,12 @@
 """The kernels' own arithmetic (indy-plenum_amd/csrc/*.h), compiled for the HOST with bound
 assertions enabled (tests/native/hostcheck.hip), against Python big integers, the oracle, the
-golden libsodium verdicts and libsodium itself. Same source as the GPU code, so a pass here means
-the GPU arithmetic is right up to compilation; tests/test_gpu_parity.py closes that gap."""
+golden libsodium verdicts and libsodium itself. A pass here proves the algorithms, the limb bounds
+and every line the host and device builds share. It does NOT prove the branches the headers take only
+under __HIP_DEVICE_COMPILE__ (fe_mul_pre / fe_sq's inline-asm product columns, dbl32, v_rcp_f32 and
+__all in sc_halfsize, sha512.h's alignbit / bitop3 / perm): the host build compiles the plain C on the
+other side of each switch. tests/test_gpu_devarith.py runs those branches on the GPU with the same edge
+inputs (tests/devarith_cases.py holds the shared vectors); tests/test_gpu_parity.py checks them end
+to end."""
 import ctypes
 import json
 import os
@@ -10,12 +15,14 @@ import subprocess
 
 import pytest
 
+from devarith_cases import (HALFSIZE_EDGES, L, LP_HALFSIZE_EDGES, N8L, NWIN16_EDGES, P, SC_CANONICAL_EDGES,  # noqa: F401
+                            SC_MUL_EDGES, SC_RECODE_ANY_EDGES, SC_RECODE_EDGES, SC_REDUCE_EDGES, TOBYTES_EDGES,
+                            TOBYTES_UNNORMALISED, W, WIDE_RECODE_TOO_LARGE, from_limbs, max_mul_input, to_limbs,
+                            wide_f_operand_pairs, wide_recode_edges)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "native", "libhostcheck.so")
-P = 2 ** 255 - 19
-L = 2 ** 252 + 27742317777372353535851937790883648493
-W = [26 if i % 2 == 0 else 25 for i in range(10)]
 A10 = ctypes.c_uint32 * 10
 
 
@@ -38,26 +45,6 @@ def hc():
     return ctypes.CDLL(LIB)
 
 
-def to_limbs(x):
-    out, off = [], 0
-    for w in W:
-        out.append((x >> off) & ((1 << w) - 1))
-        off += w
-    return out
-
-
-def from_limbs(lim):
-    v, off = 0, 0
-    for i, w in enumerate(W):
-        v += lim[i] << off
-        off += w
-    return v
-
-
-def max_mul_input():
-    return [3 * (1 << w) + (1 << 18) - 1 for w in W]
-
-
 def test_fe_mul_sq_random_and_extreme(hc):
     rng = random.Random(7)
     cases = [(max_mul_input(), max_mul_input())]
@@ -78,12 +65,8 @@ def test_fe_mul_wide_f_operand_bounds(hc):
     """The f side of fe_mul may be an uncarried value (ge_p2_dbl's r.X = S + 4p - r.Y, the niels
     F = 2Z + 2p - c): at those maxima, against the largest g each call site passes, every
     product column still fits 64 bits (the bounds build asserts it) and the product is right."""
-    R = [(1 << w) + (1 << 17) - 1 for w in W]                       # reduced output bound
-    G3 = [3 * (1 << w) + (1 << 18) - 1 for w in W]                  # sum / difference of R values
-    dbl_rx = [R[i] + (0xFFFFFB4 if i == 0 else (0x7FFFFFC if i % 2 else 0xFFFFFFC)) for i in range(10)]
-    niels_f = [2 * R[i] + (0x7FFFFDA if i == 0 else (0x3FFFFFE if i % 2 else 0x7FFFFFE)) for i in range(10)]
     h = A10()
-    for f, g in [(dbl_rx, R), (niels_f, G3), (G3, G3)]:
+    for f, g in wide_f_operand_pairs():  # (dbl_rx, R), (niels_f, G3), (G3, G3)
         hc.hc_fe_mul(h, A10(*f), A10(*g))
         assert from_limbs(list(h)) % P == from_limbs(f) * from_limbs(g) % P
         assert all(v < (1 << w) + (1 << 19) for v, w in zip(h, W))
@@ -91,10 +74,10 @@ def test_fe_mul_wide_f_operand_bounds(hc):
 
 def test_fe_tobytes_canonical_edges(hc):
     s = ctypes.create_string_buffer(32)
-    for v in [0, 1, 18, 19, P - 1, P, P + 1, P + 18, 2 ** 255 - 1]:
+    for v in TOBYTES_EDGES:
         hc.hc_fe_tobytes(s, A10(*to_limbs(v)))
         assert int.from_bytes(s.raw, "little") == v % P, v
-    for v in [P, 2 * P - 1, 2 * P, 2 * P + 7, 3 * P]:  # non-normalised representations
+    for v in TOBYTES_UNNORMALISED:  # non-normalised representations
         lim = to_limbs(v % 2 ** 255)
         lim[0] += v - from_limbs(lim)
         if lim[0] < 2 ** 31:
@@ -116,13 +99,12 @@ def test_fe_invert_pow(hc):
 def test_scalar_reduce_canonical_recode(hc):
     rng = random.Random(9)
     r = ctypes.create_string_buffer(32)
-    edges = [0, 2 ** 512 - 1, L, L - 1, L + 1, 2 ** 256, 2 ** 252, 2 * L, L * 2 ** 259, 2 ** 511]
-    for x in edges + [rng.getrandbits(512) for _ in range(5000)]:
+    for x in SC_REDUCE_EDGES + [rng.getrandbits(512) for _ in range(5000)]:
         hc.hc_sc_reduce64(r, x.to_bytes(64, "little"))
         assert int.from_bytes(r.raw, "little") == x % L
-    for s in [L, L - 1, L + 1, 0, 2 ** 256 - 1, 2 ** 253] + [rng.getrandbits(256) for _ in range(2000)]:
+    for s in SC_CANONICAL_EDGES + [rng.getrandbits(256) for _ in range(2000)]:
         assert hc.hc_sc_is_canonical(s.to_bytes(32, "little")) == (s < L)
-    for a in [0, 1, L - 1, 2 ** 252] + [rng.randrange(L) for _ in range(2000)]:
+    for a in SC_RECODE_EDGES + [rng.randrange(L) for _ in range(2000)]:
         hc.hc_sc_recode16(r, a.to_bytes(32, "little"))
         nib = [(r.raw[i // 2] >> (4 * (i % 2))) & 15 for i in range(64)]
         assert sum((n - 16 if n >= 8 else n) * 16 ** i for i, n in enumerate(nib)) == a
@@ -134,7 +116,7 @@ def test_scalar_reduce_canonical_recode(hc):
         assert sum((h - 65536 if h >= 32768 else h) * 65536 ** i for i, h in enumerate(hw)) == a
     # the closed-form recodings ((a + M) xor M) against the digit-by-digit carry loop they replaced,
     # for any 256-bit input (the top digit unreduced)
-    for a in [2 ** 256 - 1, 2 ** 255, 0x7777777777777777] + [rng.getrandbits(256) for _ in range(2000)]:
+    for a in SC_RECODE_ANY_EDGES + [rng.getrandbits(256) for _ in range(2000)]:
         for w, fn in ((4, hc.hc_sc_recode16), (8, hc.hc_sc_recode256), (16, hc.hc_sc_recode65536)):
             out, carry, n = 0, 0, 256 // w
             for i in range(n):
@@ -259,7 +241,7 @@ def test_wide_comb_recode(hc):
     rng = random.Random(31)
     for w, npos in ((16, 16), (20, 13), (22, 12), (24, 11)):
         top = 253 - w * (npos - 1)
-        vals = [0, 1, L - 1, L, 2 ** 252, 2 ** 253 - 1, (1 << (w - 1)), (1 << w) - 1] + \
+        vals = wide_recode_edges(w) + \
                [rng.randrange(L) for _ in range(1500)] + [rng.getrandbits(253) for _ in range(500)]
         for s in vals:
             d = _recode_w(hc, w, s)
@@ -267,7 +249,7 @@ def test_wide_comb_recode(hc):
             assert sum(x << (w * j) for j, x in enumerate(d)) == s, (w, s)
             assert all(-(1 << (w - 1)) <= x < (1 << (w - 1)) for x in d[:-1])
             assert 0 <= d[-1] <= (1 << top)
-        for s in (2 ** 253, 2 ** 255 + 12345, 2 ** 256 - 1):
+        for s in WIDE_RECODE_TOO_LARGE:
             d = _recode_w(hc, w, s)
             assert all(-(1 << (w - 1)) <= x < (1 << (w - 1)) for x in d[:-1]) and 0 <= d[-1] <= (1 << top)
 
@@ -372,9 +354,6 @@ def test_comb_sparse_fill_matches_full_fill(hc, oracle):
             assert hc.hc_comb_fill_sparse_check(pk, ctypes.c_uint32(j * 7 + 1), ctypes.c_double(density)) == 0, density
 
 
-N8L = 8 * L
-
-
 def _halfsize(hc, k):
     k1 = ctypes.create_string_buffer(32)
     k2 = ctypes.create_string_buffer(32)
@@ -389,9 +368,7 @@ def test_halfsize_split_invariants(hc):
     |k1| < 2^128 and k2 < 2^160 unless the (k, 1) fallback was taken; random scalars never fall back,
     and the edge scalars (0, tiny, 2^128 boundary, huge first quotients, L - 1) stay exact."""
     rng = random.Random(41)
-    edges = [0, 1, 2, 3, 2 ** 64, 2 ** 127, 2 ** 128 - 1, 2 ** 128, 2 ** 128 + 1, L - 1, L - 2,
-             N8L // 3, N8L // 2 ** 20, N8L // 2 ** 31, N8L // 2 ** 32, N8L // 2 ** 33, N8L // 2 ** 60,
-             2 ** 200, 2 ** 252, (2 ** 252) | 1]
+    edges = HALFSIZE_EDGES
     fallbacks, bits = 0, []
     for k in edges + [rng.randrange(L) for _ in range(20000)]:
         k1, k2, fb = _halfsize(hc, k)
@@ -410,7 +387,7 @@ def test_halfsize_split_invariants(hc):
 def test_sc_mul_mod_l(hc):
     rng = random.Random(42)
     r = ctypes.create_string_buffer(32)
-    for a, b in [(0, 0), (L - 1, L - 1), (2 ** 256 - 1, 2 ** 256 - 1), (1, L + 5)] + \
+    for a, b in SC_MUL_EDGES + \
             [(rng.getrandbits(256), rng.getrandbits(256)) for _ in range(3000)]:
         hc.hc_sc_mul(r, a.to_bytes(32, "little"), b.to_bytes(32, "little"))
         assert int.from_bytes(r.raw, "little") == a * b % L
@@ -418,7 +395,7 @@ def test_sc_mul_mod_l(hc):
 
 def test_nwin16(hc):
     rng = random.Random(43)
-    for a in [0, 1, 7, 8, 15, 16, 2 ** 128 - 1, 2 ** 131, L - 1] + [rng.randrange(L) for _ in range(500)]:
+    for a in NWIN16_EDGES + [rng.randrange(L) for _ in range(500)]:
         d, c = [], 0
         for i in range(64):
             v = ((a >> (4 * i)) & 15) + c
@@ -454,7 +431,7 @@ def test_lp_halfsize_matches_per_lane_split(hc):
     """lp_halfsize (the latency path's limb-parallel split: the multiword state across the lanes of
     a wave, matrix updates as lane products + DPP carry passes) gives exactly sc_halfsize's split."""
     rng = random.Random(45)
-    edges = [0, 1, 2 ** 64, 2 ** 128 - 1, 2 ** 128, 2 ** 131 + 5, L - 1, N8L // 3, N8L // 2 ** 33, 2 ** 252]
+    edges = LP_HALFSIZE_EDGES
     for k in edges + [rng.randrange(L) for _ in range(3000)] + [rng.getrandbits(253) for _ in range(200)]:
         b = k.to_bytes(32, "little")
         outs = []
