@@ -630,6 +630,36 @@ int pv_stream_sync(void* stream);
  *                           round trip (alignment and readability as pv_merkle_append_batch_device;
  *                           d_final_root and d_proof 16-byte aligned). A reply whose end is not in
  *                           (tree_size, tree_size + n] gets status 6 and verdict 0.
+ *   pv_merkle_prove_plan    host-only arithmetic for q proof queries against a hash store of n_leaves leaves.
+ *                           Query i is (kind[i], a[i], b[i]):
+ *                             PV_MK_Q_INCLUSION 0    CompactMerkleTree.inclusion_proof(a, b) (ledger/
+ *                                                    compact_merkle_tree.py:217-219 over _path :237-249), the
+ *                                                    audit path of leaf a in the tree of b leaves that
+ *                                                    Ledger.merkleInfo / auditProof (ledger/ledger.py:196-217)
+ *                                                    send with a read reply; 0 <= a < b <= n_leaves
+ *                             PV_MK_Q_CONSISTENCY 1  consistency_proof(a, b) (:213-215 over _subproof :221-235),
+ *                                                    what plenum/server/catchup/seeder_service.py:85-150 builds
+ *                                                    per CatchupReq and LedgerStatus; 1 <= a <= b <= n_leaves,
+ *                                                    empty when a == b
+ *                             PV_MK_Q_ROOT 2         merkle_tree_hash(0, b) (:198-211), one hash; 1 <= b <=
+ *                                                    n_leaves, a ignored
+ *                           out_off[q + 1] receives the prefix sum of the proofs' lengths in 32-byte units
+ *                           (out_off[0] = 0; a proof has at most 49 hashes), status[i] (may be NULL) 0, or 1
+ *                           for a query outside those ranges or of an unknown kind, whose length is 0.
+ *   pv_merkle_prove_batch   the q proofs themselves, byte for byte what the reference's methods return: proof
+ *                           i at out[32 out_off[i] : 32 out_off[i+1]], out holding out_off[q] hashes. The store
+ *                           is leaf_hash[32 n_leaves] (the writeLeaf values by 0-based leaf index) and
+ *                           node_hash[32 (n_leaves - popcount(n_leaves))] (the writeNode hashes in hash-store
+ *                           order), exactly what pv_merkle_append_batch writes. Host buffers, synchronous, GPU
+ *                           or C++ host path (pv_merkle_path; AUTO from PV_MERKLE_AUTO_MIN_PROVE queries); works
+ *                           without a device and never returns PV_ERR_NOT_INIT. status[i]: 0 written, 1 out of
+ *                           range (nothing written), 2 the query's own length differs from the room of its
+ *                           slot, out_off[i+1] - out_off[i], or the slot ends beyond out_off[q]: nothing is
+ *                           written, so a wrong out_off never makes a write land outside out.
+ *   pv_merkle_prove_batch_device
+ *                           the same on device buffers (16-byte aligned hash arrays), enqueued on `stream`
+ *                           without synchronising, no workspace: a device-resident ledger appends, proves and
+ *                           verifies without a hash leaving device memory. d_out_off is the plan's.
  *   pv_merkle_chunk         leaves (or proofs) per device pass; larger batches are chained chunk by
  *                           chunk through the frontier. 0 restores the default, 1,048,576; at most
  *                           PV_MERKLE_CHUNK_MAX (the upper levels of a chunk run in one workgroup).
@@ -639,8 +669,9 @@ int pv_stream_sync(void* stream);
  *                           PV_MERKLE_AUTO_MIN_VERIFY proofs for the check): the smallest measured sizes
  *                           at which the device path won by more than the run-to-run spread on one
  *                           MI355X; PV_MERKLE_AUTO_MIN_CONSISTENCY proofs for the consistency
- *                           check, measured the same way.
- * Bad arguments (decreasing offsets, tree_size + n >= 2^48, a tree size >= 2^48, no frontier for tree_size
+ *                           check and PV_MERKLE_AUTO_MIN_PROVE queries for proof generation, measured the
+ *                           same way.
+ * Bad arguments (decreasing offsets, a store of 2^48 or more leaves, 2^32 or more queries, tree_size + n >= 2^48, a tree size >= 2^48, no frontier for tree_size
  * > 0, path without path_off, 2^32 or more proofs or replies, reply ends out of order or range) return
  * PV_ERR_ARG before anything is launched. */
 #define PV_MERKLE_AUTO 0
@@ -650,6 +681,7 @@ int pv_stream_sync(void* stream);
 #define PV_MERKLE_AUTO_MIN_PROOFS 1024 /* appends with per-leaf roots or audit paths */
 #define PV_MERKLE_AUTO_MIN_VERIFY 512  /* the proof check */
 #define PV_MERKLE_AUTO_MIN_CONSISTENCY 256 /* the consistency check */
+#define PV_MERKLE_AUTO_MIN_PROVE 32768 /* proof generation: the host-buffer call uploads the whole store */
 #define PV_MERKLE_CHUNK 1048576
 #define PV_MERKLE_CHUNK_MAX 16777216 /* 2^24: the largest chunk pv_merkle_chunk accepts */
 typedef struct {
@@ -690,6 +722,19 @@ int pv_merkle_catchup_batch_device(uint64_t tree_size, const uint8_t* d_frontier
                                    uint64_t final_size, const uint8_t* d_final_root, const uint8_t* d_proof,
                                    const uint64_t* d_proof_off, const PvMerkleOut* d_out, uint8_t* d_status,
                                    uint64_t* d_verdict_words, void* stream);
+#ifndef PV_MK_Q_INCLUSION
+#define PV_MK_Q_INCLUSION 0
+#define PV_MK_Q_CONSISTENCY 1
+#define PV_MK_Q_ROOT 2
+#endif
+int pv_merkle_prove_plan(uint64_t n_leaves, const uint8_t* kind, const uint64_t* a, const uint64_t* b, uint64_t q,
+                         uint64_t* out_off, uint8_t* status);
+int pv_merkle_prove_batch(const uint8_t* leaf_hash, uint64_t n_leaves, const uint8_t* node_hash, const uint8_t* kind,
+                          const uint64_t* a, const uint64_t* b, uint64_t q, const uint64_t* out_off, uint8_t* out,
+                          uint8_t* status);
+int pv_merkle_prove_batch_device(const uint8_t* d_leaf_hash, uint64_t n_leaves, const uint8_t* d_node_hash,
+                                 const uint8_t* d_kind, const uint64_t* d_a, const uint64_t* d_b, uint64_t q,
+                                 const uint64_t* d_out_off, uint8_t* d_out, uint8_t* d_status, void* stream);
 int pv_merkle_chunk(uint64_t leaves);
 int pv_merkle_path(int mode);
 

@@ -1,8 +1,9 @@
 // Index arithmetic of the batched ledger Merkle append (ledger/compact_merkle_tree.py:95-160 append /
 // _push_subtree, :81-88 root_hash), of the audit-path check (ledger/merkle_verifier.py:155-181) and of the
-// consistency check (:23-153). One source for the kernels (pv_merkle.hip), the host path (merkle_host.cpp)
-// and the host-compiled check libraries (tests/native/merklecheck.hip, conscheck.hip); no hashing here,
-// hashes pass through template hooks.
+// consistency check (:23-153), and of proof generation from a hash store (ledger/compact_merkle_tree.py:
+// 198-249). One source for the kernels (pv_merkle.hip), the host path (merkle_host.cpp) and the check
+// libraries (tests/native/merklecheck.hip, conscheck.hip, provecheck.hip); no hashing here, hashes pass
+// through template hooks.
 //
 // A tree is its size s and its frontier: one hash per set bit of s, largest subtree first. A batch
 // appends n leaves with absolute indices s .. s + n - 1. The node of height h >= 1 "completed at size
@@ -183,6 +184,125 @@ PV_HD uint32_t pv_merkle_consistency_check(uint64_t old_size, uint64_t new_size,
     if (!eq(new_acc, new_root)) return PV_MK_NEW_DIFFERS;
     if (!eq(old_acc, old_root)) return PV_MK_OLD_DIFFERS;
     return PV_MK_CONSISTENT;
+}
+
+// ---- proof generation from a hash store (ledger/compact_merkle_tree.py:198-249 merkle_tree_hash,
+// consistency_proof, inclusion_proof, _subproof, _path), bottom-up and without recursion -----------------------
+// A query (kind, a, b) against a store of n leaves: leaf hashes by 0-based index, node hashes by
+// pv_merkle_node_pos. Every hash of a proof is an aligned full subtree (one gather) or the ragged range
+// [x, b) that ends at the query's own b: the right-to-left fold of the full subtrees of b below the level
+// it is asked at, so all ragged hashes of one query are prefixes of one fold.
+#ifndef PV_MK_Q_INCLUSION  // as include/plenum_verify.h
+#define PV_MK_Q_INCLUSION 0    // inclusion_proof(a, b) = PATH(a, D[0:b]), 0 <= a < b <= n
+#define PV_MK_Q_CONSISTENCY 1  // consistency_proof(a, b) = PROOF(a, D[0:b]), 1 <= a <= b <= n, empty when a == b
+#define PV_MK_Q_ROOT 2         // merkle_tree_hash(0, b), 1 <= b <= n, one hash, a ignored
+#endif
+enum : uint32_t { PV_MK_PROVED = 0, PV_MK_Q_RANGE = 1, PV_MK_Q_ROOM = 2 };  // status of a query
+enum : uint32_t { PV_MK_E_LEAF = 0, PV_MK_E_NODE = 1, PV_MK_E_RAGGED = 2 };
+struct PvMerkleElem {
+    uint32_t tag;  // PV_MK_E_LEAF: leaf hash idx; PV_MK_E_NODE: node store position idx;
+    uint64_t idx;  // PV_MK_E_RAGGED: the fold of the full subtrees of b below level idx
+};
+
+PV_HD bool pv_merkle_query_valid(uint32_t kind, uint64_t a, uint64_t b, uint64_t n) {
+    if (b > n || b == 0) return false;
+    return kind == PV_MK_Q_INCLUSION ? a < b : kind == PV_MK_Q_CONSISTENCY ? (a >= 1 && a <= b) : kind == PV_MK_Q_ROOT;
+}
+
+// From node `node` of level l0 up to the root of the tree of b leaves: at every level the sibling, which
+// covers [sib << l, min((sib + 1) << l, b)) and does not exist when sib << l >= b. emit(k, elem) receives
+// hash k of the proof; returns the k after the last one.
+template <class Emit>
+PV_HD uint32_t pv_merkle_sibling_walk(uint64_t node, uint32_t l0, uint64_t b, uint32_t k, const Emit& emit) {
+    for (uint32_t l = l0; ((b - 1) >> l) != 0; l++, node >>= 1) {
+        const uint64_t sib = node ^ 1;
+        if ((sib << l) >= b) continue;
+        const uint64_t end = (sib + 1) << l;
+        if (end > b) emit(k++, PvMerkleElem{PV_MK_E_RAGGED, l});
+        else if (l == 0) emit(k++, PvMerkleElem{PV_MK_E_LEAF, sib});
+        else emit(k++, PvMerkleElem{PV_MK_E_NODE, pv_merkle_node_pos(end, l)});
+    }
+    return k;
+}
+
+// The proof of a valid query, hash by hash in the reference's order; returns its length (at most
+// PV_MERKLE_MAX_BITS + 1). A consistency proof starts from the largest aligned subtree that ends at a,
+// which is itself the first hash unless a is a power of two (the old root, which the verifier has).
+template <class Emit>
+PV_HD uint32_t pv_merkle_prove_walk(uint32_t kind, uint64_t a, uint64_t b, const Emit& emit) {
+    if (kind == PV_MK_Q_ROOT) {
+        emit(0, PvMerkleElem{PV_MK_E_RAGGED, PV_MERKLE_MAX_BITS});
+        return 1;
+    }
+    if (kind == PV_MK_Q_INCLUSION) return pv_merkle_sibling_walk(a, 0, b, 0, emit);
+    if (a == b) return 0;
+    const uint32_t l = (uint32_t)__builtin_ctzll(a);
+    const uint64_t node = (a >> l) - 1;
+    uint32_t k = 0;
+    if (node) {
+        if (l == 0) emit(k++, PvMerkleElem{PV_MK_E_LEAF, a - 1});
+        else emit(k++, PvMerkleElem{PV_MK_E_NODE, pv_merkle_node_pos(a, l)});
+    }
+    return pv_merkle_sibling_walk(node, l, b, k, emit);
+}
+
+// Hashes in the proof of a valid query, without a store.
+PV_HD uint32_t pv_merkle_prove_len(uint32_t kind, uint64_t a, uint64_t b) {
+    return pv_merkle_prove_walk(kind, a, b, [](uint32_t, const PvMerkleElem&) {});
+}
+
+// The ragged hashes of one query, after its walk. `levels` has bit l set for every ragged hash (asked for at
+// level l) and `slots` bit k for its place in the proof; both grow along the walk, so their i-th set bits
+// belong together. One fold over the full subtrees of b from the smallest up, acc = hash_children(larger,
+// acc): after the subtree of bit j the fold is the ragged hash of every level in (j, next set bit of b], and
+// no two ragged hashes of one proof share such a span (they would cover the same leaves). At most popcount(b)
+// - 1 hash_children, none when the query has no ragged hash. get(elem, out) loads a leaf or node hash,
+// put(k, acc) stores hash k of the proof. The fold is apart from the walk so that the lanes of a wave,
+// which meet their ragged hashes at different levels, hash in step: one subtree of b per iteration.
+template <class T, class Get, class Hash, class Put>
+PV_HD void pv_merkle_ragged_fold(uint64_t b, uint64_t levels, uint64_t slots, const Get& get, const Hash& hash,
+                                 const Put& put) {
+    T acc;
+    bool have = false;
+    for (uint64_t rest = b; levels && rest;) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(rest);
+        const uint64_t u = ((b >> (j + 1)) << (j + 1)) + (1ull << j);  // the full subtree of bit j ends here
+        const PvMerkleElem e = j ? PvMerkleElem{PV_MK_E_NODE, pv_merkle_node_pos(u, j)} : PvMerkleElem{PV_MK_E_LEAF, u - 1};
+        if (have) {
+            T larger, next;
+            get(e, larger);
+            hash(next, larger, acc);
+            acc = next;
+        } else {
+            get(e, acc);
+            have = true;
+        }
+        rest &= rest - 1;
+        const uint32_t upto = rest ? (uint32_t)__builtin_ctzll(rest) : 63;
+        while (levels && (uint32_t)__builtin_ctzll(levels) <= upto) {
+            put((uint32_t)__builtin_ctzll(slots), acc);
+            levels &= levels - 1;
+            slots &= slots - 1;
+        }
+    }
+}
+
+// A whole query: the walk stores the aligned hashes through copy(k, elem) and notes the ragged ones, the fold
+// follows. Returns the proof's length.
+template <class T, class Copy, class Get, class Hash, class Put>
+PV_HD uint32_t pv_merkle_prove(uint32_t kind, uint64_t a, uint64_t b, const Copy& copy, const Get& get, const Hash& hash,
+                               const Put& put) {
+    uint64_t levels = 0, slots = 0;
+    const uint32_t len = pv_merkle_prove_walk(kind, a, b, [&](uint32_t k, const PvMerkleElem& e) {
+        if (e.tag == PV_MK_E_RAGGED) {
+            levels |= 1ull << e.idx;
+            slots |= 1ull << k;
+        } else {
+            copy(k, e);
+        }
+    });
+    pv_merkle_ragged_fold<T>(b, levels, slots, get, hash, put);
+    return len;
 }
 
 // ---- the level kernel's tiling (absolute indices, so node alignment is the tree's) ----------------

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <thread>
 #include <vector>
 
@@ -25,9 +26,9 @@ constexpr uint64_t MK_PER_THREAD = 2048;  // below this much work a thread is no
 
 // f(lo, hi) over [0, n) split over up to MK_THREADS threads
 template <class F>
-void parallel_for(uint64_t n, const F& f) {
+void parallel_for(uint64_t n, const F& f, unsigned max_threads = MK_THREADS) {
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const uint64_t t = std::min<uint64_t>(std::min(MK_THREADS, hw), (n + MK_PER_THREAD - 1) / MK_PER_THREAD);
+    const uint64_t t = std::min<uint64_t>(std::min(max_threads, hw), (n + MK_PER_THREAD - 1) / MK_PER_THREAD);
     if (t <= 1) {
         if (n) f(0, n);
         return;
@@ -226,4 +227,46 @@ void pv_merkle_host_catchup(uint64_t s, const uint8_t* frontier, const uint8_t* 
         }
     });
     pack_verdicts(ok, verdict_bits);
+}
+
+// One query at a time: the walker of merkle_core.h gathers aligned subtrees from the store, one fold follows
+// for the ragged ones. A query whose length is not its slot's room writes nothing (status 2).
+void pv_merkle_host_prove(const uint8_t* leaf_hash, uint64_t n_leaves, const uint8_t* node_hash, const uint8_t* kind,
+                          const uint64_t* a, const uint64_t* b, uint64_t q, const uint64_t* out_off, uint8_t* out,
+                          uint8_t* status, unsigned threads) {
+    const H32* leaf = reinterpret_cast<const H32*>(leaf_hash);
+    const H32* node = reinterpret_cast<const H32*>(node_hash);
+    const uint64_t out_end = out_off[q];
+    auto get = [&](const PvMerkleElem& e, H32& o) { o = e.tag == PV_MK_E_LEAF ? leaf[e.idx] : node[e.idx]; };
+    auto hash = [](H32& o, const H32& l, const H32& r) { hash_children(o, l, r); };
+    parallel_for(q, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            if (!pv_merkle_query_valid(kind[i], a[i], b[i], n_leaves)) {
+                status[i] = PV_MK_Q_RANGE;
+                continue;
+            }
+            if (out_off[i + 1] - out_off[i] != pv_merkle_prove_len(kind[i], a[i], b[i]) || out_off[i + 1] > out_end) {
+                status[i] = PV_MK_Q_ROOM;
+                continue;
+            }
+            H32* dst = reinterpret_cast<H32*>(out) + out_off[i];
+            pv_merkle_prove<H32>(
+                kind[i], a[i], b[i], [&](uint32_t k, const PvMerkleElem& e) { get(e, dst[k]); }, get, hash,
+                [&](uint32_t k, const H32& acc) { dst[k] = acc; });
+            status[i] = PV_MK_PROVED;
+        }
+    }, threads ? threads : MK_THREADS);
+}
+
+uint64_t pv_merkle_host_prove_unwritten(uint64_t n_leaves, const uint8_t* kind, const uint64_t* a, const uint64_t* b, uint64_t q,
+                                        const uint64_t* out_off) {
+    std::atomic<uint64_t> bad{0};
+    parallel_for(q, [&](uint64_t lo, uint64_t hi) {
+        uint64_t n = 0;
+        for (uint64_t i = lo; i < hi; i++)
+            n += !pv_merkle_query_valid(kind[i], a[i], b[i], n_leaves) ||
+                 out_off[i + 1] - out_off[i] != pv_merkle_prove_len(kind[i], a[i], b[i]);
+        bad += n;
+    });
+    return bad.load();
 }

@@ -20,7 +20,9 @@
 //                               that size folded from the chunk's view, then the consistency walk against
 //                               the call's final size and root.
 // and pv_merkle_verify_kernel / pv_merkle_consistency_kernel (MerkleVerifier.verify_tree_consistency,
-// ledger/merkle_verifier.py:23-153), one lane per proof. Launches per chunk: at most six, whatever n is;
+// ledger/merkle_verifier.py:23-153), one lane per proof, and pv_merkle_prove_kernel (inclusion_proof,
+// consistency_proof and merkle_tree_hash from a hash store, ledger/compact_merkle_tree.py:198-249), one lane
+// per query. Launches per chunk: at most six, whatever n is;
 // no host round trip between them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -308,6 +310,50 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_catchup_kernel(MkView v, M
     if ((threadIdx.x & 63) == 0 && word) atomicOr(reinterpret_cast<unsigned long long*>(q.verdict + (r >> 6)), word);
 }
 
+// The queries of a proof generation (merkle_core.h): one lane per query, the store's leaf hashes by leaf
+// index and node hashes by store position. Proof i goes to out[8 out_off[i]...] (32-bit words), and only
+// if its own length is the room of its slot and the slot ends at or before *out_end.
+struct MkProve {
+    const uint32_t* leaf;
+    const uint32_t* node;
+    uint64_t n_leaves;
+    const uint8_t* kind;
+    const uint64_t* a;
+    const uint64_t* b;
+    const uint64_t* out_off;
+    const uint64_t* out_end;
+    uint32_t* out;
+    uint8_t* status;
+};
+
+// Aligned subtrees are 32-byte gathers made along the walk; the ragged ones are prefixes of one fold kept in
+// registers, run after the walk so that the lanes of a wave hash in step (with the fold inside the walk each
+// lane hashed at its own levels, and 4 of 64 lanes were active per instruction on mixed queries). Lanes still
+// diverge on the fold length.
+__global__ __launch_bounds__(MK_BLOCK) void pv_merkle_prove_kernel(MkProve p, uint64_t q) {
+    const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+    if (i >= q) return;
+    const uint32_t kind = p.kind[i];
+    const uint64_t a = p.a[i], b = p.b[i];
+    if (!pv_merkle_query_valid(kind, a, b, p.n_leaves)) {
+        p.status[i] = PV_MK_Q_RANGE;
+        return;
+    }
+    const uint64_t at = p.out_off[i], end = p.out_off[i + 1];
+    if (end - at != pv_merkle_prove_len(kind, a, b) || end > *p.out_end) {
+        p.status[i] = PV_MK_Q_ROOM;
+        return;
+    }
+    uint32_t* dst = p.out + 8 * at;
+    auto src = [&](const PvMerkleElem& e) { return (e.tag == PV_MK_E_LEAF ? p.leaf : p.node) + 8 * e.idx; };
+    pv_merkle_prove<MkHash>(
+        kind, a, b, [&](uint32_t k, const PvMerkleElem& e) { mk_copy(dst + 8 * k, src(e)); },
+        [&](const PvMerkleElem& e, MkHash& o) { o = mk_load(src(e)); },
+        [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); },
+        [&](uint32_t k, const MkHash& acc) { mk_store(dst + 8 * k, acc); });
+    p.status[i] = PV_MK_PROVED;
+}
+
 // --------------------------------------------------------------------------------------------- host
 
 // The Merkle code's own workspace: allocated on first use (an engine that never hashes a leaf holds
@@ -552,6 +598,16 @@ int mk_consistency_enqueue(const uint64_t* d_old_size, const uint64_t* d_new_siz
     return PV_OK;
 }
 
+int mk_prove_enqueue(const MkProve& p, uint64_t q, hipStream_t stream) {
+    for (uint64_t c0 = 0; c0 < q; c0 += g_mk_chunk) {
+        const uint64_t m = std::min<uint64_t>(g_mk_chunk, q - c0);
+        MkProve c = p;
+        c.kind += c0, c.a += c0, c.b += c0, c.out_off += c0, c.status += c0;  // offsets are absolute: out stays
+        PV_LAUNCH(pv_merkle_prove_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0, stream, c, m);
+    }
+    return PV_OK;
+}
+
 // the append arguments every append-like entry checks
 int mk_check_append_args(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
                          const std::string& who) {
@@ -775,6 +831,81 @@ int pv_merkle_verify_consistency_batch_device(const uint64_t* d_old_size, const 
     std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
     return mk_consistency_enqueue(d_old_size, d_new_size, d_old_root, d_new_root, d_proof, d_proof_off, n, d_status,
                                   d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+}
+
+int pv_merkle_prove_plan(uint64_t n_leaves, const uint8_t* kind, const uint64_t* a, const uint64_t* b, uint64_t q,
+                         uint64_t* out_off, uint8_t* status) {
+    const char* who = "pv_merkle_prove_plan";
+    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, std::string(who) + ": the store must stay below 2^48 leaves");
+    if (q >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 queries");
+    if (!out_off || (q && (!kind || !a || !b))) return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
+    out_off[0] = 0;
+    for (uint64_t i = 0; i < q; i++) {
+        const bool ok = pv_merkle_query_valid(kind[i], a[i], b[i], n_leaves);
+        out_off[i + 1] = out_off[i] + (ok ? pv_merkle_prove_len(kind[i], a[i], b[i]) : 0);
+        if (status) status[i] = ok ? PV_MK_PROVED : PV_MK_Q_RANGE;
+    }
+    return PV_OK;
+}
+
+int pv_merkle_prove_batch(const uint8_t* leaf_hash, uint64_t n_leaves, const uint8_t* node_hash, const uint8_t* kind,
+                          const uint64_t* a, const uint64_t* b, uint64_t q, const uint64_t* out_off, uint8_t* out,
+                          uint8_t* status) {
+    const std::string who = "pv_merkle_prove_batch";
+    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": the store must stay below 2^48 leaves");
+    if (q >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 queries");
+    if (q == 0) return PV_OK;
+    const uint64_t n_nodes = pv_merkle_node_count(n_leaves);
+    if (!kind || !a || !b || !out_off || !status || (n_leaves && !leaf_hash) || (n_nodes && !node_hash))
+        return pv_fail(PV_ERR_ARG, who + ": null pointer");
+    if (!pv_offsets_monotone(out_off, q) || (!out && out_off[q] != out_off[0]))
+        return pv_fail(PV_ERR_ARG, who + ": out_off must be non-decreasing over an output array");
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    bool device;
+    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, q, PV_MERKLE_AUTO_MIN_PROVE, who.c_str(), &device);
+    if (rc) return rc;
+    if (!device) {
+        lk.unlock();
+        pv_merkle_host_prove(leaf_hash, n_leaves, node_hash, kind, a, b, q, out_off, out, status);
+        return PV_OK;
+    }
+    // a slot no lane writes keeps the caller's bytes: out goes up as well only when there is one
+    const bool all_written = out_off[0] == 0 && pv_merkle_host_prove_unwritten(n_leaves, kind, a, b, q, out_off) == 0;
+    const hipStream_t st = pv_engine_stream();
+    return mk_run(st, [&]() -> int {
+        PvStage& g = g_mk.stage;
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        // the store and the queries staged whole; out keeps its absolute offsets
+        const int i_leaf = g.in(leaf_hash, 32 * n_leaves), i_node = g.in(node_hash, 32 * n_nodes), i_kind = g.in(kind, q),
+                  i_a = g.in(a, 8 * q), i_b = g.in(b, 8 * q), i_off = g.in(out_off, 8 * (q + 1)),
+                  o_out = all_written ? g.out(out, 32 * out_off[q]) : g.inout(out, out, 32 * out_off[q]), o_status = g.out(status, q);
+        if ((rc = g.upload())) return rc;
+        const MkProve p{g.dev<const uint32_t>(i_leaf), g.dev<const uint32_t>(i_node), n_leaves, g.dev<const uint8_t>(i_kind),
+                        g.dev<const uint64_t>(i_a), g.dev<const uint64_t>(i_b), g.dev<const uint64_t>(i_off),
+                        g.dev<const uint64_t>(i_off) + q, g.dev<uint32_t>(o_out), g.dev<uint8_t>(o_status)};
+        if ((rc = mk_prove_enqueue(p, q, st))) return rc;
+        return g.download();
+    });
+}
+
+int pv_merkle_prove_batch_device(const uint8_t* d_leaf_hash, uint64_t n_leaves, const uint8_t* d_node_hash,
+                                 const uint8_t* d_kind, const uint64_t* d_a, const uint64_t* d_b, uint64_t q,
+                                 const uint64_t* d_out_off, uint8_t* d_out, uint8_t* d_status, void* stream) {
+    const std::string who = "pv_merkle_prove_batch_device";
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, who + ": call pv_init first");
+    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": the store must stay below 2^48 leaves");
+    if (q >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 queries");
+    if (q == 0) return PV_OK;
+    if (!d_kind || !d_a || !d_b || !d_out_off || !d_out || !d_status || (n_leaves && !d_leaf_hash) ||
+        (pv_merkle_node_count(n_leaves) && !d_node_hash))
+        return pv_fail(PV_ERR_ARG, who + ": null pointer");
+    if (mk_misaligned(d_leaf_hash) || mk_misaligned(d_node_hash) || mk_misaligned(d_out))
+        return pv_fail(PV_ERR_ARG, who + ": hash arrays must be 16-byte aligned");
+    const MkProve p{reinterpret_cast<const uint32_t*>(d_leaf_hash), reinterpret_cast<const uint32_t*>(d_node_hash), n_leaves,
+                    d_kind, d_a, d_b, d_out_off, d_out_off + q, reinterpret_cast<uint32_t*>(d_out), d_status};
+    std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
+    return mk_prove_enqueue(p, q, stream ? (hipStream_t)stream : pv_engine_stream());
 }
 
 int pv_merkle_catchup_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,

@@ -131,6 +131,12 @@ SIGNATURES = {
     "pv_merkle_catchup_batch_device": (ctypes.c_int, [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
                                        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64] +
                                        [ctypes.c_void_p] * 7),
+    "pv_merkle_prove_plan": (ctypes.c_int, [ctypes.c_uint64] + [ctypes.c_void_p] * 3 + [ctypes.c_uint64] +
+                             [ctypes.c_void_p] * 2),
+    "pv_merkle_prove_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + [ctypes.c_uint64] +
+                              [ctypes.c_void_p] * 3),
+    "pv_merkle_prove_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 +
+                                     [ctypes.c_uint64] + [ctypes.c_void_p] * 4),
     "pv_merkle_chunk": (ctypes.c_int, [ctypes.c_uint64]),
     "pv_merkle_path": (ctypes.c_int, [ctypes.c_int]),
     "pv_sha3_256_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
@@ -658,6 +664,9 @@ PV_MERKLE_AUTO_MIN_CONSISTENCY = 256  # the same for consistency proofs
 # status of a consistency check (csrc/merkle_core.h pv_merkle_consistency_check)
 (PV_MK_CONSISTENT, PV_MK_OLD_LARGER, PV_MK_CONS_TOO_SHORT, PV_MK_NEW_DIFFERS, PV_MK_OLD_DIFFERS, PV_MK_SAME_SIZE,
  PV_MK_REPLY_RANGE) = range(7)
+PV_MERKLE_AUTO_MIN_PROVE = 32768  # queries from which AUTO generates proofs on the device
+PV_MK_Q_INCLUSION, PV_MK_Q_CONSISTENCY, PV_MK_Q_ROOT = 0, 1, 2  # kinds of a proof query
+PV_MK_PROVED, PV_MK_Q_RANGE, PV_MK_Q_ROOM = 0, 1, 2  # status of a proof query
 PV_MERKLE_CHUNK = 1048576
 MERKLE_OUTPUTS = ("leaf_hash", "node_hash", "frontier", "root", "roots", "path")
 
@@ -831,6 +840,45 @@ def merkle_catchup(tree_size, frontier, blob, off, reply_end, final_size, final_
     res = merkle_append(tree_size, frontier, blob, off, want=want,
                         _catchup=(ends if R else np.zeros(1, np.uint64)[:0], int(final_size), root, pbuf, poff, status, bits))
     return np.unpackbits(bits, count=R, bitorder="little").view(bool), status[:R], res
+
+
+def merkle_prove_plan(n_leaves, kinds, a, b):
+    """pv_merkle_prove_plan: (out_off uint64[q + 1], status uint8[q]) of q queries against a store of n_leaves."""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+    q = kinds.shape[0]
+    if a.shape != (q,) or b.shape != (q,):
+        raise ValueError("merkle_prove: one kind, a and b per query")
+    out_off, status = np.zeros(q + 1, np.uint64), np.zeros(max(q, 1), np.uint8)
+    check(lib().pv_merkle_prove_plan(n_leaves, _ptr(kinds), _ptr(a), _ptr(b), q, _ptr(out_off), _ptr(status)),
+          "pv_merkle_prove_plan")
+    return out_off, status[:q]
+
+
+def merkle_prove(leaf_hashes, node_hashes, kinds, a, b):
+    """q proofs from a hash store as one pv_merkle_prove_batch. leaf_hashes / node_hashes: the store's two
+    sequences as contiguous bytes (32 per hash, anything with the buffer protocol; the node hashes of
+    len(leaf_hashes) / 32 leaves). Query i is (kinds[i], a[i], b[i]): PV_MK_Q_INCLUSION inclusion_proof(a, b),
+    PV_MK_Q_CONSISTENCY consistency_proof(a, b), PV_MK_Q_ROOT merkle_tree_hash(0, b). Returns (out_off uint64[q + 1],
+    hashes uint8[out_off[q], 32], status uint8[q]): proof i is hashes[out_off[i]:out_off[i + 1]]; status 1 marks a
+    query out of range, which has no hashes."""
+    leaf = np.frombuffer(leaf_hashes, dtype=np.uint8)
+    node = np.frombuffer(node_hashes, dtype=np.uint8)
+    n = leaf.size // 32
+    if leaf.size % 32 or node.size != 32 * (n - bin(n).count("1")):
+        raise ValueError("merkle_prove: the store must hold 32 n bytes of leaf hashes and 32 (n - popcount(n)) of node hashes")
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+    q = kinds.shape[0]
+    _merkle_device_ready(q, PV_MERKLE_AUTO_MIN_PROVE)
+    out_off, status = merkle_prove_plan(n, kinds, a, b)
+    out = np.zeros((int(out_off[q]), 32), np.uint8)
+    if q:
+        pad = np.zeros(32, np.uint8)
+        check(lib().pv_merkle_prove_batch(_ptr(leaf if leaf.size else pad), n, _ptr(node if node.size else pad), _ptr(kinds),
+                                          _ptr(a), _ptr(b), q, _ptr(out_off), _ptr(out if out.size else pad), _ptr(status)),
+              "pv_merkle_prove_batch")
+    return out_off, out, status
 
 
 # -------------------------------------------------------------------------------------- state trie

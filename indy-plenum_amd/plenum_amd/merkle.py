@@ -15,9 +15,16 @@ RFC 6962 definitions of MTH, PATH and PROOF. Added: one library call for a whole
     CompactMerkleTree.verify_catchup_replies(replies, final_size, final_root)
                                               a chain of CatchupReps checked as plenum/server/catchup/
                                               catchup_rep_service.py:375-426 checks them one by one
+    CompactMerkleTree.inclusion_proof_batch(pairs) / consistency_proof_batch(pairs) / merkle_tree_hash_batch(sizes)
+                                              the store-backed proofs and roots, many per call
+    CompactMerkleTree.audit_proofs(seq_nos, size=None)
+                                              Ledger.auditProof / merkleInfo (ledger/ledger.py:196-217) per read
+    CompactMerkleTree.catchup_proofs(reply_ends, catchup_till)
+                                              the seeder's consistency_proof(end, catchupTill) per CatchupReq
+                                              (plenum/server/catchup/seeder_service.py:85)
 
 The batch calls go through libplenum_verify (pv_merkle_append_batch, pv_merkle_verify_inclusion_batch,
-pv_merkle_verify_consistency_batch, pv_merkle_catchup_batch), which runs them on the GPU or, for small
+pv_merkle_verify_consistency_batch, pv_merkle_catchup_batch, pv_merkle_prove_batch), which runs them on the GPU or, for small
 batches and on a machine without one, in C++ on the host; the results are byte-identical to the
 sequential methods below. Not here: the persistent hash stores and the Ledger class."""
 import hashlib
@@ -107,7 +114,8 @@ class MemoryHashStore:
     HashStore / MemoryHashStore). writeNode takes the (size, height, hash) tuple a tree writes, or a bare
     hash, and keeps the hash. Nodes lie in completion order: the node of height h whose last leaf is
     leaf number u follows every node completed earlier, u - 1 - popcount(u - 1) of them, and the lower
-    nodes completed by the same leaf."""
+    nodes completed by the same leaf. Beside the two lists it keeps the same hashes as two contiguous byte
+    arrays (hash_arrays), so a batched proof call hands the library the whole store without joining it."""
 
     def __init__(self):
         self.reset()
@@ -119,9 +127,19 @@ class MemoryHashStore:
 
     def writeLeaf(self, leafHash):
         self._leafs.append(leafHash)
+        self._leaf_bytes += leafHash
 
     def writeNode(self, node):
-        self._nodes.append(node[2] if isinstance(node, tuple) else node)
+        node = node[2] if isinstance(node, tuple) else node
+        self._nodes.append(node)
+        self._node_bytes += node
+
+    def hash_arrays(self):
+        """(leaf hashes, node hashes) as two bytearrays, hash after hash in store order; None when a hash of
+        another length than 32 bytes was written (a hasher other than SHA-256)."""
+        if len(self._leaf_bytes) != 32 * len(self._leafs) or len(self._node_bytes) != 32 * len(self._nodes):
+            return None
+        return self._leaf_bytes, self._node_bytes
 
     def readLeaf(self, pos):
         return self._leafs[pos - 1]
@@ -173,6 +191,7 @@ class MemoryHashStore:
 
     def reset(self):
         self._nodes, self._leafs = [], []
+        self._leaf_bytes, self._node_bytes = bytearray(), bytearray()
         return True
 
     def open(self):
@@ -315,7 +334,7 @@ class CompactMerkleTree:
         new_tree.extend(new_leaves)
         return new_tree
 
-    # ---- store-backed hashes and proofs (RFC 6962 section 2.1 over readLeaf / readNode; not hot) -------
+    # ---- store-backed hashes and proofs (RFC 6962 section 2.1 over readLeaf / readNode, one at a time) ----
     def merkle_tree_hash_hex(self, start, end):
         return hexlify(self.merkle_tree_hash(start, end))
 
@@ -361,6 +380,95 @@ class CompactMerkleTree:
         if not whole:
             parts.append((lo, hi))
         return [self.merkle_tree_hash(a, b) for a, b in reversed(parts)]
+
+    # ---- the same proofs in batches: one library call (pv_merkle_prove_batch) over the store's arrays ----
+    def _store_arrays(self):
+        """(leaf bytes, node bytes) of the store for the library, or None (a hasher other than SHA-256, or a
+        store that cannot hand them over): the caller then loops over the sequential methods. A store without
+        hash_arrays is read once through readLeafs / readNodes."""
+        if self._hasher.hashfunc is not hashlib.sha256:
+            return None
+        store = self._store
+        if hasattr(store, "hash_arrays"):
+            return store.hash_arrays()
+        try:
+            n = store.leafCount
+            leafs = store.readLeafs(1, n)
+            nodes = [x[2] if isinstance(x, tuple) else x for x in store.readNodes(1, self.get_expected_node_count(n))]
+            leaf_bytes, node_bytes = b"".join(leafs), b"".join(nodes)
+        except Exception:  # whatever a foreign store raises: the sequential methods will say it
+            return None
+        if len(leaf_bytes) != 32 * n or len(node_bytes) != 32 * self.get_expected_node_count(n):
+            return None
+        return leaf_bytes, node_bytes
+
+    def _check_queries(self, who, queries, arrays):
+        """ValueError naming the first query outside its kind's range (the sequential methods do not define
+        those cases, and some never return)."""
+        n = len(arrays[0]) // 32 if arrays else self._store.leafCount
+        for i, (kind, a, b) in enumerate(queries):
+            try:
+                ok = int(a) == a and int(b) == b and b <= n and (
+                    0 <= a < b if kind == _native.PV_MK_Q_INCLUSION else 1 <= a <= b if kind == _native.PV_MK_Q_CONSISTENCY
+                    else 1 <= b)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("%s: query %d %r is out of range for a store of %d leaves" % (
+                    who, i, (b,) if kind == _native.PV_MK_Q_ROOT else (a, b), n))
+
+    def _prove(self, who, queries):
+        """queries: (kind, a, b). Returns one list of hashes per query."""
+        queries = list(queries)
+        arrays = self._store_arrays()
+        self._check_queries(who, queries, arrays)
+        if arrays is None:
+            return [self.inclusion_proof(a, b) if kind == _native.PV_MK_Q_INCLUSION
+                    else self.consistency_proof(a, b) if kind == _native.PV_MK_Q_CONSISTENCY
+                    else [self.merkle_tree_hash(0, b)] for kind, a, b in queries]
+        if not queries:
+            return []
+        off, hashes, status = _native.merkle_prove(arrays[0], arrays[1], [q[0] for q in queries],
+                                                   [int(q[1]) for q in queries], [int(q[2]) for q in queries])
+        if status.any():
+            raise _native.NativeError("%s: the library refused a query it was given in range" % who)
+        flat, off = hashes.tobytes(), off.tolist()
+        return [[flat[32 * j:32 * j + 32] for j in range(off[i], off[i + 1])] for i in range(len(queries))]
+
+    def inclusion_proof_batch(self, pairs):
+        """inclusion_proof(start, end) for every (start, end) of pairs, 0 <= start < end <= leafCount."""
+        return self._prove("inclusion_proof_batch", [(_native.PV_MK_Q_INCLUSION, a, b) for a, b in pairs])
+
+    def consistency_proof_batch(self, pairs):
+        """consistency_proof(first, second) for every (first, second) of pairs, 1 <= first <= second <= leafCount."""
+        return self._prove("consistency_proof_batch", [(_native.PV_MK_Q_CONSISTENCY, a, b) for a, b in pairs])
+
+    def merkle_tree_hash_batch(self, sizes):
+        """merkle_tree_hash(0, size) for every size of sizes, 1 <= size <= leafCount."""
+        return [x[0] for x in self._prove("merkle_tree_hash_batch", [(_native.PV_MK_Q_ROOT, 0, b) for b in sizes])]
+
+    def audit_proofs(self, seq_nos, size=None):
+        """Per 1-based sequence number, (root_hash, audit_path, size): the contents of Ledger.auditProof
+        (ledger/ledger.py:207-217) for the tree of `size` leaves (default: all the store holds). size may also
+        be one size per sequence number; with the numbers themselves, audit_proofs(seq_nos, seq_nos), each is
+        proved in the tree that ends with it: the contents of Ledger.merkleInfo (:196-205). Raw hashes;
+        hashToStr stays with the caller. One library call for all roots and paths."""
+        seq_nos = [int(x) for x in seq_nos]
+        if size is None:
+            size = self._store.leafCount
+        sizes = [int(size)] * len(seq_nos) if isinstance(size, int) else [int(x) for x in size]
+        if len(sizes) != len(seq_nos):
+            raise ValueError("audit_proofs: one size per sequence number")
+        distinct = sorted(set(sizes))
+        queries = [(_native.PV_MK_Q_INCLUSION, s - 1, b) for s, b in zip(seq_nos, sizes)]
+        got = self._prove("audit_proofs", queries + [(_native.PV_MK_Q_ROOT, 0, b) for b in distinct])
+        roots = {b: got[len(seq_nos) + k][0] for k, b in enumerate(distinct)}
+        return [(roots[b], got[i], b) for i, b in enumerate(sizes)]
+
+    def catchup_proofs(self, reply_ends, catchup_till):
+        """consistency_proof(end, catchup_till) for every end of reply_ends: what the seeder builds per
+        CatchupReq (plenum/server/catchup/seeder_service.py:85), one library call for all of them."""
+        return self.consistency_proof_batch([(end, catchup_till) for end in reply_ends])
 
     def get_tree_head(self, seq=None):
         seq = self._size if seq is None else seq
