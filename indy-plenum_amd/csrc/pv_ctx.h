@@ -7,14 +7,13 @@
 #include <stdint.h>
 
 #include <atomic>
-#include <list>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "copy_pool.h"
 #include "kc_admit.h"
+#include "kc_index.h"
 #include "keycache.h"
 #include "pv_engine_dev.h"
 #include "pv_internal.h"
@@ -29,6 +28,44 @@ inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e && *e ? atoi(e) : dflt;
 }
+
+// Node-side key cache (keycache.h): the device arrays and the host index over their slots.
+struct KeyCache {
+    PvOwner own;  // the device and pinned blocks below: they live from one configure call to the next
+    uint32_t cap = 0;
+    uint32_t* d_htab = nullptr;
+    uint32_t* d_keys = nullptr;
+    uint32_t* d_flags = nullptr;
+    uint4* d_tab = nullptr;
+    uint4* d_ntab = nullptr;      // the tables with every entry divided by its Z (comb path), or null
+    uint4* d_wtab = nullptr;      // radix-65536 niels rows of slots < wcap (comb.h PV_KW_*), or null
+    uint32_t wcap = 0;
+    uint32_t* d_wscr = nullptr;   // Z products of one group of wide-row builds
+    uint8_t* d_put_pk = nullptr;  // keys of one put batch
+    uint32_t* d_put_slot = nullptr;
+    uint32_t hmask = 0, seed = 0;
+    bool enabled = true;  // consulted by the latency path
+    pvhost::KcIndex index;  // which slot holds which key, the LRU, the free slots (kc_index.h)
+    bool broken = false;  // a failed hash-table upload left the device table stale: not consulted
+    // automatic admission (pv_key_cache_auto): a key is put on its auto_min-th VERIFIED appearance
+    // in pv_verify_batch calls (every request of calls of <= PV_KC_AUTO_MAX_BATCH requests, a
+    // sample of larger ones). Appearances are counted in a table of full keys hashed by NH +
+    // multiply-shift under a per-process secret, with bounded probing (kc_admit.h); an evicted key is
+    // forgotten there, so it can be re-admitted
+    uint32_t auto_min = 0;
+    pvhost::AdmitTable seen;
+    uint64_t auto_admitted = 0, auto_failed = 0;
+    // LRU refresh on use: every launch that consults the cache stamps the slots it reads with its
+    // epoch (d_stamp, pv_kc_lookup); before a put evicts, the slots stamped since the last fold
+    // move to the front of the host LRU (kc_fold_hits)
+    uint32_t* d_stamp = nullptr;
+    uint32_t epoch = 1, fold_epoch = 1;
+    // pinned staging of an asynchronous put (keys, slots, hash table), reused once ev_async is done
+    uint8_t* h_async = nullptr;
+    uint64_t h_async_cap = 0;
+    hipEvent_t ev_async = nullptr;  // the context's (Ctx::own): it outlives a reconfigure
+    bool async_pending = false;
+};
 
 struct Ctx {
     int device = -1;
@@ -105,45 +142,7 @@ struct Ctx {
     int ev_used = 0;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-    // node-side key cache (keycache.h): device arrays + host index (LRU, most recent first)
-    struct {
-        PvOwner own;  // the device and pinned blocks below: they live from one configure call to the next
-        uint32_t cap = 0;
-        uint32_t* d_htab = nullptr;
-        uint32_t* d_keys = nullptr;
-        uint32_t* d_flags = nullptr;
-        uint4* d_tab = nullptr;
-        uint4* d_ntab = nullptr;      // the tables with every entry divided by its Z (comb path), or null
-        uint4* d_wtab = nullptr;      // radix-65536 niels rows of slots < wcap (comb.h PV_KW_*), or null
-        uint32_t wcap = 0;
-        uint32_t* d_wscr = nullptr;   // Z products of one group of wide-row builds
-        uint8_t* d_put_pk = nullptr;  // keys of one put batch
-        uint32_t* d_put_slot = nullptr;
-        uint32_t hmask = 0, seed = 0;
-        bool enabled = true;  // consulted by the latency path
-        std::unordered_map<std::string, std::list<uint32_t>::iterator> index;  // key bytes -> LRU node
-        std::list<uint32_t> lru;                                                 // slots, most recent first
-        std::vector<std::string> slot_key;
-        std::vector<uint32_t> free_slots;
-        bool broken = false;  // a failed hash-table upload left the device table stale: not consulted
-        // automatic admission (pv_key_cache_auto): a key is put on its auto_min-th VERIFIED appearance
-        // in pv_verify_batch calls (every request of calls of <= PV_KC_AUTO_MAX_BATCH requests, a
-        // sample of larger ones). Appearances are counted in a SipHash-keyed table of full keys with
-        // bounded probing (kc_admit.h); an evicted key is forgotten there, so it can be re-admitted
-        uint32_t auto_min = 0;
-        pvhost::AdmitTable seen;
-        uint64_t auto_admitted = 0, auto_failed = 0;
-        // LRU refresh on use: every launch that consults the cache stamps the slots it reads with its
-        // epoch (d_stamp, pv_kc_lookup); before a put evicts, the slots stamped since the last fold
-        // move to the front of the host LRU (kc_fold_hits)
-        uint32_t* d_stamp = nullptr;
-        uint32_t epoch = 1, fold_epoch = 1;
-        // pinned staging of an asynchronous put (keys, slots, hash table), reused once ev_async is done
-        uint8_t* h_async = nullptr;
-        uint64_t h_async_cap = 0;
-        hipEvent_t ev_async = nullptr;  // the context's (Ctx::own): it outlives a reconfigure
-        bool async_pending = false;
-    } kc;
+    KeyCache kc;  // node-side key cache (pv_keycache.hip)
     // zero-copy verdict bytes (pinned, coherent: the host reads them while the kernel runs)
     uint8_t* h_zc_verdict = nullptr;
     bool last_zero_copy = false;  // the most recent pv_verify_batch took the zero-copy form
@@ -201,11 +200,14 @@ int fail(int code, const std::string& msg);
     } while (0)
 
 // pv_engine.hip
-PvKeyCacheView kc_view();
+int kc_build_tables(const pvhost::KcIndex::Assigned& put, bool async);
 int launch(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
            hipStream_t stream);
 int check_device_index(int device, const char* who);
 int ctx_init(int device);
+// pv_keycache.hip
+void kc_free();
+PvKeyCacheView kc_view();
 int kc_put_locked(const uint8_t* pks, uint64_t n, bool async);
 // pv_host.hip
 void pinned_cache_drain();

@@ -1,8 +1,9 @@
 // libplenum_verify: MI355X batch Ed25519 verification engine: the verification kernels, the device
-// context (pv_ctx.h Ctx: lifecycle, launch, control and statistics entries), the node-side key cache and
-// the device-buffer entry. The rest of the engine lives beside it: signing in pv_sign.hip, the
-// host-buffer entries in pv_host.hip, RCCL and in-process multi-GPU in pv_multi.hip, the latency path in
-// pv_latency.hip; the device types they share are pv_engine_dev.h.
+// context (pv_ctx.h Ctx: lifecycle, launch, control and statistics entries), the table build of a
+// key-cache put and the device-buffer entry. The rest of the engine lives beside it: signing in
+// pv_sign.hip, the host-buffer entries in pv_host.hip, the key cache's host side in pv_keycache.hip, RCCL
+// and in-process multi-GPU in pv_multi.hip, the latency path in pv_latency.hip; the device types they
+// share are pv_engine_dev.h.
 //
 // One lane per request, 256-thread workgroups, two workgroups per CU (2 waves/SIMD: measured
 // v_mad_u64_u32 throughput saturates at >= 2 waves/SIMD, profiles/r01_isa_rates.jsonl). The grid is
@@ -21,8 +22,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <list>
-#include <unordered_map>
 #include <mutex>
 #include <atomic>
 #include <random>
@@ -1487,10 +1486,6 @@ __global__ __launch_bounds__(PV_BLOCK) void pv_bc2_build_kernel(uint4* __restric
 // [j0, j0 + g) of the put batch: one thread per run of PV_BC2_RUN entries of one row, the row's base
 // [65536^q](-A) = the chain's P_{2q}; pv_bc2_build_run (double-and-add start, P-steps, one inversion
 // per run) writes affine niels entries, the Z products in scratch.
-#ifndef PV_KC_WIDE_KEYS
-#define PV_KC_WIDE_KEYS 1024  // keys that get wide rows (67 MB each)
-#endif
-static constexpr uint32_t PV_KW_GROUP = 64;  // keys per wide build launch (scratch: 1.35 GB)
 static constexpr uint32_t PV_KW_RUNS = (PV_KW_ENT + PV_BC2_RUN - 1) / PV_BC2_RUN;  // runs per row
 __global__ __launch_bounds__(PV_BLOCK) void pv_kc_wide_kernel(KeyWork kw, const uint32_t* __restrict__ slots,
                                                               uint32_t j0, uint32_t g, uint32_t wcap,
@@ -1791,53 +1786,6 @@ thread_local int t_dev = -1;
 thread_local std::string g_err;
 
 namespace {
-
-// Empties the key cache. enabled, auto_min, the admission counters, seed and ev_async survive: a
-// reconfigure keeps them.
-void kc_free() {
-    auto& k = g_ctx.kc;
-    if (k.async_pending && k.ev_async) (void)hipEventSynchronize(k.ev_async);  // the put reads h_async
-    k.async_pending = false;
-    k.own.release_all();
-    k.d_htab = k.d_keys = k.d_flags = k.d_put_slot = k.d_wscr = k.d_stamp = nullptr;
-    k.d_tab = k.d_ntab = k.d_wtab = nullptr;
-    k.d_put_pk = k.h_async = nullptr;
-    k.wcap = 0;
-    k.h_async_cap = 0;
-    k.cap = k.hmask = 0;
-    k.broken = false;
-    k.seen.reset();
-    k.epoch = k.fold_epoch = 1;
-    k.index.clear();
-    k.lru.clear();
-    k.slot_key.clear();
-    k.free_slots.clear();
-}
-
-// Rebuild the open-addressing table from the index and upload it (stream-ordered). hbuf: pinned
-// room for hmask + 1 words whose copy the caller lets run asynchronously; nullptr = a local buffer
-// and a synchronous upload.
-int kc_upload_htab(hipStream_t s, uint32_t* hbuf = nullptr) {
-    auto& k = g_ctx.kc;
-    std::vector<uint32_t> local;
-    uint32_t* h = hbuf;
-    if (!h) {
-        local.assign((size_t)k.hmask + 1, PV_KC_EMPTY);
-        h = local.data();
-    } else {
-        std::fill(h, h + k.hmask + 1, PV_KC_EMPTY);
-    }
-    for (auto& e : k.index) {
-        uint32_t A[8];
-        memcpy(A, e.first.data(), 32);
-        uint32_t p = pv_kc_hash(A, k.seed) & k.hmask;
-        while (h[p] != PV_KC_EMPTY) p = (p + 1) & k.hmask;
-        h[p] = *e.second;
-    }
-    PV_HIP(hipMemcpyAsync(k.d_htab, h, ((size_t)k.hmask + 1) * 4, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-    if (!hbuf) PV_HIP(hipStreamSynchronize(s), PV_ERR_LAUNCH);  // h is a local buffer
-    return PV_OK;
-}
 
 int ensure_events(int count) {
     while ((int)g_ctx.ev.size() < count) {
@@ -2357,13 +2305,16 @@ void ctx_free() {
     g_ctx = Ctx();
 }
 
-// Builds the fresh keys' tables (slot PV_KC_EMPTY = evicted again within the same put) into their
-// cache slots, in batches of the workspace's comb capacity. async: one batch only (the caller caps
+}  // namespace
+
+// What the engine's other translation units call (declared in pv_ctx.h).
+
+// Builds the tables of a put's fresh keys (slot PV_KC_EMPTY = evicted again within the same put) into
+// their cache slots, in batches of the workspace's comb capacity. async: one batch only (the caller caps
 // the keys), staged through the pinned h_async area and left running on the engine stream (the
 // next launch is stream-ordered after it). PV_TEST_FAIL_KC_PUT_BATCH=b (tests only) reports a
 // failure after batch b has been enqueued, to exercise the rollback.
-static int kc_build_tables(const std::vector<std::string>& fresh, const std::vector<uint32_t>& fresh_slot,
-                           bool async) {
+int kc_build_tables(const pvhost::KcIndex::Assigned& put, bool async) {
     auto& k = g_ctx.kc;
     hipStream_t s = g_ctx.stream;
     if (int rc = g_ctx.hand.begin(s)) return rc;
@@ -2378,7 +2329,7 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
     std::vector<uint8_t> lpk;
     std::vector<uint32_t> lslot;
     long batch = 0;
-    for (size_t f0 = 0; f0 < fresh.size();) {
+    for (size_t f0 = 0; f0 < put.fresh.size();) {
         uint8_t* bpk;
         uint32_t* bslot;
         if (async) {  // pinned: keys [kcap][32], then slots [kcap]
@@ -2390,16 +2341,10 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
             bpk = lpk.data();
             bslot = lslot.data();
         }
-        uint32_t m = 0;
-        size_t f = f0;
-        for (; f < fresh.size() && m < kw.kcap; f++) {
-            if (fresh_slot[f] == PV_KC_EMPTY) continue;
-            memcpy(bpk + 32ull * m, fresh[f].data(), 32);
-            bslot[m++] = fresh_slot[f];
-        }
-        f0 = f;
+        uint32_t m;
+        f0 = pvhost::KcIndex::pack(put, f0, kw.kcap, bpk, bslot, m);
         if (m == 0) continue;
-        if (async && f0 < fresh.size()) return fail(PV_ERR_ARG, "kc_build_tables: asynchronous put above one batch");
+        if (async && f0 < put.fresh.size()) return fail(PV_ERR_ARG, "kc_build_tables: asynchronous put above one batch");
         if (g_ctx.dir_on && m <= scratch_keys) {
             kw.ctab = scratch_tab;
         } else {
@@ -2437,48 +2382,9 @@ static int kc_build_tables(const std::vector<std::string>& fresh, const std::vec
     return PV_OK;
 }
 
-// LRU refresh on use: the slots that launches read since the last fold (d_stamp newer than
-// fold_epoch) move to the front of the LRU, least recently read first, so eviction takes the least
-// recently USED keys rather than the least recently put. Launches still running on other streams are
-// folded at the next eviction.
-static int kc_fold_hits() {
-    auto& k = g_ctx.kc;
-    if (!k.d_stamp || k.cap == 0) return PV_OK;
-    std::vector<uint32_t> st(k.cap);
-    PV_HIP(hipMemcpyAsync(st.data(), k.d_stamp, (uint64_t)k.cap * 4, hipMemcpyDeviceToHost, g_ctx.stream), PV_ERR_LAUNCH);
-    PV_HIP(hipStreamSynchronize(g_ctx.stream), PV_ERR_LAUNCH);
-    std::vector<std::pair<uint32_t, uint32_t>> used;  // (age of the stamp past the fold, slot), LRU order
-    for (auto it = k.lru.rbegin(); it != k.lru.rend(); ++it) {
-        const uint32_t age = st[*it] - k.fold_epoch;
-        if ((int32_t)age > 0) used.emplace_back(age, *it);
-    }
-    std::stable_sort(used.begin(), used.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    for (const auto& u : used) {
-        auto it = k.index.find(k.slot_key[u.second]);
-        if (it != k.index.end() && *it->second == u.second) k.lru.splice(k.lru.begin(), k.lru, it->second);
-    }
-    k.fold_epoch = k.epoch;
-    return PV_OK;
-}
-
-}  // namespace
-
-// What the engine's other translation units call (declared in pv_ctx.h).
-
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
-}
-
-PvKeyCacheView kc_view() {
-    auto& k = g_ctx.kc;
-    PvKeyCacheView v{k.d_htab, k.d_keys, k.d_flags, k.d_tab, 0u, k.seed, k.d_wtab, k.wcap};
-    if (k.enabled && !k.broken && k.cap > 0 && !k.index.empty()) {
-        v.hmask = k.hmask;
-        v.stamp = k.d_stamp;
-        v.epoch = ++k.epoch;
-    }
-    return v;
 }
 
 // One batch on `stream` (caller holds g_mu). Chunks of at most work.stride requests (a multiple of
@@ -2514,88 +2420,6 @@ int ctx_init(int device) {
         ctx_free();
         g_err = err;
     }
-    return rc;
-}
-
-// pv_key_cache_put under g_mu. async (automatic admission): at most kcap new keys, nothing waited
-// for (pinned staging; the hash-table upload and the hand-over event are stream-ordered after the build).
-int kc_put_locked(const uint8_t* pks, uint64_t n, bool async) {
-    auto& k = g_ctx.kc;
-    if (async) {
-        if (k.async_pending) PV_HIP(hipEventSynchronize(k.ev_async), PV_ERR_LAUNCH);  // h_async is free again
-        k.async_pending = false;
-    }
-    // slots for the new keys (at most cap of them: the last cap distinct keys of the call win).
-    // The device hash table still holds the state before this call until kc_upload_htab below.
-    std::vector<std::string> fresh;
-    std::vector<uint32_t> fresh_slot, touched;
-    if (k.free_slots.size() < n && !k.lru.empty()) {
-        const int rc = kc_fold_hits();  // evictions ahead: take the launches' reads into account
-        if (rc != PV_OK) return rc;
-    }
-    for (uint64_t i = 0; i < n; i++) {
-        std::string key(reinterpret_cast<const char*>(pks + 32 * i), 32);
-        auto it = k.index.find(key);
-        if (it != k.index.end()) {  // refresh
-            k.lru.splice(k.lru.begin(), k.lru, it->second);
-            continue;
-        }
-        uint32_t slot;
-        if (!k.free_slots.empty()) {
-            slot = k.free_slots.back();
-            k.free_slots.pop_back();
-        } else {  // evict the least recently put key
-            slot = k.lru.back();
-            k.lru.pop_back();
-            k.index.erase(k.slot_key[slot]);
-            k.seen.forget(reinterpret_cast<const uint8_t*>(k.slot_key[slot].data()));  // re-admissible
-            for (size_t f = 0; f < fresh.size(); f++)
-                if (fresh_slot[f] == slot) fresh_slot[f] = PV_KC_EMPTY;  // evicted before it was built
-        }
-        k.lru.push_front(slot);
-        k.index[key] = k.lru.begin();
-        k.slot_key[slot] = key;
-        fresh.push_back(key);
-        fresh_slot.push_back(slot);
-        touched.push_back(slot);
-    }
-    int rc = kc_build_tables(fresh, fresh_slot, async);
-    if (rc != PV_OK) {
-        // roll back to a state in which every indexed key's table is built: every slot this call
-        // assigned (its new key's table may be unbuilt, and its evicted key's table may already be
-        // overwritten) leaves the index and returns to the free list; the keys this call did not
-        // touch keep their slots. Then the device hash table is re-uploaded; if even that fails,
-        // the cache is switched off (kc_view() reports it empty) until configure / clear.
-        const std::string err = g_err;
-        std::vector<char> seen(k.cap, 0);
-        for (uint32_t slot : touched) {
-            if (seen[slot]) continue;
-            seen[slot] = 1;
-            auto it = k.index.find(k.slot_key[slot]);
-            if (it != k.index.end() && *it->second == slot) {
-                k.lru.erase(it->second);
-                k.index.erase(it);
-            }
-            k.slot_key[slot].clear();
-            k.free_slots.push_back(slot);
-        }
-        (void)hipStreamSynchronize(g_ctx.stream);
-        if (kc_upload_htab(g_ctx.stream) != PV_OK) k.broken = true;
-        g_err = err;
-        return rc;
-    }
-    g_ctx.last_keyed = false;
-    if (async) {
-        rc = kc_upload_htab(g_ctx.stream, reinterpret_cast<uint32_t*>(k.h_async + (uint64_t)g_ctx.kw.kcap * 36));
-        if (rc == PV_OK) {
-            PV_HIP(hipEventRecord(k.ev_async, g_ctx.stream), PV_ERR_LAUNCH);
-            k.async_pending = true;
-        }
-    } else {
-        rc = kc_upload_htab(g_ctx.stream);
-    }
-    if (int rc2 = g_ctx.hand.end(g_ctx.stream)) return rc2;
-    k.broken = rc != PV_OK;  // a complete upload also repairs an earlier failed one
     return rc;
 }
 
@@ -2821,122 +2645,6 @@ int pv_test_clock_stamps(uint64_t* out, uint32_t max_blocks) {
 int pv_sync(void) {
     PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
     return PV_OK;
-}
-int pv_key_cache_configure(uint32_t capacity) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_key_cache_configure: call pv_init first");
-    PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);  // no launch may still read the old tables
-    kc_free();
-    if (capacity == 0) return PV_OK;
-    if (capacity > (1u << 20)) return fail(PV_ERR_ARG, "pv_key_cache_configure: capacity above 2^20 keys");
-    auto& k = g_ctx.kc;
-    uint32_t H = 2;
-    while (H < 2 * capacity) H <<= 1;
-    const uint64_t per = (uint64_t)PV_COMB_POS * PV_COMB_ENT * 160;  // bytes per key table
-    const uint64_t kcap = g_ctx.kw.kcap, async_bytes = kcap * 36 + (uint64_t)H * 4;
-    auto make = [&]() -> int {
-        if (int rc = k.own.dev(k.d_tab, per * capacity)) return rc;
-        if (int rc = k.own.dev(k.d_keys, (uint64_t)capacity * 32)) return rc;
-        if (int rc = k.own.dev(k.d_flags, (uint64_t)capacity * 4)) return rc;
-        if (int rc = k.own.dev(k.d_htab, (uint64_t)H * 4)) return rc;
-        if (int rc = k.own.dev(k.d_stamp, (uint64_t)capacity * 4)) return rc;
-        PV_HIP(hipMemset(k.d_stamp, 0, (uint64_t)capacity * 4), PV_ERR_ALLOC);
-        if (int rc = k.own.dev(k.d_put_pk, kcap * 32)) return rc;
-        if (int rc = k.own.dev(k.d_put_slot, kcap * 4)) return rc;
-        if (int rc = k.own.pinned(k.h_async, async_bytes, hipHostMallocDefault)) return rc;
-        // the context's, not the cache's: made on the first configure, kept across every later one
-        if (!k.ev_async) return g_ctx.own.event(k.ev_async, hipEventDisableTiming);
-        return PV_OK;
-    };
-    if (int rc = make()) {
-        kc_free();
-        return rc;
-    }
-    k.h_async_cap = async_bytes;
-    // the affine rows (660 KB per key): optional -- without them cached keys use the cached-form rows
-    static const bool affine = env_int("PV_KC_AFFINE", 1) != 0;
-    if (affine && k.own.dev(k.d_ntab, per * capacity) != PV_OK) (void)hipGetLastError();
-    // the wide rows (67 MB per key) for the first min(capacity, PV_KC_WIDE_KEYS) slots: optional, and
-    // kept only together with their scratch
-    {
-        const uint32_t want = std::min<uint32_t>(capacity, (uint32_t)std::max(0, env_int("PV_KC_WIDE_KEYS", PV_KC_WIDE_KEYS)));
-        const uint64_t per_w = (uint64_t)PV_KW_POS * PV_KW_ENT * 128;
-        if (want > 0 && k.own.dev(k.d_wtab, per_w * want) == PV_OK &&
-            k.own.dev(k.d_wscr, (uint64_t)PV_KW_GROUP * PV_KW_POS * PV_KW_ENT * 40) == PV_OK) {
-            k.wcap = want;
-        } else {
-            (void)hipGetLastError();
-            k.own.drop(k.d_wtab);
-            k.d_wtab = nullptr;
-            k.wcap = 0;
-        }
-    }
-    k.cap = capacity;
-    k.hmask = H - 1;
-    k.seed = (uint32_t)std::random_device{}() | 1u;
-    k.slot_key.assign(capacity, std::string());
-    for (uint32_t i = capacity; i-- > 0;) k.free_slots.push_back(i);
-    return kc_upload_htab(g_ctx.stream);
-}
-
-int pv_key_cache_put(const uint8_t* pks, uint64_t n) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto& k = g_ctx.kc;
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_key_cache_put: call pv_init first");
-    if (k.cap == 0) return fail(PV_ERR_NOT_INIT, "pv_key_cache_put: cache not configured");
-    if (n > 0 && !pks) return fail(PV_ERR_ARG, "pv_key_cache_put: null pointer");
-    return kc_put_locked(pks, n, false);
-}
-
-int pv_key_cache_auto(uint32_t min_seen) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_ctx.device < 0) return fail(PV_ERR_NOT_INIT, "pv_key_cache_auto: call pv_init first");
-    if (min_seen > 254) return fail(PV_ERR_ARG, "pv_key_cache_auto: min_seen above 254");
-    g_ctx.kc.auto_min = min_seen;
-    g_ctx.kc.seen.reset();
-    return PV_OK;
-}
-
-int pv_key_cache_auto_stats(uint64_t* admitted, uint64_t* failed) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (admitted) *admitted = g_ctx.kc.auto_admitted;
-    if (failed) *failed = g_ctx.kc.auto_failed;
-    return PV_OK;
-}
-
-int pv_key_cache_clear(void) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto& k = g_ctx.kc;
-    if (k.cap == 0) return PV_OK;
-    PV_HIP(hipDeviceSynchronize(), PV_ERR_LAUNCH);
-    k.index.clear();
-    k.lru.clear();
-    k.free_slots.clear();
-    for (uint32_t i = k.cap; i-- > 0;) k.free_slots.push_back(i);
-    for (auto& sk : k.slot_key) sk.clear();
-    k.seen.reset();  // every key may be admitted again
-    const int rc = kc_upload_htab(g_ctx.stream);
-    k.broken = rc != PV_OK;
-    return rc;
-}
-
-int pv_key_cache_enable(int enable) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_ctx.kc.enabled = enable != 0;
-    return PV_OK;
-}
-
-int pv_key_cache_stats(uint32_t* size, uint32_t* capacity) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (size) *size = (uint32_t)g_ctx.kc.index.size();
-    if (capacity) *capacity = g_ctx.kc.cap;
-    return PV_OK;
-}
-
-int pv_key_cache_contains(const uint8_t* pk) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!pk) return 0;
-    return g_ctx.kc.index.count(std::string(reinterpret_cast<const char*>(pk), 32)) ? 1 : 0;
 }
 
 int pv_stream_create(void** stream) {

@@ -261,6 +261,10 @@ static constexpr uint32_t PV_WIDE_DEFAULT = 2048;   // slots of the wide pool (3
 static constexpr uint32_t PV_WIDE_THREADS = 384;    // pv_dir_widen_kernel: one run per thread, 23 x 16 = 368 used
 static constexpr uint32_t PV_WIDE_GRID = 512;       // its workgroups, each with 0.98 MB of scratch (503 MB)
 static_assert(PV_KR_POS * PV_KR_RUNS <= PV_WIDE_THREADS, "one thread per run of a table");
+#ifndef PV_KC_WIDE_KEYS
+#define PV_KC_WIDE_KEYS 1024  // key-cache slots that get radix-65536 rows (67 MB each)
+#endif
+static constexpr uint32_t PV_KW_GROUP = 64;  // keys per wide build launch of a key-cache put (scratch: 1.35 GB)
 static constexpr uint32_t PV_EMPTY = 0xFFFFFFFFu;
 static constexpr uint32_t PV_CSLOT_XT = 0x40000000u;  // cache slot in the call's shared store (KeyWork::xt_*)
 static constexpr uint32_t PV_CSLOT_DIR = 0x20000000u;  // slot of kw.ctab listed in the resident-table directory
