@@ -3,7 +3,8 @@
 // key-cache put and the device-buffer entry. The rest of the engine lives beside it: signing in
 // pv_sign.hip, the host-buffer entries in pv_host.hip, the key cache's host side in pv_keycache.hip, RCCL
 // and in-process multi-GPU in pv_multi.hip, the latency path in pv_latency.hip; the device types they
-// share are pv_engine_dev.h.
+// share are pv_engine_dev.h. What a launch decides on the host (path, lookup views, KeyWork scalars, launch
+// shape, grids) is chunk_plan.h, with the thresholds those rules read; launch_chunk applies it.
 //
 // One lane per request, 256-thread workgroups, two workgroups per CU (2 waves/SIMD: measured
 // v_mad_u64_u32 throughput saturates at >= 2 waves/SIMD, profiles/r01_isa_rates.jsonl). The grid is
@@ -54,27 +55,9 @@
 #ifndef PV_PREP_MINBLOCKS
 #define PV_PREP_MINBLOCKS 2  // Straus prep (decompression + SHA-512 + recoding)
 #endif
-// An all-comb chunk of at most PV_SPARSE_CHUNK requests and at most PV_SPARSE_PER_KEY requests per key
-// on average builds only the table entries its digits use (comb.h pv_comb_fill_sparse; the need
-// masks are set by pv_comb_prep_req_kernel). A/B on MI355X (1,024 signers, device time,
-// profiles/r02/ab_sparse_fill.txt): 6k requests 0.71 -> 0.54 ms, 10k 0.70 -> 0.56; at 32 requests
-// per key the per-position thread's serial additions outlast the parallel full fill (32k 0.69 ->
-// 0.72, 64k 0.74 -> 0.89), hence the per-key bound.
-#ifndef PV_SPARSE_CHUNK
-#define PV_SPARSE_CHUNK 65536
-#endif
+// requests per key, on average, up to which an all-comb chunk fills sparsely (chunk_plan.h PV_SPARSE_CHUNK has the A/B)
 #ifndef PV_SPARSE_PER_KEY
 #define PV_SPARSE_PER_KEY 16
-#endif
-#ifndef PV_LP_CHAIN_BLOCKS
-#define PV_LP_CHAIN_BLOCKS 2048  // waves of the limb-parallel key chain (one key each at a time)
-#endif
-// Dedup contention (1,024 signers x ~1,000 requests each per 1M chunk). Kernel times on MI355X
-// (rocprofv3, profiles/r02/ab_dedup_seed.txt): insert + assign 143 us with one atomic counter per
-// key and an atomic first read; 95 us with the seed pre-pass; 92 with a plain first read; 85 us
-// (+ 8 us seed) with the counters split 8 ways (16: 86, 32: 87 -- the assign kernel's sums grow).
-#ifndef PV_KEY_SEED
-#define PV_KEY_SEED 4096  // requests of a keyed chunk whose keys are inserted first (pv_key_seed_kernel)
 #endif
 // Per-key request counters of the dedup are split PV_RANK_SUB ways (sub-table = the request's
 // workgroup index mod PV_RANK_SUB), so the ~1,000 requests of a hot key queue on PV_RANK_SUB
@@ -186,10 +169,6 @@ struct DevDigits {
     __device__ __forceinline__ uint32_t nw() const { return d.ld(PV_NW_ROW, slot); }
     __device__ __forceinline__ int fb(int j) const { return (int)d.ld(8 + j, slot); }
 };
-
-#ifndef PV_COMB_MIN_REQ
-#define PV_COMB_MIN_REQ 48
-#endif
 
 // A 10-piece entry whose pieces 5 and 6 (words 20..27) are skipped on lanes with `skip` (affine comb rows:
 // their Z2 words are not read). Lanes that skip leave those pieces of their staging column stale.
@@ -443,12 +422,7 @@ __device__ __forceinline__ uint32_t pv_key_hash(const uint32_t A[8], uint32_t se
     return h;
 }
 
-// The insert kernel's workgroup takes PV_INS_REQS consecutive requests, counts their keys in an LDS
-// table and makes ONE device atomic per (key, workgroup) for the whole group's ranks (per-request
-// atomics on the keys' counters were ~56 of the kernel's ~74 us at 1M requests). The sub-table of
-// request i's per-key counter is its insert-workgroup index mod PV_RANK_SUB.
-static constexpr uint32_t PV_INS_THREADS = 1024, PV_INS_PER_THREAD = 4;
-static constexpr uint32_t PV_INS_REQS = PV_INS_THREADS * PV_INS_PER_THREAD;
+// The insert kernel's workgroup (chunk_plan.h PV_INS_*) counts its requests' keys in an LDS table:
 static constexpr uint32_t PV_INS_LT = 4096;  // LDS table entries (more distinct keys: direct atomics)
 __device__ __forceinline__ uint32_t pv_rank_sub(uint32_t i) {
     return (i / PV_INS_REQS) & (PV_RANK_SUB - 1u);
@@ -1634,13 +1608,8 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_a_kerne
 // the wave's staging area) run inside the issue-bound comb kernel, where the other waves of the SIMD
 // cover their fetch latency, instead of as a latency-bound kernel of their own between comb_prep and
 // the per-key tables; and acc never round-trips through q. The kernel then starts as soon as the
-// per-key tables are built. The launcher takes it for chunks above PV_FUSED_MIN_REQ requests. Below
-// that the two-kernel form stays: a small chunk's [S]B kernel is a latency-bound chain of 10 dependent
-// HBM lookups that the split form hides beside the table fill, while the fused kernel would add it
-// after the fill (4,096-32,768-request calls were 0.08-0.12 ms slower fused).
-#ifndef PV_FUSED_MIN_REQ
-#define PV_FUSED_MIN_REQ 262144
-#endif
+// per-key tables are built. The launcher takes it for chunks above PV_FUSED_MIN_REQ requests
+// (chunk_plan.h has why the two-kernel form stays below that).
 // Diagnostic build only (PV_CLOCK_PROBE=1, tools/clock_probe.py; MI355X_MICROARCH "DVFS give-back"
 // item 6): wave 0 of every comb_ab workgroup stamps the shader clock (s_memtime) and the 100 MHz
 // constant clock (s_memrealtime) at entry and exit into a buffer of its own, which no other code reads;
@@ -1698,17 +1667,7 @@ __global__ __launch_bounds__(PV_BLOCK, PV_COMB_A_MINBLOCKS) void pv_comb_ab_kern
 // Kernel 3: encode Q for B requests per lane with one shared inversion, compare with R, one __ballot
 // per request group. Wave w covers requests [64 B w, 64 B (w + 1)): lane l handles 64 B w + l + 64 t,
 // t = 0..B-1, so every load is coalesced and group t's ballot is verdict word B w + t. Points are
-// re-read from q rather than held. B = 16 (two groups of 8 under one inversion, verify_core.h) for
-// chunks of >= PV_ENC16_MIN requests, else PV_ENC_SMALL_B = 8. With each lane's own inversion chain 16
-// won at 1M requests (0.185-0.190 ms against 0.191-0.198 for 2,048 waves of 8, profiles/r05/
-// ab_encode_prefetch.txt); with the wave's limb-parallel inversion 8 wins everywhere (0.145-0.148 vs
-// 0.159-0.161 ms at 1M, 4 per lane 0.185-0.191: profiles/r06/ab/ab_encode_batch.txt), so 16 is off.
-#ifndef PV_ENC_SMALL_B
-#define PV_ENC_SMALL_B 8
-#endif
-#ifndef PV_ENC16_MIN
-#define PV_ENC16_MIN 0xffffffffu
-#endif
+// re-read from q rather than held. B is 16 or PV_ENC_SMALL_B = 8 (chunk_plan.h PV_ENC16_MIN has the A/Bs).
 template <int B>
 struct DevEncSrc {
     Soa q;
@@ -1796,279 +1755,292 @@ int ensure_events(int count) {
     return PV_OK;
 }
 
-// Chunk c of the batch on `stream` (the workspace is the context's; key / fill / side streams join it).
+static_assert(PV_FILL_ITEMS_PER_KEY == PV_COMB_POS * PV_COMB_BLOCKS, "chunk_plan.h: fill work items per key");
+// bytes of one table's radix-2^11 rows in the wide pool
+constexpr uint64_t PV_WIDE_TABLE_BYTES = (uint64_t)PV_KR_POS * PV_KR_ENT * PV_BCOMB_STRIDE * 4;
+
+// One chunk's launch sequence: what its stages share. Every decision is in `p` (chunk_plan.h); the stages
+// below enqueue what it names, record and wait on events, and keep the dirty flags in step with the enqueues.
+struct ChunkLaunch {
+    const pvhost::ChunkPlan& p;
+    const KeyWork& kw;  // the context's, with the plan applied (apply_plan)
+    Gate gate;
+    const uint8_t* d_sm;
+    const uint64_t* d_off;  // the chunk's first offset
+    uint64_t m;
+    const uint8_t* d_pk;  // the chunk's first key
+    uint64_t* d_verdict;  // the chunk's first verdict word
+    hipStream_t stream;
+    hipEvent_t* e;  // the chunk's PV_NSTAGES + 1 timing events, or null
+    int mark(int k) const {
+        if (e) PV_HIP(hipEventRecord(e[k], stream), PV_ERR_LAUNCH);
+        return PV_OK;
+    }
+};
+
+// The plan's scalars into the chunk's KeyWork, and the pointers its lookup arrangement names: kcv / xtv are
+// the probe's first and second view, kc_flags the flags of the first.
+void apply_plan(const pvhost::ChunkPlan& p, KeyWork& kw, PvKeyCacheView& kcv, PvKeyCacheView& xtv,
+                const uint32_t*& kc_flags) {
+    const PvKeyCacheView xv{g_ctx.xt.htab, g_ctx.xt.keys, g_ctx.xt.flags, g_ctx.xt.tab, PV_XT_HASH - 1, g_ctx.kw.seed};
+    const bool xt_only = p.lookup == pvhost::LOOKUP_XT_ONLY, xt_second = p.lookup == pvhost::LOOKUP_NODE_THEN_XT;
+    xtv = xt_second ? xv : PvKeyCacheView{nullptr, nullptr, nullptr, nullptr, 0u, 0u};
+    if (xt_only) kcv = xv;
+    kc_flags = xt_only ? g_ctx.xt.flags : g_ctx.kc.d_flags;
+    kw.kc_tab = xt_only ? g_ctx.xt.tab : g_ctx.kc.d_tab;
+    kw.kc_ntab = xt_only ? nullptr : g_ctx.kc.d_ntab;
+    kw.kc_wtab = xt_only ? nullptr : g_ctx.kc.d_wtab;
+    kw.xt_flags = xt_second ? g_ctx.xt.flags : nullptr;
+    kw.xt_tab = xt_second ? g_ctx.xt.tab : nullptr;
+    kw.wide_tab = g_ctx.d_wide.as<uint4>();
+    kw.wide_scr = g_ctx.d_wide_scr.as<uint32_t>();
+    if (p.dense_only) kw.ctab = g_ctx.xt.tab;  // sub-batch 0 of a pipelined host call builds into the shared store
+    kw.min_req = p.min_req;
+    kw.kc_on = p.kc_on;
+    kw.kc_wcap = p.kc_wcap;
+    kw.dir_on = p.dir_on;
+    kw.dir_cap = p.dir_cap;
+    kw.dir_pub = p.dir_pub;
+    kw.aff_conv = p.aff_conv;
+    kw.wide_cap = p.wide_cap;
+    kw.wide_conv = p.wide_conv;
+    kw.chunk_n = p.chunk_n;
+    kw.seg_cap = p.seg_cap;
+    kw.lat_choice = p.lat_choice;
+    kw.dense_only = p.dense_only;
+    kw.kcap = p.kcap;
+}
+
+// The wide pool's allocation, when plan_wide_pool asks for it. A failure turns the feature off and is
+// reported once through the error string; the chunk goes on without wide rows.
+void wide_pool_attempt(uint64_t wide_want) {
+    if (g_ctx.d_wide.grow(wide_want) != PV_OK ||
+        g_ctx.d_wide_scr.grow((uint64_t)PV_WIDE_GRID * PV_KR_RUN * 10 * PV_WIDE_THREADS * 4) != PV_OK) {
+        (void)hipGetLastError();  // clear the failed allocation's sticky error
+        g_ctx.d_wide.release();
+        g_ctx.d_wide_scr.release();
+        g_ctx.wide_failed = true;
+        (void)fail(PV_ERR_ALLOC, "wide rows of resident tables: no memory for the pool, the feature is off");
+    }
+}
+
+// Key stage of a keyed chunk: the clears the dirty flags force, dedup (seed, insert, assign), the probe of
+// the lookup views, the scan, the scatter on the main stream and the chain and fill on the key stream.
+int launch_key_stage(const ChunkLaunch& L, const PvKeyCacheView& kcv, const PvKeyCacheView& xtv,
+                     const uint32_t* kc_flags) {
+    const pvhost::ChunkPlan& p = L.p;
+    const KeyWork& kw = L.kw;
+    hipStream_t stream = L.stream;
+    if (p.clear_slots) {
+        PV_HIP(hipMemsetAsync(kw.slot, 0xFF, (uint64_t)(kw.hmask + 1) * 4, stream), PV_ERR_LAUNCH);
+        PV_HIP(hipMemsetAsync(kw.slot_cnt, 0, (uint64_t)(kw.hmask + 1) * 4 * PV_RANK_SUB, stream), PV_ERR_LAUNCH);
+        PV_HIP(hipMemsetAsync(kw.need, 0, (uint64_t)PV_ALLCOMB_KEYS * PV_COMB_POS * 5 * 4, stream), PV_ERR_LAUNCH);
+    }
+    g_ctx.slots_dirty = true;  // until this chunk's unpermute kernel is enqueued
+    if (p.clear_dir) {
+        PV_HIP(hipMemsetAsync(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4, stream), PV_ERR_LAUNCH);
+        PV_HIP(hipMemsetAsync(kw.dir_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);
+        PV_HIP(hipMemsetAsync(kw.wide_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);  // the pool empties with it
+    }
+    if (p.mark_dir_dirty) g_ctx.dir_dirty = true;  // until the chunk is enqueued whole
+    // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
+    if (p.seed_reqs) {
+        PV_LAUNCH(pv_key_seed_kernel, dim3(pvhost::block_grid(p.seed_reqs)), dim3(PV_BLOCK), 0, stream, L.d_pk,
+                  p.seed_reqs, kw);
+    }
+    PV_LAUNCH(pv_key_insert_lds_kernel, dim3(p.ins_grid), dim3(PV_INS_THREADS), 0, stream, L.d_pk, L.m, kw);
+    PV_LAUNCH(pv_key_assign_kernel, dim3(p.req_grid), dim3(PV_BLOCK), 0, stream, L.m, kw);
+    if (p.run_probe) {
+        PvKeyCacheView dirv{kw.dir_htab, kw.dir_keys, kw.dir_flags, kw.ctab, p.dir_use ? PV_DIR_HASH - 1 : 0u, kw.seed};
+        PV_LAUNCH(pv_key_cache_probe_kernel, dim3(p.probe_grid), dim3(PV_BLOCK), 0, stream, L.d_pk, kw, kcv, xtv, dirv);
+    }
+    // key-sorted slot order: comb keys' requests first, then the Straus requests
+    PV_LAUNCH(pv_key_scan_kernel, dim3(1), dim3(PV_SCAN_THREADS), 0, stream, kw, kc_flags);
+    // the per-key chain (few, long-latency lanes) and the table fill run on kstream, overlapped
+    // with the scatter and the per-request prep on the main stream: the chain needs only the
+    // scan's comb-key list (comb_key, comb_cslot), so kstream forks before the scatter
+    PV_HIP(hipEventRecord(g_ctx.ev_scan_done, stream), PV_ERR_LAUNCH);
+    PV_HIP(hipStreamWaitEvent(g_ctx.kstream, g_ctx.ev_scan_done, 0), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_key_scatter_kernel, dim3(p.req_grid), dim3(PV_BLOCK), 0, stream, L.m, kw);
+    PV_HIP(hipEventRecord(g_ctx.ev_keys_ready, stream), PV_ERR_LAUNCH);
+    // one chain launch over all positions, then the fill. direct_fill: back to back on kstream
+    // and the tables-ready event right after the fill (no event hop to fstream, no gated
+    // sparse-fill launch in the dependency chain of the comb kernel). Otherwise the fill runs on
+    // fstream, where the sparse fill follows it (launch_comb_stage).
+    hipStream_t fs = p.direct_fill ? g_ctx.kstream : g_ctx.fstream;
+    PV_LAUNCH(pv_key_chain_lp_kernel, dim3(p.chain_blocks), dim3(64), 0, g_ctx.kstream, L.d_pk, kw, L.gate, 0,
+              PV_COMB_POS);
+    if (!p.direct_fill) {
+        PV_HIP(hipEventRecord(g_ctx.ev_chain, g_ctx.kstream), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamWaitEvent(fs, g_ctx.ev_chain, 0), PV_ERR_LAUNCH);
+    }
+    PV_LAUNCH(pv_key_fill_kernel, dim3(p.fill_grid), dim3(PV_BLOCK), 0, fs, kw, L.gate, 0, PV_COMB_POS);
+    if (p.direct_fill) PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.kstream), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+// The Straus-path slots of a split chunk (keys without a table: usually a few thousand one-off requests)
+// run on their own stream beside the comb kernels: their waves take ~1 ms from start to end however few
+// they are, which on the main stream would delay the whole comb path. Their blocks are dispatched from
+// the END of the slot range (where the Straus slots are), and blocks of comb slots exit at once.
+int launch_straus_side(const ChunkLaunch& L) {
+    hipStream_t ss = g_ctx.sstream;
+    const dim3 grid(L.p.side_grid), block(PV_BLOCK);
+    PV_HIP(hipStreamWaitEvent(ss, g_ctx.ev_keys_ready, 0), PV_ERR_LAUNCH);
+    PV_LAUNCH_BC2(pv_prep_kernel, grid, block, 0, ss, L.d_sm, L.d_off, L.m, L.d_pk, g_ctx.work, L.gate);
+    PV_LAUNCH_BC2(pv_split_kernel, grid, block, 0, ss, L.d_sm, L.d_off, L.m, g_ctx.work, L.gate);
+    PV_LAUNCH(pv_table_kernel, grid, block, 0, ss, L.d_sm, L.d_off, L.m, L.d_pk, g_ctx.work, L.gate);
+    PV_LAUNCH_BC2(pv_msm_kernel, grid, block, 0, ss, L.d_sm, L.d_off, L.m, g_ctx.d_btab, g_ctx.work, g_ctx.d_bc2,
+                  L.gate);
+    PV_HIP(hipEventRecord(g_ctx.ev_straus_done, ss), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+// Comb stage of a keyed chunk on the main stream: the per-request prep and digits while the key stream
+// builds the tables, then [S]B + [k](-A) once they are ready, then the join with the Straus side.
+int launch_comb_stage(const ChunkLaunch& L) {
+    const pvhost::ChunkPlan& p = L.p;
+    const KeyWork& kw = L.kw;
+    hipStream_t stream = L.stream;
+    const dim3 grid(p.req_grid), block(PV_BLOCK);
+    int rc;
+    PV_LAUNCH_BC2(pv_comb_prep_req_kernel, grid, block, g_ctx.prep_lds_pad, stream, L.d_sm, L.d_off, L.m, L.d_pk,
+                  g_ctx.work, kw, L.gate);
+    if (!p.direct_fill) {
+        // a small chunk's sparse table fill (needs the chain's bases and the need masks comb_prep
+        // writes) runs on fstream after the full fill; for a large chunk it exits at once
+        PV_HIP(hipEventRecord(g_ctx.ev_prep_done, stream), PV_ERR_LAUNCH);
+        PV_HIP(hipStreamWaitEvent(g_ctx.fstream, g_ctx.ev_prep_done, 0), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_key_fill_sparse_kernel, dim3(PV_ALLCOMB_KEYS * PV_COMB_POS / PV_BLOCK), block, 0, g_ctx.fstream,
+                  kw, L.gate);
+        PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.fstream), PV_ERR_LAUNCH);
+    }
+    // the per-request results to slot-ordered rows, while the key stream finishes the tables
+    PV_LAUNCH_BC2(pv_comb_digits_kernel, grid, block, 0, stream, g_ctx.work, kw, L.gate);
+    if ((rc = L.mark(PV_STAGE_TABLE))) return rc;
+    if (!p.fused)  // [S]B while the key stream finishes the tables, then join
+        PV_LAUNCH_BC2(pv_comb_b_kernel, grid, block, 0, stream, L.m, g_ctx.work, kw, g_ctx.d_bc2, L.gate);
+    PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_tables_ready, 0), PV_ERR_LAUNCH);
+    if ((rc = L.mark(PV_STAGE_MSM))) return rc;
+    if (p.fused)  // [S]B + [k](-A) in one kernel as soon as the tables are built
+        PV_LAUNCH_BC2(pv_comb_ab_kernel, grid, block, 0, stream, L.m, g_ctx.work, kw, g_ctx.d_bc2, L.gate);
+    else
+        PV_LAUNCH(pv_comb_a_kernel, grid, block, 0, stream, L.m, g_ctx.work, kw, L.gate);
+    PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_straus_done, 0), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+// A chunk with no key kernels: every request on the Straus path, on the main stream.
+int launch_straus_only(const ChunkLaunch& L) {
+    hipStream_t stream = L.stream;
+    const dim3 grid(L.p.req_grid), block(PV_BLOCK);
+    int rc;
+    PV_LAUNCH_BC2(pv_prep_kernel, grid, block, 0, stream, L.d_sm, L.d_off, L.m, L.d_pk, g_ctx.work, L.gate);
+    PV_LAUNCH_BC2(pv_split_kernel, grid, block, 0, stream, L.d_sm, L.d_off, L.m, g_ctx.work, L.gate);
+    if ((rc = L.mark(PV_STAGE_TABLE))) return rc;
+    PV_LAUNCH(pv_table_kernel, grid, block, 0, stream, L.d_sm, L.d_off, L.m, L.d_pk, g_ctx.work, L.gate);
+    if ((rc = L.mark(PV_STAGE_MSM))) return rc;
+    PV_LAUNCH_BC2(pv_msm_kernel, grid, block, 0, stream, L.d_sm, L.d_off, L.m, g_ctx.d_btab, g_ctx.work, g_ctx.d_bc2,
+                  L.gate);
+    return PV_OK;
+}
+
+// Epilogue: the encode; for a keyed chunk the verdicts back to request order, the publishes and conversions
+// for the chunks that follow, and the latency launch of a device-side choice.
+int launch_epilogue(const ChunkLaunch& L) {
+    const pvhost::ChunkPlan& p = L.p;
+    const KeyWork& kw = L.kw;
+    hipStream_t stream = L.stream;
+    if (p.enc16)
+        PV_LAUNCH(pv_encode_kernel<16>, dim3(p.enc_grid), dim3(PV_BLOCK), 0, stream, L.d_sm, L.d_off, L.m, g_ctx.work,
+                  L.d_verdict, kw, L.gate);
+    else
+        PV_LAUNCH(pv_encode_kernel<PV_ENC_SMALL_B>, dim3(p.enc_grid), dim3(PV_BLOCK), 0, stream, L.d_sm, L.d_off, L.m,
+                  g_ctx.work, L.d_verdict, kw, L.gate);
+    if (!p.keyed) return PV_OK;
+    PV_LAUNCH(pv_unpermute_kernel, dim3(p.req_grid), dim3(PV_BLOCK), 0, stream, L.m, kw, L.d_verdict, L.gate);
+    g_ctx.slots_dirty = false;
+    if (p.run_xtab_publish)
+        PV_LAUNCH(pv_xtab_publish_kernel, dim3(PV_XT_KEYS / PV_BLOCK), dim3(PV_BLOCK), 0, stream, L.d_pk, kw,
+                  g_ctx.xt.htab, PV_XT_HASH - 1, g_ctx.kw.seed, g_ctx.xt.keys, g_ctx.xt.flags);
+    if (p.run_dir_publish)
+        PV_LAUNCH(pv_dir_publish_kernel, dim3(p.pub_grid), dim3(PV_BLOCK), 0, stream, L.d_pk, kw);
+    if (p.run_affine) PV_LAUNCH(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
+    if (p.run_widen) PV_LAUNCH(pv_dir_widen_kernel, dim3(PV_WIDE_GRID), dim3(PV_WIDE_THREADS), 0, stream, kw);
+    if (p.dir_use) g_ctx.dir_dirty = false;
+    if (p.run_dev_latency)  // the words were zeroed by the unpermute kernel
+        return pv_latency_launch(L.d_sm, L.d_off, L.m, L.d_pk, g_ctx.d_bcomb, kc_view(), L.d_verdict, true, stream,
+                                 kw.nkeys + PV_SPLIT_LAT);
+    return PV_OK;
+}
+
+// Chunk c of the batch on `stream` (the workspace is the context's; key / fill / side streams join it):
+// plan (chunk_plan.h), apply, launch.
 int launch_chunk(int c, uint64_t n, const uint8_t* d_sm, const uint64_t* d_off, const uint8_t* d_pk,
-                 uint64_t* d_verdict, hipStream_t stream, bool latency, bool dev_choice, int evb) {
+                 uint64_t* d_verdict, hipStream_t stream, const pvhost::BatchPlan& batch, int evb) {
     constexpr int NE = PV_NSTAGES + 1;
     const uint64_t cap = g_ctx.work.stride;
-    {
-        const uint64_t c0 = (uint64_t)c * cap;
-        const uint64_t m = std::min<uint64_t>(cap, n - c0);
-        const unsigned grid = (unsigned)((m + PV_BLOCK - 1) / PV_BLOCK);
-        hipEvent_t* e = g_ctx.timing ? &g_ctx.ev[evb + NE * c] : nullptr;
-        auto mark = [&](int k) -> int {
-            if (e) PV_HIP(hipEventRecord(e[k], stream), PV_ERR_LAUNCH);
-            return PV_OK;
-        };
-        int rc = mark(PV_STAGE_KEYS);
+    const uint64_t c0 = (uint64_t)c * cap;
+    const uint64_t m = std::min<uint64_t>(cap, n - c0);
+    pvhost::ChunkPlan p;
+    KeyWork kw = g_ctx.kw;
+    ChunkLaunch L{p, kw, Gate{nullptr, nullptr}, d_sm, d_off + c0, m, d_pk + 32 * c0, d_verdict + c0 / 64, stream,
+                  g_ctx.timing ? &g_ctx.ev[evb + NE * c] : nullptr};
+    int rc = L.mark(PV_STAGE_KEYS);
+    if (rc) return rc;
+    if (batch.latency) {
+        // one kernel: every stage of the verification inside it (timed as MSM)
+        g_ctx.last_keyed = false;
+        for (int k = PV_STAGE_PREP; k <= PV_STAGE_MSM; k++)
+            if ((rc = L.mark(k))) return rc;
+        rc = pv_latency_launch(d_sm, L.d_off, m, L.d_pk, g_ctx.d_bcomb, kc_view(), L.d_verdict, g_ctx.verdict_zeroed,
+                               stream, nullptr);
         if (rc) return rc;
-        if (latency) {
-            // one kernel: every stage of the verification inside it (timed as MSM)
-            g_ctx.last_keyed = false;
-            for (int k = PV_STAGE_PREP; k <= PV_STAGE_MSM; k++)
-                if ((rc = mark(k))) return rc;
-            rc = pv_latency_launch(d_sm, d_off + c0, m, d_pk + 32 * c0, g_ctx.d_bcomb, kc_view(),
-                                   d_verdict + c0 / 64, g_ctx.verdict_zeroed, stream, nullptr);
-            if (rc) return rc;
-            if ((rc = mark(PV_STAGE_ENCODE)) || (rc = mark(PV_NSTAGES))) return rc;
-            return PV_OK;
-        }
-        // Path split (measured round-1 costs on MI355X): a key's comb table costs ~0.47 us of device
-        // time (chain + 4,128-entry fill) and then saves ~10 ns per request against the Straus
-        // path (~3 vs ~13 ns), so AUTO gives a table to keys with >= PV_COMB_MIN_REQ requests in
-        // the chunk and verifies every other request on the Straus path in the same launch. The
-        // split is computed on the device by the dedup/sort kernels (Gate); nothing synchronises.
-        // Chunks below PV_KEYED_MIN (the latency path's range; only the tail chunk of a large
-        // batch can be that small) skip dedup and go Straus. A key in the node-side key cache has
-        // its comb table already built: its requests take the comb path at any count.
-        PvKeyCacheView kcv = kc_view();
-        PvKeyCacheView xtv{nullptr, nullptr, nullptr, nullptr, 0u, 0u};
-        const uint32_t* kc_flags = g_ctx.kc.d_flags;
-        const uint4* kc_tab = g_ctx.kc.d_tab;
-        const bool node_kc = kcv.hmask != 0;
-        bool xt_only = false;
-        if (g_ctx.xt_use) {  // a later sub-batch of a pipelined host call: the call's shared tables
-            const PvKeyCacheView xv{g_ctx.xt.htab, g_ctx.xt.keys, g_ctx.xt.flags, g_ctx.xt.tab, PV_XT_HASH - 1,
-                                    g_ctx.kw.seed};
-            if (node_kc) {  // the node cache first, then the shared store for the keys it misses
-                xtv = xv;
-            } else {        // the shared store is the only view
-                kcv = xv;
-                kc_flags = g_ctx.xt.flags;
-                kc_tab = g_ctx.xt.tab;
-                xt_only = true;
-            }
-        }
-        const bool kc_active = kcv.hmask != 0;
-        const bool keyed = g_ctx.path == PV_PATH_COMB ||
-                           (g_ctx.path == PV_PATH_AUTO &&
-                            (m >= PV_KEYED_MIN || g_ctx.keyed_hint || dev_choice || kc_active));
-        Gate gate{nullptr, nullptr};
-        g_ctx.last_keyed = keyed;
-        if (keyed) g_ctx.last_nkeys = g_ctx.kw.nkeys;
-        KeyWork kw = g_ctx.kw;
-        kw.min_req = g_ctx.path == PV_PATH_COMB ? 1u : (uint32_t)PV_COMB_MIN_REQ;
-        // Table reuse: the chunk's keys are looked up in the resident-table directory as well, and the
-        // scan's allocator keeps what it builds off the listed slots. It decides where a table is read
-        // from and nothing else: kc_active, keyed and the scan's candidate rule do not see it. Sub-batch 0
-        // of a pipelined host call builds into the call's store, not into ctab: it stays outside.
-        const bool dir_use = g_ctx.dir_on && !g_ctx.xt_fill;
-        kw.kc_on = kc_active || dir_use ? 1u : 0u;
-        kw.dir_on = dir_use ? 1u : 0u;
-        kw.dir_cap = g_ctx.dir_cap;
-        kw.dir_pub = dir_use && m > PV_SPARSE_CHUNK ? 1u : 0u;  // direct_fill below: the tables are whole
-        kw.aff_conv = kw.dir_pub && g_ctx.aff_on ? 1u : 0u;
-        // Wide rows: the pool is allocated by the first dense chunk that can widen a table -- the fourth since
-        // pv_init at the earliest (build, first hit, affine rows, then this) -- and not at pv_init. When the
-        // allocation fails the feature turns itself off and says so once through the error string.
-        // A pool that has to grow (pv_table_wide) is replaced: that call marked the directory dirty already.
-        const uint64_t wide_want = (uint64_t)g_ctx.wide_cap * PV_KR_POS * PV_KR_ENT * PV_BCOMB_STRIDE * 4;
-        if (keyed && kw.dir_pub && !g_ctx.wide_failed && g_ctx.d_wide.cap < wide_want && ++g_ctx.wide_dense >= 4) {
-            if (g_ctx.d_wide.grow(wide_want) != PV_OK ||
-                g_ctx.d_wide_scr.grow((uint64_t)PV_WIDE_GRID * PV_KR_RUN * 10 * PV_WIDE_THREADS * 4) != PV_OK) {
-                (void)hipGetLastError();  // clear the failed allocation's sticky error
-                g_ctx.d_wide.release();
-                g_ctx.d_wide_scr.release();
-                g_ctx.wide_failed = true;
-                (void)fail(PV_ERR_ALLOC, "wide rows of resident tables: no memory for the pool, the feature is off");
-            }
-        }
-        kw.wide_tab = g_ctx.d_wide.as<uint4>();
-        kw.wide_scr = g_ctx.d_wide_scr.as<uint32_t>();
-        const uint64_t wide_have = g_ctx.d_wide.cap / ((uint64_t)PV_KR_POS * PV_KR_ENT * PV_BCOMB_STRIDE * 4);
-        kw.wide_cap = dir_use ? (uint32_t)std::min<uint64_t>(g_ctx.wide_cap, wide_have) : 0u;
-        kw.wide_conv = kw.dir_pub && kw.wide_cap ? 1u : 0u;
-        kw.chunk_n = (uint32_t)m;
-        // a key-id segment holds the owners among its waves (every PV_NSEG-th wave of the chunk)
-        kw.seg_cap = (uint32_t)((((m + 63) / 64) + PV_NSEG - 1) / PV_NSEG * 64);
-        kw.lat_choice = dev_choice ? 1u : 0u;
-        kw.kc_tab = kc_tab;
-        kw.kc_ntab = xt_only ? nullptr : g_ctx.kc.d_ntab;
-        kw.kc_wtab = xt_only ? nullptr : g_ctx.kc.d_wtab;
-        kw.kc_wcap = xt_only ? 0u : g_ctx.kc.wcap;
-        kw.xt_flags = xtv.hmask ? g_ctx.xt.flags : nullptr;
-        kw.xt_tab = xtv.hmask ? g_ctx.xt.tab : nullptr;
-        kw.dense_only = 0;
-        if (g_ctx.xt_fill) {  // sub-batch 0 of a pipelined host call: its tables go to the shared store, whole
-            kw.ctab = g_ctx.xt.tab;
-            kw.kcap = std::min<uint32_t>(kw.kcap, PV_XT_KEYS);
-            kw.dense_only = 1;
-        }
-        const uint32_t limit = kw.kcap;  // comb keys a chunk can hold (launch grids of the key stream)
-        // a chunk above PV_SPARSE_CHUNK never fills sparsely: its fill follows the chain on kstream
-        const bool direct_fill = m > PV_SPARSE_CHUNK;
-        if (keyed) {
-            // the hash table and need masks are left empty by the previous keyed chunk (unpermute and
-            // sparse fill kernels); after an enqueue failure they may not be, and are cleared here
-            if (g_ctx.slots_dirty) {
-                PV_HIP(hipMemsetAsync(kw.slot, 0xFF, (uint64_t)(kw.hmask + 1) * 4, stream), PV_ERR_LAUNCH);
-                PV_HIP(hipMemsetAsync(kw.slot_cnt, 0, (uint64_t)(kw.hmask + 1) * 4 * PV_RANK_SUB, stream),
-                       PV_ERR_LAUNCH);
-                PV_HIP(hipMemsetAsync(kw.need, 0, (uint64_t)PV_ALLCOMB_KEYS * PV_COMB_POS * 5 * 4, stream),
-                       PV_ERR_LAUNCH);
-            }
-            g_ctx.slots_dirty = true;  // until this chunk's unpermute kernel is enqueued
-            // the directory likewise: emptied here when it may be stale, stale until the chunk is enqueued
-            // whole. A chunk outside it builds into ctab[j], over whatever is listed.
-            if (dir_use && g_ctx.dir_dirty) {
-                PV_HIP(hipMemsetAsync(kw.dir_htab, 0xFF, (uint64_t)PV_DIR_HASH * 4, stream), PV_ERR_LAUNCH);
-                PV_HIP(hipMemsetAsync(kw.dir_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);
-                PV_HIP(hipMemsetAsync(kw.wide_cnt, 0, 2 * 4, stream), PV_ERR_LAUNCH);  // the pool empties with it
-            }
-            if (!g_ctx.xt_fill) g_ctx.dir_dirty = true;
-            // kw.nkeys is cleared by pv_key_insert_lds_kernel (m >= 1 here: the grid has a thread 0)
-            if (PV_KEY_SEED > 0 && m > 16ull * PV_KEY_SEED) {  // small chunks: no contention worth a launch
-                const uint64_t ms = std::min<uint64_t>(m, PV_KEY_SEED);
-                PV_LAUNCH(pv_key_seed_kernel, dim3((unsigned)((ms + PV_BLOCK - 1) / PV_BLOCK)), dim3(PV_BLOCK), 0,
-                          stream, d_pk + 32 * c0, ms, kw);
-            }
-            PV_LAUNCH(pv_key_insert_lds_kernel, dim3((unsigned)((m + PV_INS_REQS - 1) / PV_INS_REQS)),
-                      dim3(PV_INS_THREADS), 0, stream, d_pk + 32 * c0, m, kw);
-            PV_LAUNCH(pv_key_assign_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
-            if (kc_active || dir_use) {
-                PvKeyCacheView dirv{kw.dir_htab, kw.dir_keys, kw.dir_flags, kw.ctab, dir_use ? PV_DIR_HASH - 1 : 0u,
-                                    kw.seed};
-                PV_LAUNCH(pv_key_cache_probe_kernel, dim3((PV_NSEG * kw.seg_cap + PV_BLOCK - 1) / PV_BLOCK),
-                          dim3(PV_BLOCK), 0, stream, d_pk + 32 * c0,
-                          kw, kcv, xtv, dirv);
-            }
-            gate = Gate{kw.nkeys, kw.slot_req};
-            // key-sorted slot order: comb keys' requests first, then the Straus requests
-            PV_LAUNCH(pv_key_scan_kernel, dim3(1), dim3(PV_SCAN_THREADS), 0, stream, kw, kc_flags);
-            // the per-key chain (few, long-latency lanes) and the table fill run on kstream, overlapped
-            // with the scatter and the per-request prep on the main stream: the chain needs only the
-            // scan's comb-key list (comb_key, comb_cslot), so kstream forks before the scatter
-            PV_HIP(hipEventRecord(g_ctx.ev_scan_done, stream), PV_ERR_LAUNCH);
-            PV_HIP(hipStreamWaitEvent(g_ctx.kstream, g_ctx.ev_scan_done, 0), PV_ERR_LAUNCH);
-            PV_LAUNCH(pv_key_scatter_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw);
-            PV_HIP(hipEventRecord(g_ctx.ev_keys_ready, stream), PV_ERR_LAUNCH);
-            // one chain launch over all positions, then the fill. direct_fill: back to back on kstream
-            // and the tables-ready event right after the fill (no event hop to fstream, no gated
-            // sparse-fill launch in the dependency chain of the comb kernel). Otherwise the fill runs on
-            // fstream, where the sparse fill follows it (below).
-            const uint64_t items = (uint64_t)limit * PV_COMB_POS * PV_COMB_BLOCKS;
-            const unsigned fgrid = (unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096);
-            hipStream_t fs = direct_fill ? g_ctx.kstream : g_ctx.fstream;
-            PV_LAUNCH(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(limit, PV_LP_CHAIN_BLOCKS)), dim3(64), 0,
-                      g_ctx.kstream, d_pk + 32 * c0, kw, gate, 0, PV_COMB_POS);
-            if (!direct_fill) {
-                PV_HIP(hipEventRecord(g_ctx.ev_chain, g_ctx.kstream), PV_ERR_LAUNCH);
-                PV_HIP(hipStreamWaitEvent(fs, g_ctx.ev_chain, 0), PV_ERR_LAUNCH);
-            }
-            PV_LAUNCH(pv_key_fill_kernel, dim3(fgrid), dim3(PV_BLOCK), 0, fs, kw, gate, 0, PV_COMB_POS);
-            if (direct_fill) PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.kstream), PV_ERR_LAUNCH);
-        }
-        if ((rc = mark(PV_STAGE_PREP))) return rc;
-        if (keyed) {
-            // The Straus-path slots of a split chunk (keys without a table: usually a few
-            // thousand one-off requests) run on their own stream beside the comb kernels: their
-            // waves take ~1 ms from start to end however few they are, which on the main stream
-            // would delay the whole comb path. Their blocks are dispatched from the END of the slot
-            // range (where the Straus slots are), and blocks of comb slots exit at once.
-            hipStream_t ss = g_ctx.sstream;
-#ifndef PV_SIDE_GRID_PER_CU
-#define PV_SIDE_GRID_PER_CU 2
-#endif
-            const unsigned sgrid = std::min<unsigned>(
-                grid, std::max(1u, (unsigned)(PV_SIDE_GRID_PER_CU * std::max(1, g_ctx.cus))));
-            PV_HIP(hipStreamWaitEvent(ss, g_ctx.ev_keys_ready, 0), PV_ERR_LAUNCH);
-            PV_LAUNCH_BC2(pv_prep_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m,
-                               d_pk + 32 * c0, g_ctx.work, gate);
-            PV_LAUNCH_BC2(pv_split_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.work, gate);
-            PV_LAUNCH(pv_table_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, d_pk + 32 * c0,
-                      g_ctx.work, gate);
-            PV_LAUNCH_BC2(pv_msm_kernel, dim3(sgrid), dim3(PV_BLOCK), 0, ss, d_sm, d_off + c0, m, g_ctx.d_btab,
-                          g_ctx.work, g_ctx.d_bc2, gate);
-            PV_HIP(hipEventRecord(g_ctx.ev_straus_done, ss), PV_ERR_LAUNCH);
-            PV_LAUNCH_BC2(pv_comb_prep_req_kernel, dim3(grid), dim3(PV_BLOCK), g_ctx.prep_lds_pad, stream, d_sm,
-                          d_off + c0, m, d_pk + 32 * c0, g_ctx.work, kw, gate);
-            if (!direct_fill) {
-                // a small chunk's sparse table fill (needs the chain's bases and the need masks comb_prep
-                // writes) runs on fstream after the full fill; for a large chunk it exits at once
-                PV_HIP(hipEventRecord(g_ctx.ev_prep_done, stream), PV_ERR_LAUNCH);
-                PV_HIP(hipStreamWaitEvent(g_ctx.fstream, g_ctx.ev_prep_done, 0), PV_ERR_LAUNCH);
-                PV_LAUNCH(pv_key_fill_sparse_kernel, dim3(PV_ALLCOMB_KEYS * PV_COMB_POS / PV_BLOCK),
-                          dim3(PV_BLOCK), 0, g_ctx.fstream, kw, gate);
-                PV_HIP(hipEventRecord(g_ctx.ev_tables_ready, g_ctx.fstream), PV_ERR_LAUNCH);
-            }
-            // the per-request results to slot-ordered rows, while the key stream finishes the tables
-            PV_LAUNCH_BC2(pv_comb_digits_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, g_ctx.work, kw, gate);
-            if ((rc = mark(PV_STAGE_TABLE))) return rc;
-            const bool fused = m > PV_FUSED_MIN_REQ;
-            if (!fused) {  // [S]B while the key stream finishes the tables, then join
-                PV_LAUNCH_BC2(pv_comb_b_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
-                              gate);
-            }
-            PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_tables_ready, 0), PV_ERR_LAUNCH);
-            if ((rc = mark(PV_STAGE_MSM))) return rc;
-            if (fused)  // [S]B + [k](-A) in one kernel as soon as the tables are built
-                PV_LAUNCH_BC2(pv_comb_ab_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, g_ctx.d_bc2,
-                              gate);
-            else
-                PV_LAUNCH(pv_comb_a_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, g_ctx.work, kw, gate);
-            PV_HIP(hipStreamWaitEvent(stream, g_ctx.ev_straus_done, 0), PV_ERR_LAUNCH);
-        } else {
-            PV_LAUNCH_BC2(pv_prep_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
-                               d_pk + 32 * c0, g_ctx.work, gate);
-            PV_LAUNCH_BC2(pv_split_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.work, gate);
-            if ((rc = mark(PV_STAGE_TABLE))) return rc;
-            PV_LAUNCH(pv_table_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, d_pk + 32 * c0,
-                      g_ctx.work, gate);
-            if ((rc = mark(PV_STAGE_MSM))) return rc;
-            PV_LAUNCH_BC2(pv_msm_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m, g_ctx.d_btab,
-                          g_ctx.work, g_ctx.d_bc2, gate);
-        }
-        if ((rc = mark(PV_STAGE_ENCODE))) return rc;
-        if (m >= PV_ENC16_MIN) {
-            const unsigned egrid = (unsigned)((m + PV_BLOCK * 16 - 1) / (PV_BLOCK * 16));
-            PV_LAUNCH(pv_encode_kernel<16>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
-                      g_ctx.work, d_verdict + c0 / 64, kw, gate);
-        } else {
-            const unsigned egrid = (unsigned)((m + PV_BLOCK * PV_ENC_SMALL_B - 1) / (PV_BLOCK * PV_ENC_SMALL_B));
-            PV_LAUNCH(pv_encode_kernel<PV_ENC_SMALL_B>, dim3(egrid), dim3(PV_BLOCK), 0, stream, d_sm, d_off + c0, m,
-                      g_ctx.work, d_verdict + c0 / 64, kw, gate);
-        }
-        if (keyed) {
-            PV_LAUNCH(pv_unpermute_kernel, dim3(grid), dim3(PV_BLOCK), 0, stream, m, kw,
-                      d_verdict + c0 / 64, gate);
-            g_ctx.slots_dirty = false;
-            if (g_ctx.xt_fill) {  // publish this chunk's tables for the call's later sub-batches
-                PV_LAUNCH(pv_xtab_publish_kernel, dim3(PV_XT_KEYS / PV_BLOCK), dim3(PV_BLOCK), 0, stream,
-                          d_pk + 32 * c0, kw, g_ctx.xt.htab, PV_XT_HASH - 1, g_ctx.kw.seed, g_ctx.xt.keys,
-                          g_ctx.xt.flags);
-            }
-            if (dir_use) {
-                if (kw.dir_pub) {  // list this chunk's tables for the chunks and calls that follow
-                    PV_LAUNCH(pv_dir_publish_kernel, dim3((limit + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0,
-                              stream, d_pk + 32 * c0, kw);
-                }
-                if (kw.aff_conv) {  // the listed tables this chunk hit: affine rows for the chunks that follow
-                    PV_LAUNCH(pv_dir_affine_kernel, dim3(PV_AFF_CAP), dim3(PV_AFF_THREADS), 0, stream, kw);
-                }
-                if (kw.wide_conv) {  // the affine tables this chunk hit: radix-2^11 rows for the chunks that follow
-                    PV_LAUNCH(pv_dir_widen_kernel, dim3(PV_WIDE_GRID), dim3(PV_WIDE_THREADS), 0, stream, kw);
-                }
-                g_ctx.dir_dirty = false;
-            }
-            if (dev_choice) {  // runs only when the scan picked latency (the words were zeroed above)
-                rc = pv_latency_launch(d_sm, d_off + c0, m, d_pk + 32 * c0, g_ctx.d_bcomb, kc_view(),
-                                       d_verdict + c0 / 64, true, stream, kw.nkeys + PV_SPLIT_LAT);
-                if (rc) return rc;
-            }
-        }
-        if ((rc = mark(PV_NSTAGES))) return rc;
+        if ((rc = L.mark(PV_STAGE_ENCODE)) || (rc = L.mark(PV_NSTAGES))) return rc;
+        return PV_OK;
     }
-    return PV_OK;
+    PvKeyCacheView kcv = kc_view(), xtv;
+    pvhost::ChunkFacts f{};
+    f.m = m;
+    f.path = g_ctx.path;
+    f.keyed_hint = g_ctx.keyed_hint;
+    f.node_kc = kcv.hmask != 0;
+    f.kc_wcap = g_ctx.kc.wcap;
+    f.xt_use = g_ctx.xt_use;
+    f.xt_fill = g_ctx.xt_fill;
+    f.dir_on = g_ctx.dir_on;
+    f.dir_cap = g_ctx.dir_cap;
+    f.aff_on = g_ctx.aff_on;
+    f.wide_cap = g_ctx.wide_cap;
+    f.kcap = g_ctx.kw.kcap;
+    f.cus = g_ctx.cus;
+    f.slots_dirty = g_ctx.slots_dirty;
+    f.dir_dirty = g_ctx.dir_dirty;
+    const bool keyed = pvhost::chunk_keyed(batch, f);
+    g_ctx.last_keyed = keyed;
+    if (keyed) g_ctx.last_nkeys = g_ctx.kw.nkeys;
+    const uint64_t wide_want = (uint64_t)g_ctx.wide_cap * PV_WIDE_TABLE_BYTES;
+    const pvhost::WideTrigger wt = pvhost::plan_wide_pool(keyed, pvhost::chunk_dir_pub(f), g_ctx.wide_failed,
+                                                         g_ctx.d_wide.cap, wide_want, g_ctx.wide_dense);
+    g_ctx.wide_dense = wt.dense;
+    if (wt.attempt) wide_pool_attempt(wide_want);
+    f.wide_have = g_ctx.d_wide.cap / PV_WIDE_TABLE_BYTES;
+    p = pvhost::plan_chunk(batch, f);
+    const uint32_t* kc_flags;
+    apply_plan(p, kw, kcv, xtv, kc_flags);
+    if (p.keyed) {
+        L.gate = Gate{kw.nkeys, kw.slot_req};
+        if ((rc = launch_key_stage(L, kcv, xtv, kc_flags))) return rc;
+    }
+    if ((rc = L.mark(PV_STAGE_PREP))) return rc;
+    if (p.keyed) {
+        if ((rc = launch_straus_side(L)) || (rc = launch_comb_stage(L))) return rc;
+    } else {
+        if ((rc = launch_straus_only(L))) return rc;
+    }
+    if ((rc = L.mark(PV_STAGE_ENCODE))) return rc;
+    if ((rc = launch_epilogue(L))) return rc;
+    return L.mark(PV_NSTAGES);
 }
 
 int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const uint8_t* d_pk, uint64_t* d_verdict,
@@ -2076,19 +2048,10 @@ int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const 
     const uint64_t cap = g_ctx.work.stride;
     const int nchunks = (int)((n + cap - 1) / cap);
     constexpr int NE = PV_NSTAGES + 1;
-    // small batches: one wave pair per request (pv_latency.hip); forced LATENCY takes it at any size.
-    // Between PV_KEYED_HINT_MIN and PV_LATENCY_MAX requests AUTO picks by key repeats: the host-buffer
-    // call counted the keys (keyed_hint, hint_set); a device-buffer call lets the dedup kernels count
-    // them and decide on the device (dev_choice: the keyed kernels exit at once and the latency kernel
-    // runs when the scan picks latency; no host round trip). A non-empty key cache keeps the latency
-    // path there (cached keys make it faster still).
-    const bool kc_nonempty = kc_view().hmask != 0;
-    const bool dev_choice = g_ctx.path == PV_PATH_AUTO && !g_ctx.hint_set && !kc_nonempty &&
-                            n >= PV_KEYED_HINT_MIN && n <= PV_LATENCY_MAX;
-    const bool latency = g_ctx.path == PV_PATH_LATENCY ||
-                         (g_ctx.path == PV_PATH_AUTO && n <= PV_LATENCY_MAX && !g_ctx.keyed_hint && !dev_choice);
-    g_ctx.last_latency = latency;
-    g_ctx.last_dev_choice = dev_choice;
+    const pvhost::BatchPlan batch =
+        pvhost::plan_batch({g_ctx.path, n, g_ctx.hint_set, g_ctx.keyed_hint, kc_view().hmask != 0});
+    g_ctx.last_latency = batch.latency;
+    g_ctx.last_dev_choice = batch.dev_choice;
     int evb = 0;
     if (g_ctx.timing) {
         evb = g_ctx.ev_used;
@@ -2098,7 +2061,7 @@ int launch_chunks(const uint8_t* d_sm, const uint64_t* d_off, uint64_t n, const 
     }
     int rc = PV_OK;
     for (int c = 0; c < nchunks && rc == PV_OK; c++)
-        rc = launch_chunk(c, n, d_sm, d_off, d_pk, d_verdict, stream, latency, dev_choice, evb);
+        rc = launch_chunk(c, n, d_sm, d_off, d_pk, d_verdict, stream, batch, evb);
     return rc;
 }
 
@@ -2355,11 +2318,9 @@ int kc_build_tables(const pvhost::KcIndex::Assigned& put, bool async) {
         PV_HIP(hipMemcpyAsync(k.d_put_slot, bslot, (uint64_t)m * 4, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
         PV_LAUNCH(pv_kc_put_prep_kernel, dim3((m + PV_BLOCK - 1) / PV_BLOCK), dim3(PV_BLOCK), 0, s, kw, m);
         const Gate gate{kw.nkeys, kw.slot_req};
-        PV_LAUNCH(pv_key_chain_lp_kernel, dim3(std::min<uint32_t>(m, PV_LP_CHAIN_BLOCKS)), dim3(64), 0, s,
-                  k.d_put_pk, kw, gate, 0, PV_COMB_POS);
-        const uint64_t items = (uint64_t)m * PV_COMB_POS * PV_COMB_BLOCKS;
-        PV_LAUNCH(pv_key_fill_kernel, dim3((unsigned)std::min<uint64_t>((items + PV_BLOCK - 1) / PV_BLOCK, 4096)),
-                  dim3(PV_BLOCK), 0, s, kw, gate, 0, PV_COMB_POS);
+        PV_LAUNCH(pv_key_chain_lp_kernel, dim3(pvhost::chain_blocks(m)), dim3(64), 0, s, k.d_put_pk, kw, gate, 0,
+                  PV_COMB_POS);
+        PV_LAUNCH(pv_key_fill_kernel, dim3(pvhost::fill_grid(m)), dim3(PV_BLOCK), 0, s, kw, gate, 0, PV_COMB_POS);
         PV_LAUNCH(pv_kc_scatter_kernel, dim3(64, m), dim3(PV_BLOCK), 0, s, kw.ctab, kw.key_flag, k.d_put_pk,
                   k.d_put_slot, m, k.d_tab, k.d_flags, k.d_keys);
         if (k.d_ntab) {

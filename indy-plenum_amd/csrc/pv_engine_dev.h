@@ -7,10 +7,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "chunk_plan.h"  // PV_BLOCK, PV_KEY_CAP and the thresholds the launch rules read
 #include "comb.h"
 #include "lp25519.h"
-
-static constexpr int PV_BLOCK = 256;
 
 // Dynamic LDS requested by every pv_comb_prep_req_kernel workgroup, unused: it caps the kernel's residency
 // so that the key chain, launched beside it on the key stream, finds a wave slot on every SIMD at
@@ -22,17 +21,7 @@ static constexpr int PV_BLOCK = 256;
 #define PV_PREP_LDS_PAD 41984
 #endif
 static constexpr uint64_t PV_CHUNK = 1ull << 20;  // requests per launch sequence (workspace ~1.8 GB)
-static constexpr uint32_t PV_KEY_CAP = 16384;     // distinct keys the comb tables hold (10.8 GB)
-// AUTO: chunks above the latency path's range go keyed (dedup, then comb keys / Straus side). At
-// medium sizes (4k-256k requests) the Straus side's one-lane latency (~0.9 ms) is paid by the whole
-// launch as soon as it has any request, so a chunk with few distinct keys makes EVERY key a comb
-// key (PV_ALLCOMB_*): tools/latency_probe.py on MI355X, 1,024 signers, device time per call --
-// 10k requests 0.77 ms all-comb vs 0.91 Straus, 32k 0.76 vs 0.95 (and 1.02 split at >= 48 requests
-// per key); bounded so the fill never exceeds 2,048 keys' tables (~0.5 ms).
-static constexpr uint64_t PV_KEYED_MIN = 4097;
-static constexpr uint32_t PV_ALLCOMB_KEYS = 2048;
-static constexpr uint32_t PV_ALLCOMB_CHUNK = 262144;
-static constexpr uint32_t PV_XT_KEYS = 2048;      // tables shared by a pipelined call's sub-batches (1.35 GB)
+static constexpr uint32_t PV_ALLCOMB_CHUNK = 262144;  // the all-comb rule of chunk_plan.h PV_ALLCOMB_KEYS: chunks up to this size
 static constexpr uint32_t PV_XT_HASH = 4096;      // their hash table (>= 2 x keys)
 static constexpr uint32_t PV_DIR_HASH = 2 * PV_KEY_CAP;  // hash words of the resident-table directory (KeyWork::dir_*)
 // Slots the directory lists by default: the rest of ctab is scratch for the tables of a chunk that lists
@@ -40,15 +29,6 @@ static constexpr uint32_t PV_DIR_HASH = 2 * PV_KEY_CAP;  // hash words of the re
 // AUTO (all-comb, or PV_SPARSE_CHUNK / PV_COMB_MIN_REQ of them, or keys whose tables exist already). Only
 // forced PV_PATH_COMB (every key a comb key) can bring more misses than fit, and then resets the directory.
 static constexpr uint32_t PV_DIR_DEFAULT_CAP = PV_KEY_CAP - PV_ALLCOMB_KEYS;
-#ifndef PV_LATENCY_MAX
-#define PV_LATENCY_MAX 4096  // AUTO: batches up to this size take the latency path (pv_latency.hip)
-#endif
-// AUTO picks latency vs keyed by key repeats from this size up to PV_LATENCY_MAX (pv_keyed_hint on
-// the host, the dedup's lat_choice on the device)
-#ifndef PV_KEYED_HINT_MIN
-#define PV_KEYED_HINT_MIN 2049
-#endif
-
 // Radix of the wide fixed-base comb chosen at pv_init: PV_BC2_W (24: 10.7 GB of HBM) or, when that
 // allocation fails (or PV_FORCE_BCOMB16 is set), W = 16 over the radix-65536 comb T_B the latency
 // path already holds (the same layout and digits: comb.h). Kernels that recode or read S's digits
@@ -100,7 +80,6 @@ static constexpr int PV_SPLIT_SLOTS = 2;       // requests (slots) of those keys
 static constexpr int PV_SPLIT_SPARSE = 3;      // 1: the comb tables are filled sparsely (small chunk)
 static constexpr int PV_SPLIT_LAT = 4;         // 1: the dedup chose the latency path for this chunk
 static constexpr uint32_t PV_SPLIT_WORDS = 8;  // counters cleared per keyed chunk
-static constexpr uint32_t PV_NSEG = 8;         // key-id segments (pv_key_assign_kernel)
 // segment g's id counter: word PV_SEG_BASE + g * PV_SEG_STRIDE of the split buffer, one counter per
 // 1 KB so that the segments' atomics land on different memory channels (same-line counters
 // serialise like one)

@@ -496,15 +496,15 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
     if (!offsets_nondecreasing(sm_off, n)) return fail(PV_ERR_ARG, "sm_off must be non-decreasing");
     std::lock_guard<std::mutex> lk(g_mu);
     {
-        // a small call that takes the latency path (the same choice launch_chunks makes for a host-buffer
-        // call) and whose records fit a 2 KB slot: the kernel reads the pinned staging slots over PCIe
-        // and stores one verdict byte per request back -- no copy kernels around it
+        // a small call that takes the latency path (plan_batch, chunk_plan.h: the choice launch_chunks makes
+        // for a host-buffer call, which sets the hint it counted; the cache's state is not read then) and
+        // whose records fit a 2 KB slot: the kernel reads the pinned staging slots over PCIe and stores one
+        // verdict byte per request back -- no copy kernels around it
         uint64_t maxlen = 0;
         for (uint64_t i = 0; i < n && n <= PV_ZC_MAX_REQ; i++) maxlen = std::max(maxlen, sm_off[i + 1] - sm_off[i]);
         const uint64_t stride = (4ull * PV_ZC_REC_WORD + maxlen + PV_ZC_SLACK + 63) & ~63ull;
         if (!g_ctx.timing && n <= PV_ZC_MAX_REQ && stride <= PV_ZC_MAX_STRIDE &&
-            (g_ctx.path == PV_PATH_LATENCY ||
-             (g_ctx.path == PV_PATH_AUTO && n <= PV_LATENCY_MAX && !pv_keyed_hint(pk, n)))) {
+            pvhost::plan_batch({g_ctx.path, n, true, pv_keyed_hint(pk, n), false}).latency) {
             int rc = ensure_stage(n * stride, 0);
             if (rc) return rc;
             uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
