@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <random>
 #include <vector>
 
@@ -158,5 +159,18 @@ class AdmitTableT {
 
 // 2^17 entries (5.2 MB, allocated on first use): windows of 32,768 distinct keys
 using AdmitTable = AdmitTableT<17>;
+
+// The requests of a host batch of n whose keys are counted: all of a batch of <= max_batch (an empty
+// sample), else one request from each block of ceil(n / max_batch), at a hashed position in the block (a
+// fixed stride would alias with periodic signer orders).
+__attribute__((visibility("hidden"))) inline std::vector<uint64_t> admit_sample(uint64_t n, uint64_t max_batch) {
+    std::vector<uint64_t> sample;
+    if (n <= max_batch) return sample;
+    const uint64_t stride = (n + max_batch - 1) / max_batch;
+    sample.reserve(n / stride + 1);
+    for (uint64_t b = 0, t = 0; b < n; b += stride, t++)
+        sample.push_back(b + ((t * 0x9E3779B97F4A7C15ull) >> 40) % std::min(stride, n - b));
+    return sample;
+}
 
 }  // namespace pvhost

@@ -1,6 +1,11 @@
-// libplenum_verify: the host-buffer entries of the verification engine. pv_verify_batch (zero-copy form
-// for small calls, else stage_and_launch: pinned staging, the sub-batch H2D pipeline on the copy stream),
-// the pinned-memory registry and cache (pv_host_*), the copy workers, the host-side key-repeat hint,
+// libplenum_verify: the host-buffer entries of the verification engine. pv_verify_batch reads: validate,
+// lock, the zero-copy form if the gate says so (verify_zero_copy), otherwise stage_and_launch, copy back,
+// admit. stage_and_launch plans the call (host_plan.h: layout, sub-batch bounds, form), sizes the staging
+// and runs one of two straight-line forms: stage_one_dma (one host copy, one DMA, the kernels) or
+// stage_pipelined (per sub-batch: pinned staging, H2D on the copy stream, kernels on the engine stream).
+// What depends on numbers alone is decided in host_plan.h and kc_admit.h and tested on a CPU; this file
+// reads the facts and enqueues. The environment is read in three places: PV_PINNED_CACHE_MB, PV_PIPE_SUB,
+// PV_ENABLE_TEST_HOOKS. Also here: the pinned-memory registry and cache (pv_host_*), the copy workers,
 // automatic key-cache admission after a batch, and the ordered copies (pv_memcpy_*, pv_dev_alloc). No
 // kernel is defined here: everything is enqueued through pv_engine.hip's launch() and pv_latency.hip.
 #include <hip/hip_runtime.h>
@@ -15,6 +20,7 @@
 #include <vector>
 
 #include "copy_pool.h"
+#include "host_plan.h"
 #include "kc_admit.h"
 #include "keycache.h"
 #include "pv_ctx.h"
@@ -90,9 +96,6 @@ static int pv_stage_to_device(uint8_t* d_dst, uint8_t* h_stage, const uint8_t* s
     return err.load() ? fail(PV_ERR_LAUNCH, "hipMemcpyAsync (request blob) failed") : PV_OK;
 }
 
-#ifndef PV_KC_AUTO_MAX_BATCH
-#define PV_KC_AUTO_MAX_BATCH 4096  // automatic admission counts every key of host batches up to this size (a sample above)
-#endif
 // Automatic admission: count the VERIFIED appearances of this batch's keys (idx: the sampled requests,
 // or null for all n; pre: each one's entry located by kc_auto_locate while the kernels ran, or -1); the
 // keys reaching auto_min appearances in the window are returned, at most kcap of them. The verdicts are
@@ -129,45 +132,14 @@ static void kc_auto_locate(const uint8_t* pk, const uint64_t* idx, uint64_t n, s
 static bool pv_keyed_hint(const uint8_t* pk, uint64_t n) {
     if (g_ctx.path != PV_PATH_AUTO || n < PV_KEYED_HINT_MIN || n > PV_LATENCY_MAX) return false;
     if (g_ctx.kc.enabled && !g_ctx.kc.index.empty()) return false;
-    // distinct keys by open addressing on the keys' first 16 bytes (a heuristic: a rare collision
-    // only miscounts, the verdicts do not depend on the path)
-    constexpr uint32_t H = 16384;  // > 2 x PV_LATENCY_MAX
-    static_assert(H >= 2 * PV_LATENCY_MAX, "hint table too small");
-    static thread_local std::vector<uint64_t> tab;
-    tab.assign(2 * H, 0);
-    uint64_t distinct = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        uint64_t a, b;
-        memcpy(&a, pk + 32 * i, 8);
-        memcpy(&b, pk + 32 * i + 8, 8);
-        a |= 1;  // (0, 0) marks an empty entry
-        uint32_t h = (uint32_t)((a * 0x9E3779B97F4A7C15ull) >> 50) & (H - 1);
-        while (tab[2 * h] && !(tab[2 * h] == a && tab[2 * h + 1] == b)) h = (h + 1) & (H - 1);
-        if (!tab[2 * h]) {
-            tab[2 * h] = a;
-            tab[2 * h + 1] = b;
-            distinct++;
-        }
-    }
-    return distinct <= PV_ALLCOMB_KEYS && 3 * distinct <= n;
+    return pvhost::few_distinct_keys(pk, n);
 }
 
-// Requests per sub-batch of the pipelined host-buffer form (a multiple of 64; env PV_PIPE_SUB overrides
-// it for A/Bs). Sub-batch j's H2D runs on the copy stream while sub-batch j-1's kernels run, so a large
-// host batch costs about its PCIe time plus the last sub-batch's kernels instead of their sum.
-#ifndef PV_PIPE_SUB
-#define PV_PIPE_SUB 262144
-#endif
-#ifndef PV_PIPE_END_DEFAULT
-#define PV_PIPE_END_DEFAULT (PV_PIPE_SUB / 2)
-#endif
-static constexpr uint64_t PV_PIPE_MAX = 64;                // sub-batches per call (copy events)
-static constexpr uint64_t PV_PIPE_MIN_BLOB = 8ull << 20;   // smaller blobs: one piece
+// Requests per sub-batch of the pipelined form: the environment's PV_PIPE_SUB, read once, else the default.
 static uint64_t pipe_sub() {
     static const uint64_t v = [] {
         const char* e = getenv("PV_PIPE_SUB");
-        const uint64_t x = e && *e ? strtoull(e, nullptr, 10) : (uint64_t)PV_PIPE_SUB;
-        return std::max<uint64_t>(8192, x / 64 * 64);
+        return pvhost::pipe_sub_of(e && *e ? strtoull(e, nullptr, 10) : (uint64_t)PV_PIPE_SUB);
     }();
     return v;
 }
@@ -202,19 +174,13 @@ static int ensure_xtab() {
 int kc_auto_after_batch(const uint8_t* pk, uint64_t n, hipStream_t s, const uint8_t* vb, const uint64_t* hver) {
     auto& k = g_ctx.kc;
     const bool on = k.auto_min > 0 && k.cap > 0 && k.enabled && !k.broken;
-    // the requests counted: all of a batch of <= 4,096, else a sample of one request from each block of
-    // ceil(n / 4,096), at a hashed position in the block (a fixed stride would alias with periodic
-    // signer orders); their table entries are located while the kernels still run
+    // the requests counted: all of a batch of <= 4,096, else a sample (kc_admit.h admit_sample); their
+    // table entries are located while the kernels still run
     std::vector<uint64_t> sample;
     std::vector<int32_t> pre;
     uint64_t gen = 0;
     if (on) {
-        if (n > PV_KC_AUTO_MAX_BATCH) {
-            const uint64_t stride = (n + PV_KC_AUTO_MAX_BATCH - 1) / PV_KC_AUTO_MAX_BATCH;
-            sample.reserve(n / stride + 1);
-            for (uint64_t b = 0, t = 0; b < n; b += stride, t++)
-                sample.push_back(b + ((t * 0x9E3779B97F4A7C15ull) >> 40) % std::min(stride, n - b));
-        }
+        sample = pvhost::admit_sample(n, PV_KC_AUTO_MAX_BATCH);
         gen = k.seen.generation();
         kc_auto_locate(pk, sample.empty() ? nullptr : sample.data(), sample.empty() ? n : sample.size(), pre);
     }
@@ -274,216 +240,224 @@ bool offsets_nondecreasing(const uint64_t* off, uint64_t n) {
     return good.load();
 }
 
-// The copy form of a host-buffer batch on the calling thread's context: moves the keys, offsets and
-// records to the device staging area and enqueues the verification on the context's stream. d_out:
-// where the verdict words go (nullptr = the staging area's own verdict section); *dver / *hver receive
-// the device verdict section and a pinned buffer for the caller's copy back.
-//   * small batches (blob < 8 MB, no input in pinned memory): one host copy into pinned staging in the
-//     device layout, one DMA, the kernels (the quota sizes: fewest packets on the path);
-//   * otherwise, in sub-batches of pipe_sub() requests: the copy workers stage sub-batch j's pageable
-//     inputs (inputs inside pv_host_alloc / pv_host_register memory are not copied: the DMA reads them
-//     where they are), its H2D goes on the copy stream, and its kernels on the engine stream after an
-//     event -- so PCIe, host staging and kernels of consecutive sub-batches overlap.
-// Staging layout (host and device, 256-B aligned sections): [pk n*32][off (n+1) u64][verdict][blob +
-// PV_BLOB_SLACK]. A failure after DMAs were enqueued returns only after both streams drained, so no copy
-// still reads the caller's or the staging buffers.
-int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk, uint64_t* d_out,
-                            uint64_t** dver_out, uint64_t** hver_out) {
+namespace {
+
+// One staged call: the caller's pointers, the layout and the plan (host_plan.h), and the sections of the
+// host and device staging areas they resolve to.
+struct HostCall {
+    const uint8_t* sm;
+    const uint64_t* sm_off;
+    uint64_t n;
+    const uint8_t* pk;
+    uint64_t* d_out;      // where the verdict words go (nullptr: dver)
+    uint64_t base, blob;  // sm_off[0], and the records' bytes from there
+    pvhost::HostLayout lay;
+    pvhost::CallPlan plan;
+    uint8_t *h, *d;  // host (pinned) and device staging
+    uint64_t *hoff, *doff, *dver;
+    uint8_t *hblob, *dblob;
+};
+
+// Requests [lo, hi) of the call, staged on the device, enqueued on the engine stream.
+int launch_piece(const HostCall& k, uint64_t lo, uint64_t hi) {
     Ctx& c = g_ctx;
-    c.last_zero_copy = false;
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t pk_bytes = up(n * 32), off_bytes = up((n + 1) * 8), vwords = (n + 63) / 64;
-    const uint64_t v_bytes = up(vwords * 8);
-    const uint64_t base = sm_off[0], blob = sm_off[n] - base;
-    const uint64_t total = pk_bytes + off_bytes + v_bytes + blob + PV_BLOB_SLACK;
-    const bool pin_sm = pv_is_pinned(sm + base, blob), pin_pk = pv_is_pinned(pk, 32 * n);
-    const bool pin_off = base == 0 && pv_is_pinned(sm_off, 8 * (n + 1));
-    const bool any_pin = pin_sm || pin_pk || pin_off, all_pin = pin_sm && pin_pk && pin_off;
-    const uint64_t sub = pipe_sub();
-    // sub-batch bounds (64-aligned). The call ends one sub-batch's kernels after the last H2D, and
-    // the first sub-batch's kernels (which also build the shared tables) start only after the first
-    // H2D, so with >= 2 full sub-batches the first and the last are half-size
-    // (profiles/r05/host_path: 1M requests, 0.5 + 3 x 1 + 0.5 of 262,144)
-    std::vector<uint64_t> bnd{0};
-    static const bool halves = env_int("PV_PIPE_HALF_ENDS", 1) != 0;
-    // first / last piece size (env PV_PIPE_END, A/B): half a sub-batch by default. Smaller ends are slower
-    // (1M arena: 116.8-119.1 M/s at 131,072, 113.6-114.1 at 65,536, 110.4-112.7 at 32,768; profiles/r06/
-    // host_path/ab_pipe_end.txt): the copies are the critical path and a sub-batch's kernels beside a DMA
-    // take longer than a small last piece's copy, so the last FULL piece's kernels become the tail
-    static const uint64_t end_req = (uint64_t)std::max(8192, env_int("PV_PIPE_END", (int)(PV_PIPE_END_DEFAULT)));
-    if (blob >= PV_PIPE_MIN_BLOB && halves && n >= 3 * sub) {
-        const uint64_t h = std::min<uint64_t>(end_req, sub) / 64 * 64;
-        const uint64_t mid = n - 2 * h;
-        const uint64_t k = std::min<uint64_t>(PV_PIPE_MAX - 2, std::max<uint64_t>(1, (mid + sub / 2) / sub));
-        bnd.push_back(h);
-        for (uint64_t j = 1; j < k; j++) bnd.push_back(h + (mid * j / k) / 64 * 64);
-        bnd.push_back((n - h) & ~63ull);  // every bound a whole verdict word (n itself need not be)
-    } else if (blob >= PV_PIPE_MIN_BLOB) {
-        const uint64_t k = std::min<uint64_t>(PV_PIPE_MAX, std::max<uint64_t>(1, n / sub));
-        for (uint64_t j = 1; j < k; j++) bnd.push_back((n * j / k) & ~63ull);
-    }
-    bnd.push_back(n);
-    const uint64_t np = bnd.size() - 1;
+    c.verdict_zeroed = k.d_out == nullptr;
+    c.keyed_hint = pv_keyed_hint(k.pk + 32 * lo, hi - lo);
+    c.hint_set = true;
+    const int r = launch(k.dblob, k.doff + lo, hi - lo, k.d + 32 * lo, (k.d_out ? k.d_out : k.dver) + lo / 64, c.stream);
+    c.verdict_zeroed = false;
+    c.keyed_hint = false;
+    c.hint_set = false;
+    return r;
+}
+
+int injected_failure() {
+    g_ctx.inject_stage--;
+    return fail(PV_ERR_ALLOC, "stage_and_launch: injected staging failure (pv_test_inject)");
+}
+
+// The quota sizes: everything in the device layout in pinned staging, one DMA, the kernels.
+int stage_one_dma(const HostCall& k, uint64_t** dver_out, uint64_t** hver_out) {
+    Ctx& c = g_ctx;
     hipStream_t s = c.stream;
-    int rc = ensure_stage(all_pin ? 0 : total, total);
-    if (rc) return rc;
-    uint8_t* h = c.h_stage.p;
-    uint8_t* d = c.d_stage.p;
-    uint64_t* dver = reinterpret_cast<uint64_t*>(d + pk_bytes + off_bytes);
-    uint8_t* dblob = d + pk_bytes + off_bytes + v_bytes;
-    auto finish_piece = [&](uint64_t lo, uint64_t hi) -> int {
-        c.verdict_zeroed = d_out == nullptr;
-        c.keyed_hint = pv_keyed_hint(pk + 32 * lo, hi - lo);
-        c.hint_set = true;
-        const int r = launch(dblob, reinterpret_cast<const uint64_t*>(d + pk_bytes) + lo, hi - lo, d + 32 * lo,
-                             (d_out ? d_out : dver) + lo / 64, s);
-        c.verdict_zeroed = false;
-        c.keyed_hint = false;
-        c.hint_set = false;
-        return r;
-    };
-    if (np == 1 && !any_pin) {
-        // the quota sizes: everything in the device layout in pinned staging, one DMA
-        uint64_t* hoff = reinterpret_cast<uint64_t*>(h + pk_bytes);
-        const unsigned k = n >= (1u << 16) ? 8u : 1u;
-        cur_pool().run(k, [&](unsigned t) {
-            const uint64_t a = n * t / k, b = n * (t + 1) / k;
-            memcpy(h + 32 * a, pk + 32 * a, 32 * (b - a));
-            for (uint64_t i = a; i < b; i++) hoff[i] = sm_off[i] - base;
-        });
-        hoff[n] = sm_off[n] - base;
-        uint8_t* hblob = h + pk_bytes + off_bytes + v_bytes;
-        memset(h + pk_bytes + off_bytes, 0, v_bytes);  // the verdict words travel zeroed
-        memset(hblob + blob, 0, PV_BLOB_SLACK);
-        if (c.inject_stage > 0) {
-            c.inject_stage--;
-            return fail(PV_ERR_ALLOC, "stage_and_launch: injected staging failure (pv_test_inject)");
-        }
-        if (blob < (256ull << 10)) {
-            memcpy(hblob, sm + base, blob);
-        } else {
-            rc = pv_stage_to_device(dblob, hblob, sm + base, blob, s, false);
-            if (rc) return rc;
-        }
-        PV_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
-        if ((rc = finish_piece(0, n))) return rc;
-        *dver_out = dver;
-        *hver_out = reinterpret_cast<uint64_t*>(h + pk_bytes + off_bytes);
-        return PV_OK;
+    const uint64_t n = k.n;
+    const unsigned w = n >= (1u << 16) ? 8u : 1u;
+    cur_pool().run(w, [&](unsigned t) {
+        const uint64_t a = n * t / w, b = n * (t + 1) / w;
+        memcpy(k.h + 32 * a, k.pk + 32 * a, 32 * (b - a));
+        for (uint64_t i = a; i < b; i++) k.hoff[i] = k.sm_off[i] - k.base;
+    });
+    k.hoff[n] = k.sm_off[n] - k.base;
+    memset(k.h + k.lay.ver, 0, k.lay.ver_bytes);  // the verdict words travel zeroed
+    memset(k.hblob + k.blob, 0, PV_BLOB_SLACK);
+    if (c.inject_stage > 0) return injected_failure();
+    if (k.blob < (256ull << 10)) {
+        memcpy(k.hblob, k.sm + k.base, k.blob);
+    } else if (int rc = pv_stage_to_device(k.dblob, k.hblob, k.sm + k.base, k.blob, s, false)) {
+        return rc;
     }
-    if ((rc = c.h_ver.grow(std::max<uint64_t>(v_bytes, 64 << 10), hipHostMallocPortable))) return rc;
-    while (c.ev_copy.size() < np) {
+    PV_HIP(hipMemcpyAsync(k.d, k.h, k.lay.total, hipMemcpyHostToDevice, s), PV_ERR_LAUNCH);
+    if (int rc = launch_piece(k, 0, n)) return rc;
+    *dver_out = k.dver;
+    *hver_out = reinterpret_cast<uint64_t*>(k.h + k.lay.ver);
+    return PV_OK;
+}
+
+// Sub-batch j's pageable inputs into pinned staging (copy workers), its H2D on the copy stream, then
+// ev_copy[j].
+int copy_piece(const HostCall& k, uint64_t j) {
+    Ctx& c = g_ctx;
+    hipStream_t cs = c.cstream;
+    const pvhost::CallPlan& p = k.plan;
+    const uint64_t lo = p.bnd[j], hi = p.bnd[j + 1];
+    const uint64_t b0 = k.sm_off[lo] - k.base, b1 = k.sm_off[hi] - k.base;
+    if (!p.all_pin) {
+        pvhost::CopyPool& pool = cur_pool();
+        const unsigned w = std::max(1u, std::min(pool.threads(), (unsigned)((b1 - b0) >> 22)));
+        pool.run(w, [&](unsigned t) {
+            const uint64_t a = lo + (hi - lo) * t / w, b = lo + (hi - lo) * (t + 1) / w;
+            if (!p.pin_pk) memcpy(k.h + 32 * a, k.pk + 32 * a, 32 * (b - a));
+            if (!p.pin_off)
+                for (uint64_t i = a; i < b; i++) k.hoff[i] = k.sm_off[i] - k.base;
+            if (!p.pin_sm) memcpy(k.hblob + (k.sm_off[a] - k.base), k.sm + k.sm_off[a], k.sm_off[b] - k.sm_off[a]);
+        });
+        if (!p.pin_off) k.hoff[hi] = k.sm_off[hi] - k.base;
+    }
+    // an input in pinned memory is DMA'd where it is, the others from pinned staging
+    const uint8_t* spk = p.pin_pk ? k.pk : k.h;
+    const uint64_t* soff = p.pin_off ? k.sm_off : k.hoff;
+    const uint8_t* sblob = p.pin_sm ? k.sm + k.base : k.hblob;
+    PV_HIP(hipMemcpyAsync(k.d + 32 * lo, spk + 32 * lo, 32 * (hi - lo), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
+    PV_HIP(hipMemcpyAsync(k.doff + lo, soff + lo, 8 * (hi - lo + 1), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
+    if (b1 > b0) PV_HIP(hipMemcpyAsync(k.dblob + b0, sblob + b0, b1 - b0, hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
+    PV_HIP(hipEventRecord(c.ev_copy[j], cs), PV_ERR_LAUNCH);
+    return PV_OK;
+}
+
+// The pipeline's enqueues: the copies on the copy stream, each sub-batch's kernels on the engine stream
+// behind its copies' event. `share`: the sub-batches share one set of comb tables (CallPlan::may_share).
+int enqueue_pipeline(const HostCall& k, bool share) {
+    Ctx& c = g_ctx;
+    hipStream_t s = c.stream, cs = c.cstream;
+    const pvhost::CallPlan& p = k.plan;
+    if (share) PV_HIP(hipMemsetAsync(c.xt.htab, 0xFF, PV_XT_HASH * 4, s), PV_ERR_LAUNCH);
+    if (!k.d_out) PV_HIP(hipMemsetAsync(k.dver, 0, k.lay.vwords * 8, s), PV_ERR_LAUNCH);  // the latency path ORs bits
+    PV_HIP(hipMemsetAsync(k.dblob + k.blob, 0, PV_BLOB_SLACK, cs), PV_ERR_LAUNCH);
+    if (int rc = copy_piece(k, 0)) return rc;
+    for (uint64_t j = 0; j < p.np; j++) {
+        // sub-batch j + 1's copies are enqueued BEFORE sub-batch j's kernels: should the copy stream share a
+        // hardware queue with one of the engine's streams, no copy waits behind kernels enqueued before it
+        // (the other order is never faster: profiles/r05/host_path/ab_prio_lookahead.txt)
+        if (j + 1 < p.np)
+            if (int rc = copy_piece(k, j + 1)) return rc;
+        if (c.inject_stage > 0 && j == p.inject_at) return injected_failure();
+        PV_HIP(hipStreamWaitEvent(s, c.ev_copy[j], 0), PV_ERR_LAUNCH);
+        c.xt_fill = share && j == 0;
+        c.xt_use = share && j > 0;
+        const int rc = launch_piece(k, p.bnd[j], p.bnd[j + 1]);
+        c.xt_fill = c.xt_use = false;
+        if (rc) return rc;
+    }
+    return PV_OK;
+}
+
+// Everything else, in the plan's sub-batches, so that PCIe, host staging and kernels of consecutive
+// sub-batches overlap. How the copies and kernels interleave is seen in a kernel and memory-copy trace
+// (profiles/r05/host_path/overlap.txt).
+int stage_pipelined(const HostCall& k, uint64_t** dver_out, uint64_t** hver_out) {
+    Ctx& c = g_ctx;
+    hipStream_t s = c.stream, cs = c.cstream;
+    if (int rc = c.h_ver.grow(std::max<uint64_t>(k.lay.ver_bytes, 64 << 10), hipHostMallocPortable)) return rc;
+    while (c.ev_copy.size() < k.plan.np) {
         hipEvent_t e;
-        if ((rc = c.own.event(e, hipEventDisableTiming))) return rc;
+        if (int rc = c.own.event(e, hipEventDisableTiming)) return rc;
         c.ev_copy.push_back(e);
     }
-    hipStream_t cs = c.cstream;
-    const uint8_t* spk = pin_pk ? pk : h;
-    const uint64_t* soff = pin_off ? sm_off : reinterpret_cast<const uint64_t*>(h + pk_bytes);
-    const uint8_t* sblob = pin_sm ? sm + base : h + pk_bytes + off_bytes + v_bytes;
-    uint64_t* hoff = reinterpret_cast<uint64_t*>(h + pk_bytes);
-    uint8_t* hblob = h + pk_bytes + off_bytes + v_bytes;
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d + pk_bytes);
     // the copy stream starts after everything enqueued so far (the previous users of the staging area)
     PV_HIP(hipEventRecord(c.ev_cstart, s), PV_ERR_LAUNCH);
     PV_HIP(hipStreamWaitEvent(cs, c.ev_cstart, 0), PV_ERR_LAUNCH);
-    if ((rc = c.hand.wait(cs, s))) return rc;
-    // sub-batch j = requests [lo(j), lo(j + 1))
-    auto lo_of = [&](uint64_t j) -> uint64_t { return bnd[std::min<uint64_t>(j, np)]; };
-    pvhost::CopyPool& pool = cur_pool();
-    // sub-batch j's pageable inputs into pinned staging (copy workers), its H2D on the copy stream, then
-    // ev_copy[j]
-    auto stage_copy = [&](uint64_t j) -> int {
-        const uint64_t lo = lo_of(j), hi = lo_of(j + 1);
-        const uint64_t b0 = sm_off[lo] - base, b1 = sm_off[hi] - base;
-        if (!all_pin) {  // this sub-batch's pageable inputs into pinned staging, on the copy workers
-            const unsigned k = std::max(1u, std::min(pool.threads(), (unsigned)((b1 - b0) >> 22)));
-            pool.run(k, [&](unsigned t) {
-                const uint64_t a = lo + (hi - lo) * t / k, b = lo + (hi - lo) * (t + 1) / k;
-                if (!pin_pk) memcpy(h + 32 * a, pk + 32 * a, 32 * (b - a));
-                if (!pin_off)
-                    for (uint64_t i = a; i < b; i++) hoff[i] = sm_off[i] - base;
-                if (!pin_sm) memcpy(hblob + (sm_off[a] - base), sm + sm_off[a], sm_off[b] - sm_off[a]);
-            });
-            if (!pin_off) hoff[hi] = sm_off[hi] - base;
-        }
-        PV_HIP(hipMemcpyAsync(d + 32 * lo, spk + 32 * lo, 32 * (hi - lo), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        PV_HIP(hipMemcpyAsync(doff + lo, soff + lo, 8 * (hi - lo + 1), hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        if (b1 > b0)
-            PV_HIP(hipMemcpyAsync(dblob + b0, sblob + b0, b1 - b0, hipMemcpyHostToDevice, cs), PV_ERR_LAUNCH);
-        PV_HIP(hipEventRecord(c.ev_copy[j], cs), PV_ERR_LAUNCH);
-        return PV_OK;
-    };
-    // PV_PIPE_TRACE=1 (development): timing events after each sub-batch's copies and kernels, printed to
-    // stderr relative to the call's first event -- the untraced pipeline timeline
-    static const bool ptrace = env_int("PV_PIPE_TRACE", 0) != 0;
-    static const int lookahead = env_int("PV_PIPE_LOOKAHEAD", 1);
-    std::vector<hipEvent_t> tev;
-    auto tmark = [&](hipStream_t st) {
-        if (!ptrace) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) == hipSuccess) {
-            (void)hipEventRecord(e, st);
-            tev.push_back(e);
-        }
-    };
-    // the sub-batches share one set of comb tables: sub-batch 0 builds the tables of its comb keys that
-    // the node-side key cache does not hold, the later ones read the cache's for cached keys and the
-    // shared store's for the rest (pv_key_cache_probe_kernel's two views)
-    static const bool share_env = env_int("PV_PIPE_SHARE", 1) != 0;
-    const bool share = share_env && np > 1 && (c.path == PV_PATH_AUTO || c.path == PV_PATH_COMB) &&
-                       ensure_xtab() == PV_OK;
-    auto run = [&]() -> int {
-        tmark(cs);
-        if (share) PV_HIP(hipMemsetAsync(c.xt.htab, 0xFF, PV_XT_HASH * 4, s), PV_ERR_LAUNCH);
-        if (!d_out) PV_HIP(hipMemsetAsync(dver, 0, vwords * 8, s), PV_ERR_LAUNCH);  // the latency path ORs bits
-        PV_HIP(hipMemsetAsync(dblob + blob, 0, PV_BLOB_SLACK, cs), PV_ERR_LAUNCH);
-        int r = stage_copy(0);
-        tmark(cs);
-        // sub-batch j + 1's copies are enqueued BEFORE sub-batch j's kernels: should the copy stream share a
-        // hardware queue with one of the engine's streams, no copy waits behind kernels enqueued before it
-        for (uint64_t j = 0; j < np && r == PV_OK; j++) {
-            if (lookahead && j + 1 < np) {
-                if ((r = stage_copy(j + 1)) != PV_OK) break;
-                tmark(cs);
-            }
-            if (c.inject_stage > 0 && j == std::min<uint64_t>(1, np - 1)) {  // sub-batch 0's kernels in flight
-                c.inject_stage--;
-                return fail(PV_ERR_ALLOC, "stage_and_launch: injected staging failure (pv_test_inject)");
-            }
-            PV_HIP(hipStreamWaitEvent(s, c.ev_copy[j], 0), PV_ERR_LAUNCH);
-            c.xt_fill = share && j == 0;
-            c.xt_use = share && j > 0;
-            r = finish_piece(lo_of(j), lo_of(j + 1));
-            c.xt_fill = c.xt_use = false;
-            tmark(s);
-            if (!lookahead && r == PV_OK && j + 1 < np) {
-                if ((r = stage_copy(j + 1)) != PV_OK) break;
-                tmark(cs);
-            }
-        }
-        return r;
-    };
-    if ((rc = run()) != PV_OK) {
+    if (int rc = c.hand.wait(cs, s)) return rc;
+    const bool share = k.plan.may_share && ensure_xtab() == PV_OK;
+    if (int rc = enqueue_pipeline(k, share)) {
         (void)hipStreamSynchronize(cs);  // no DMA may still read the caller's or the staging buffers
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    if (ptrace && !tev.empty()) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize(cs);
-        std::string line = "pv_pipe: n " + std::to_string(n) + " pieces " + std::to_string(np) + " us:";
-        for (size_t i = 1; i < tev.size(); i++) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, tev[0], tev[i]);
-            line += " " + std::to_string((int)(ms * 1000));
-        }
-        fprintf(stderr, "%s\n", line.c_str());
-        for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-    }
-    *dver_out = dver;
+    *dver_out = k.dver;
     *hver_out = c.h_ver.as<uint64_t>();
     return PV_OK;
+}
+
+// The zero-copy form of a small call that takes the latency path and whose records fit a 2 KB slot: the
+// kernel reads the pinned staging slots over PCIe and stores one verdict byte per request back -- no copy
+// kernels around it.
+int verify_zero_copy(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk, uint64_t stride,
+                     uint8_t* verdict_bits) {
+    int rc = ensure_stage(n * stride, 0);
+    if (rc) return rc;
+    uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
+    uint8_t* slots = g_ctx.h_stage.p;
+    memset(vb, 0xFF, n);  // pending: the host spins on these bytes instead of a stream sync
+    const bool one = n == 1 && stride <= sizeof(PvZcOne);  // the slot goes in the kernel arguments
+    PvZcOne one_slot;
+    if (one) {
+        pvhost::zc_fill_slots(reinterpret_cast<uint8_t*>(one_slot.w), stride, sm, sm_off, pk, 0, 1);
+    } else if (n * stride < (128u << 10)) {
+        pvhost::zc_fill_slots(slots, stride, sm, sm_off, pk, 0, n);
+    } else {  // node-quota sizes: the slots are written by the copy pool's threads
+        const unsigned w = 8;
+        cur_pool().run(w, [&](unsigned t) {
+            pvhost::zc_fill_slots(slots, stride, sm, sm_off, pk, n * t / w, n * (t + 1) / w);
+        });
+    }
+    hipStream_t s = g_ctx.stream;
+    if ((rc = g_ctx.hand.begin(s))) return rc;
+    g_ctx.last_latency = true;
+    g_ctx.last_keyed = false;
+    g_ctx.last_dev_choice = false;
+    g_ctx.last_zero_copy = true;
+    rc = one ? pv_latency_launch_zc_one(one_slot, (uint32_t)stride, g_ctx.d_bcomb, kc_view(), vb, s)
+             : pv_latency_launch_zc(slots, (uint32_t)stride, n, g_ctx.d_bcomb, kc_view(), vb, s);
+    if (int rc2 = g_ctx.hand.end(s)) return rc2;
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    rc = kc_auto_after_batch(pk, n, s, vb, nullptr);  // returns once the verdict bytes are written
+    if (rc) return rc;
+    memset(verdict_bits, 0, (n + 7) / 8);
+    for (uint64_t i = 0; i < n; i++) verdict_bits[i >> 3] |= (uint8_t)((vb[i] & 1u) << (i & 7));
+    return PV_OK;
+}
+
+}  // namespace
+
+// The copy form of a host-buffer batch on the calling thread's context: moves the keys, offsets and
+// records to the device staging area and enqueues the verification on the context's stream. d_out:
+// where the verdict words go (nullptr = the staging area's own verdict section); *dver / *hver receive
+// the device verdict section and a pinned buffer for the caller's copy back. Three steps: plan the call
+// (host_plan.h: the layout, the sub-batch bounds, the form), size the staging, run the form. A failure
+// after DMAs were enqueued returns only after both streams drained, so no copy still reads the caller's
+// or the staging buffers.
+int stage_and_launch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const uint8_t* pk, uint64_t* d_out,
+                     uint64_t** dver_out, uint64_t** hver_out) {
+    Ctx& c = g_ctx;
+    c.last_zero_copy = false;
+    HostCall k{sm, sm_off, n, pk, d_out, sm_off[0], sm_off[n] - sm_off[0]};
+    k.lay = pvhost::plan_layout(n, k.blob);
+    k.plan = pvhost::plan_call(pvhost::plan_pieces(n, k.blob, pipe_sub(), pvhost::pipe_end_req()),
+                               pv_is_pinned(sm + k.base, k.blob), pv_is_pinned(pk, 32 * n),
+                               k.base == 0 && pv_is_pinned(sm_off, 8 * (n + 1)), c.path, k.lay.total);
+    if (int rc = ensure_stage(k.plan.host_bytes, k.lay.total)) return rc;
+    k.h = c.h_stage.p;
+    k.d = c.d_stage.p;
+    k.hoff = reinterpret_cast<uint64_t*>(k.h + k.lay.off);
+    k.doff = reinterpret_cast<uint64_t*>(k.d + k.lay.off);
+    k.dver = reinterpret_cast<uint64_t*>(k.d + k.lay.ver);
+    k.hblob = k.h + k.lay.blob;
+    k.dblob = k.d + k.lay.blob;
+    return k.plan.form == pvhost::ONE_DMA ? stage_one_dma(k, dver_out, hver_out)
+                                          : stage_pipelined(k, dver_out, hver_out);
 }
 
 extern "C" {
@@ -495,62 +469,15 @@ int pv_verify_batch(const uint8_t* sm, const uint64_t* sm_off, uint64_t n, const
     if (!sm || !sm_off || !pk || !verdict_bits) return fail(PV_ERR_ARG, "null pointer");
     if (!offsets_nondecreasing(sm_off, n)) return fail(PV_ERR_ARG, "sm_off must be non-decreasing");
     std::lock_guard<std::mutex> lk(g_mu);
-    {
-        // a small call that takes the latency path (plan_batch, chunk_plan.h: the choice launch_chunks makes
-        // for a host-buffer call, which sets the hint it counted; the cache's state is not read then) and
-        // whose records fit a 2 KB slot: the kernel reads the pinned staging slots over PCIe and stores one
-        // verdict byte per request back -- no copy kernels around it
-        uint64_t maxlen = 0;
-        for (uint64_t i = 0; i < n && n <= PV_ZC_MAX_REQ; i++) maxlen = std::max(maxlen, sm_off[i + 1] - sm_off[i]);
-        const uint64_t stride = (4ull * PV_ZC_REC_WORD + maxlen + PV_ZC_SLACK + 63) & ~63ull;
-        if (!g_ctx.timing && n <= PV_ZC_MAX_REQ && stride <= PV_ZC_MAX_STRIDE &&
-            pvhost::plan_batch({g_ctx.path, n, true, pv_keyed_hint(pk, n), false}).latency) {
-            int rc = ensure_stage(n * stride, 0);
-            if (rc) return rc;
-            uint8_t* vb = g_ctx.h_zc_verdict;  // coherent pinned memory, read while the kernel runs
-            uint8_t* slots = g_ctx.h_stage.p;
-            memset(vb, 0xFF, n);  // pending: the host spins on these bytes instead of a stream sync
-            auto fill_at = [&](uint8_t* base, uint64_t a, uint64_t b) {
-                for (uint64_t i = a; i < b; i++) {
-                    uint8_t* sl = base + i * stride;
-                    const uint64_t len = sm_off[i + 1] - sm_off[i];
-                    const uint32_t hdr[PV_ZC_PK_WORD] = {(uint32_t)len, 0u, 0u, 0u};
-                    memcpy(sl, hdr, sizeof(hdr));
-                    memcpy(sl + 4 * PV_ZC_PK_WORD, pk + 32 * i, 32);
-                    memcpy(sl + 4 * PV_ZC_REC_WORD, sm + sm_off[i], len);
-                    memset(sl + 4 * PV_ZC_REC_WORD + len, 0, stride - 4 * PV_ZC_REC_WORD - len);
-                }
-            };
-            const bool one = n == 1 && stride <= sizeof(PvZcOne);  // the slot goes in the kernel arguments
-            PvZcOne one_slot;
-            if (one) {
-                fill_at(reinterpret_cast<uint8_t*>(one_slot.w), 0, 1);
-            } else if (n * stride < (128u << 10)) {
-                fill_at(slots, 0, n);
-            } else {  // node-quota sizes: the slots are written by the copy pool's threads
-                const unsigned k = 8;
-                cur_pool().run(k, [&](unsigned t) { fill_at(slots, n * t / k, n * (t + 1) / k); });
-            }
-            hipStream_t s = g_ctx.stream;
-            if ((rc = g_ctx.hand.begin(s))) return rc;
-            g_ctx.last_latency = true;
-            g_ctx.last_keyed = false;
-            g_ctx.last_dev_choice = false;
-            g_ctx.last_zero_copy = true;
-            rc = one ? pv_latency_launch_zc_one(one_slot, (uint32_t)stride, g_ctx.d_bcomb, kc_view(), vb, s)
-                     : pv_latency_launch_zc(slots, (uint32_t)stride, n, g_ctx.d_bcomb, kc_view(), vb, s);
-            if (int rc2 = g_ctx.hand.end(s)) return rc2;
-            if (rc) {
-                (void)hipStreamSynchronize(s);
-                return rc;
-            }
-            rc = kc_auto_after_batch(pk, n, s, vb, nullptr);  // returns once the verdict bytes are written
-            if (rc) return rc;
-            memset(verdict_bits, 0, (n + 7) / 8);
-            for (uint64_t i = 0; i < n; i++) verdict_bits[i >> 3] |= (uint8_t)((vb[i] & 1u) << (i & 7));
-            return PV_OK;
-        }
-    }
+    // the zero-copy gate: the call takes the latency path (plan_batch, chunk_plan.h: the choice launch_chunks
+    // makes for a host-buffer call, which sets the hint it counted; the cache's state is not read then) and
+    // its longest record fits a slot
+    uint64_t maxlen = 0;
+    for (uint64_t i = 0; i < n && n <= PV_ZC_MAX_REQ; i++) maxlen = std::max(maxlen, sm_off[i + 1] - sm_off[i]);
+    const uint64_t stride = pvhost::zc_stride(maxlen);
+    if (!g_ctx.timing && n <= PV_ZC_MAX_REQ && stride <= PV_ZC_MAX_STRIDE &&
+        pvhost::plan_batch({g_ctx.path, n, true, pv_keyed_hint(pk, n), false}).latency)
+        return verify_zero_copy(sm, sm_off, n, pk, stride, verdict_bits);
     uint64_t *dver = nullptr, *hver = nullptr;
     int rc = stage_and_launch(sm, sm_off, n, pk, nullptr, &dver, &hver);
     if (rc) return rc;
