@@ -5,7 +5,7 @@
 // tests/native/chunk_plan_check.cpp runs them on a CPU; launch_chunks / launch_chunk (pv_engine.hip) gather
 // the facts from the context, apply the plan to the KeyWork and enqueue what it names. The thresholds the
 // rules read are defined here, each once, with what was measured for them (pv_engine_dev.h includes this
-// file: the kernels read the same constants). The #ifndef ones are tuning knobs that microbench/
+// file: the kernels, in the kern_*.h headers of pv_engine.hip, read the same constants). The #ifndef ones are tuning knobs that microbench/
 // build_variants.sh varies with -D.
 #pragma once
 #include <stdint.h>

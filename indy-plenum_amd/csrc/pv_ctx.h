@@ -1,5 +1,5 @@
 // Host state of the verification engine shared by its translation units: the device context Ctx
-// (pv_engine.hip builds, frees and launches on it; pv_sign.hip, pv_host.hip and pv_multi.hip work on it
+// (pv_engine.hip builds, frees and launches the kernels of its kern_*.h headers on it; pv_sign.hip, pv_host.hip and pv_multi.hip work on it
 // under its mutex), the calling thread's error string, the kernel-launch helpers, and the functions
 // that cross a file boundary. Everything declared here is internal to libplenum_verify.so (hidden).
 #pragma once

@@ -1,7 +1,8 @@
 // Device-visible types of the verification engine that more than one translation unit names, and the
-// constants they use: pv_engine.hip (the verification kernels, the device context's launches),
+// constants they use: pv_engine.hip (the verification kernels' unit, the device context's launches),
 // pv_sign.hip (the signing kernels) and pv_ctx.h (Ctx holds a Work and a KeyWork). What only the
-// verification kernels use (Soa, DevATab, DevDigits, the staged comb loops) stays in pv_engine.hip.
+// verification kernels use is in the kern_*.h headers that pv_engine.hip alone includes: Soa and DevDigits
+// in kern_access.h, DevATab in kern_straus.h, the staged comb loops' accessors in kern_comb.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -3,7 +3,7 @@
 // LRU refresh from the launches' stamps, the hash-table upload and the view the launches read the cache
 // through. The slot bookkeeping is pvhost::KcIndex (kc_index.h); here are the copies, the
 // synchronisation and the error handling around it. No kernel is defined here: a put's tables are built by
-// kc_build_tables (pv_engine.hip).
+// kc_build_tables (pv_engine.hip) with the kernels of kern_tables.h and kern_wide.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>

@@ -73,6 +73,25 @@ PV_HD void ge_cached_load_words(ge_cached& c, const uint32_t w[40]) {
         c.T2d.v[i] = w[30 + i];
     }
 }
+// An extended point as the same 40 words: X, Y, Z, T limbs.
+PV_HD void ge_p3_store_words(uint32_t w[40], const ge_p3& p) {
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+        w[i] = p.X.v[i];
+        w[10 + i] = p.Y.v[i];
+        w[20 + i] = p.Z.v[i];
+        w[30 + i] = p.T.v[i];
+    }
+}
+PV_HD void ge_p3_load_words(ge_p3& p, const uint32_t w[40]) {
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+        p.X.v[i] = w[i];
+        p.Y.v[i] = w[10 + i];
+        p.Z.v[i] = w[20 + i];
+        p.T.v[i] = w[30 + i];
+    }
+}
 
 // Build the 9-entry table of [j](-A), j = 0..8, in cached form (entry 0 = identity): one doubling, then
 // six additions of entry 1.
