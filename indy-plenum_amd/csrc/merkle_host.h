@@ -1,6 +1,7 @@
 // The host path of the Merkle entries (merkle_host.cpp): the contract of pv_merkle_append_batch,
-// pv_merkle_verify_inclusion_batch, pv_merkle_verify_consistency_batch, pv_merkle_catchup_batch and pv_merkle_prove_batch in C++ over merkle_core.h and the host SHA-256, arguments already
-// validated. Internal, not ABI.
+// pv_merkle_verify_inclusion_batch, pv_merkle_verify_consistency_batch, pv_merkle_catchup_batch and
+// pv_merkle_prove_batch in C++ over merkle_core.h and the host SHA-256, arguments already validated
+// (merkle_plan.h). Internal, not ABI.
 #ifndef PV_MERKLE_HOST_H
 #define PV_MERKLE_HOST_H
 

@@ -1,7 +1,8 @@
 // The ledger's SHA-256 Merkle tree on the GPU: n sequential CompactMerkleTree.append calls
 // (ledger/compact_merkle_tree.py:95-160) as one batch, and MerkleVerifier.verify_leaf_inclusion
 // (ledger/merkle_verifier.py:155-266) for a batch of proofs. Index arithmetic: merkle_core.h (shared with
-// the host path and the host-compiled check library); hashing: sha256.h.
+// the host path and the host-compiled check library); hashing: sha256.h; the chunks of a call, where a
+// chunk's outputs lie, and the entries' argument checks: merkle_plan.h (tested on a CPU).
 //
 // A batch of n leaves appended to a tree of size s needs no sequential walk (merkle_core.h): every hash
 // the reference would write or return is a leaf hash, an aligned node completed inside the batch, or an
@@ -22,8 +23,7 @@
 // and pv_merkle_verify_kernel / pv_merkle_consistency_kernel (MerkleVerifier.verify_tree_consistency,
 // ledger/merkle_verifier.py:23-153), one lane per proof, and pv_merkle_prove_kernel (inclusion_proof,
 // consistency_proof and merkle_tree_hash from a hash store, ledger/compact_merkle_tree.py:198-249), one lane
-// per query. Launches per chunk: at most six, whatever n is;
-// no host round trip between them.
+// per query. Launches per chunk: at most six, whatever n is; no host round trip between them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -35,8 +35,16 @@
 #include "../../include/plenum_verify.h"
 #include "merkle_core.h"
 #include "merkle_host.h"
+#include "merkle_plan.h"
 #include "pv_internal.h"
 #include "sha256.h"
+
+using namespace pvhost;  // merkle_plan.h
+
+// The library's dynamic symbol table has always held this instantiation (the entries built their messages
+// through it out of line, forty times; the two sites left are inlined). Instantiated here so that the table
+// stays what it was.
+template std::string std::operator+(const std::string&, const char*);
 
 namespace {
 
@@ -86,6 +94,27 @@ __device__ __forceinline__ MkHash mk_leaf_hash(const uint8_t* data, uint64_t len
     const PvRecordWords words(data, len);
     sha256_prefixed<1>(h.w, 0u, len, words);
     return h;
+}
+
+// The hooks of merkle_core.h's walks: hash_children, a hash of the chunk's view, and hash k of the proof that
+// starts at hash p0 of `proof`.
+struct MkCombine {
+    __device__ __forceinline__ void operator()(MkHash& o, const MkHash& l, const MkHash& r) const { o = mk_children(l, r); }
+};
+struct MkViewLoad {
+    const MkView& v;
+    __device__ __forceinline__ void operator()(const PvMerkleRef& r, MkHash& o) const { o = mk_load(v.at(r)); }
+};
+struct MkProofLoad {
+    const uint32_t* proof;
+    uint64_t p0;
+    __device__ __forceinline__ void operator()(uint64_t k, MkHash& o) const { o = mk_load(proof + 8 * (p0 + k)); }
+};
+__device__ __forceinline__ bool mk_equal(const MkHash& a, const MkHash& b) {
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) diff |= a.w[k] ^ b.w[k];
+    return diff == 0;
 }
 
 // ------------------------------------------------------------------------------------------ kernels
@@ -173,8 +202,8 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_proof_kernel(MkView v, uin
     if (roots) {
         MkHash acc;
         pv_merkle_fold_root(
-            acc, v.s, t + 1, [&](const PvMerkleRef& r, MkHash& o) { o = mk_load(v.at(r)); },
-            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+            acc, v.s, t + 1, MkViewLoad{v},
+            MkCombine());
         mk_store(roots + 8 * i, acc);
     }
 }
@@ -200,13 +229,15 @@ __global__ __launch_bounds__(64) void pv_merkle_finish_kernel(MkView v, uint32_t
     } else if (root && lane == 0) {
         MkHash acc;
         pv_merkle_fold_root(
-            acc, v.s, t, [&](const PvMerkleRef& r, MkHash& o) { o = mk_load(v.at(r)); },
-            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+            acc, v.s, t, MkViewLoad{v},
+            MkCombine());
         mk_store(root, acc);
     }
 }
 
-// One lane per proof; verdict word w bit b = proof 64 w + b (one ballot per wave).
+// One lane per proof; verdict word w bit b = proof 64 w + b (one ballot per wave). The comparison with the
+// root and the ballot's store are written out here and in pv_merkle_consistency_kernel: through mk_equal or
+// through a shared epilogue function the compiler emits other instructions for these two kernels.
 __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
     const uint8_t* __restrict__ data, const uint64_t* __restrict__ off, const uint32_t* __restrict__ leaf_hash,
     const uint64_t* __restrict__ leaf_index, const uint64_t* __restrict__ tree_size, const uint32_t* __restrict__ proof,
@@ -224,8 +255,8 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
         }
         const uint64_t p0 = proof_off[i], plen = proof_off[i + 1] - p0;
         const uint32_t st = pv_merkle_path_check(
-            acc, leaf_index[i], tree_size[i], plen, [&](uint64_t k, MkHash& o) { o = mk_load(proof + 8 * (p0 + k)); },
-            [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); });
+            acc, leaf_index[i], tree_size[i], plen, MkProofLoad{proof, p0},
+            MkCombine());
         status[i] = (uint8_t)st;
         if (st == PV_MK_COMPARED) {
             const MkHash want = mk_load(root + 8 * i);
@@ -239,19 +270,13 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_verify_kernel(
     if ((threadIdx.x & 63) == 0 && i < n) verdict[i >> 6] = word;
 }
 
-__device__ __forceinline__ bool mk_equal(const MkHash& a, const MkHash& b) {
-    uint32_t diff = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) diff |= a.w[k] ^ b.w[k];
-    return diff == 0;
-}
 // the consistency walk of merkle_core.h over proof hashes [p0, p0 + plen) of `proof`
 __device__ __forceinline__ uint32_t mk_consistency(uint64_t old_size, uint64_t new_size, const MkHash& old_root,
                                                    const MkHash& new_root, const uint32_t* __restrict__ proof,
                                                    uint64_t p0, uint64_t plen) {
     return pv_merkle_consistency_check(
-        old_size, new_size, old_root, new_root, plen, [&](uint64_t k, MkHash& o) { o = mk_load(proof + 8 * (p0 + k)); },
-        [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); },
+        old_size, new_size, old_root, new_root, plen, MkProofLoad{proof, p0},
+        MkCombine(),
         [](const MkHash& a, const MkHash& b) { return mk_equal(a, b); });
 }
 
@@ -297,8 +322,8 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_catchup_kernel(MkView v, M
         if (e > v.s && e <= v.s + v.n) {
             MkHash old_root;
             pv_merkle_fold_root(
-                old_root, v.s, e, [&](const PvMerkleRef& ref, MkHash& o) { o = mk_load(v.at(ref)); },
-                [](MkHash& o, const MkHash& l, const MkHash& rr) { o = mk_children(l, rr); });
+                old_root, v.s, e, MkViewLoad{v},
+                MkCombine());
             const uint64_t p0 = q.proof_off[r];
             const uint32_t st = mk_consistency(e, q.final_size, old_root, mk_load(q.final_root), q.proof, p0,
                                                q.proof_off[r + 1] - p0);
@@ -349,7 +374,7 @@ __global__ __launch_bounds__(MK_BLOCK) void pv_merkle_prove_kernel(MkProve p, ui
     pv_merkle_prove<MkHash>(
         kind, a, b, [&](uint32_t k, const PvMerkleElem& e) { mk_copy(dst + 8 * k, src(e)); },
         [&](const PvMerkleElem& e, MkHash& o) { o = mk_load(src(e)); },
-        [](MkHash& o, const MkHash& l, const MkHash& r) { o = mk_children(l, r); },
+        MkCombine(),
         [&](uint32_t k, const MkHash& acc) { mk_store(dst + 8 * k, acc); });
     p.status[i] = PV_MK_PROVED;
 }
@@ -370,7 +395,6 @@ MkWork g_mk;
 std::mutex g_mk_mu;
 uint64_t g_mk_chunk = PV_MERKLE_CHUNK;
 int g_mk_path = PV_MERKLE_AUTO;
-constexpr uint64_t MK_CHUNK_BYTES = 1ull << 30;  // a host-entry chunk also ends at this many data bytes
 constexpr uint64_t MK_FRONT_BYTES = 64 * 32;
 
 // One use of the workspace on `stream`: the frontiers exist, and the hand-over around `body`. Caller
@@ -382,25 +406,16 @@ int mk_run(hipStream_t stream, F&& body) {
 }
 uint32_t* mk_front(int which) { return g_mk.front.as<uint32_t>() + which * (MK_FRONT_BYTES / 4); }
 
-struct MkChunkOut {  // device pointers, null = not wanted
-    uint32_t* leaf;
-    uint32_t* node;
-    uint32_t* roots;
-    uint32_t* path;
-    uint64_t* path_off;
-    uint64_t poff_base;
-    uint32_t* root;
-};
-
-// One chunk: m > 0 leaves (d_off[0..m] into d_data) appended at size s with input frontier d_fin; the
-// frontier after it goes to d_fout. rep (may be null): the replies to check against this chunk. Caller
-// holds g_mk_mu and is inside mk_run.
-int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uint64_t* d_off, uint64_t m,
-             const MkChunkOut& o, uint32_t* d_fout, hipStream_t stream, const MkReplies* rep = nullptr) {
-    uint64_t n_nodes, n_front, n_path;
-    pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
-    uint32_t* leaf = o.leaf;
-    uint32_t* node = o.node;
+// One chunk (merkle_plan.h): c.m > 0 leaves (d_off[0..m] into d_data) appended at size c.s with input frontier
+// d_fin; the frontier after it goes to d_fout. d: the chunk's outputs as device pointers, null = not wanted
+// (its frontier is not looked at). rep (may be null): the replies to check against this chunk. Caller holds
+// g_mk_mu and is inside mk_run.
+int mk_chunk(const MkChunk& c, const uint32_t* d_fin, const uint8_t* d_data, const uint64_t* d_off, const PvMerkleOut& d,
+             uint32_t* d_fout, hipStream_t stream, const MkReplies* rep = nullptr) {
+    const auto words = [](uint8_t* p) { return reinterpret_cast<uint32_t*>(p); };
+    const uint64_t m = c.m;
+    uint32_t* leaf = words(d.leaf_hash);
+    uint32_t* node = words(d.node_hash);
     int rc;
     if (!leaf) {
         if ((rc = g_mk.leaf.grow(std::max<uint64_t>(m, 4096) * 32))) return rc;
@@ -410,26 +425,26 @@ int mk_chunk(uint64_t s, const uint32_t* d_fin, const uint8_t* d_data, const uin
         if ((rc = g_mk.node.grow((std::max<uint64_t>(m, 4096) + 64) * 32))) return rc;  // n_nodes < m + 48
         node = g_mk.node.as<uint32_t>();
     }
-    const MkView v{s, m, d_fin, leaf, node};
+    const MkView v{c.s, m, d_fin, leaf, node};
     const unsigned grid = (unsigned)((m + MK_BLOCK - 1) / MK_BLOCK);
     PV_LAUNCH(pv_merkle_leaf_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, d_data, d_off, m, leaf);
-    if (n_nodes) {
+    if (c.n_nodes) {
         uint64_t first, count;
-        pv_merkle_tiles(s, m, 0, &first, &count);
+        pv_merkle_tiles(c.s, m, 0, &first, &count);
         PV_LAUNCH(pv_merkle_tile_kernel, dim3((unsigned)count), dim3(MK_BLOCK), 0, stream, v, first, node);
-        if (pv_merkle_any_above(s, m, PV_MERKLE_TILE_LOG)) {
+        if (pv_merkle_any_above(c.s, m, PV_MERKLE_TILE_LOG)) {
             PV_LAUNCH(pv_merkle_upper_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, v, node);
         }
     }
-    if (o.path || o.roots) {
-        PV_LAUNCH(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, o.path, o.path_off,
-                  o.poff_base, o.roots);
+    if (d.path || d.roots) {
+        PV_LAUNCH(pv_merkle_proof_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, v, words(d.path), d.path_off, c.pbase,
+                  words(d.roots));
     }
     if (rep && rep->r1 > rep->r0) {
         PV_LAUNCH(pv_merkle_catchup_kernel, dim3((unsigned)((rep->r1 - rep->r0 + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK),
                   0, stream, v, *rep);
     }
-    PV_LAUNCH(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, o.root);
+    PV_LAUNCH(pv_merkle_finish_kernel, dim3(1), dim3(64), 0, stream, v, d_fout, words(d.root));
     return PV_OK;
 }
 
@@ -440,20 +455,11 @@ int mk_replies_preset(const MkReplies& q, uint64_t n_replies, hipStream_t stream
     return PV_OK;
 }
 
-int mk_check_out(const PvMerkleOut* out, const char* who) {
-    if (!out) return pv_fail(PV_ERR_ARG, std::string(who) + ": null output struct");
-    if ((out->path != nullptr) != (out->path_off != nullptr))
-        return pv_fail(PV_ERR_ARG, std::string(who) + ": path and path_off go together");
-    return PV_OK;
-}
-bool mk_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
-// Device buffers, n > 0, on `stream`. Caller holds g_mk_mu.
+// Device buffers on `stream`. Caller holds g_mk_mu.
 // rep (may be null): a catch-up's replies, every chunk looks at all of them (their ends are device data).
 int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, const uint64_t* d_off, uint64_t n,
                const PvMerkleOut& out, hipStream_t stream, const MkReplies* rep = nullptr) {
     return mk_run(stream, [&]() -> int {
-        const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
         int cur = 0;
         if (rep)
             if (int rc = mk_replies_preset(*rep, rep->r1, stream)) return rc;
@@ -466,29 +472,20 @@ int mk_enqueue(uint64_t s0, const uint8_t* d_frontier, const uint8_t* d_data, co
             if (out.path_off) PV_HIP(hipMemsetAsync(out.path_off, 0, 8, stream), PV_ERR_LAUNCH);
             fin = mk_front(0);
         }
-        for (uint64_t c0 = 0; c0 < n; c0 += g_mk_chunk) {
-            const uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0), s = s0 + c0;
-            const bool is_last = c0 + m == n;
-            const uint64_t pbase = pv_merkle_popc_sum(s) - paths0;
-            const MkChunkOut o{out.leaf_hash ? reinterpret_cast<uint32_t*>(out.leaf_hash + 32 * c0) : nullptr,
-                               out.node_hash ? reinterpret_cast<uint32_t*>(out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0))
-                                             : nullptr,
-                               out.roots ? reinterpret_cast<uint32_t*>(out.roots + 32 * c0) : nullptr,
-                               out.path ? reinterpret_cast<uint32_t*>(out.path + 32 * pbase) : nullptr,
-                               out.path ? out.path_off + c0 : nullptr,
-                               pbase,
-                               is_last ? reinterpret_cast<uint32_t*>(out.root) : nullptr};
-            if (int rc = mk_chunk(s, fin, d_data, d_off + c0, m, o, mk_front(cur), stream, rep)) return rc;
-            fin = mk_front(cur);
-            cur ^= 1;
-        }
+        // the caller's arrays from each chunk's first element on; the leaf bound only
+        if (int rc = for_each_append_chunk(s0, n, g_mk_chunk, nullptr, 0, [&](const MkChunk& c) -> int {
+                if (int rc = mk_chunk(c, fin, d_data, d_off + c.c0, chunk_outputs(out, c), mk_front(cur), stream, rep)) return rc;
+                fin = mk_front(cur);
+                cur ^= 1;
+                return PV_OK;
+            }))
+            return rc;
         if (out.frontier)
             PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToDevice, stream), PV_ERR_LAUNCH);
         return PV_OK;
     });
 }
 
-// The device path of the host entry: chunk by chunk through the stage. Arguments validated, n > 0.
 // A catch-up's replies as the host entry has them (validated: ends strictly increasing in (s0, s0 + n]).
 struct MkHostReplies {
     const uint64_t* end;
@@ -500,126 +497,118 @@ struct MkHostReplies {
     uint8_t* verdict_bits;
 };
 
-int mk_host_entry_device(uint64_t s0, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
-                         const PvMerkleOut& out, const MkHostReplies* hr = nullptr) {
-    const hipStream_t st = pv_engine_stream();
-    return mk_run(st, [&]() -> int {
-        const uint64_t nodes0 = pv_merkle_node_count(s0), paths0 = pv_merkle_popc_sum(s0);
-        MkReplies rep{};
-        if (hr) {  // staged once for all chunks, in a stage of their own
-            PvStage& q = g_mk.replies;
-            const uint64_t R = hr->count;
-            int rc = q.reset(st, false);
-            if (rc) return rc;
-            const int i_end = q.in(hr->end, 8 * R), i_poff = q.in_offsets(hr->proof_off, R),
-                      i_root = q.in(hr->final_root, 32),
-                      i_proof = q.in(hr->proof + 32 * hr->proof_off[0], 32 * (hr->proof_off[R] - hr->proof_off[0]), 32),
-                      o_status = q.out(hr->status, R), o_words = q.out(hr->verdict_bits, (R + 7) / 8, 8);
-            if ((rc = q.upload())) return rc;
-            rep = MkReplies{q.dev<const uint64_t>(i_end), q.dev<const uint32_t>(i_proof), q.dev<const uint64_t>(i_poff),
-                            q.dev<const uint32_t>(i_root), hr->final_size, 0, R, q.dev<uint8_t>(o_status),
-                            q.dev<uint64_t>(o_words)};
-            if ((rc = mk_replies_preset(rep, R, st))) return rc;
+// The device path of the host entry on the engine stream `st`: chunk by chunk through the stage. Arguments
+// validated, n > 0. Caller holds g_mk_mu and is inside mk_run.
+int mk_host_entry_device(hipStream_t st, uint64_t s0, const uint8_t* frontier, const uint8_t* data, const uint64_t* off,
+                         uint64_t n, const PvMerkleOut& out, const MkHostReplies* hr = nullptr) {
+    MkReplies rep{};
+    if (hr) {  // staged once for all chunks, in a stage of their own
+        PvStage& q = g_mk.replies;
+        const uint64_t R = hr->count;
+        int rc = q.reset(st, false);
+        if (rc) return rc;
+        const int i_end = q.in(hr->end, 8 * R), i_poff = q.in_offsets(hr->proof_off, R), i_root = q.in(hr->final_root, 32),
+                  i_proof = q.in(hr->proof + 32 * hr->proof_off[0], 32 * (hr->proof_off[R] - hr->proof_off[0]), 32),
+                  o_status = q.out(hr->status, R), o_words = q.out(hr->verdict_bits, (R + 7) / 8, 8);
+        if ((rc = q.upload())) return rc;
+        rep = MkReplies{q.dev<const uint64_t>(i_end), q.dev<const uint32_t>(i_proof), q.dev<const uint64_t>(i_poff),
+                        q.dev<const uint32_t>(i_root), hr->final_size, 0, R, q.dev<uint8_t>(o_status),
+                        q.dev<uint64_t>(o_words)};
+        if ((rc = mk_replies_preset(rep, R, st))) return rc;
+    }
+    if (s0) PV_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+    const uint32_t* fin = mk_front(2);
+    int cur = 0;
+    PvStage& g = g_mk.stage;
+    const int rc = for_each_append_chunk(s0, n, g_mk_chunk, off, MK_CHUNK_BYTES, [&](const MkChunk& c) -> int {
+        int rc = g.reset(st, false);
+        if (rc) return rc;
+        const PvMerkleOut h = chunk_outputs(out, c);  // in the caller's memory
+        const auto section = [&](void* dst, uint64_t bytes) { return dst ? g.out(dst, bytes) : -1; };  // none if not taken
+        const uint64_t* o = off + c.c0;
+        const int i_off = g.in_offsets(o, c.m), i_data = g.in(data + o[0], o[c.m] - o[0], PV_BLOB_SLACK),
+                  o_leaf = section(h.leaf_hash, 32 * c.m), o_node = section(h.node_hash, 32 * c.n_nodes),
+                  o_roots = section(h.roots, 32 * c.m), o_poff = section(h.path_off, 8 * (c.m + 1)),
+                  o_path = section(h.path, 32 * c.n_path), o_root = section(h.root, 32);
+        if ((rc = g.upload())) return rc;
+        const PvMerkleOut d{g.dev<uint8_t>(o_leaf),  g.dev<uint8_t>(o_node), nullptr, g.dev<uint8_t>(o_root),
+                            g.dev<uint8_t>(o_roots), g.dev<uint8_t>(o_path), g.dev<uint64_t>(o_poff)};  // ... and in the stage
+        if (hr) {
+            const MkWindow w = reply_window(hr->end, hr->count, c.s, c.m);
+            rep.r0 = w.r0, rep.r1 = w.r1;
         }
-        if (s0) PV_HIP(hipMemcpyAsync(mk_front(2), frontier, 32ull * pv_popc64(s0), hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
-        const uint32_t* fin = mk_front(2);
-        int cur = 0;
-        PvStage& g = g_mk.stage;
-        for (uint64_t c0 = 0; c0 < n;) {
-            uint64_t m = std::min<uint64_t>(g_mk_chunk, n - c0);
-            if (off[c0 + m] - off[c0] > MK_CHUNK_BYTES) {  // the byte bound: the longest prefix within it, at least one leaf
-                const uint64_t* e = std::upper_bound(off + c0 + 1, off + c0 + m + 1, off[c0] + MK_CHUNK_BYTES);
-                m = std::max<uint64_t>(1, (uint64_t)(e - (off + c0)) - 1);
-            }
-            const uint64_t s = s0 + c0, pbase = pv_merkle_popc_sum(s) - paths0;
-            const bool is_last = c0 + m == n;
-            uint64_t n_nodes, n_front, n_path;
-            pv_merkle_plan_core(s, m, &n_nodes, &n_front, &n_path);
-            int rc = g.reset(st, false);
-            if (rc) return rc;
-            // an output the caller does not take has no section
-            uint8_t* const nodes = out.node_hash + 32 * (pv_merkle_node_count(s) - nodes0);
-            const int i_off = g.in_offsets(off + c0, m),
-                      i_data = g.in(data + off[c0], off[c0 + m] - off[c0], PV_BLOB_SLACK),
-                      o_leaf = out.leaf_hash ? g.out(out.leaf_hash + 32 * c0, 32 * m) : -1,
-                      o_node = out.node_hash ? g.out(nodes, 32 * n_nodes) : -1,
-                      o_roots = out.roots ? g.out(out.roots + 32 * c0, 32 * m) : -1,
-                      o_poff = out.path ? g.out(out.path_off + c0, 8 * (m + 1)) : -1,
-                      o_path = out.path ? g.out(out.path + 32 * pbase, 32 * n_path) : -1,
-                      o_root = is_last && out.root ? g.out(out.root, 32) : -1;
-            if ((rc = g.upload())) return rc;
-            const MkChunkOut o{g.dev<uint32_t>(o_leaf), g.dev<uint32_t>(o_node), g.dev<uint32_t>(o_roots),
-                               g.dev<uint32_t>(o_path), g.dev<uint64_t>(o_poff), pbase, g.dev<uint32_t>(o_root)};
-            if (hr) {  // the replies that end in this chunk, from the start of the first one's verdict word
-                const uint64_t* e = hr->end;
-                rep.r0 = (uint64_t)(std::upper_bound(e, e + hr->count, s) - e) & ~63ull;
-                rep.r1 = (uint64_t)(std::upper_bound(e, e + hr->count, s + m) - e);
-            }
-            if ((rc = mk_chunk(s, fin, g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), m, o, mk_front(cur), st,
-                               hr ? &rep : nullptr)))
-                return rc;
-            fin = mk_front(cur);
-            cur ^= 1;
-            if (is_last && out.frontier)
-                PV_HIP(hipMemcpyAsync(out.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
-            if ((rc = g.download())) return rc;  // synchronised: the stage is free for the next chunk
-            c0 += m;
-        }
-        return hr ? g_mk.replies.download() : PV_OK;
+        if ((rc = mk_chunk(c, fin, g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off), d, mk_front(cur), st,
+                           hr ? &rep : nullptr)))
+            return rc;
+        fin = mk_front(cur);
+        cur ^= 1;
+        if (h.frontier) PV_HIP(hipMemcpyAsync(h.frontier, fin, MK_FRONT_BYTES, hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+        return g.download();  // synchronised: the stage is free for the next chunk
     });
+    if (rc) return rc;
+    return hr ? g_mk.replies.download() : PV_OK;
 }
 
+// The proof checks in chunks of whole verdict words, proof generation in chunks of the leaf bound
+// (merkle_plan.h). Caller holds g_mk_mu (the chunk setting).
 int mk_verify_enqueue(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash, const uint64_t* d_index,
                       const uint64_t* d_size, const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
                       uint64_t n, uint8_t* d_status, uint64_t* d_verdict, hipStream_t stream) {
-    const uint64_t chunk = (g_mk_chunk + 63) & ~63ull;  // whole verdict words per chunk
-    for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
-        const uint64_t m = std::min<uint64_t>(chunk, n - c0);
+    return for_each_span(n, verdict_chunk(g_mk_chunk), [&](uint64_t c0, uint64_t m) -> int {
         PV_LAUNCH(pv_merkle_verify_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
                   stream, d_data, d_off ? d_off + c0 : nullptr,
                   d_leaf_hash ? reinterpret_cast<const uint32_t*>(d_leaf_hash + 32 * c0) : nullptr, d_index + c0,
                   d_size + c0, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off + c0,
                   reinterpret_cast<const uint32_t*>(d_root + 32 * c0), m, d_status + c0, d_verdict + c0 / 64);
-    }
-    return PV_OK;
+        return PV_OK;
+    });
 }
 
 int mk_consistency_enqueue(const uint64_t* d_old_size, const uint64_t* d_new_size, const uint8_t* d_old_root,
                            const uint8_t* d_new_root, const uint8_t* d_proof, const uint64_t* d_proof_off, uint64_t n,
                            uint8_t* d_status, uint64_t* d_verdict, hipStream_t stream) {
-    const uint64_t chunk = (g_mk_chunk + 63) & ~63ull;  // whole verdict words per chunk
-    for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
-        const uint64_t m = std::min<uint64_t>(chunk, n - c0);
+    return for_each_span(n, verdict_chunk(g_mk_chunk), [&](uint64_t c0, uint64_t m) -> int {
         PV_LAUNCH(pv_merkle_consistency_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0,
                   stream, d_old_size + c0, d_new_size + c0, reinterpret_cast<const uint32_t*>(d_old_root + 32 * c0),
                   reinterpret_cast<const uint32_t*>(d_new_root + 32 * c0), reinterpret_cast<const uint32_t*>(d_proof),
                   d_proof_off + c0, m, d_status + c0, d_verdict + c0 / 64);
-    }
-    return PV_OK;
+        return PV_OK;
+    });
 }
 
 int mk_prove_enqueue(const MkProve& p, uint64_t q, hipStream_t stream) {
-    for (uint64_t c0 = 0; c0 < q; c0 += g_mk_chunk) {
-        const uint64_t m = std::min<uint64_t>(g_mk_chunk, q - c0);
+    return for_each_span(q, g_mk_chunk, [&](uint64_t c0, uint64_t m) -> int {
         MkProve c = p;
         c.kind += c0, c.a += c0, c.b += c0, c.out_off += c0, c.status += c0;  // offsets are absolute: out stays
         PV_LAUNCH(pv_merkle_prove_kernel, dim3((unsigned)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0, stream, c, m);
-    }
-    return PV_OK;
+        return PV_OK;
+    });
 }
 
-// the append arguments every append-like entry checks
-int mk_check_append_args(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
-                         const std::string& who) {
-    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
-        return pv_fail(PV_ERR_ARG, who + ": tree_size + n must stay below 2^48");
-    if (tree_size > 0 && !frontier) return pv_fail(PV_ERR_ARG, who + ": a tree of size > 0 needs its frontier");
-    if (n > 0) {
-        if (!off) return pv_fail(PV_ERR_ARG, who + ": null offsets");
-        if (!pv_offsets_monotone(off, n)) return pv_fail(PV_ERR_ARG, who + ": offsets must be non-decreasing");
-        if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, who + ": null data");
+// An entry's refusals: `why` from merkle_plan.h's checks, or the entry's own.
+int mk_refuse(const std::string& who, const char* why) { return pv_fail(PV_ERR_ARG, who + ": " + why); }
+int mk_no_init(const std::string& who) { return pv_fail(PV_ERR_NOT_INIT, who + ": call pv_init first"); }
+// the store and the count of the three proof-generation entries
+const char* mk_check_store(uint64_t n_leaves, uint64_t q) {
+    return check_sizes(n_leaves, 0, "the store must stay below 2^48 leaves") ?: check_count(q, "more than 2^32 - 1 queries");
+}
+hipStream_t mk_stream(void* stream) { return stream ? (hipStream_t)stream : pv_engine_stream(); }
+
+// A host-buffer entry after its checks: the path chosen under g_mk_mu (work and auto_min as pv_choose_path;
+// host_only: a device path has nothing to do), then host() with the lock released (the host path shares no
+// workspace: CPU-only callers run side by side), or device(st) inside mk_run on the engine stream st.
+template <class H, class D>
+int mk_dispatch(const char* who, uint64_t work, uint64_t auto_min, bool host_only, H&& host, D&& device) {
+    std::unique_lock<std::mutex> lk(g_mk_mu);
+    bool dev;
+    if (int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, work, auto_min, who, &dev)) return rc;
+    if (!dev || host_only) {
+        lk.unlock();
+        host();
+        return PV_OK;
     }
-    return PV_OK;
+    const hipStream_t st = pv_engine_stream();
+    return mk_run(st, [&]() -> int { return device(st); });
 }
 
 }  // namespace
@@ -637,11 +626,11 @@ void pv_merkle_shutdown() {
     g_mk.hand.destroy();
 }
 
+// In every entry `why` is the first refusal in the order of the checks: a ?: b asks b only if a passed.
 extern "C" {
 
 int pv_merkle_plan(uint64_t tree_size, uint64_t n, uint64_t* n_nodes, uint64_t* n_frontier, uint64_t* path_hashes) {
-    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_plan: tree_size + n must stay below 2^48");
+    if (const char* why = check_sizes(tree_size, n)) return mk_refuse("pv_merkle_plan", why);
     uint64_t a, b, c;
     pv_merkle_plan_core(tree_size, n, &a, &b, &c);
     if (n_nodes) *n_nodes = a;
@@ -667,112 +656,80 @@ int pv_merkle_path(int mode) {
 
 int pv_merkle_append_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off,
                            uint64_t n, const PvMerkleOut* out) {
-    int rc = mk_check_out(out, "pv_merkle_append_batch");
-    if (rc) return rc;
-    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: tree_size + n must stay below 2^48");
-    if (tree_size > 0 && !frontier) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: a tree of size > 0 needs its frontier");
-    if (n > 0) {
-        if (!off) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null offsets");
-        if (!pv_offsets_monotone(off, n)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: offsets must be non-decreasing");
-        if (!data && off[n] != off[0]) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch: null data");
-    }
-    std::unique_lock<std::mutex> lk(g_mk_mu);
-    bool device;
-    if ((rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n,
-                             out->roots || out->path ? PV_MERKLE_AUTO_MIN_PROOFS : PV_MERKLE_AUTO_MIN,
-                             "pv_merkle_append_batch", &device)))
-        return rc;
-    if (!device || n == 0) {
-        lk.unlock();  // the host path shares no workspace: CPU-only callers run side by side
-        pv_merkle_host_append(tree_size, frontier, data, off, n, out);
-        return PV_OK;
-    }
-    return mk_host_entry_device(tree_size, frontier, data, off, n, *out);
+    const char* who = "pv_merkle_append_batch";
+    if (const char* why = check_out(out) ?: check_append_host(tree_size, frontier, data, off, n)) return mk_refuse(who, why);
+    return mk_dispatch(
+        who, n, out->roots || out->path ? PV_MERKLE_AUTO_MIN_PROOFS : PV_MERKLE_AUTO_MIN, n == 0,
+        [&] { pv_merkle_host_append(tree_size, frontier, data, off, n, out); },
+        [&](hipStream_t st) { return mk_host_entry_device(st, tree_size, frontier, data, off, n, *out); });
 }
 
 int pv_merkle_append_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
                                   const uint64_t* d_off, uint64_t n, const PvMerkleOut* d_out, void* stream) {
-    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_merkle_append_batch_device: call pv_init first");
-    int rc = mk_check_out(d_out, "pv_merkle_append_batch_device");
-    if (rc) return rc;
-    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: tree_size + n must stay below 2^48");
-    if (tree_size > 0 && !d_frontier)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: a tree of size > 0 needs its frontier");
-    if (n > 0 && (!d_data || !d_off)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: null pointer");
-    for (const void* p : {(const void*)d_frontier, (const void*)d_out->leaf_hash, (const void*)d_out->node_hash,
-                          (const void*)d_out->frontier, (const void*)d_out->root, (const void*)d_out->roots,
-                          (const void*)d_out->path})
-        if (mk_misaligned(p)) return pv_fail(PV_ERR_ARG, "pv_merkle_append_batch_device: hash arrays must be 16-byte aligned");
+    const char* who = "pv_merkle_append_batch_device";
+    if (!pv_engine_stream()) return mk_no_init(who);
+    if (const char* why = check_out(d_out) ?: check_append_device(tree_size, d_frontier, d_data, d_off, n)
+                              ?: check_append_aligned(d_frontier, *d_out))
+        return mk_refuse(who, why);
     std::lock_guard<std::mutex> lk(g_mk_mu);
-    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, stream ? (hipStream_t)stream : pv_engine_stream());
+    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, mk_stream(stream));
 }
 
 int pv_merkle_verify_inclusion_batch(const uint8_t* data, const uint64_t* off, const uint8_t* leaf_hash,
                                      const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* proof,
                                      const uint64_t* proof_off, const uint8_t* root, uint64_t n, uint8_t* status,
                                      uint8_t* verdict_bits) {
+    const char* who = "pv_merkle_verify_inclusion_batch";
     if (n == 0) return PV_OK;
-    if (!leaf_index || !tree_size || !proof_off || !root || !status || !verdict_bits)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: null pointer");
-    if ((leaf_hash != nullptr) == (off != nullptr))
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: give either data and off, or leaf_hash");
-    if (off && (!pv_offsets_monotone(off, n) || (!data && off[n] != off[0])))
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: offsets must be non-decreasing over a data blob");
-    if (!pv_offsets_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: proof offsets must be non-decreasing over a proof array");
-    if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch: more than 2^32 - 1 proofs");
-    std::unique_lock<std::mutex> lk(g_mk_mu);
-    bool device;
-    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_VERIFY,
-                            "pv_merkle_verify_inclusion_batch", &device);
-    if (rc) return rc;
-    if (!device) {
-        lk.unlock();
-        pv_merkle_host_verify(data, off, leaf_hash, leaf_index, tree_size, proof, proof_off, root, n, status, verdict_bits);
-        return PV_OK;
-    }
-    const hipStream_t st = pv_engine_stream();
-    return mk_run(st, [&]() -> int {
-        PvStage& g = g_mk.stage;
-        int rc = g.reset(st, false);
-        if (rc) return rc;
-        // staged whole: the leaves as data and offsets or as hashes, and the proofs with room for one hash more
-        const int i_off = off ? g.in_offsets(off, n) : -1,
-                  i_data = off ? g.in(data + off[0], off[n] - off[0], PV_BLOB_SLACK) : -1,
-                  i_leaf = off ? -1 : g.in(leaf_hash, 32 * n), i_index = g.in(leaf_index, 8 * n),
-                  i_size = g.in(tree_size, 8 * n),
-                  i_poff = g.in_offsets(proof_off, n), i_root = g.in(root, 32 * n),
-                  i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
-                  o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
-        if ((rc = g.upload()) ||
-            (rc = mk_verify_enqueue(g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off),
-                                    g.dev<const uint8_t>(i_leaf), g.dev<const uint64_t>(i_index),
-                                    g.dev<const uint64_t>(i_size), g.dev<const uint8_t>(i_proof),
-                                    g.dev<const uint64_t>(i_poff), g.dev<const uint8_t>(i_root), n,
-                                    g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
-            return rc;
-        return g.download();
-    });
+    const char* why;
+    if (!leaf_index || !tree_size || !proof_off || !root || !status || !verdict_bits) why = "null pointer";
+    else if ((leaf_hash != nullptr) == (off != nullptr)) why = "give either data and off, or leaf_hash";
+    else if (off && (!pv_offsets_monotone(off, n) || (!data && off[n] != off[0])))
+        why = "offsets must be non-decreasing over a data blob";
+    else why = check_proof_offsets(proof, proof_off, n) ?: check_count(n, "more than 2^32 - 1 proofs");
+    if (why) return mk_refuse(who, why);
+    return mk_dispatch(
+        who, n, PV_MERKLE_AUTO_MIN_VERIFY, false,
+        [&] { pv_merkle_host_verify(data, off, leaf_hash, leaf_index, tree_size, proof, proof_off, root, n, status, verdict_bits); },
+        [&](hipStream_t st) -> int {
+            PvStage& g = g_mk.stage;
+            int rc = g.reset(st, false);
+            if (rc) return rc;
+            // staged whole: the leaves as data and offsets or as hashes, and the proofs with room for one hash more
+            const int i_off = off ? g.in_offsets(off, n) : -1,
+                      i_data = off ? g.in(data + off[0], off[n] - off[0], PV_BLOB_SLACK) : -1,
+                      i_leaf = off ? -1 : g.in(leaf_hash, 32 * n), i_index = g.in(leaf_index, 8 * n),
+                      i_size = g.in(tree_size, 8 * n), i_poff = g.in_offsets(proof_off, n), i_root = g.in(root, 32 * n),
+                      i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
+                      o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
+            if ((rc = g.upload()) ||
+                (rc = mk_verify_enqueue(g.dev<const uint8_t>(i_data), g.dev<const uint64_t>(i_off),
+                                        g.dev<const uint8_t>(i_leaf), g.dev<const uint64_t>(i_index),
+                                        g.dev<const uint64_t>(i_size), g.dev<const uint8_t>(i_proof),
+                                        g.dev<const uint64_t>(i_poff), g.dev<const uint8_t>(i_root), n,
+                                        g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
+                return rc;
+            return g.download();
+        });
 }
 
 int pv_merkle_verify_inclusion_batch_device(const uint8_t* d_data, const uint64_t* d_off, const uint8_t* d_leaf_hash,
                                             const uint64_t* d_leaf_index, const uint64_t* d_tree_size,
                                             const uint8_t* d_proof, const uint64_t* d_proof_off, const uint8_t* d_root,
                                             uint64_t n, uint8_t* d_status, uint64_t* d_verdict_words, void* stream) {
-    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_merkle_verify_inclusion_batch_device: call pv_init first");
+    const char* who = "pv_merkle_verify_inclusion_batch_device";
+    if (!pv_engine_stream()) return mk_no_init(who);
     if (n == 0) return PV_OK;
+    const char* why;
     if (!d_leaf_index || !d_tree_size || !d_proof || !d_proof_off || !d_root || !d_status || !d_verdict_words)
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: null pointer");
-    if ((d_leaf_hash != nullptr) == (d_off != nullptr) || (d_off && !d_data))
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: give either data and off, or leaf_hash");
-    if (mk_misaligned(d_leaf_hash) || mk_misaligned(d_proof) || mk_misaligned(d_root))
-        return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: hash arrays must be 16-byte aligned");
-    if (n >> 32) return pv_fail(PV_ERR_ARG, "pv_merkle_verify_inclusion_batch_device: more than 2^32 - 1 proofs");
+        why = "null pointer";
+    else if ((d_leaf_hash != nullptr) == (d_off != nullptr) || (d_off && !d_data))
+        why = "give either data and off, or leaf_hash";
+    else why = check_aligned({d_leaf_hash, d_proof, d_root}) ?: check_count(n, "more than 2^32 - 1 proofs");
+    if (why) return mk_refuse(who, why);
     std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
     return mk_verify_enqueue(d_data, d_off, d_leaf_hash, d_leaf_index, d_tree_size, d_proof, d_proof_off, d_root, n, d_status,
-                             d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+                             d_verdict_words, mk_stream(stream));
 }
 
 int pv_merkle_verify_consistency_batch(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_root,
@@ -781,39 +738,31 @@ int pv_merkle_verify_consistency_batch(const uint64_t* old_size, const uint64_t*
     const char* who = "pv_merkle_verify_consistency_batch";
     if (n == 0) return PV_OK;
     if (!old_size || !new_size || !old_root || !new_root || !proof_off || !status || !verdict_bits)
-        return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
-    if (n >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 proofs");
-    if (!pv_offsets_monotone(proof_off, n) || (!proof && proof_off[n] != proof_off[0]))
-        return pv_fail(PV_ERR_ARG, std::string(who) + ": proof offsets must be non-decreasing over a proof array");
+        return mk_refuse(who, "null pointer");
+    if (const char* why = check_count(n, "more than 2^32 - 1 proofs") ?: check_proof_offsets(proof, proof_off, n))
+        return mk_refuse(who, why);
     uint64_t all = 0;
     for (uint64_t i = 0; i < n; i++) all |= old_size[i] | new_size[i];
-    if (all >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, std::string(who) + ": tree sizes must stay below 2^48");
-    std::unique_lock<std::mutex> lk(g_mk_mu);
-    bool device;
-    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_CONSISTENCY, who, &device);
-    if (rc) return rc;
-    if (!device) {
-        lk.unlock();
-        pv_merkle_host_consistency(old_size, new_size, old_root, new_root, proof, proof_off, n, status, verdict_bits);
-        return PV_OK;
-    }
-    const hipStream_t st = pv_engine_stream();
-    return mk_run(st, [&]() -> int {
-        PvStage& g = g_mk.stage;
-        int rc = g.reset(st, false);
-        if (rc) return rc;
-        const int i_old = g.in(old_size, 8 * n), i_new = g.in(new_size, 8 * n), i_oroot = g.in(old_root, 32 * n),
-                  i_nroot = g.in(new_root, 32 * n), i_poff = g.in_offsets(proof_off, n),
-                  i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
-                  o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
-        if ((rc = g.upload()) ||
-            (rc = mk_consistency_enqueue(g.dev<const uint64_t>(i_old), g.dev<const uint64_t>(i_new),
-                                         g.dev<const uint8_t>(i_oroot), g.dev<const uint8_t>(i_nroot),
-                                         g.dev<const uint8_t>(i_proof), g.dev<const uint64_t>(i_poff), n,
-                                         g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
-            return rc;
-        return g.download();
-    });
+    if (const char* why = check_sizes(all, 0, "tree sizes must stay below 2^48")) return mk_refuse(who, why);
+    return mk_dispatch(
+        who, n, PV_MERKLE_AUTO_MIN_CONSISTENCY, false,
+        [&] { pv_merkle_host_consistency(old_size, new_size, old_root, new_root, proof, proof_off, n, status, verdict_bits); },
+        [&](hipStream_t st) -> int {
+            PvStage& g = g_mk.stage;
+            int rc = g.reset(st, false);
+            if (rc) return rc;
+            const int i_old = g.in(old_size, 8 * n), i_new = g.in(new_size, 8 * n), i_oroot = g.in(old_root, 32 * n),
+                      i_nroot = g.in(new_root, 32 * n), i_poff = g.in_offsets(proof_off, n),
+                      i_proof = g.in(proof + 32 * proof_off[0], 32 * (proof_off[n] - proof_off[0]), 32),
+                      o_status = g.out(status, n), o_words = g.out(verdict_bits, (n + 7) / 8, 8);  // whole words written
+            if ((rc = g.upload()) ||
+                (rc = mk_consistency_enqueue(g.dev<const uint64_t>(i_old), g.dev<const uint64_t>(i_new),
+                                             g.dev<const uint8_t>(i_oroot), g.dev<const uint8_t>(i_nroot),
+                                             g.dev<const uint8_t>(i_proof), g.dev<const uint64_t>(i_poff), n,
+                                             g.dev<uint8_t>(o_status), g.dev<uint64_t>(o_words), st)))
+                return rc;
+            return g.download();
+        });
 }
 
 int pv_merkle_verify_consistency_batch_device(const uint64_t* d_old_size, const uint64_t* d_new_size,
@@ -821,24 +770,22 @@ int pv_merkle_verify_consistency_batch_device(const uint64_t* d_old_size, const 
                                               const uint64_t* d_proof_off, uint64_t n, uint8_t* d_status,
                                               uint64_t* d_verdict_words, void* stream) {
     const char* who = "pv_merkle_verify_consistency_batch_device";
-    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, std::string(who) + ": call pv_init first");
+    if (!pv_engine_stream()) return mk_no_init(who);
     if (n == 0) return PV_OK;
     if (!d_old_size || !d_new_size || !d_old_root || !d_new_root || !d_proof || !d_proof_off || !d_status || !d_verdict_words)
-        return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
-    if (mk_misaligned(d_old_root) || mk_misaligned(d_new_root) || mk_misaligned(d_proof))
-        return pv_fail(PV_ERR_ARG, std::string(who) + ": hash arrays must be 16-byte aligned");
-    if (n >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 proofs");
+        return mk_refuse(who, "null pointer");
+    if (const char* why = check_aligned({d_old_root, d_new_root, d_proof}) ?: check_count(n, "more than 2^32 - 1 proofs"))
+        return mk_refuse(who, why);
     std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
     return mk_consistency_enqueue(d_old_size, d_new_size, d_old_root, d_new_root, d_proof, d_proof_off, n, d_status,
-                                  d_verdict_words, stream ? (hipStream_t)stream : pv_engine_stream());
+                                  d_verdict_words, mk_stream(stream));
 }
 
 int pv_merkle_prove_plan(uint64_t n_leaves, const uint8_t* kind, const uint64_t* a, const uint64_t* b, uint64_t q,
                          uint64_t* out_off, uint8_t* status) {
     const char* who = "pv_merkle_prove_plan";
-    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, std::string(who) + ": the store must stay below 2^48 leaves");
-    if (q >> 32) return pv_fail(PV_ERR_ARG, std::string(who) + ": more than 2^32 - 1 queries");
-    if (!out_off || (q && (!kind || !a || !b))) return pv_fail(PV_ERR_ARG, std::string(who) + ": null pointer");
+    if (const char* why = mk_check_store(n_leaves, q)) return mk_refuse(who, why);
+    if (!out_off || (q && (!kind || !a || !b))) return mk_refuse(who, "null pointer");
     out_off[0] = 0;
     for (uint64_t i = 0; i < q; i++) {
         const bool ok = pv_merkle_query_valid(kind[i], a[i], b[i], n_leaves);
@@ -851,94 +798,79 @@ int pv_merkle_prove_plan(uint64_t n_leaves, const uint8_t* kind, const uint64_t*
 int pv_merkle_prove_batch(const uint8_t* leaf_hash, uint64_t n_leaves, const uint8_t* node_hash, const uint8_t* kind,
                           const uint64_t* a, const uint64_t* b, uint64_t q, const uint64_t* out_off, uint8_t* out,
                           uint8_t* status) {
-    const std::string who = "pv_merkle_prove_batch";
-    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": the store must stay below 2^48 leaves");
-    if (q >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 queries");
+    const char* who = "pv_merkle_prove_batch";
+    if (const char* why = mk_check_store(n_leaves, q)) return mk_refuse(who, why);
     if (q == 0) return PV_OK;
     const uint64_t n_nodes = pv_merkle_node_count(n_leaves);
     if (!kind || !a || !b || !out_off || !status || (n_leaves && !leaf_hash) || (n_nodes && !node_hash))
-        return pv_fail(PV_ERR_ARG, who + ": null pointer");
+        return mk_refuse(who, "null pointer");
     if (!pv_offsets_monotone(out_off, q) || (!out && out_off[q] != out_off[0]))
-        return pv_fail(PV_ERR_ARG, who + ": out_off must be non-decreasing over an output array");
-    std::unique_lock<std::mutex> lk(g_mk_mu);
-    bool device;
-    int rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, q, PV_MERKLE_AUTO_MIN_PROVE, who.c_str(), &device);
-    if (rc) return rc;
-    if (!device) {
-        lk.unlock();
-        pv_merkle_host_prove(leaf_hash, n_leaves, node_hash, kind, a, b, q, out_off, out, status);
-        return PV_OK;
-    }
-    // a slot no lane writes keeps the caller's bytes: out goes up as well only when there is one
-    const bool all_written = out_off[0] == 0 && pv_merkle_host_prove_unwritten(n_leaves, kind, a, b, q, out_off) == 0;
-    const hipStream_t st = pv_engine_stream();
-    return mk_run(st, [&]() -> int {
-        PvStage& g = g_mk.stage;
-        int rc = g.reset(st, false);
-        if (rc) return rc;
-        // the store and the queries staged whole; out keeps its absolute offsets
-        const int i_leaf = g.in(leaf_hash, 32 * n_leaves), i_node = g.in(node_hash, 32 * n_nodes), i_kind = g.in(kind, q),
-                  i_a = g.in(a, 8 * q), i_b = g.in(b, 8 * q), i_off = g.in(out_off, 8 * (q + 1)),
-                  o_out = all_written ? g.out(out, 32 * out_off[q]) : g.inout(out, out, 32 * out_off[q]), o_status = g.out(status, q);
-        if ((rc = g.upload())) return rc;
-        const MkProve p{g.dev<const uint32_t>(i_leaf), g.dev<const uint32_t>(i_node), n_leaves, g.dev<const uint8_t>(i_kind),
-                        g.dev<const uint64_t>(i_a), g.dev<const uint64_t>(i_b), g.dev<const uint64_t>(i_off),
-                        g.dev<const uint64_t>(i_off) + q, g.dev<uint32_t>(o_out), g.dev<uint8_t>(o_status)};
-        if ((rc = mk_prove_enqueue(p, q, st))) return rc;
-        return g.download();
-    });
+        return mk_refuse(who, "out_off must be non-decreasing over an output array");
+    return mk_dispatch(
+        who, q, PV_MERKLE_AUTO_MIN_PROVE, false,
+        [&] { pv_merkle_host_prove(leaf_hash, n_leaves, node_hash, kind, a, b, q, out_off, out, status); },
+        [&](hipStream_t st) -> int {
+            // a slot no lane writes keeps the caller's bytes: out goes up as well only when there is one
+            const bool all_written = out_off[0] == 0 && pv_merkle_host_prove_unwritten(n_leaves, kind, a, b, q, out_off) == 0;
+            PvStage& g = g_mk.stage;
+            int rc = g.reset(st, false);
+            if (rc) return rc;
+            // the store and the queries staged whole; out keeps its absolute offsets
+            const int i_leaf = g.in(leaf_hash, 32 * n_leaves), i_node = g.in(node_hash, 32 * n_nodes), i_kind = g.in(kind, q),
+                      i_a = g.in(a, 8 * q), i_b = g.in(b, 8 * q), i_off = g.in(out_off, 8 * (q + 1)),
+                      o_out = all_written ? g.out(out, 32 * out_off[q]) : g.inout(out, out, 32 * out_off[q]),
+                      o_status = g.out(status, q);
+            if ((rc = g.upload())) return rc;
+            const MkProve p{g.dev<const uint32_t>(i_leaf), g.dev<const uint32_t>(i_node), n_leaves, g.dev<const uint8_t>(i_kind),
+                            g.dev<const uint64_t>(i_a), g.dev<const uint64_t>(i_b), g.dev<const uint64_t>(i_off),
+                            g.dev<const uint64_t>(i_off) + q, g.dev<uint32_t>(o_out), g.dev<uint8_t>(o_status)};
+            if ((rc = mk_prove_enqueue(p, q, st))) return rc;
+            return g.download();
+        });
 }
 
 int pv_merkle_prove_batch_device(const uint8_t* d_leaf_hash, uint64_t n_leaves, const uint8_t* d_node_hash,
                                  const uint8_t* d_kind, const uint64_t* d_a, const uint64_t* d_b, uint64_t q,
                                  const uint64_t* d_out_off, uint8_t* d_out, uint8_t* d_status, void* stream) {
-    const std::string who = "pv_merkle_prove_batch_device";
-    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, who + ": call pv_init first");
-    if (n_leaves >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": the store must stay below 2^48 leaves");
-    if (q >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 queries");
+    const char* who = "pv_merkle_prove_batch_device";
+    if (!pv_engine_stream()) return mk_no_init(who);
+    if (const char* why = mk_check_store(n_leaves, q)) return mk_refuse(who, why);
     if (q == 0) return PV_OK;
     if (!d_kind || !d_a || !d_b || !d_out_off || !d_out || !d_status || (n_leaves && !d_leaf_hash) ||
         (pv_merkle_node_count(n_leaves) && !d_node_hash))
-        return pv_fail(PV_ERR_ARG, who + ": null pointer");
-    if (mk_misaligned(d_leaf_hash) || mk_misaligned(d_node_hash) || mk_misaligned(d_out))
-        return pv_fail(PV_ERR_ARG, who + ": hash arrays must be 16-byte aligned");
+        return mk_refuse(who, "null pointer");
+    if (const char* why = check_aligned({d_leaf_hash, d_node_hash, d_out})) return mk_refuse(who, why);
     const MkProve p{reinterpret_cast<const uint32_t*>(d_leaf_hash), reinterpret_cast<const uint32_t*>(d_node_hash), n_leaves,
                     d_kind, d_a, d_b, d_out_off, d_out_off + q, reinterpret_cast<uint32_t*>(d_out), d_status};
     std::lock_guard<std::mutex> lk(g_mk_mu);  // the chunk setting; this entry uses no workspace, so no hand-over
-    return mk_prove_enqueue(p, q, stream ? (hipStream_t)stream : pv_engine_stream());
+    return mk_prove_enqueue(p, q, mk_stream(stream));
 }
 
 int pv_merkle_catchup_batch(uint64_t tree_size, const uint8_t* frontier, const uint8_t* data, const uint64_t* off, uint64_t n,
                             const uint64_t* reply_end, uint64_t n_replies, uint64_t final_size, const uint8_t* final_root,
                             const uint8_t* proof, const uint64_t* proof_off, const PvMerkleOut* out, uint8_t* status,
                             uint8_t* verdict_bits) {
-    const std::string who = "pv_merkle_catchup_batch";
+    const char* who = "pv_merkle_catchup_batch";
     const PvMerkleOut none{};
     if (!out) out = &none;
-    int rc = mk_check_out(out, who.c_str());
-    if (rc || (rc = mk_check_append_args(tree_size, frontier, data, off, n, who))) return rc;
-    if (final_size >> PV_MERKLE_MAX_BITS) return pv_fail(PV_ERR_ARG, who + ": final_size must stay below 2^48");
-    if (n_replies >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 replies");
-    if (n_replies) {
-        if (!reply_end || !final_root || !proof_off || !status || !verdict_bits) return pv_fail(PV_ERR_ARG, who + ": null pointer");
-        if (!pv_offsets_monotone(proof_off, n_replies) || (!proof && proof_off[n_replies] != proof_off[0]))
-            return pv_fail(PV_ERR_ARG, who + ": proof offsets must be non-decreasing over a proof array");
-        uint64_t bad = reply_end[0] <= tree_size || reply_end[n_replies - 1] > tree_size + n;
-        for (uint64_t r = 1; r < n_replies; r++) bad |= reply_end[r] <= reply_end[r - 1];
-        if (bad) return pv_fail(PV_ERR_ARG, who + ": reply ends must increase strictly within (tree_size, tree_size + n]");
+    const char* why = check_out(out) ?: check_append_host(tree_size, frontier, data, off, n)
+                          ?: check_sizes(final_size, 0, "final_size must stay below 2^48")
+                          ?: check_count(n_replies, "more than 2^32 - 1 replies");
+    if (!why && n_replies) {
+        if (!reply_end || !final_root || !proof_off || !status || !verdict_bits) why = "null pointer";
+        else why = check_proof_offsets(proof, proof_off, n_replies) ?: check_reply_ends(reply_end, n_replies, tree_size, n);
     }
-    std::unique_lock<std::mutex> lk(g_mk_mu);
-    bool device;
-    if ((rc = pv_choose_path(g_mk_path, pv_engine_stream() != nullptr, n, PV_MERKLE_AUTO_MIN_PROOFS, who.c_str(), &device)))
-        return rc;
-    if (!device || n == 0) {
-        lk.unlock();
-        pv_merkle_host_catchup(tree_size, frontier, data, off, n, reply_end, n_replies, final_size, final_root, proof, proof_off,
-                               out, status, verdict_bits);
-        return PV_OK;
-    }
+    if (why) return mk_refuse(who, why);
     const MkHostReplies hr{reply_end, n_replies, final_size, final_root, proof, proof_off, status, verdict_bits};
-    return mk_host_entry_device(tree_size, frontier, data, off, n, *out, n_replies ? &hr : nullptr);
+    return mk_dispatch(
+        who, n, PV_MERKLE_AUTO_MIN_PROOFS, n == 0,
+        [&] {
+            pv_merkle_host_catchup(tree_size, frontier, data, off, n, reply_end, n_replies, final_size, final_root, proof,
+                                   proof_off, out, status, verdict_bits);
+        },
+        [&](hipStream_t st) {
+            return mk_host_entry_device(st, tree_size, frontier, data, off, n, *out, n_replies ? &hr : nullptr);
+        });
 }
 
 int pv_merkle_catchup_batch_device(uint64_t tree_size, const uint8_t* d_frontier, const uint8_t* d_data,
@@ -946,29 +878,22 @@ int pv_merkle_catchup_batch_device(uint64_t tree_size, const uint8_t* d_frontier
                                    uint64_t final_size, const uint8_t* d_final_root, const uint8_t* d_proof,
                                    const uint64_t* d_proof_off, const PvMerkleOut* d_out, uint8_t* d_status,
                                    uint64_t* d_verdict_words, void* stream) {
-    const std::string who = "pv_merkle_catchup_batch_device";
-    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, who + ": call pv_init first");
+    const char* who = "pv_merkle_catchup_batch_device";
+    if (!pv_engine_stream()) return mk_no_init(who);
     const PvMerkleOut none{};
     if (!d_out) d_out = &none;
-    int rc = mk_check_out(d_out, who.c_str());
-    if (rc) return rc;
-    if (tree_size >> PV_MERKLE_MAX_BITS || n >> PV_MERKLE_MAX_BITS || (tree_size + n) >> PV_MERKLE_MAX_BITS ||
-        final_size >> PV_MERKLE_MAX_BITS)
-        return pv_fail(PV_ERR_ARG, who + ": tree_size + n and final_size must stay below 2^48");
-    if (n_replies >> 32) return pv_fail(PV_ERR_ARG, who + ": more than 2^32 - 1 replies");
-    if (tree_size > 0 && !d_frontier) return pv_fail(PV_ERR_ARG, who + ": a tree of size > 0 needs its frontier");
-    if (n > 0 && (!d_data || !d_off)) return pv_fail(PV_ERR_ARG, who + ": null pointer");
-    if (n_replies && (!d_reply_end || !d_final_root || !d_proof || !d_proof_off || !d_status || !d_verdict_words))
-        return pv_fail(PV_ERR_ARG, who + ": null pointer");
-    for (const void* p : {(const void*)d_frontier, (const void*)d_out->leaf_hash, (const void*)d_out->node_hash,
-                          (const void*)d_out->frontier, (const void*)d_out->root, (const void*)d_out->roots,
-                          (const void*)d_out->path, (const void*)d_final_root, (const void*)d_proof})
-        if (mk_misaligned(p)) return pv_fail(PV_ERR_ARG, who + ": hash arrays must be 16-byte aligned");
+    const char* const sizes = "tree_size + n and final_size must stay below 2^48";
+    const char* why = check_out(d_out) ?: check_sizes(tree_size, n, sizes) ?: check_sizes(final_size, 0, sizes)
+                          ?: check_count(n_replies, "more than 2^32 - 1 replies")
+                          ?: check_append_device(tree_size, d_frontier, d_data, d_off, n);
+    if (!why && n_replies && (!d_reply_end || !d_final_root || !d_proof || !d_proof_off || !d_status || !d_verdict_words))
+        why = "null pointer";
+    if (!why) why = check_append_aligned(d_frontier, *d_out) ?: check_aligned({d_final_root, d_proof});
+    if (why) return mk_refuse(who, why);
     const MkReplies rep{d_reply_end, reinterpret_cast<const uint32_t*>(d_proof), d_proof_off,
                         reinterpret_cast<const uint32_t*>(d_final_root), final_size, 0, n_replies, d_status, d_verdict_words};
     std::lock_guard<std::mutex> lk(g_mk_mu);
-    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, stream ? (hipStream_t)stream : pv_engine_stream(),
-                      n_replies ? &rep : nullptr);
+    return mk_enqueue(tree_size, d_frontier, d_data, d_off, n, *d_out, mk_stream(stream), n_replies ? &rep : nullptr);
 }
 
 }  // extern "C"

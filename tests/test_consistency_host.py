@@ -271,6 +271,75 @@ def test_argument_errors(native, golden):
             native.merkle_path(native.PV_MERKLE_AUTO)
 
 
+def test_argument_errors_code_and_message(native, golden):
+    """One bad call per check of pv_merkle_verify_consistency_batch and pv_merkle_catchup_batch, and pairs of bad
+    arguments for the order of the checks: the return code and the message as the library gave them when every
+    entry wrote its checks out itself (they are csrc/merkle_plan.h's now). Both entries look at the count before
+    they walk an array, so 2^32 is safe to pass."""
+    from test_merkle_host import assert_refusals
+    L, ARG = native.lib(), native.PV_ERR_ARG
+    c = golden["pairs"][-1]
+    case = (c["old"], c["new"], bytes.fromhex(c["old_root"]), bytes.fromhex(c["new_root"]), [bytes.fromhex(h) for h in c["proof"]])
+    good = [ptr(a) for a in arrays([case, case])] + [2, ptr(np.zeros(2, np.uint8)), ptr(np.zeros(8, np.uint8))]
+    dec = np.array([0, 5, 3], np.uint64)
+
+    def cons(**kw):
+        args = list(good)
+        for k, v in kw.items():
+            args[int(k[1:])] = v
+        return L.pv_merkle_verify_consistency_batch(*args)
+
+    blob, off = np.zeros(16, np.uint8), np.array([0, 4, 8, 12], np.uint64)
+    root, pf, po = np.zeros(32, np.uint8), np.zeros(64, np.uint8), np.array([0, 1, 2], np.uint64)
+    st, bits = np.zeros(2, np.uint8), np.zeros(8, np.uint8)
+    paths = native.PvMerkleOut()
+    paths.path = root.ctypes.data
+
+    def catchup(ends=(1, 3), tree_size=0, frontier=None, data=ptr(blob), off_=ptr(off), n_replies=2, final=3, proof=ptr(pf),
+                poff_=ptr(po), out=None, status=ptr(st)):
+        e = None if ends is None else ptr(np.array(ends, np.uint64))
+        return L.pv_merkle_catchup_batch(tree_size, frontier, data, off_, 3, e, n_replies, final, ptr(root), proof, poff_, out,
+                                         status, ptr(bits))
+
+    V, K, SIZES = "pv_merkle_verify_consistency_batch: ", "pv_merkle_catchup_batch: ", "tree_size + n must stay below 2^48"
+    POFF, ENDS = "proof offsets must be non-decreasing over a proof array", \
+        "reply ends must increase strictly within (tree_size, tree_size + n]"
+    assert cons() == native.PV_OK and catchup() == native.PV_OK
+    assert_refusals(L, [
+        (lambda: cons(a2=None), ARG, V + "null pointer"),
+        (lambda: cons(a6=2 ** 32), ARG, V + "more than 2^32 - 1 proofs"),
+        (lambda: cons(a5=ptr(dec)), ARG, V + POFF),
+        (lambda: cons(a4=None), ARG, V + POFF),
+        (lambda: cons(a1=ptr(np.array([1, 2 ** 48], np.uint64))), ARG, V + "tree sizes must stay below 2^48"),
+        # two at once: a null pointer before the count, the count before the offsets, the offsets before the sizes
+        (lambda: cons(a2=None, a6=2 ** 32), ARG, V + "null pointer"),
+        (lambda: cons(a6=2 ** 32, a5=ptr(dec)), ARG, V + "more than 2^32 - 1 proofs"),
+        (lambda: cons(a5=ptr(dec), a0=ptr(np.array([2 ** 48, 1], np.uint64))), ARG, V + POFF),
+        (lambda: catchup(out=ctypes.byref(paths)), ARG, K + "path and path_off go together"),
+        (lambda: catchup(tree_size=2 ** 48 - 3, frontier=ptr(blob), ends=(2 ** 48 - 2, 2 ** 48)), ARG, K + SIZES),
+        (lambda: catchup(tree_size=5, ends=(6, 7)), ARG, K + "a tree of size > 0 needs its frontier"),
+        (lambda: catchup(off_=None), ARG, K + "null offsets"),
+        (lambda: catchup(off_=ptr(np.array([0, 8, 4, 12], np.uint64))), ARG, K + "offsets must be non-decreasing"),
+        (lambda: catchup(data=None), ARG, K + "null data"),
+        (lambda: catchup(final=2 ** 48), ARG, K + "final_size must stay below 2^48"),
+        (lambda: catchup(n_replies=2 ** 32), ARG, K + "more than 2^32 - 1 replies"),
+        (lambda: catchup(ends=None), ARG, K + "null pointer"),
+        (lambda: catchup(status=None), ARG, K + "null pointer"),
+        (lambda: catchup(poff_=ptr(dec)), ARG, K + POFF),
+        (lambda: catchup(proof=None), ARG, K + POFF),
+        (lambda: catchup(ends=(0, 3)), ARG, K + ENDS),
+        (lambda: catchup(ends=(2, 2)), ARG, K + ENDS),
+        (lambda: catchup(ends=(1, 4)), ARG, K + ENDS),
+        # two at once, in the order of the checks
+        (lambda: catchup(out=ctypes.byref(paths), tree_size=5), ARG, K + "path and path_off go together"),
+        (lambda: catchup(data=None, final=2 ** 48), ARG, K + "null data"),
+        (lambda: catchup(final=2 ** 48, n_replies=2 ** 32), ARG, K + "final_size must stay below 2^48"),
+        (lambda: catchup(n_replies=2 ** 32, ends=None), ARG, K + "more than 2^32 - 1 replies"),
+        (lambda: catchup(status=None, poff_=ptr(dec)), ARG, K + "null pointer"),
+        (lambda: catchup(poff_=ptr(dec), ends=(3, 1)), ARG, K + POFF),
+    ])
+
+
 # ------------------------------------------------------------------------------- the Python methods
 
 def check_outcome(got, out, what):

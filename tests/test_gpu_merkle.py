@@ -314,3 +314,104 @@ def test_no_leaves_and_single_leaf_into_the_empty_tree(dev):
     finally:
         for x in (d_f, d_front, d_root, d_path, d_poff):
             x.free()
+
+
+def test_device_entries_argument_errors(dev):
+    """One bad call per check of the five device-buffer entries, with small valid device buffers and one bad
+    argument (a null pointer, a hash array at offset 8, a size of 2^48, a count of 2^32): the return code and the
+    message as the library gave them when every entry wrote its checks out itself (they are csrc/merkle_plan.h's
+    now). Without a device these entries answer PV_ERR_NOT_INIT before their checks, so only a GPU run sees the
+    strings. Every bad call returns before anything is enqueued; a valid append on the same stream afterwards
+    still gives the reference root."""
+    from test_merkle_host import assert_refusals
+    L, ARG = dev.lib(), dev.PV_ERR_ARG
+    buf = DevBuf(dev, np.zeros(4096, np.uint8))
+    bufs = [buf]
+    p, p8 = buf.p, buf.p + 8
+    assert p % 16 == 0
+
+    def outs(**kw):
+        o = dev.PvMerkleOut()
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return ctypes.byref(o)
+
+    def replace(good, kw):
+        args = list(good)
+        for k, v in kw.items():
+            args[int(k[1:])] = v
+        return args
+
+    def append(**kw):  # tree_size, frontier, data, off, n, out, stream
+        return L.pv_merkle_append_batch_device(*replace([0, None, p, p, 2, outs(root=p), None], kw))
+
+    def catchup(**kw):  # ... n, reply_end, n_replies, final_size, final_root, proof, proof_off, out, status, words, stream
+        return L.pv_merkle_catchup_batch_device(*replace([0, None, p, p, 2, p, 1, 2, p, p, p, None, p, p, None], kw))
+
+    def verify(**kw):  # data, off, leaf_hash, leaf_index, tree_size, proof, proof_off, root, n, status, words, stream
+        return L.pv_merkle_verify_inclusion_batch_device(*replace([p, p, None, p, p, p, p, p, 2, p, p, None], kw))
+
+    def cons(**kw):  # old_size, new_size, old_root, new_root, proof, proof_off, n, status, words, stream
+        return L.pv_merkle_verify_consistency_batch_device(*replace([p, p, p, p, p, p, 2, p, p, None], kw))
+
+    def prove(**kw):  # leaf_hash, n_leaves, node_hash, kind, a, b, q, out_off, out, status, stream
+        return L.pv_merkle_prove_batch_device(*replace([p, 4, p, p, p, p, 1, p, p, p, None], kw))
+
+    A, K, V = "pv_merkle_append_batch_device: ", "pv_merkle_catchup_batch_device: ", "pv_merkle_verify_inclusion_batch_device: "
+    C_, P = "pv_merkle_verify_consistency_batch_device: ", "pv_merkle_prove_batch_device: "
+    NULL, ALIGNED, FRONTIER = "null pointer", "hash arrays must be 16-byte aligned", "a tree of size > 0 needs its frontier"
+    EITHER, BOTH_SIZES = "give either data and off, or leaf_hash", "tree_size + n and final_size must stay below 2^48"
+    try:
+        assert_refusals(L, [
+            (lambda: append(a5=None), ARG, A + "null output struct"),
+            (lambda: append(a5=outs(path=p)), ARG, A + "path and path_off go together"),
+            (lambda: append(a0=2 ** 48, a1=p, a4=0), ARG, A + "tree_size + n must stay below 2^48"),
+            (lambda: append(a0=5), ARG, A + FRONTIER),
+            (lambda: append(a2=None), ARG, A + NULL),
+            (lambda: append(a3=None), ARG, A + NULL),
+            (lambda: append(a0=5, a1=p8), ARG, A + ALIGNED),
+            (lambda: append(a5=outs(root=p8)), ARG, A + ALIGNED),
+            (lambda: append(a5=outs(leaf_hash=p8)), ARG, A + ALIGNED),
+            (lambda: append(a5=outs(path=p8, path_off=p8)), ARG, A + ALIGNED),
+            (lambda: catchup(a11=outs(path=p)), ARG, K + "path and path_off go together"),
+            (lambda: catchup(a0=2 ** 48, a1=p), ARG, K + BOTH_SIZES),
+            (lambda: catchup(a7=2 ** 48), ARG, K + BOTH_SIZES),
+            (lambda: catchup(a6=2 ** 32), ARG, K + "more than 2^32 - 1 replies"),
+            (lambda: catchup(a0=5), ARG, K + FRONTIER),
+            (lambda: catchup(a2=None), ARG, K + NULL),
+            (lambda: catchup(a5=None), ARG, K + NULL),
+            (lambda: catchup(a12=None), ARG, K + NULL),
+            (lambda: catchup(a8=p8), ARG, K + ALIGNED),
+            (lambda: catchup(a9=p8), ARG, K + ALIGNED),
+            (lambda: catchup(a11=outs(frontier=p8)), ARG, K + ALIGNED),
+            (lambda: verify(a3=None), ARG, V + NULL),
+            (lambda: verify(a5=None), ARG, V + NULL),
+            (lambda: verify(a2=p), ARG, V + EITHER),
+            (lambda: verify(a0=None, a1=None), ARG, V + EITHER),
+            (lambda: verify(a0=None), ARG, V + EITHER),
+            (lambda: verify(a5=p8), ARG, V + ALIGNED),
+            (lambda: verify(a7=p8), ARG, V + ALIGNED),
+            (lambda: verify(a0=None, a1=None, a2=p8), ARG, V + ALIGNED),
+            (lambda: verify(a8=2 ** 32), ARG, V + "more than 2^32 - 1 proofs"),
+            (lambda: cons(a0=None), ARG, C_ + NULL),
+            (lambda: cons(a8=None), ARG, C_ + NULL),
+            (lambda: cons(a2=p8), ARG, C_ + ALIGNED),
+            (lambda: cons(a4=p8), ARG, C_ + ALIGNED),
+            (lambda: cons(a6=2 ** 32), ARG, C_ + "more than 2^32 - 1 proofs"),
+            (lambda: prove(a1=2 ** 48), ARG, P + "the store must stay below 2^48 leaves"),
+            (lambda: prove(a6=2 ** 32), ARG, P + "more than 2^32 - 1 queries"),
+            (lambda: prove(a3=None), ARG, P + NULL),
+            (lambda: prove(a0=None), ARG, P + NULL),
+            (lambda: prove(a2=None), ARG, P + NULL),
+            (lambda: prove(a0=p8), ARG, P + ALIGNED),
+            (lambda: prove(a8=p8), ARG, P + ALIGNED),
+        ])
+        # nothing was enqueued, and the workspace serves the next call on the same stream
+        leaves = [b"first", b"second"]
+        blob, off = R.pack(leaves)
+        got, sizes = device_entry(dev, 0, [], blob, off, 2, None, bufs)
+        dev.check(L.pv_stream_sync(None), "pv_stream_sync")
+        assert got["root"].read(32).tobytes() == R.append_all(0, [], leaves)["root"]
+    finally:
+        for x in bufs:
+            x.free()

@@ -357,6 +357,73 @@ def test_argument_errors(native):
             native.merkle_path(native.PV_MERKLE_AUTO)
 
 
+def assert_refusals(L, table):
+    """Every row's call answers its (return code, pv_last_error()) exactly."""
+    for i, (call, rc, msg) in enumerate(table):
+        assert (call(), L.pv_last_error().decode()) == (rc, msg), (i, msg)
+
+
+def test_argument_errors_code_and_message(native):
+    """One bad call per check of pv_merkle_plan, pv_merkle_append_batch and pv_merkle_verify_inclusion_batch, and
+    pairs of bad arguments for the order of the checks: the return code and the message as the library gave them
+    when every entry wrote its checks out itself (they are csrc/merkle_plan.h's now). The host-buffer entries
+    answer without a device. pv_merkle_verify_inclusion_batch walks both offset arrays before it looks at the
+    count, so its "more than 2^32 - 1 proofs" would take arrays of 2^32 offsets to reach and has no row."""
+    L, ARG = native.lib(), native.PV_ERR_ARG
+    out, paths = native.PvMerkleOut(), native.PvMerkleOut()
+    root = np.zeros(32, np.uint8)
+    out.root = paths.path = root.ctypes.data
+    blob, off, dec = np.zeros(16, np.uint8), np.array([0, 4, 8], np.uint64), np.array([0, 8, 4], np.uint64)
+
+    def append(tree_size=0, frontier=None, data=ptr(blob), off_=ptr(off), n=2, o=ctypes.byref(out)):
+        return L.pv_merkle_append_batch(tree_size, frontier, data, off_, n, o)
+
+    idx, size = np.zeros(2, np.uint64), np.ones(2, np.uint64)
+    st, bits, roots = np.zeros(2, np.uint8), np.zeros(1, np.uint8), np.zeros(64, np.uint8)
+    poff = np.array([0, 1, 2], np.uint64)
+
+    def verify(data=ptr(blob), off_=ptr(off), leaf_hash=None, index=ptr(idx), proof=ptr(roots), poff_=ptr(poff)):
+        return L.pv_merkle_verify_inclusion_batch(data, off_, leaf_hash, index, ptr(size), proof, poff_, ptr(roots), 2, ptr(st),
+                                                  ptr(bits))
+
+    A, V, SIZES = "pv_merkle_append_batch: ", "pv_merkle_verify_inclusion_batch: ", "tree_size + n must stay below 2^48"
+    assert append() == native.PV_OK and verify() == native.PV_OK
+    assert_refusals(L, [
+        (lambda: L.pv_merkle_plan(2 ** 48 - 1, 1, None, None, None), ARG, "pv_merkle_plan: " + SIZES),
+        (lambda: L.pv_merkle_plan(0, 2 ** 48, None, None, None), ARG, "pv_merkle_plan: " + SIZES),
+        (lambda: append(o=None), ARG, A + "null output struct"),
+        (lambda: append(o=ctypes.byref(paths)), ARG, A + "path and path_off go together"),
+        (lambda: append(tree_size=2 ** 48, frontier=ptr(blob), n=0), ARG, A + SIZES),
+        (lambda: append(tree_size=2 ** 48 - 1, frontier=ptr(blob)), ARG, A + SIZES),
+        (lambda: append(tree_size=5), ARG, A + "a tree of size > 0 needs its frontier"),
+        (lambda: append(off_=None), ARG, A + "null offsets"),
+        (lambda: append(off_=ptr(dec)), ARG, A + "offsets must be non-decreasing"),
+        (lambda: append(data=None), ARG, A + "null data"),
+        # two at once: the output struct before the sizes, the sizes before the frontier, the offsets before the data
+        (lambda: append(tree_size=2 ** 48, o=None), ARG, A + "null output struct"),
+        (lambda: append(tree_size=2 ** 48), ARG, A + SIZES),
+        (lambda: append(tree_size=5, off_=None), ARG, A + "a tree of size > 0 needs its frontier"),
+        (lambda: append(data=None, off_=ptr(dec)), ARG, A + "offsets must be non-decreasing"),
+        (lambda: verify(index=None), ARG, V + "null pointer"),
+        (lambda: verify(leaf_hash=ptr(roots)), ARG, V + "give either data and off, or leaf_hash"),
+        (lambda: verify(data=None, off_=None), ARG, V + "give either data and off, or leaf_hash"),
+        (lambda: verify(off_=ptr(dec)), ARG, V + "offsets must be non-decreasing over a data blob"),
+        (lambda: verify(data=None), ARG, V + "offsets must be non-decreasing over a data blob"),
+        (lambda: verify(poff_=ptr(dec)), ARG, V + "proof offsets must be non-decreasing over a proof array"),
+        (lambda: verify(proof=None), ARG, V + "proof offsets must be non-decreasing over a proof array"),
+        (lambda: verify(off_=ptr(dec), poff_=ptr(dec)), ARG, V + "offsets must be non-decreasing over a data blob"),
+    ])
+    native.merkle_path(native.PV_MERKLE_DEVICE)
+    try:
+        if L.pv_device_count() == 0:  # a forced device path is refused after the checks, also for no leaves
+            no_dev = ": the device path is forced and no device is initialised"
+            assert_refusals(L, [(lambda: append(n=0), native.PV_ERR_NO_DEVICE, A[:-2] + no_dev),
+                                (lambda: append(off_=None), ARG, A + "null offsets"),
+                                (verify, native.PV_ERR_NO_DEVICE, V[:-2] + no_dev)])
+    finally:
+        native.merkle_path(native.PV_MERKLE_AUTO)
+
+
 # ------------------------------------------------------------------------------- the Python classes
 
 def test_python_tree_against_goldens(host_path, golden):

@@ -238,6 +238,55 @@ def test_argument_errors(native, tree70):
         native.merkle_path(native.PV_MERKLE_AUTO)
 
 
+def test_argument_errors_code_and_message(native, tree70):
+    """One bad call per check of pv_merkle_prove_plan and pv_merkle_prove_batch, and pairs of bad arguments for
+    the order of the checks: the return code and the message as the library gave them when every entry wrote its
+    checks out itself (the bounds are csrc/merkle_plan.h's now)."""
+    from test_merkle_host import assert_refusals
+    store, queries, _ = tree70
+    L, ARG = native.lib(), native.PV_ERR_ARG
+    kind, a, b = q_arrays(queries[:3])
+    off, _ = plan(native, 70, queries[:3])
+    out, st = np.zeros(32 * int(off[3]) + 32, np.uint8), np.zeros(3, np.uint8)
+    good = [ptr(store[0]), 70, ptr(store[1]), ptr(kind), ptr(a), ptr(b), 3, ptr(off), ptr(out), ptr(st)]
+    dec = np.array([0, 3, 2, 4], np.uint64)
+
+    def batch(**kw):
+        args = list(good)
+        for k, v in kw.items():
+            args[int(k[1:])] = v
+        return L.pv_merkle_prove_batch(*args)
+
+    def planned(n_leaves=70, q=3, out_off=ptr(off), kind_=ptr(kind)):
+        return L.pv_merkle_prove_plan(n_leaves, kind_, ptr(a), ptr(b), q, out_off, None)
+
+    P, B = "pv_merkle_prove_plan: ", "pv_merkle_prove_batch: "
+    STORE, COUNT = "the store must stay below 2^48 leaves", "more than 2^32 - 1 queries"
+    native.merkle_path(native.PV_MERKLE_HOST)
+    try:
+        assert batch() == native.PV_OK and planned() == native.PV_OK
+        assert_refusals(L, [
+            (lambda: planned(n_leaves=2 ** 48), ARG, P + STORE),
+            (lambda: planned(q=2 ** 32), ARG, P + COUNT),
+            (lambda: planned(out_off=None), ARG, P + "null pointer"),
+            (lambda: planned(kind_=None), ARG, P + "null pointer"),
+            (lambda: planned(n_leaves=2 ** 48, q=2 ** 32), ARG, P + STORE),
+            (lambda: planned(q=2 ** 32, out_off=None), ARG, P + COUNT),
+            (lambda: batch(a1=2 ** 48), ARG, B + STORE),
+            (lambda: batch(a6=2 ** 32), ARG, B + COUNT),
+            (lambda: batch(a3=None), ARG, B + "null pointer"),
+            (lambda: batch(a0=None), ARG, B + "null pointer"),
+            (lambda: batch(a2=None), ARG, B + "null pointer"),
+            (lambda: batch(a7=ptr(dec)), ARG, B + "out_off must be non-decreasing over an output array"),
+            (lambda: batch(a8=None), ARG, B + "out_off must be non-decreasing over an output array"),
+            (lambda: batch(a1=2 ** 48, a6=2 ** 32), ARG, B + STORE),
+            (lambda: batch(a6=2 ** 32, a3=None), ARG, B + COUNT),
+            (lambda: batch(a9=None, a7=ptr(dec)), ARG, B + "null pointer"),
+        ])
+    finally:
+        native.merkle_path(native.PV_MERKLE_AUTO)
+
+
 def test_auto_serves_a_machine_without_a_device(native, tree70, monkeypatch):
     store, queries, want = tree70
     native.merkle_path(native.PV_MERKLE_AUTO)
