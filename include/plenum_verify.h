@@ -800,6 +800,56 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
                          const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, PvTrieOut* out);
 int pv_trie_path(int mode);
 
+/* ---- The state trie built from empty: the root of n key-value pairs ("Device builder") ----
+ * What PruningState.root_of answers, for keys of one length: on the device path the structural half runs as
+ * kernels too (sort, deduplicate, structure, sizes, emit), so nothing proportional to n crosses to the host.
+ *   pv_trie_root         host buffers. Key i is the key_len bytes at keys + i * key_len, key_len 1 ..
+ *                        PV_TRIE_BUILD_MAX_KEY: one length for all, so no key is a prefix of another (mixed
+ *                        lengths, the empty key and longer keys stay with pv_trie_update_batch). Value i is
+ *                        val_blob[val_off[i] .. val_off[i + 1]). flags & PV_TRIE_ROOT_WRAP: the trie stores
+ *                        rlp([value]), as PruningState.set does, wrapped on the device while the leaf is
+ *                        written; a value may then be empty. Without it a value is stored as given and has at
+ *                        least one byte. Either way the stored length stays below 2^24. A later entry of a key
+ *                        wins. n = 0 gives the blank root; n is below 2^31. The root comes in out->root.
+ *                        On the device or the host path as pv_trie_path says: PV_TRIE_HOST packs the arguments
+ *                        for the structural half of pv_trie_update_batch from the blank root, PV_TRIE_DEVICE
+ *                        runs the builder (PV_ERR_NO_DEVICE without a device, never the host path instead),
+ *                        PV_TRIE_AUTO the builder from PV_TRIE_BUILD_AUTO_MIN pairs on.
+ *                        PV_ERR_ARG: null pointers, key_len out of range, decreasing offsets, a value outside
+ *                        the limits. PV_ERR_ALLOC: the builder's workspace (about 300 bytes per pair, plus the
+ *                        nodes) does not fit the device.
+ *   pv_trie_root_device  the same on device buffers, on `stream` (null = the library's); d_root: 32 bytes on the
+ *                        device. The sizes of the second phase depend on the data, so the call synchronises
+ *                        `stream` ONCE, between its two phases, to read a few hundred bytes (counts, arena
+ *                        bytes, the error word, the per-depth record counts); the hashing and the copy of the
+ *                        root to d_root are enqueued and not waited for. Nothing the host cannot see is
+ *                        validated before that: the kernels set an error word for decreasing offsets and
+ *                        values outside the limits, no kernel uses such an offset, and the call returns
+ *                        PV_ERR_ARG after the read. d_val_blob must be readable up to d_val_off[n].
+ *                        PV_ERR_NOT_INIT without pv_init.
+ * PvTrieRootOut reports how the call ran. The device builder fills every field: n_nodes counts leaves, branches
+ * and extensions, embedded ones included; max_depth is the greatest node depth, the root being 0; launches and
+ * tail_records are the hashing's, as in PvTrieOut. The host path fills n_records and arena_bytes and leaves the
+ * rest 0. The new nodes themselves are not returned. */
+#define PV_TRIE_BUILD_MAX_KEY 64
+#define PV_TRIE_ROOT_WRAP 1u
+#define PV_TRIE_BUILD_AUTO_MIN 512 /* pairs from which AUTO runs the device builder */
+typedef struct {
+    uint8_t root[32];    /* pv_trie_root; pv_trie_root_device leaves it zero (the root goes to d_root) */
+    uint64_t n_keys;     /* distinct keys */
+    uint64_t n_nodes;
+    uint64_t n_records;  /* nodes hashed: RLP of 32 bytes and more, and the root */
+    uint64_t arena_bytes;
+    uint64_t max_depth;
+    uint64_t launches;
+    uint64_t tail_records;
+    uint64_t built_on_device; /* 1: the device builder ran */
+} PvTrieRootOut;
+int pv_trie_root(const uint8_t* keys, uint32_t key_len, uint64_t n, const uint8_t* val_blob, const uint64_t* val_off,
+                 uint32_t flags, PvTrieRootOut* out);
+int pv_trie_root_device(const uint8_t* d_keys, uint32_t key_len, uint64_t n, const uint8_t* d_val_blob,
+                        const uint64_t* d_val_off, uint32_t flags, uint8_t* d_root, PvTrieRootOut* out, void* stream);
+
 /* ---- State proofs: batched verification with SHA3-256 proof-node hashing ----
  * PruningState.verify_state_proof (state/pruning_state.py:113-122 over pruning_trie.py:1100-1119) for many
  * queries at once. A proof is a pool of node records (each one node's RLP); a query names its proof, a root,

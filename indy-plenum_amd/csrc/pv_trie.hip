@@ -9,13 +9,18 @@
 //                         levels): a long, thin top of the trie costs no launches.
 // and pv_sha3_blob_kernel, the primitive on its own: records in a blob plus offsets, at any alignment.
 // Further down, the read path: pv_proof_node_kernel and pv_proof_walk_kernel verify batches of state proofs.
+// And the structural half itself for a trie built from empty (pv_trie_root): the passes of trie_build.h as the
+// kernels of kern_trie_build.h, with rocPRIM's radix sort and scan between them, driven by tb_build below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 #include <mutex>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <string>
+#include <vector>
 
 #include "../../include/plenum_verify.h"
 #include "keccak.h"
@@ -125,6 +130,8 @@ __global__ __launch_bounds__(TR_BLOCK) void pv_proof_walk_kernel(const PvProofIn
     status[i] = st;
 }
 
+#include "kern_trie_build.h"
+
 // --------------------------------------------------------------------------------------------- host
 
 // The trie code's own workspace: allocated on first use (an engine that never touches a trie holds
@@ -133,14 +140,18 @@ __global__ __launch_bounds__(TR_BLOCK) void pv_proof_walk_kernel(const PvProofIn
 struct TrWork {
     PvStage stage;  // in: the arena and its records, a blob and its offsets, or proofs; out: digests, flags, statuses
     PvHandover hand;
+    PvDevBuf build;  // the device builder's arrays (tb_build), and what its second phase writes and hashes
+    PvDevBuf built;
 };
 TrWork g_tr;
 std::mutex g_tr_mu;
 int g_tr_path = PV_TRIE_AUTO;
 
-// The launches for nr records on device buffers. Caller holds g_tr_mu.
-int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs, uint64_t nr, uint64_t* d_hashes,
-               hipStream_t st, uint64_t* launches, uint64_t* tail_records) {
+// The launches for nr records on device buffers; next(i0) is the end of the depth that starts at record i0,
+// asked once per depth in order. Caller holds g_tr_mu.
+template <class Next>
+int tr_enqueue_runs(uint8_t* d_arena, const PvTrieRec* d_recs, uint64_t nr, uint64_t* d_hashes, hipStream_t st,
+                    uint64_t* launches, uint64_t* tail_records, const Next& next) {
     for (uint64_t i0 = 0; i0 < nr;) {
         if (nr - i0 <= TR_TAIL_MAX) {
             PV_LAUNCH(pv_sha3_tail_kernel, dim3(1), dim3(TR_BLOCK), 0, st, d_arena, d_recs, (uint32_t)i0,
@@ -149,13 +160,27 @@ int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs,
             *tail_records = nr - i0;
             break;
         }
-        const uint64_t i1 = recs[i0].next, count = i1 - i0;
+        const uint64_t i1 = next(i0), count = i1 - i0;
         PV_LAUNCH(pv_sha3_batch_kernel, dim3((unsigned)((count + TR_BLOCK - 1) / TR_BLOCK)), dim3(TR_BLOCK), 0, st,
                   d_arena, d_recs, (uint32_t)i0, (uint32_t)count, d_hashes);
         ++*launches;
         i0 = i1;
     }
     return PV_OK;
+}
+
+// ... with the depth boundaries read from a host copy of the records
+int tr_enqueue(uint8_t* d_arena, const PvTrieRec* d_recs, const PvTrieRec* recs, uint64_t nr, uint64_t* d_hashes,
+               hipStream_t st, uint64_t* launches, uint64_t* tail_records) {
+    return tr_enqueue_runs(d_arena, d_recs, nr, d_hashes, st, launches, tail_records,
+                           [&](uint64_t i0) { return (uint64_t)recs[i0].next; });
+}
+// ... and from a small host array: ends[k] is the end of the k-th depth, deepest first
+int tr_enqueue_bounds(uint8_t* d_arena, const PvTrieRec* d_recs, const std::vector<uint32_t>& ends, uint64_t nr,
+                      uint64_t* d_hashes, hipStream_t st, uint64_t* launches, uint64_t* tail_records) {
+    size_t k = 0;
+    return tr_enqueue_runs(d_arena, d_recs, nr, d_hashes, st, launches, tail_records,
+                           [&](uint64_t) { return (uint64_t)ends[k++]; });
 }
 
 // arena and records staged whole, hashed, copied back: arena -> blob, digests -> hashes
@@ -229,6 +254,145 @@ int tr_proof_device(const PvProofIn& in, uint8_t* status) {
     });
 }
 
+// The device builder on device buffers: phase one (sort, deduplicate, structure, sizes, record order), one
+// read of the header, phase two (emit, hash), the root copied to d_root on the device. Caller holds g_tr_mu
+// and is inside the workspace's hand-over on `st`.
+int tb_build(const uint8_t* d_keys, uint32_t key_len, uint64_t n64, const uint8_t* d_val, const uint64_t* d_voff,
+             uint32_t flags, uint8_t* d_root, PvTrieRootOut* out, hipStream_t st) {
+    // node ids are 32-bit and there are 3 n of them; that many pairs need more device memory than there is
+    if ((3 * n64) >> 32) return pv_fail(PV_ERR_ALLOC, "pv_trie_root: the device builder's workspace for n pairs does not fit");
+    const uint32_t n = (uint32_t)n64, n3 = 3 * n, W = (key_len + 7) / 8;
+    size_t t_sort = 0, t_scan = 0, t_scan64 = 0, t_dsort = 0;
+    PV_HIP(rocprim::radix_sort_keys(nullptr, t_sort, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64, st), PV_ERR_LAUNCH);
+    PV_HIP(rocprim::exclusive_scan(nullptr, t_scan, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(), st),
+           PV_ERR_LAUNCH);
+    PV_HIP(rocprim::exclusive_scan(nullptr, t_scan64, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n3,
+                                   rocprim::plus<uint64_t>(), st), PV_ERR_LAUNCH);
+    PV_HIP(rocprim::radix_sort_pairs(nullptr, t_dsort, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr,
+                                     (uint32_t*)nullptr, n3, 0, 8, st), PV_ERR_LAUNCH);
+    const size_t t_bytes = std::max(std::max(t_sort, t_scan), std::max(t_scan64, t_dsort));
+    PvLayout lay;
+    const uint64_t o_hdr = lay.add(sizeof(TbHdr)), o_idx = lay.add(4ull * n), o_idx2 = lay.add(4ull * n),
+                   o_wk = lay.add(8ull * n), o_wk2 = lay.add(8ull * n), o_keep = lay.add(4ull * n), o_pos = lay.add(4ull * n),
+                   o_sidx = lay.add(4ull * n), o_skey = lay.add(8ull * n * W), o_h = lay.add(n), o_isrep = lay.add(n),
+                   o_ct = lay.add(64ull * n), o_lpar = lay.add(4ull * n), o_bpar = lay.add(4ull * n), o_lsz = lay.add(4ull * n),
+                   o_bsmall = lay.add(4ull * n), o_bsz = lay.add(4ull * n), o_esz = lay.add(4ull * n),
+                   o_rlen8 = lay.add(8ull * n3), o_roff = lay.add(8ull * n3), o_dkey = lay.add(n3), o_ndepth = lay.add(n3),
+                   o_nid = lay.add(4ull * n3), o_dkey_s = lay.add(n3), o_order = lay.add(4ull * n3),
+                   o_rank = lay.add(4ull * n3), o_temp = lay.add(t_bytes);
+    PvDevBuf& b = g_tr.build;
+    if (int rc = b.grow(lay.at)) return rc;
+    auto at = [&](uint64_t o) { return b.p + o; };
+    TbCtx c{};
+    c.keys = d_keys;
+    c.val = d_val;
+    c.voff = d_voff;
+    c.key_len = key_len;
+    c.n = n;
+    c.wrap = (flags & PV_TRIE_ROOT_WRAP) ? 1 : 0;
+    c.W = W;
+    c.hdr = (TbHdr*)at(o_hdr);
+    c.idx = (uint32_t*)at(o_idx);
+    c.keep = (uint32_t*)at(o_keep);
+    c.pos = (uint32_t*)at(o_pos);
+    c.sidx = (uint32_t*)at(o_sidx);
+    c.skey = (uint64_t*)at(o_skey);
+    c.h = at(o_h);
+    c.isrep = at(o_isrep);
+    c.ct = (uint32_t*)at(o_ct);
+    c.lpar = (uint32_t*)at(o_lpar);
+    c.bpar = (uint32_t*)at(o_bpar);
+    c.lsz = (uint32_t*)at(o_lsz);
+    c.bsmall = (uint32_t*)at(o_bsmall);
+    c.bsz = (uint32_t*)at(o_bsz);
+    c.esz = (uint32_t*)at(o_esz);
+    c.rlen8 = (uint64_t*)at(o_rlen8);
+    c.roff = (uint64_t*)at(o_roff);
+    c.dkey = at(o_dkey);
+    c.ndepth = at(o_ndepth);
+    c.nid = (uint32_t*)at(o_nid);
+    c.dkey_s = at(o_dkey_s);
+    c.order = (uint32_t*)at(o_order);
+    c.rank = (uint32_t*)at(o_rank);
+    void* temp = at(o_temp);
+    uint64_t *wk = (uint64_t*)at(o_wk), *wk2 = (uint64_t*)at(o_wk2);
+    uint32_t* idx2 = (uint32_t*)at(o_idx2);
+    const dim3 blk(TR_BLOCK), gn((n + TR_BLOCK - 1) / TR_BLOCK), gn3((unsigned)(((uint64_t)n3 + TR_BLOCK - 1) / TR_BLOCK));
+
+    PV_HIP(hipMemsetAsync(c.hdr, 0, sizeof(TbHdr), st), PV_ERR_LAUNCH);
+    PV_LAUNCH(pv_tb_init_kernel, gn, blk, 0, st, c, n);
+    // LSD sort of the entry indices by big-endian 32-bit key parts, the least significant part first. A pass
+    // sorts (part, position) keys, all distinct, so entries of one key keep the order they were given in
+    // whatever the sort does with equal keys; the entry indices follow by a gather.
+    for (uint32_t w = (key_len + 3) / 4; w-- > 0;) {
+        size_t tb = t_bytes;
+        PV_LAUNCH(pv_tb_word_kernel, gn, blk, 0, st, c, n, w, wk);
+        PV_HIP(rocprim::radix_sort_keys(temp, tb, wk, wk2, n, 0, 64, st), PV_ERR_LAUNCH);
+        PV_LAUNCH(pv_tb_gather_kernel, gn, blk, 0, st, c, n, (const uint64_t*)wk2, idx2);
+        std::swap(c.idx, idx2);
+    }
+    PV_LAUNCH(pv_tb_keep_kernel, gn, blk, 0, st, c, n);
+    {
+        size_t tb = t_bytes;
+        PV_HIP(rocprim::exclusive_scan(temp, tb, c.keep, c.pos, 0u, n, rocprim::plus<uint32_t>(), st), PV_ERR_LAUNCH);
+    }
+    PV_LAUNCH(pv_tb_compact_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_lcp_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_branch_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_leaf_size_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_small_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_size_kernel, gn, blk, 0, st, c, n);
+    PV_LAUNCH(pv_tb_mark_kernel, gn3, blk, 0, st, c, n3);
+    {
+        size_t tb = t_bytes;
+        PV_HIP(rocprim::exclusive_scan(temp, tb, c.rlen8, c.roff, (uint64_t)0, n3, rocprim::plus<uint64_t>(), st), PV_ERR_LAUNCH);
+        tb = t_bytes;
+        PV_HIP(rocprim::radix_sort_pairs(temp, tb, c.dkey, c.dkey_s, c.nid, c.order, n3, 0, 8, st), PV_ERR_LAUNCH);
+    }
+    PV_LAUNCH(pv_tb_bounds_kernel, gn3, blk, 0, st, c, n3);
+    // the one read between the phases: counts, arena bytes, the error word, the per-depth record ranges
+    TbHdr hdr;
+    PV_HIP(hipMemcpyAsync(&hdr, c.hdr, sizeof(TbHdr), hipMemcpyDeviceToHost, st), PV_ERR_LAUNCH);
+    PV_HIP(hipStreamSynchronize(st), PV_ERR_LAUNCH);
+    if (hdr.err)
+        return pv_fail(PV_ERR_ARG, "pv_trie_root: value offsets decrease, or a value is empty without PV_TRIE_ROOT_WRAP or not below 2^24 bytes stored");
+    std::vector<uint32_t> ends;
+    for (uint32_t d = TB_DEPTHS; d-- > 0;)
+        if (hdr.dend[d] > hdr.dstart[d]) ends.push_back(hdr.dend[d]);
+    const uint64_t nr = hdr.dend[0];  // the root is the last record
+    if (nr == 0 || ends.empty() || ends.back() != nr) return pv_fail(PV_ERR_LAUNCH, "pv_trie_root: the builder left no root record");
+    PvLayout la;
+    const uint64_t o_arena = la.add(hdr.arena_bytes + 8), o_recs = la.add(sizeof(PvTrieRec) * nr), o_hash = la.add(32 * nr);
+    PvDevBuf& a = g_tr.built;
+    if (int rc = a.grow(la.at)) return rc;
+    c.arena = a.p + o_arena;
+    c.recs = (PvTrieRec*)(a.p + o_recs);
+    uint64_t* d_hashes = (uint64_t*)(a.p + o_hash);
+    PV_LAUNCH(pv_tb_emit_kernel, dim3((unsigned)((nr + TR_BLOCK - 1) / TR_BLOCK)), blk, 0, st, c, (uint32_t)nr);
+    out->launches = out->tail_records = 0;
+    if (int rc = tr_enqueue_bounds(c.arena, c.recs, ends, nr, d_hashes, st, &out->launches, &out->tail_records)) return rc;
+    PV_HIP(hipMemcpyAsync(d_root, d_hashes + 4 * (nr - 1), 32, hipMemcpyDeviceToDevice, st), PV_ERR_LAUNCH);
+    out->n_keys = hdr.m;
+    out->n_nodes = (uint64_t)hdr.m + hdr.n_branch + hdr.n_ext;
+    out->n_records = nr;
+    out->arena_bytes = hdr.arena_bytes;
+    out->max_depth = hdr.max_depth;
+    return PV_OK;
+}
+
+// PV_OK or PV_ERR_ARG: the stored length of a value of `len` bytes (first byte b0) is within the limits
+bool tb_value_ok(uint64_t len, uint32_t flags) {
+    if (!(flags & PV_TRIE_ROOT_WRAP)) return len >= 1 && len <= PV_TRIE_MAX_VALUE;
+    const uint64_t s = len == 1 ? 2 : tr_prefix_size(len) + len;
+    return tr_list_size(s) <= PV_TRIE_MAX_VALUE;
+}
+
+void tb_out_clear(PvTrieRootOut* out) {
+    out->n_keys = out->n_nodes = out->n_records = out->arena_bytes = out->max_depth = out->launches = out->tail_records = 0;
+    out->built_on_device = 0;
+    memset(out->root, 0, 32);
+}
+
 }  // namespace
 
 void pv_trie_forget_stream(void* stream) {
@@ -239,6 +403,8 @@ void pv_trie_forget_stream(void* stream) {
 void pv_trie_shutdown() {
     std::lock_guard<std::mutex> lk(g_tr_mu);
     g_tr.stage.release();
+    g_tr.build.release();
+    g_tr.built.release();
     g_tr.hand.destroy();
 }
 
@@ -348,6 +514,98 @@ int pv_trie_update_batch(const uint8_t* root, const uint8_t* known_hash, const u
     }
     memcpy(out->root, out->node_hash + 32 * (nr - 1), 32);  // the root is the last record
     return PV_OK;
+}
+
+int pv_trie_root(const uint8_t* keys, uint32_t key_len, uint64_t n, const uint8_t* val_blob, const uint64_t* val_off,
+                 uint32_t flags, PvTrieRootOut* out) {
+    if (!out) return pv_fail(PV_ERR_ARG, "pv_trie_root: null output struct");
+    tb_out_clear(out);
+    uint8_t* root = out->root;
+    if (key_len < 1 || key_len > PV_TRIE_BUILD_MAX_KEY) return pv_fail(PV_ERR_ARG, "pv_trie_root: key_len must be 1 .. 64");
+    if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_trie_root: more than 2^31 - 1 pairs");
+    if (n == 0) {
+        memcpy(root, PV_TRIE_BLANK_ROOT, 32);
+        return PV_OK;
+    }
+    if (!keys || !val_off) return pv_fail(PV_ERR_ARG, "pv_trie_root: null keys or offsets");
+    if (!pv_offsets_monotone(val_off, n)) return pv_fail(PV_ERR_ARG, "pv_trie_root: offsets must be non-decreasing");
+    if (!val_blob && val_off[n] != val_off[0]) return pv_fail(PV_ERR_ARG, "pv_trie_root: null value blob");
+    bool ok = true;
+    for (uint64_t i = 0; i < n; i++) ok &= tb_value_ok(val_off[i + 1] - val_off[i], flags);
+    if (!ok)
+        return pv_fail(PV_ERR_ARG, "pv_trie_root: a value is empty without PV_TRIE_ROOT_WRAP or not below 2^24 bytes stored");
+    std::unique_lock<std::mutex> lk(g_tr_mu);
+    bool device;
+    if (int rc = tr_choose(n, PV_TRIE_BUILD_AUTO_MIN, "pv_trie_root", &device)) return rc;
+    if (device) {
+        const hipStream_t st = pv_engine_stream();
+        return g_tr.hand.run(st, [&]() -> int {
+            PvStage& g = g_tr.stage;
+            int rc = g.reset(st, false);
+            if (rc) return rc;
+            const int i_keys = g.in(keys, n * key_len), i_off = g.in_offsets(val_off, n),
+                      i_val = g.in(val_blob ? val_blob + val_off[0] : nullptr, val_off[n] - val_off[0]), o_root = g.out(root, 32);
+            if ((rc = g.upload()) || (rc = tb_build(g.dev<const uint8_t>(i_keys), key_len, n, g.dev<const uint8_t>(i_val),
+                                                    g.dev<const uint64_t>(i_off), flags, g.dev<uint8_t>(o_root), out, st)))
+                return rc;
+            out->built_on_device = 1;
+            return g.download();
+        });
+    }
+    lk.unlock();  // the host path shares no workspace: the arguments packed for the structural half of pv_trie_update_batch
+    std::vector<uint64_t> key_off(n + 1), woff;
+    for (uint64_t i = 0; i <= n; i++) key_off[i] = i * key_len;
+    std::vector<uint8_t> wrapped;
+    const uint8_t* vb = val_blob;
+    const uint64_t* vo = val_off;
+    if (flags & PV_TRIE_ROOT_WRAP) {  // rlp([value]) of every value
+        woff.resize(n + 1);
+        wrapped.resize(val_off[n] - val_off[0] + 8 * n + 8);
+        uint64_t at = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint8_t* p = val_blob + val_off[i];
+            const uint64_t len = val_off[i + 1] - val_off[i];
+            woff[i] = at;
+            at += tr_put_prefix(wrapped.data() + at, tr_str_size(p, len), 0xc0);
+            at += tr_put_str(wrapped.data() + at, p, len);
+        }
+        woff[n] = at;
+        vb = wrapped.data();
+        vo = woff.data();
+    }
+    const PvTrieIn in{PV_TRIE_BLANK_ROOT, nullptr, nullptr, nullptr, 0, keys, key_off.data(), vb, vo, n};
+    PvTriePlan plan;
+    std::string err;
+    if (int rc = pv_trie_host_build(in, &plan, &err)) return pv_fail(rc, "pv_trie_root: " + err);
+    const uint64_t nr = plan.recs.size();
+    if (nr == 0) return pv_fail(PV_ERR_ARG, "pv_trie_root: the host path built no node");
+    std::vector<uint8_t> hashes(32 * nr);
+    pv_trie_host_hash(reinterpret_cast<uint8_t*>(plan.arena.data()), plan.recs.data(), nr, hashes.data());
+    memcpy(root, hashes.data() + 32 * (nr - 1), 32);
+    out->n_records = nr;
+    out->arena_bytes = plan.arena_bytes;
+    return PV_OK;
+}
+
+int pv_trie_root_device(const uint8_t* d_keys, uint32_t key_len, uint64_t n, const uint8_t* d_val_blob,
+                        const uint64_t* d_val_off, uint32_t flags, uint8_t* d_root, PvTrieRootOut* out, void* stream) {
+    if (!pv_engine_stream()) return pv_fail(PV_ERR_NOT_INIT, "pv_trie_root_device: call pv_init first");
+    if (!d_root || !out) return pv_fail(PV_ERR_ARG, "pv_trie_root_device: null root or output struct");
+    tb_out_clear(out);
+    if (key_len < 1 || key_len > PV_TRIE_BUILD_MAX_KEY) return pv_fail(PV_ERR_ARG, "pv_trie_root_device: key_len must be 1 .. 64");
+    if (n >> 31) return pv_fail(PV_ERR_ARG, "pv_trie_root_device: more than 2^31 - 1 pairs");
+    const hipStream_t st = stream ? (hipStream_t)stream : pv_engine_stream();
+    if (n == 0) {
+        PV_HIP(hipMemcpyAsync(d_root, PV_TRIE_BLANK_ROOT, 32, hipMemcpyHostToDevice, st), PV_ERR_LAUNCH);
+        return PV_OK;
+    }
+    if (!d_keys || !d_val_off || !d_val_blob) return pv_fail(PV_ERR_ARG, "pv_trie_root_device: null pointer");
+    std::lock_guard<std::mutex> lk(g_tr_mu);
+    return g_tr.hand.run(st, [&]() -> int {
+        if (int rc = tb_build(d_keys, key_len, n, d_val_blob, d_val_off, flags, d_root, out, st)) return rc;
+        out->built_on_device = 1;
+        return PV_OK;
+    });
 }
 
 int pv_trie_verify_proofs(const PvProofIn* in, uint8_t* status) {

@@ -33,7 +33,7 @@ static constexpr uint64_t PV_TRIE_MAX_VALUE = (1ull << 24) - 1;  // value bytes 
 // ------------------------------------------------------------------------------------------- RLP
 
 // bytes of the length prefix of a payload of `len` bytes (strings of one byte below 0x80 have none)
-inline uint32_t tr_prefix_size(uint64_t len) {
+PV_HD uint32_t tr_prefix_size(uint64_t len) {
     if (len < 56) return 1;
     uint32_t ll = 0;
     for (uint64_t x = len; x; x >>= 8) ll++;
@@ -42,10 +42,10 @@ inline uint32_t tr_prefix_size(uint64_t len) {
 inline uint64_t tr_str_size(const uint8_t* p, uint64_t len) {
     return len == 1 && p[0] < 0x80 ? 1 : tr_prefix_size(len) + len;
 }
-inline uint64_t tr_list_size(uint64_t payload) { return tr_prefix_size(payload) + payload; }
+PV_HD uint64_t tr_list_size(uint64_t payload) { return tr_prefix_size(payload) + payload; }
 
 // writes the prefix (base 0x80 string, 0xc0 list), returns the bytes written
-inline uint32_t tr_put_prefix(uint8_t* dst, uint64_t len, uint8_t base) {
+PV_HD uint32_t tr_put_prefix(uint8_t* dst, uint64_t len, uint8_t base) {
     if (len < 56) {
         dst[0] = (uint8_t)(base + len);
         return 1;
@@ -110,7 +110,7 @@ PV_HD bool tr_rlp_item(const uint8_t* p, const uint8_t* end, TrItem* it) {
 // ------------------------------------------------------------------------------------ hex prefix
 
 // hp(nibbles[0..n), terminator): n / 2 + 1 bytes to dst
-inline uint32_t tr_hp_size(uint32_t n) { return n / 2 + 1; }
+PV_HD uint32_t tr_hp_size(uint32_t n) { return n / 2 + 1; }
 inline void tr_hp_pack(uint8_t* dst, const uint8_t* nib, uint32_t n, bool term) {
     const uint8_t flags = (uint8_t)((term ? 2 : 0) | (n & 1));
     uint32_t i = 0;

@@ -145,6 +145,11 @@ SIGNATURES = {
     "pv_trie_update_batch": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64] + [ctypes.c_void_p] * 4
                              + [ctypes.c_uint64, ctypes.c_void_p]),
     "pv_trie_path": (ctypes.c_int, [ctypes.c_int]),
+    "pv_trie_root": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_uint32, ctypes.c_void_p]),
+    "pv_trie_root_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "pv_trie_verify_proofs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pv_trie_verify_proofs_device": (ctypes.c_int, [ctypes.c_void_p] * 4),
     "pv_trie_proof_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 3
@@ -898,7 +903,8 @@ class PvTrieOut(ctypes.Structure):
 
 _trie_mode = PV_TRIE_AUTO
 _trie_no_device = False
-trie_last = {"launches": 0, "tail_records": 0, "nodes": 0, "rounds": 0}  # how the last trie_update ran
+# how the last trie_update or trie_root ran; built_on_device: the structure too was built by kernels (trie_root)
+trie_last = {"launches": 0, "tail_records": 0, "nodes": 0, "rounds": 0, "built_on_device": False}
 
 
 def trie_path(mode=PV_TRIE_AUTO):
@@ -993,8 +999,44 @@ def trie_update(root, fetch, keys, values):
             caps["node_cap"], caps["blob_cap"] = int(out.n_nodes), int(out.blob_bytes)
             continue
         check(rc, "pv_trie_update_batch")
-        trie_last.update(launches=int(out.launches), tail_records=int(out.tail_records), nodes=len(nodes), rounds=rounds)
+        trie_last.update(launches=int(out.launches), tail_records=int(out.tail_records), nodes=len(nodes), rounds=rounds,
+                         built_on_device=False)
         return new_root, nodes
+
+
+PV_TRIE_BUILD_MAX_KEY, PV_TRIE_ROOT_WRAP = 64, 1
+PV_TRIE_BUILD_AUTO_MIN = 512  # include/plenum_verify.h: pairs from which AUTO runs the device builder
+
+
+class PvTrieRootOut(ctypes.Structure):
+    _fields_ = [("root", ctypes.c_uint8 * 32), ("n_keys", ctypes.c_uint64), ("n_nodes", ctypes.c_uint64),
+                ("n_records", ctypes.c_uint64), ("arena_bytes", ctypes.c_uint64), ("max_depth", ctypes.c_uint64),
+                ("launches", ctypes.c_uint64), ("tail_records", ctypes.c_uint64), ("built_on_device", ctypes.c_uint64)]
+
+
+def trie_root(keys, val_blob, val_off, wrap=True):
+    """The root of the trie built from empty of keys[i] -> val_blob[val_off[i]:val_off[i+1]], one pv_trie_root:
+    keys a (n, key_len) uint8 array with key_len 1 .. 64, wrap: the trie stores rlp([value]) as PruningState.set
+    does. No per-item Python. Returns the 32 root bytes; trie_last says how the call ran."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    if keys.ndim != 2:
+        raise ValueError("trie_root: keys must be a (n, key_len) array")
+    n, key_len = keys.shape
+    val_off = np.ascontiguousarray(val_off, dtype=np.uint64)
+    val_blob = np.ascontiguousarray(val_blob, dtype=np.uint8).reshape(-1)
+    if val_off.shape[0] != n + 1:
+        raise ValueError("trie_root: offsets must hold n + 1 entries")
+    if n and int(val_off.max()) > val_blob.size:
+        raise ValueError("trie_root: offsets reach past the blob")
+    _trie_device_ready(n, PV_TRIE_BUILD_AUTO_MIN)
+    out = PvTrieRootOut()
+    check(lib().pv_trie_root(_ptr(keys if keys.size else np.zeros(1, np.uint8)), key_len, n,
+                             _ptr(val_blob if val_blob.size else np.zeros(1, np.uint8)), _ptr(val_off),
+                             PV_TRIE_ROOT_WRAP if wrap else 0, ctypes.byref(out)), "pv_trie_root")
+    trie_last.update(launches=int(out.launches), tail_records=int(out.tail_records), nodes=int(out.n_records), rounds=1,
+                     built_on_device=bool(out.built_on_device), n_keys=int(out.n_keys), n_nodes=int(out.n_nodes),
+                     max_depth=int(out.max_depth), arena_bytes=int(out.arena_bytes))
+    return bytes(out.root)
 
 
 # ------------------------------------------------------------------------------------- state proofs

@@ -11,10 +11,12 @@ call chain for a whole batch.
     Trie.update_batch(items)         n updates          (pruning_trie.py:1006-1027 Trie.update)
     PruningState.set_batch(items)    n sets             (pruning_state.py:60-61; update_state over a 3PC batch)
     PruningState.root_of(items)      the root of a mapping built from empty, nothing stored (state rebuild,
-                                     catch-up check)
+                                     catch-up check); root_of_arrays the same from numpy arrays
 
 The batch calls go through libplenum_verify (pv_trie_update_batch): the structure in C++ on the host, the
-SHA3-256 of every new node on the GPU or, for small batches and without one, on host threads.
+SHA3-256 of every new node on the GPU or, for small batches and without one, on host threads. root_of with
+keys of one length (1 to 64 bytes) goes through pv_trie_root, which on the device path builds the structure
+with kernels as well; any other root_of goes where it went before.
 
 State proofs (pruning_trie.py:1043-1170, pruning_state.py:104-128): generate_state_proof and its prefix form,
 verify_state_proof and verify_state_proof_multi, and for many proofs at once
@@ -35,6 +37,8 @@ An embedded node (RLP under 32 bytes) travels inside its parent and is no proof 
 
 Not here: remove / delete, prefix iteration, persistent stores."""
 import hashlib
+
+import numpy as np
 
 from . import _native
 
@@ -658,7 +662,16 @@ class PruningState:
     def root_of(items):
         """headHash of a state built from empty by set(key, value) for every (key, value) of `items`; no
         store is written (rebuilding state from the ledger, the catch-up check)."""
-        items = [(_to_bytes(k, "Key"), PruningState._stored(v)) for k, v in items]
+        items = [(_to_bytes(k, "Key"), _to_bytes(v, "Value")) for k, v in items]
+        key_len = len(items[0][0]) if items else 0
+        if (1 <= key_len <= _native.PV_TRIE_BUILD_MAX_KEY and all(len(k) == key_len for k, _ in items)
+                and all(len(v) <= _native.PV_TRIE_MAX_VALUE - 8 for _, v in items)):
+            # one key length: the from-empty entry, which builds the structure on the device too and wraps each value
+            # as rlp([value]) while it writes the leaf
+            val_blob, val_off = _native._blob([v for _, v in items])
+            keys = np.frombuffer(b"".join(k for k, _ in items), np.uint8).reshape(len(items), key_len)
+            return _native.trie_root(keys, val_blob, val_off, wrap=True)
+        items = [(k, PruningState._stored(v)) for k, v in items]
         if any(len(k) > _native.PV_TRIE_MAX_KEY or len(v) > _native.PV_TRIE_MAX_VALUE for k, v in items):
             trie = Trie(KeyValueStorageInMemory())
             for k, v in items:
@@ -667,6 +680,13 @@ class PruningState:
         if not items:
             return BLANK_ROOT
         return _native.trie_update(BLANK_ROOT, None, [k for k, _ in items], [v for _, v in items])[0]
+
+    @staticmethod
+    def root_of_arrays(keys, val_blob, val_off):
+        """root_of for callers that hold arrays: keys a (n, key_len) uint8 array with key_len 1 .. 64, value i the
+        bytes val_blob[val_off[i]:val_off[i + 1]] as given to set (the library wraps them). One library call, no
+        per-item Python."""
+        return _native.trie_root(keys, val_blob, val_off, wrap=True)
 
     def get(self, key, isCommitted=True):
         if not isCommitted:

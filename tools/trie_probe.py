@@ -13,7 +13,15 @@
              alternately in one process, REPS calls each (min / median / max) and the number of nodes
              hashed: the table PV_TRIE_AUTO_MIN comes from
 
+  build      the root of the N pairs from empty through the device builder: pv_trie_root from host buffers,
+             pv_trie_root_device on buffers already on the device, and pv_trie_update_batch from empty (the
+             call root_of made before), the three interleaved in one process, --reps rounds after a warm-up
+             (min / median / max); then root_of and root_of_arrays through Python
+  build_crossover  pv_trie_root for n = 64 .. 65,536 pairs, the device builder and the host structural path
+             forced alternately, REPS calls each: the table PV_TRIE_BUILD_AUTO_MIN comes from
+
     python tools/trie_probe.py [--n 1048576] [--python-sets 20000] [--out FILE]
+    python tools/trie_probe.py --build-only [--n 1048576] [--reps 5] [--out FILE]     the last two legs alone
 """
 import argparse
 import ctypes
@@ -69,6 +77,98 @@ class Call:
         return self.rootbuf.tobytes()
 
 
+class RootCall:
+    """pv_trie_root and pv_trie_root_device on arrays prepared once (raw values: the library wraps them)."""
+
+    def __init__(self, N, keys, raw_values):
+        self.N, self.L, self.n = N, N.lib(), len(keys)
+        self.keys = np.frombuffer(b"".join(keys), np.uint8)
+        self.vb, self.vo = N._blob(raw_values)
+        self.out = N.PvTrieRootOut()
+        self.dev = None
+
+    def run(self):
+        p = self.N._ptr
+        self.N.check(self.L.pv_trie_root(p(self.keys), KEY_BYTES, self.n, p(self.vb), p(self.vo), self.N.PV_TRIE_ROOT_WRAP,
+                                         ctypes.byref(self.out)), "pv_trie_root")
+        return bytes(self.out.root)
+
+    def upload(self):
+        self.dev = [ctypes.c_void_p() for _ in range(4)]
+        for d, a in zip(self.dev, (self.keys, self.vb, self.vo, np.zeros(32, np.uint8))):
+            self.N.check(self.L.pv_dev_alloc(ctypes.byref(d), a.nbytes), "pv_dev_alloc")
+            self.N.check(self.L.pv_memcpy_h2d(d, self.N._ptr(a), a.nbytes), "h2d")
+
+    def run_device(self):
+        d_keys, d_vb, d_vo, d_root = self.dev
+        self.N.check(self.L.pv_trie_root_device(d_keys, KEY_BYTES, self.n, d_vb, d_vo, self.N.PV_TRIE_ROOT_WRAP, d_root,
+                                                ctypes.byref(self.out), None), "pv_trie_root_device")
+        self.N.check(self.L.pv_sync(), "pv_sync")  # the root is there
+
+    def device_root(self):
+        got = np.zeros(32, np.uint8)
+        self.N.check(self.L.pv_memcpy_d2h(self.N._ptr(got), self.dev[3], 32), "d2h")
+        return got.tobytes()
+
+    def free(self):
+        for d in self.dev or ():
+            self.L.pv_dev_free(d)
+        self.dev = None
+
+
+def spread(ts, scale=1e3, digits=2):
+    xs = sorted(x * scale for x in ts)
+    return [round(xs[0], digits), round(statistics.median(xs), digits), round(xs[-1], digits)]
+
+
+def build_legs(N, S, keys, raw, wrapped, reps, out):
+    """The device builder against the call root_of made before, interleaved; then the crossover table."""
+    n = len(keys)
+    N.ensure_device()
+    N.trie_path(N.PV_TRIE_DEVICE)
+    old, new = Call(N, S.BLANK_ROOT, {}, keys, wrapped), RootCall(N, keys, raw)
+    new.upload()
+    legs = (("update_batch_from_empty", old.run), ("trie_root_host_buffers", new.run), ("trie_root_device_resident", new.run_device))
+    ts = {name: [] for name, _ in legs}
+    for rep in range(reps + 1):
+        for name, fn in legs:
+            one = timed(fn, 1)
+            if rep:  # the first round sizes the buffers and warms up
+                ts[name] += one
+    roots = (old.rootbuf.tobytes(), new.run(), new.device_root())
+    out["build_roots_equal"] = roots[0] == roots[1] == roots[2]
+    for name, _ in legs:
+        out["build_%s_ms_min_median_max" % name] = spread(ts[name])
+    out["build_counts"] = {f: int(getattr(new.out, f)) for f in ("n_keys", "n_nodes", "n_records", "arena_bytes", "max_depth",
+                                                                  "launches", "tail_records")}
+    new.free()
+    items = list(zip(keys, raw))
+    t = time.perf_counter()
+    r1 = S.PruningState.root_of(items)
+    out["build_root_of_through_python_ms"] = (time.perf_counter() - t) * 1e3
+    karr = np.frombuffer(b"".join(keys), np.uint8).reshape(n, KEY_BYTES)
+    vb, vo = N._blob(raw)
+    t = time.perf_counter()
+    r2 = S.PruningState.root_of_arrays(karr, vb, vo)
+    out["build_root_of_arrays_ms"] = (time.perf_counter() - t) * 1e3
+    out["build_python_roots_equal"] = r1 == r2 == roots[0]
+    table = []
+    for cn in CROSSOVER_N:
+        if cn > n:
+            break
+        call = RootCall(N, keys[:cn], raw[:cn])
+        ts = {"device": [], "host": []}
+        for rep in range(REPS + 1):
+            for mode, key in ((N.PV_TRIE_DEVICE, "device"), (N.PV_TRIE_HOST, "host")):
+                N.trie_path(mode)
+                one = timed(call.run, 1)
+                if rep:
+                    ts[key] += one
+        table.append({"n": cn, "device_us": spread(ts["device"], 1e6, 1), "host_us": spread(ts["host"], 1e6, 1)})
+    N.trie_path(N.PV_TRIE_AUTO)
+    out["build_crossover_us_min_median_max"] = table
+
+
 def timed(fn, reps):
     ts = []
     for _ in range(reps):
@@ -96,20 +196,43 @@ def main():
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--python-sets", type=int, default=20000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--build-only", action="store_true", help="the device-builder legs alone")
+    ap.add_argument("--reps", type=int, default=5, help="interleaved rounds of the build leg")
+    ap.add_argument("--trace-leg", action="store_true",
+                    help="pv_trie_root from host buffers --reps + 1 times and nothing else (for a kernel trace)")
     a = ap.parse_args()
     n = a.n
     from plenum_amd import _native as N
     from plenum_amd import state_trie as S
     rng = np.random.default_rng(9)
 
+    raw_of = {}
+
     def pairs(m):
         kb, vb = rng.bytes(KEY_BYTES * m), rng.bytes(VALUE_BYTES * m)
-        return ([kb[KEY_BYTES * i:KEY_BYTES * (i + 1)] for i in range(m)],
-                [S.rlp_encode([vb[VALUE_BYTES * i:VALUE_BYTES * (i + 1)]]) for i in range(m)])
+        raw_of[m] = [vb[VALUE_BYTES * i:VALUE_BYTES * (i + 1)] for i in range(m)]
+        return ([kb[KEY_BYTES * i:KEY_BYTES * (i + 1)] for i in range(m)], [S.rlp_encode([v]) for v in raw_of[m]])
 
     keys, values = pairs(n)
     out = {"probe": "trie", "n": n, "key_bytes": KEY_BYTES, "value_bytes": VALUE_BYTES,
            "hostpath_threads": min(16, len(os.sched_getaffinity(0)))}
+    raw = raw_of.pop(n)
+    if a.trace_leg:
+        N.ensure_device()
+        N.trie_path(N.PV_TRIE_DEVICE)
+        call = RootCall(N, keys, raw)
+        out["trace_leg_ms"] = [round(x * 1e3, 2) for x in timed(call.run, a.reps + 1)]
+        print(json.dumps(out))
+        return
+    if a.build_only:
+        build_legs(N, S, keys, raw, values, a.reps, out)
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     # the sequential Python loop from empty, on a slice
     m = min(a.python_sets, n)
@@ -193,6 +316,7 @@ def main():
         table.append(row)
     N.trie_path(N.PV_TRIE_AUTO)
     out["crossover_us_min_median_max"] = table
+    build_legs(N, S, keys, raw, values, a.reps, out)
     line = json.dumps(out)
     print(line)
     if a.out:
